@@ -72,7 +72,14 @@ def parse(argv=None):
                         "are stopped, the ranks still alive and the tails of their stderr are printed, exit code 124")
     p.add_argument("--rendezvous-only", action="store_true",
                    help="create the process group, barrier, print {'launcher': 'ok', ...} and exit (tests the launcher without a GPU)")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the prognostic fields of the last step (interiors, in the run's dtype) as DIR/<name>.npy; "
+                        "above 64 MB in all, a fixed seeded sample of cells (the same for every field and every run of the same grid); "
+                        "N > 1: rank 0's slab")
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -300,6 +307,37 @@ def parity_block(args):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6    # --dump-outputs: every .npy together stays below 64 MB
+DUMP_SAMPLE_CELLS = 1 << 20        # cells kept per field when the whole interiors would not fit
+DUMP_SEED = 20240917
+
+
+def dump_outputs(named, directory, budget=DUMP_BUDGET_BYTES, sample=DUMP_SAMPLE_CELLS, seed=DUMP_SEED):
+    """Write {name: 2-D tensor (interior)} as directory/<name>.npy (float32 / float64, as computed).  Whole arrays while they fit in
+    `budget` together; otherwise the same `sample` cells of every array, at flat indices drawn without replacement by a generator
+    seeded with `seed` and sorted (a 1-D array per name): two builds run with the same arguments dump the same cells.  Returns a
+    description for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    shape = tuple(next(iter(named.values())).shape)
+    total = sum(t.numel() * t.element_size() for t in named.values())
+    idx = None
+    if total > budget:
+        n = shape[0] * shape[1]
+        flat = np.sort(np.random.default_rng(seed).choice(n, size=min(sample, n), replace=False))
+        dev = next(iter(named.values())).device
+        idx = (torch.from_numpy(flat // shape[1]).to(dev), torch.from_numpy(flat % shape[1]).to(dev))
+    for name, t in named.items():
+        a = (t[idx] if idx is not None else t).detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} has dtype {a.dtype}")
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": directory, "names": sorted(named), "interior_shape": list(shape),
+            "sample": None if idx is None else {"cells": int(idx[0].numel()), "seed": seed,
+                                                "rule": "numpy default_rng(seed).choice(Nx*Ny, cells, replace=False), sorted; row-major flat index"}}
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -415,6 +453,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = t.item()
     finite = all(torch.isfinite(f.data).all().item() for f in m.fields)
+    dumped = None
+    if args.dump_outputs and rank == 0:     # the state the last timed step left, before anything below launches more work
+        dumped = dump_outputs({n: f.interior() for n, f in zip(m.names, m.fields)}, args.dump_outputs)
     box = box_probe(torch, _lib) if (rank == 0 and world == 1) else None      # right after the timed region: clocks are settled
     companion = None
     if (world > 1 or args.force_ring) and args.scaling is None and args.n is None and not args.no_companion:
@@ -448,6 +489,8 @@ def main():
         }
         if companion is not None:
             line["companion"] = companion
+        if dumped is not None:
+            line["outputs_dump"] = dumped
         default_workload = (args.config == 3 and world == 1 and not args.strict and not dec.ring and args.n is None
                             and args.formulation is None and bpe == 8)
         ks, ksrc = None, None

@@ -73,3 +73,47 @@ def test_workload_shapes(config, scaling, world, want):
     full = {3: 4096, 4: 8192, 5: 16384}[config]
     assert abs((ydom[1] - ydom[0]) / Nyg - (y1 - y0) / full) < 1e-15      # dy of the configuration is kept
     assert abs(0.5 * (ydom[0] + ydom[1]) - 0.5 * (y0 + y1)) < 1e-12       # centred on the configuration's axis
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"]])
+def test_steps_and_warmup_are_validated(argv):
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse(argv)
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
+
+
+def test_dump_outputs_whole_arrays_when_they_fit(tmp_path):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    parent = torch.arange(10 * 12, dtype=torch.float64).reshape(10, 12)
+    named = {"u": parent[2:8, 3:9], "h": (parent[2:8, 3:9] * 2).float()}      # interiors: strided views, fp64 and fp32
+    info = bench.dump_outputs(named, str(tmp_path / "out"))
+    assert info["sample"] is None and info["names"] == ["h", "u"]
+    for name, t in named.items():
+        a = np.load(tmp_path / "out" / f"{name}.npy", allow_pickle=False)
+        assert a.dtype == t.numpy().dtype and np.array_equal(a, t.numpy())
+
+
+def test_dump_outputs_samples_the_same_cells_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    named = {n: torch.rand(300, 400, generator=g, dtype=torch.float64) for n in ("u", "v", "h", "A")}
+    budget, cells = 4 * 300 * 400 * 8 - 1, 5000                              # one byte short of the whole arrays
+    a = bench.dump_outputs(named, str(tmp_path / "a"), budget=budget, sample=cells)
+    b = bench.dump_outputs(named, str(tmp_path / "b"), budget=budget, sample=cells)
+    assert a["sample"]["cells"] == cells
+    flat = np.sort(np.random.default_rng(a["sample"]["seed"]).choice(300 * 400, size=cells, replace=False))
+    total = 0
+    for n, t in named.items():
+        x, y = (np.load(tmp_path / d / f"{n}.npy") for d in ("a", "b"))
+        assert x.dtype == np.float64 and x.shape == (cells,) and np.array_equal(x, y)
+        assert np.array_equal(x, t.numpy().reshape(-1)[flat])
+        total += os.path.getsize(tmp_path / "a" / f"{n}.npy")
+    assert total <= budget
