@@ -83,6 +83,43 @@ struct TendArgs {
                           // so that one compiled kernel serves both operands without a branch (a branch there cost the other variants their
                           // register allocation: 80 B of scratch).
 };
+// ---- RK3 stage schedule of the step drivers (step_common in swmhd_api.hip, both schedules of ring_step in ring.hip) --------------
+// Oceananigans' RungeKutta3 (TimeSteppers): gamma = 8/15, 5/12, 3/4; zeta = -, -17/60, -5/12.  Fast builds (from_state): the second
+// stage takes G- = (U1 - U0) / (dt gamma1) from the two states (GM_IS_PREV_STATE, zeta2 / gamma1) -- U0 lives in the very buffer the
+// stage writes U2 to -- so the first stage stores no tendencies: 288 instead of 320 B/cell-step.
+constexpr int GM_IS_PREV_STATE = 1024;   // = SWMHD_GM_IS_PREV_STATE (swmhd.h, which the kernel sources do not include)
+template <typename T>
+struct Rk3Stage {
+    T gamma, zeta;
+    int store_G;
+    const T *const *Gm;   // G- operand: none (first stage), the G- buffers, or the new-state buffers, which still hold the previous state
+    int flags;            // GM_IS_PREV_STATE for the from-state stage, else 0
+};
+template <typename T>
+struct Rk3Buffers {
+    T *cur[4], *alt[4], *gn[4], *gm[4];   // state read, state written, G written, G- read
+    int swaps = 0;                        // stages run so far: odd = the newest state is in the caller's alternate buffers
+    bool set(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb) {
+        for (int f = 0; f < 4; ++f) {
+            if (!q[f] || !q_alt[f] || !Ga[f] || !Gb[f]) return false;
+            cur[f] = q[f]; alt[f] = q_alt[f]; gn[f] = Ga[f]; gm[f] = Gb[f];
+        }
+        return true;
+    }
+    Rk3Stage<T> stage(int st, bool from_state) const {
+        const T gam[3] = {T(8.0 / 15.0), T(5.0 / 12.0), T(3.0 / 4.0)};
+        const T zet[3] = {T(0), T(-17.0 / 60.0), T(-5.0 / 12.0)};
+        const bool fs = from_state && st == 1;
+        return {gam[st], fs ? zet[1] / gam[0] : zet[st], (st == 1 || (st == 0 && !from_state)) ? 1 : 0,
+                st == 0 ? nullptr : (fs ? alt : gm), fs ? GM_IS_PREV_STATE : 0};
+    }
+    // after a stage: the new state becomes current, and G- <- G (store_tendencies!: pointer swaps)
+    void rotate() {
+        for (int f = 0; f < 4; ++f) { T *t = cur[f]; cur[f] = alt[f]; alt[f] = t; t = gn[f]; gn[f] = gm[f]; gm[f] = t; }
+        ++swaps;
+    }
+};
+
 template <typename T>
 struct Rk3Args {
     T *U[4];
@@ -214,12 +251,15 @@ template <typename T> hipError_t launch_tendency_fast(const TendArgs<T> &a, int 
 int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, int kernel_variant, int leave_room, int wrap, int out[8]);
 template <typename T> hipError_t launch_tendency_strict(const TendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_rk3_substep_fast(const Rk3Args<T> &a, hipStream_t s);
-// internal twin of swmhd_tendencies_rk3_* for the slab driver (ring.hip): rows [j0, j1) and [j0b, j1b) of one RK3 stage in ONE launch
-// where the kernel chosen supports it (same argument checks and return codes as the exported call)
+// internal twins of swmhd_tendencies_rk3_* and swmhd_fill_halo_periodic_multi_* for the slab driver (ring.hip), same argument checks
+// and return codes; the first serves rows [j0, j1) and [j0b, j1b) of one RK3 stage in ONE launch where the kernel chosen supports it
+// (an empty second range: exactly the exported call)
 template <typename T>
 int tendencies_rk3_two_ranges(const T *const *q, T *const *qnew, T *const *Gn, const T *const *Gm, int Nx, int Ny, int Hx, int Hy, long sy,
                               T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, T gamma, T zeta, int store_G, int j0, int j1,
                               int j0b, int j1b, int flags, void *stream);
+template <typename T>
+int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which, void *stream);
 template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, hipStream_t s);
 
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory)

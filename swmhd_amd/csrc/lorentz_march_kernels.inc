@@ -121,110 +121,6 @@ __global__ __launch_bounds__(NT) void k_lorentz_jacobian_march(OpArgs<T> a, int 
     }
 }
 
-// ---- wavefront-shuffle variant of the Jacobian operator (A/B: SWMHD_OP_DPP=1; measurement in DESIGN.md 4.1) ------------------------
-// One WAVE per workgroup, one lane per column (60 output columns + 2 halo lanes per side), NO LDS and NO barriers: every x-neighbour
-// value -- A(c-1), A(c+1), Bx(c-1), By(c-1), By(c+1), h(c-1) of the rows in flight -- is fetched from the neighbouring lane with a
-// whole-wave DPP shift (v_mov_b32 ... wave_shr:1 / wave_shl:1, two per double), which is what north_star's "wavefront shuffles for the
-// cross-derivative terms" asks for.  The price is 4 halo lanes in 64 (6.7 % redundant loads and arithmetic) instead of 4 in 256.
-template <typename T> __device__ __forceinline__ T lane_left(T v) {    // value of lane - 1 (lane 0: unchanged -- a halo lane)
-    if constexpr (sizeof(T) == 8) {
-        sw_v2i p = __builtin_bit_cast(sw_v2i, v);
-        p.x = __builtin_amdgcn_update_dpp(p.x, p.x, 0x138, 0xF, 0xF, false);   // wave_shr:1
-        p.y = __builtin_amdgcn_update_dpp(p.y, p.y, 0x138, 0xF, 0xF, false);
-        return __builtin_bit_cast(T, p);
-    } else {
-        int q = __builtin_bit_cast(int, v);
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(q, q, 0x138, 0xF, 0xF, false));
-    }
-}
-template <typename T> __device__ __forceinline__ T lane_right(T v) {   // value of lane + 1 (lane 63: unchanged)
-    if constexpr (sizeof(T) == 8) {
-        sw_v2i p = __builtin_bit_cast(sw_v2i, v);
-        p.x = __builtin_amdgcn_update_dpp(p.x, p.x, 0x130, 0xF, 0xF, false);   // wave_shl:1
-        p.y = __builtin_amdgcn_update_dpp(p.y, p.y, 0x130, 0xF, 0xF, false);
-        return __builtin_bit_cast(T, p);
-    } else {
-        int q = __builtin_bit_cast(int, v);
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(q, q, 0x130, 0xF, 0xF, false));
-    }
-}
-
-template <typename T, int PF>
-__global__ __launch_bounds__(64) void k_lorentz_jacobian_dpp(OpArgs<T> a, int nstrips, int nseg, int LY) {
-    constexpr int NT = 64, XH = 2, TXO = NT - 2 * XH;
-    const unsigned bid = xcd_remap(blockIdx.x, (unsigned)(nstrips * nseg));
-    const int strip = (int)(bid % nstrips), seg = (int)(bid / nstrips);
-    const int x0 = strip * TXO;
-    const int J0 = a.j0 + seg * LY;
-    const int J1 = (J0 + LY < a.j1) ? J0 + LY : a.j1;
-    const int c = threadIdx.x;
-    const int gx = x0 - XH + c;
-    const int gxc = clampi(gx, -a.Hx, a.Nx + a.Hx - 1);
-    const int ylo = -a.Hy, yhi = a.Ny + a.Hy - 1;
-    const Geo<T> g{a.dx, a.dy, a.rdx, a.rdy};
-    const bool col_ok = (c >= XH) && (c < NT - XH) && (gx < a.Nx);
-
-    // own column: A rows jo-2 .. jo+2, h rows jo-1 .. jo+2; from the neighbours (rows jo-1 .. jo+1): A left/right, Bx left; own Bx;
-    // By own / left / right for rows jo-1 .. jo+1 (row jo+1 is used by the next iteration)
-    T aw[5], hw[4], al[3], ar[3], bxc[3], bxl[3], byc[3], byl[3], byr[3];
-    T pa[PF], ph[PF];
-    auto ldrow = [&](int row, T &na, T &nh) {
-        const long o = (long)clampi(row, ylo, yhi) * a.sy + gxc;
-        na = a.A[o]; nh = a.h[o];
-    };
-    auto centre_B = [&](T aleft, T aright, T abelow, T aabove, T hc, T &bx, T &by) {   // reference :1-7
-        const T rh = fast_recip<T>(hc);
-        by = (T(0.5) * g.rdx) * (aright - aleft) * rh;
-        bx = -(T(0.5) * g.rdy) * (aabove - abelow) * rh;
-    };
-    {   // prologue: rows J0-2 .. J0+1 and the PF rows in flight; B of rows J0-1 and J0
-        T r0, h0;
-        ldrow(J0 - 2, r0, h0); aw[1] = r0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) ldrow(J0 - 1 + k, aw[k + 2], hw[k + 1]);
-#pragma unroll
-        for (int k = 0; k < PF; ++k) ldrow(J0 + 2 + k, pa[k], ph[k]);
-        // (windows are shifted down by the first iteration: here aw[k+1] = A(J0-2+k), hw[k+1] = h(J0-1+k))
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {            // rows J0-1, J0 -> slots 1, 2 (slot 0 after the shift = row jo-1)
-            al[k + 1] = lane_left(aw[k + 2]); ar[k + 1] = lane_right(aw[k + 2]);
-            centre_B(al[k + 1], ar[k + 1], aw[k + 1], aw[k + 3], hw[k + 1], bxc[k + 1], byc[k + 1]);
-            bxl[k + 1] = lane_left(bxc[k + 1]); byl[k + 1] = lane_left(byc[k + 1]); byr[k + 1] = lane_right(byc[k + 1]);
-        }
-        al[0] = ar[0] = bxc[0] = bxl[0] = byc[0] = byl[0] = byr[0] = T(0);
-    }
-    const int niter = (J1 - J0) + 4;
-    for (int it = 4; it < niter; ++it) {
-        const int jr = J0 - 2 + it, jo = jr - 2;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) aw[k] = aw[k + 1];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) hw[k] = hw[k + 1];
-        aw[4] = pa[0]; hw[3] = ph[0];
-#pragma unroll
-        for (int k = 0; k + 1 < PF; ++k) { pa[k] = pa[k + 1]; ph[k] = ph[k + 1]; }
-        if (it + PF < niter) ldrow(jr + PF, pa[PF - 1], ph[PF - 1]);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) { al[k] = al[k + 1]; ar[k] = ar[k + 1]; bxc[k] = bxc[k + 1]; bxl[k] = bxl[k + 1]; byc[k] = byc[k + 1]; byl[k] = byl[k + 1]; byr[k] = byr[k + 1]; }
-        // row jo+1: neighbours of A by shuffle, centre B once per cell, its neighbours by shuffle
-        al[2] = lane_left(aw[3]); ar[2] = lane_right(aw[3]);
-        centre_B(al[2], ar[2], aw[2], aw[4], hw[2], bxc[2], byc[2]);
-        bxl[2] = lane_left(bxc[2]); byl[2] = lane_left(byc[2]); byr[2] = lane_right(byc[2]);
-        const T hl = lane_left(hw[1]);
-        auto A_ = [&](int di, int dj) -> T { return di == 0 ? aw[2 + dj] : (di < 0 ? al[1 + dj] : ar[1 + dj]); };
-        auto H_ = [&](int di, int dj) -> T { return di == 0 ? hw[1 + dj] : hl; };
-        auto BX_ = [&](int di, int dj) -> T { return di == 0 ? bxc[1 + dj] : bxl[1 + dj]; };
-        auto BY_ = [&](int di, int dj) -> T { return di == 0 ? byc[1 + dj] : (di < 0 ? byl[1 + dj] : byr[1 + dj]); };
-        T fx, fy;
-        jac_force<T>(A_, H_, BX_, BY_, 0, 0, g, fx, fy);
-        if (col_ok) {
-            const long o = (long)jo * a.sy + gx;
-            a.Fx[o] = fx;
-            a.Fy[o] = fy;
-        }
-    }
-}
-
 template <typename T, int NT, int PF>
 __global__ __launch_bounds__(NT) void k_lorentz_divergence_march(OpArgs<T> a, int nstrips, int nseg, int LY) {
     constexpr int XH = 3, RW = NT + 2 * XH, TXO = NT - 2 * XH;

@@ -168,13 +168,8 @@ hipError_t LAUNCH_NAME(launch_lorentz_jacobian_, LAUNCH_SFX)(const OpArgs<T> &a,
     if (ntx <= 0 || nty <= 0) return hipSuccess;
 #if !SWMHD_STRICT
     if (a.kernel_variant == 2 || (a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 2000000L)) {
-        static int dpp_cache = 0;
-        if (env_knob("SWMHD_OP_DPP", dpp_cache) > 0) {   // A/B: wavefront-shuffle kernel (one wave per workgroup, no LDS, no barriers)
-            const int rows = a.j1 - a.j0, nstrips = (a.Nx + 59) / 60;
-            const int LY = march_rows_per_segment(rows, nstrips, 20), nseg = (rows + LY - 1) / LY;
-            hipLaunchKernelGGL((k_lorentz_jacobian_dpp<T, 2>), dim3(nstrips * nseg), dim3(64), 0, s, a, nstrips, nseg, LY);
-            return hipGetLastError();
-        }
+        // (a wavefront-shuffle variant -- one wave per workgroup, x neighbours by DPP lane shifts, no LDS -- measured 10-24 % slower and
+        // was removed, DESIGN.md 4.1)
         // (fp32: a packed two-columns-per-lane variant was measured and dropped -- 117.7 vs 116.0 us at 16384 x 2048; with the hardware
         // reciprocal the unpacked kernel is HBM-bound at the fp64 kernel's rate, 4.6 TB/s.  DESIGN.md 4.1)
         constexpr int NT = 256, PF = 2, TXO = NT - 4;   // swept NT in {64,128,256,512} x PF in {1..4} on MI355X: all within 8 %

@@ -225,16 +225,6 @@ int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, in
     return SWMHD_OK;
 }
 
-template <typename T> struct Api;
-template <> struct Api<double> {
-    static constexpr auto stage = swmhd_tendencies_rk3_f64;
-    static constexpr auto halo = swmhd_fill_halo_periodic_multi_f64;
-};
-template <> struct Api<float> {
-    static constexpr auto stage = swmhd_tendencies_rk3_f32;
-    static constexpr auto halo = swmhd_fill_halo_periodic_multi_f32;
-};
-
 // nsteps RK3 steps of one y-slab.  Two schedules: the deep-halo one (Hy >= 9, x wrapped on read: ONE exchange per step, described
 // where it is implemented below) and the per-stage one.  Per stage (X = current state, Y = the other buffer set):
 //   main stream : rows [Hy, Ny-Hy) of X -> Y          (need no remote data; the exchange of X is still in flight)
@@ -251,23 +241,17 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
     if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
     if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;   // y images belong to the neighbours (x may be wrapped on read: no x-halo kernel then)
     if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;                          // a slab needs interior rows between its two strips
-    const T gam[3] = {T(8.0 / 15.0), T(5.0 / 12.0), T(3.0 / 4.0)};
-    const T zet[3] = {T(0), T(-17.0 / 60.0), T(-5.0 / 12.0)};
     hipStream_t s = (hipStream_t)stream, c = r->comm_stream;
-    T *cur[4], *alt[4], *gn[4], *gm[4];
-    for (int f = 0; f < 4; ++f) {
-        if (!q[f] || !q_alt[f] || !Ga[f] || !Gb[f]) return SWMHD_EINVAL;
-        cur[f] = q[f]; alt[f] = q_alt[f]; gn[f] = Ga[f]; gm[f] = Gb[f];
-    }
-    if (r->pending && r->pending != (const void *)cur[0]) {   // an exchange of some other state is in flight: drain it first
+    swmhd::Rk3Buffers<T> b;
+    if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
+    if (r->pending && r->pending != (const void *)b.cur[0]) {   // an exchange of some other state is in flight: drain it first
         hipError_t e = hipEventRecord(r->ev_comm, c);
         if (e == hipSuccess) e = hipStreamWaitEvent(s, r->ev_comm, 0);
         if (e != hipSuccess) return hipfail(r, "join", e);
         r->pending = nullptr;
     }
-    int swaps = 0;
     hipError_t e;
-    const bool from_state = !(flags & SWMHD_STRICT);   // fast builds: no tendency store in the first stage (see step_common in swmhd_api.hip)
+    const bool from_state = !(flags & SWMHD_STRICT);   // fast builds: no tendency store in the first stage (common.hpp: Rk3Buffers)
     // whatever the caller enqueued on its stream so far precedes everything this call puts on the comm stream
     if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return hipfail(r, "record", e);
     if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return hipfail(r, "wait", e);
@@ -277,8 +261,28 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
     auto bail = [&](int code) {
         if (hipEventRecord(r->ev_comm, c) == hipSuccess) (void)hipStreamWaitEvent(s, r->ev_comm, 0);
         r->pending = nullptr;
-        if (state_in_alt) *state_in_alt = swaps & 1;
+        if (state_in_alt) *state_in_alt = b.swaps & 1;
         return code;
+    };
+    // rows [j0, j1) and [j0b, j1b) of stage g on stream `on`
+    auto run = [&](const swmhd::Rk3Stage<T> &g, int j0, int j1, int j0b, int j1b, int fl, hipStream_t on) {
+        return swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
+                                                   lorentz, dt, g.gamma, g.zeta, g.store_G, j0, j1, j0b, j1b, fl | g.flags, (void *)on);
+    };
+    // the interior launch of a stage on the main stream, between two timing events while swmhd_ring_time_launches asks for them
+    // (timing-only events: without the system-scope fence a default event performs when it is recorded -- with the comm stream's
+    //  kernels running beside the interior launch that fence cost 16 % of the step, 1.53 vs 1.32 ms)
+    auto run_interior = [&](const swmhd::Rk3Stage<T> &g, int j0, int j1, int fl) {
+        if (r->t0.size() >= r->tcap) return run(g, j0, j1, 0, 0, fl, s);
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        if ((e = hipEventCreateWithFlags(&t0, hipEventDisableSystemFence)) != hipSuccess) return hipfail(r, "hipEventCreate", e);
+        if ((e = hipEventCreateWithFlags(&t1, hipEventDisableSystemFence)) != hipSuccess) { (void)hipEventDestroy(t0); return hipfail(r, "hipEventCreate", e); }
+        (void)hipEventRecord(t0, s);
+        const int rc = run(g, j0, j1, 0, 0, fl, s);
+        if (rc) { (void)hipEventDestroy(t0); (void)hipEventDestroy(t1); return rc; }
+        (void)hipEventRecord(t1, s);
+        r->t0.push_back(t0); r->t1.push_back(t1); r->trows.push_back(j1 - j0);
+        return 0;
     };
     if ((flags & SWMHD_WRAP_X) && Hy >= 9 && Ny >= 32) {
         // ---- deep-halo schedule: ONE exchange per step instead of one per stage ------------------------------------------------
@@ -298,114 +302,61 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
         const int bflags = flags | ((!(flags & (SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL)) && Nx >= 1024) ? SWMHD_MARCH_KERNEL : 0);
         for (int n = 0; n < nsteps; ++n) {
             for (int st = 0; st < 3; ++st) {
-                const T *cq[4] = {cur[0], cur[1], cur[2], cur[3]};
-                const T *cgm[4] = {gm[0], gm[1], gm[2], gm[3]};
-                const bool fs = from_state && st == 1;        // G- of the second stage from the two states (swmhd.h SWMHD_GM_IS_PREV_STATE)
-                if (fs) for (int f = 0; f < 4; ++f) cgm[f] = alt[f];
-                const T *const *pgm = st == 0 ? nullptr : cgm;
-                const int store = st == 1 ? 1 : (st == 0 && !from_state ? 1 : 0);
-                const T zeta_st = fs ? zet[1] / gam[0] : zet[st];
-                const int sflags = fs ? SWMHD_GM_IS_PREV_STATE : 0;
-                const int jb = ilo[st], je = Ny - ilo[st];
-                const bool timed = r->t0.size() < r->tcap;
-                hipEvent_t a = nullptr, b = nullptr;
-                if (timed) {
-                    if ((e = hipEventCreateWithFlags(&a, hipEventDisableSystemFence)) != hipSuccess) return bail(hipfail(r, "hipEventCreate", e));
-                    if ((e = hipEventCreateWithFlags(&b, hipEventDisableSystemFence)) != hipSuccess) { (void)hipEventDestroy(a); return bail(hipfail(r, "hipEventCreate", e)); }
-                    (void)hipEventRecord(a, s);
-                }
-                int rc = Api<T>::stage(cq, alt, gn, pgm, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, gam[st], zeta_st,
-                                       store, jb, je, flags | SWMHD_LEAVE_ROOM | sflags, (void *)s);
-                if (timed) {
-                    if (rc) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-                    else { (void)hipEventRecord(b, s); r->t0.push_back(a); r->t1.push_back(b); r->trows.push_back(je - jb); }
-                }
-                if (rc) return bail(rc);
+                const swmhd::Rk3Stage<T> g = b.stage(st, from_state);
+                if (int rc = run_interior(g, ilo[st], Ny - ilo[st], flags | SWMHD_LEAVE_ROOM)) return bail(rc);
                 if (st < 2) {   // the next boundary launch reads rows of this interior launch
                     if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
                 }
                 // boundary rows of this stage, both sides in one launch, behind the exchange (stage 1) / the previous boundary launch
-                if ((rc = swmhd::tendencies_rk3_two_ranges<T>(cq, alt, gn, pgm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
-                                                              lorentz, dt, gam[st], zeta_st, store, blo[st], ilo[st], Ny - ilo[st],
-                                                              Ny - blo[st], bflags | sflags, (void *)c)))
-                    return bail(rc);
+                if (int rc = run(g, blo[st], ilo[st], Ny - ilo[st], Ny - blo[st], bflags, c)) return bail(rc);
                 if (st < 2) {
                     if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
                 }
-                for (int f = 0; f < 4; ++f) { T *t = cur[f]; cur[f] = alt[f]; alt[f] = t; t = gn[f]; gn[f] = gm[f]; gm[f] = t; }
-                ++swaps;
+                b.rotate();
             }
             // end of the step: the main stream's next interior launch reads the last boundary rows; the exchange of the new state
             // (its 9 edge rows are exactly those boundary rows) follows them on the comm stream
             r->pending = nullptr;
             if ((e = hipEventRecord(r->ev_comm, c)) != hipSuccess) return bail(hipfail(r, "record", e));
             if ((e = hipStreamWaitEvent(s, r->ev_comm, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            if (int rc = exchange<T>(r, cur, 4, Nx, Ny, Hx, Hy, sy, c)) return bail(rc);
-            r->pending = cur[0];
+            if (int rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c)) return bail(rc);
+            r->pending = b.cur[0];
         }
-        if (state_in_alt) *state_in_alt = swaps & 1;
+        if (state_in_alt) *state_in_alt = b.swaps & 1;
         return SWMHD_OK;
     }
     for (int n = 0; n < nsteps; ++n)
         for (int st = 0; st < 3; ++st) {
-            const T *cq[4] = {cur[0], cur[1], cur[2], cur[3]};
-            const T *cgm[4] = {gm[0], gm[1], gm[2], gm[3]};
-            const bool fs = from_state && st == 1;
-            if (fs) for (int f = 0; f < 4; ++f) cgm[f] = alt[f];
-            const T *const *pgm = st == 0 ? nullptr : cgm;
-            const int store = st == 1 ? 1 : (st == 0 && !from_state ? 1 : 0);
-            const T zeta_st = fs ? zet[1] / gam[0] : zet[st];
-            const int sflags = fs ? SWMHD_GM_IS_PREV_STATE : 0;
-            auto run = [&](int j0, int j1, hipStream_t on, int extra = 0) {
-                return Api<T>::stage(cq, alt, gn, pgm, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, gam[st],
-                                     zeta_st, store, j0, j1, flags | extra | sflags, (void *)on);
-            };
+            const swmhd::Rk3Stage<T> g = b.stage(st, from_state);
             int rc;
             const bool split = r->pending != nullptr;
-            const int jb = split ? Hy : 0, je = split ? Ny - Hy : Ny;
-            const bool timed = r->t0.size() < r->tcap;
-            hipEvent_t a = nullptr, b = nullptr;
-            if (timed) {
-                // (timing-only events: without the system-scope fence a default event performs when it is recorded -- with the comm
-                //  stream's kernels running beside the interior launch that fence cost 16 % of the step, 1.53 vs 1.32 ms)
-                if ((e = hipEventCreateWithFlags(&a, hipEventDisableSystemFence)) != hipSuccess) return bail(hipfail(r, "hipEventCreate", e));
-                if ((e = hipEventCreateWithFlags(&b, hipEventDisableSystemFence)) != hipSuccess) { (void)hipEventDestroy(a); return bail(hipfail(r, "hipEventCreate", e)); }
-                (void)hipEventRecord(a, s);
-            }
             // (interior rows: leave a few workgroup slots free, or the exchange and the strips could not start before it ends)
-            rc = run(jb, je, s, split ? SWMHD_LEAVE_ROOM : 0);
-            if (timed) {
-                if (rc) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-                else { (void)hipEventRecord(b, s); r->t0.push_back(a); r->t1.push_back(b); r->trows.push_back(je - jb); }
-            }
-            if (rc) return bail(rc);
+            if ((rc = split ? run_interior(g, Hy, Ny - Hy, flags | SWMHD_LEAVE_ROOM) : run_interior(g, 0, Ny, flags))) return bail(rc);
             if (split) {   // both strips in one launch: they sit on the exchange -> strips -> exchange chain that bounds a thin slab
-                if ((rc = swmhd::tendencies_rk3_two_ranges<T>(cq, alt, gn, pgm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
-                                                              lorentz, dt, gam[st], zeta_st, store, 0, Hy, Ny - Hy, Ny, flags | sflags, (void *)c)))
-                    return bail(rc);
+                if ((rc = run(g, 0, Hy, Ny - Hy, Ny, flags, c))) return bail(rc);
                 if ((e = hipEventRecord(r->ev_comm, c)) != hipSuccess) return bail(hipfail(r, "record", e));
                 if ((e = hipStreamWaitEvent(s, r->ev_comm, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
             }
-            for (int f = 0; f < 4; ++f) { T *t = cur[f]; cur[f] = alt[f]; alt[f] = t; t = gn[f]; gn[f] = gm[f]; gm[f] = t; }
-            ++swaps;
+            b.rotate();
             r->pending = nullptr;   // the exchange of the OLD state has been consumed; none of the new state is in flight yet
             if (split && (flags & SWMHD_WRAP_X)) {
                 // The rows the exchange sends are exactly the strips' output and (x wrapped on read) no x-halo kernel touches them:
                 // the exchange of the new state follows the strips on the comm stream directly, without a round trip through the
                 // main stream; only the NEXT stage's strips wait for this stage's interior rows.
-                if ((rc = exchange<T>(r, cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
-                r->pending = cur[0];
+                if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
+                r->pending = b.cur[0];
                 if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
                 if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
                 continue;
             }
-            if (!(flags & SWMHD_WRAP_X) && (rc = Api<T>::halo(cur, 4, Nx, Ny, Hx, Hy, sy, SWMHD_HALO_X, (void *)s))) return bail(rc);
+            if (!(flags & SWMHD_WRAP_X) && (rc = swmhd::fill_halo_periodic_multi<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, SWMHD_HALO_X, (void *)s)))
+                return bail(rc);
             if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
             if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            if ((rc = exchange<T>(r, cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
-            r->pending = cur[0];
+            if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
+            r->pending = b.cur[0];
         }
-    if (state_in_alt) *state_in_alt = swaps & 1;
+    if (state_in_alt) *state_in_alt = b.swaps & 1;
     return SWMHD_OK;
 }
 

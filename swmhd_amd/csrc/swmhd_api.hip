@@ -179,38 +179,21 @@ int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx
                 T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt, void *stream) {
     if (!q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
     if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // the driver's halo fill is the periodic one
-    // RungeKutta3 coefficients (Oceananigans TimeSteppers: gamma = 8/15, 5/12, 3/4; zeta = -, -17/60, -5/12)
-    const T gam[3] = {T(8.0 / 15.0), T(5.0 / 12.0), T(3.0 / 4.0)};
-    const T zet[3] = {T(0), T(-17.0 / 60.0), T(-5.0 / 12.0)};
-    T *cur[4], *alt[4], *gn[4], *gm[4];
-    for (int f = 0; f < 4; ++f) {
-        if (!q[f] || !q_alt[f] || !Ga[f] || !Gb[f]) return SWMHD_EINVAL;
-        cur[f] = q[f]; alt[f] = q_alt[f]; gn[f] = Ga[f]; gm[f] = Gb[f];
-    }
-    int swaps = 0;
-    // Fast builds: the second stage takes G- = (U1 - U0) / (dt gamma1) from the two states (SWMHD_GM_IS_PREV_STATE) -- U0 lives in the
-    // very buffer the stage writes U2 to -- so the first stage stores no tendencies: 288 instead of 320 B/cell-step.
-    const bool from_state = !(flags & SWMHD_STRICT);
+    Rk3Buffers<T> b;
+    if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
+    const bool from_state = !(flags & SWMHD_STRICT);   // (common.hpp: Rk3Buffers)
+    // whatever the kernel does not wrap itself
+    const int need = (SWMHD_HALO_X | SWMHD_HALO_Y) & ~(((flags & SWMHD_WRAP_X) ? SWMHD_HALO_X : 0) | ((flags & SWMHD_WRAP_Y) ? SWMHD_HALO_Y : 0));
     for (int n = 0; n < nsteps; ++n)
         for (int st = 0; st < 3; ++st) {
-            const T *cq[4] = {cur[0], cur[1], cur[2], cur[3]};
-            const T *cgm[4] = {gm[0], gm[1], gm[2], gm[3]};
-            const bool fs = from_state && st == 1;
-            if (fs) for (int f = 0; f < 4; ++f) cgm[f] = alt[f];
-            const int store = st == 1 ? 1 : (st == 0 && !from_state ? 1 : 0);
-            int rc = tend_rk3_common<T>(cq, alt, gn, st == 0 ? nullptr : cgm, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation,
-                                        lorentz, dt, gam[st], fs ? zet[1] / gam[0] : zet[st], store, 0, Ny,
-                                        flags | (fs ? SWMHD_GM_IS_PREV_STATE : 0), stream);
+            const Rk3Stage<T> g = b.stage(st, from_state);
+            int rc = tend_rk3_common<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, g.gamma,
+                                        g.zeta, g.store_G, 0, Ny, flags | g.flags, stream);
             if (rc) return rc;
-            for (int f = 0; f < 4; ++f) { T *t = cur[f]; cur[f] = alt[f]; alt[f] = t; t = gn[f]; gn[f] = gm[f]; gm[f] = t; }
-            ++swaps;
-            const int need = (SWMHD_HALO_X | SWMHD_HALO_Y) & ~(((flags & SWMHD_WRAP_X) ? SWMHD_HALO_X : 0) | ((flags & SWMHD_WRAP_Y) ? SWMHD_HALO_Y : 0));
-            if (need) {   // whatever the kernel did not wrap itself
-                rc = halo_multi_common<T>(cur, 4, Nx, Ny, Hx, Hy, sy, need, stream);
-                if (rc) return rc;
-            }
+            b.rotate();
+            if (need && (rc = halo_multi_common<T>(b.cur, 4, Nx, Ny, Hx, Hy, sy, need, stream))) return rc;
         }
-    if (state_in_alt) *state_in_alt = swaps & 1;
+    if (state_in_alt) *state_in_alt = b.swaps & 1;
     return SWMHD_OK;
 }
 
@@ -237,9 +220,15 @@ int tendencies_rk3_two_ranges(const T *const *q, T *const *qnew, T *const *Gn, c
     return tend_rk3_common<T>(q, qnew, Gn, Gm, Nx, Ny, Hx, Hy, (int64_t)sy, dx, dy, grav, fcor, formulation, lorentz, dt, gamma, zeta,
                               store_G, j0, j1, flags, stream, j0b, j1b);
 }
+template <typename T>
+int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which, void *stream) {
+    return halo_multi_common<T>(f, nf, Nx, Ny, Hx, Hy, (int64_t)sy, which, stream);
+}
+static_assert(GM_IS_PREV_STATE == SWMHD_GM_IS_PREV_STATE, "common.hpp mirrors swmhd.h");
 #define SW_INST(T)                                                                                                                   \
     template int tendencies_rk3_two_ranges<T>(const T *const *, T *const *, T *const *, const T *const *, int, int, int, int, long, T, \
-                                              T, T, T, int, int, T, T, T, int, int, int, int, int, int, void *);
+                                              T, T, T, int, int, T, T, T, int, int, int, int, int, int, void *);                      \
+    template int fill_halo_periodic_multi<T>(T *const *, int, int, int, int, int, long, int, void *);
 SW_INST(double)
 SW_INST(float)
 #undef SW_INST

@@ -17,14 +17,6 @@
 // (needs <type_traits>)
 // Included from tendency_fast.hip inside namespace swmhd { namespace { ... } } after sw_device.inc / lorentz_device.inc.
 
-// (SW_EXPERIMENT_NO_BARRIER builds a timing-only variant without workgroup barriers -- results are wrong; it measured
-//  the barriers' cost at ~0, DESIGN.md 4.1.)
-#ifdef SW_EXPERIMENT_NO_BARRIER
-#define SW_TEND_SYNC() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
-#else
-#define SW_TEND_SYNC() __syncthreads()
-#endif
-
 // Memory operations are straight-line code (buffer stores with out-of-range offsets for lanes that own no output column,
 // compile-time stage MODE, explicit exact wait): see common.hpp.  Before: 25 % of wave time in s_waitcnt
 // (profiles/r01/tendency_pmc_sq.json), every wave waiting for the stores it had just issued.
@@ -35,10 +27,8 @@
 // (Round 1 filled the windows with six full warm-up iterations per segment: twelve barriers, twelve x-flux reconstructions, six
 // dependent HBM round trips -- 4-8 % of the launch on 1024^2 grids and 4096 x 512 slabs.)
 //
-// The row loop is unrolled by TWO with the windows one element longer than a stencil: the first body works on elements [0, n) and
-// has its prefetched row land in element n, the second works on [1, n] and lands its row in element 0 (dead by then), and ONE
-// rotation by two per pair of rows replaces two shifts by one (30 v_mov_b64 per two rows instead of 2 x 34: 6 % of the kernel's
-// VALU instructions were window moves).
+// The windows are one element longer than a stencil: each row works on elements [0, n) and has its prefetched row land in element n;
+// one shift by one per row follows.
 // Rows [J0, J1) of segment `seg`: LY-row segments of the launch's row range, then those of its optional second range (the two
 // boundary zones of a slab in one launch, TendArgs::j0b/j1b).
 template <typename TA> __device__ __forceinline__ void segment_rows(const TA &a, int seg, int LY, int &J0, int &J1) {
@@ -79,8 +69,8 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     const Geo<T> g{a.dx, a.dy, a.rdx, a.rdy};
     const bool col_ok = (c >= XH) && (c < NT - XH) && (gx < a.Nx);
 
-    // register windows of this lane's column, one element longer than the stencils (see above).  With offset OFF (0 in the first
-    // body of a pair, 1 in the second) element k+OFF holds row jo-3+k (uw) / jo-2+k (the others).
+    // register windows of this lane's column, one element longer than the stencils (see above): element k holds row jo-3+k (uw) /
+    // jo-2+k (the others).
     // zw / svw: vorticity zeta(c, j) and v(c-1, j) + v(c, j) at the vorticity points of rows jo-2 .. jo+3 -- computed ONCE per incoming row
     // (round 2 kept the left neighbour's v instead and rebuilt all six of each every iteration: ~25 instructions per row)
     T uw[8], vw[7], zw[7], svw[7], hw[7], aw[7];
@@ -126,7 +116,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             a_wm = LD(a.A, ro[2] + colm); a_em = LD(a.A, ro[2] + colp);           // A(c-1, J0-1), A(c+1, J0-1)
             a_wo = LD(a.A, ro[3] + colm); a_eo = LD(a.A, ro[3] + colp);           // A(c-1, J0),   A(c+1, J0)
         }
-        // the windows as the first iteration (OFF = 0, output row jo = J0) expects them
+        // the windows as the first iteration (output row jo = J0) expects them
 #pragma unroll
         for (int k = 0; k < 7; ++k) uw[k] = pu[k];
 #pragma unroll
@@ -155,12 +145,10 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         }
     }
 
-    // One output row.  off_tag = integral_constant<int, OFF>: which half of a pair this is (where the windows start, where the
-    // prefetched row lands).
-    auto body = [&](const int it, auto off_tag) {
-        constexpr int OFF = decltype(off_tag)::value;
-        constexpr int LU = OFF == 0 ? 7 : 0, LW = OFF == 0 ? 6 : 0;   // landing elements of the prefetched row
-        T *const U = uw + OFF, *const V = vw + OFF, *const Z = zw + OFF, *const SV = svw + OFF, *const Hh = hw + OFF, *const Aa = aw + OFF;
+    // One output row.
+    auto body = [&](const int it) {
+        constexpr int LU = 7, LW = 6;   // landing elements of the prefetched row
+        T *const U = uw, *const V = vw, *const Z = zw, *const SV = svw, *const Hh = hw, *const Aa = aw;
         const int jr = J0 - 3 + it;   // newest row in the windows
         const int jo = jr - 3;        // output row of this iteration
         {   // prefetch row jr+1 straight into the free window elements
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         RHA[s4o][lc][1] = Hh[2];  // h(c, jo)
         RHA[s4p][lc][0] = Aa[3];  // A(c, jo+1)
         Rvn[0][lc] = V[5];        // v(c, jr)
-        SW_TEND_SYNC();
+        __syncthreads();
 
         // ---- P2: left neighbour's newest v; centre B at row jo+1; Kh and x-face fluxes at row jo ----
         {   // the newest row of the vorticity windows
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             RFh[0][lc] = uadv * weno5_upwind_ordered<T>(qh, pos);
             RFA[0][lc] = uadv * weno5_upwind_ordered<T>(qa, pos);
         }
-        SW_TEND_SYNC();
+        __syncthreads();
         if constexpr (FUSE && HAS_GM) {   // G- of the output row: needed at the very end, ~2/3 of an iteration away
             const unsigned og = rowb + colb;
             gm0 = LD(a.Gm[0], og); gm1 = LD(a.Gm[1], og); gm2 = LD(a.Gm[2], og); gm3 = LD(a.Gm[3], og);
@@ -280,17 +268,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         constexpr int YOUNGER = ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0);
         wait_vmem_all_but<YOUNGER>();
     };
-    // after a pair of rows: rotate the windows by two (the row that landed in element 0 becomes the newest)
-    auto rotate2 = [&]() {
-        const T u0 = uw[0], v0 = vw[0], h0 = hw[0], a0 = aw[0];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) uw[k] = uw[k + 2];
-        uw[6] = u0;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) { vw[k] = vw[k + 2]; zw[k] = zw[k + 2]; svw[k] = svw[k + 2]; hw[k] = hw[k + 2]; aw[k] = aw[k + 2]; }
-        vw[5] = v0; hw[5] = h0; aw[5] = a0;
-    };
-    // after a single row (odd tail): shift by one
+    // after each row: shift the windows by one
     auto shift1 = [&]() {
 #pragma unroll
         for (int k = 0; k < 7; ++k) uw[k] = uw[k + 1];
@@ -303,33 +281,15 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     const int niter = (J1 - J0) + 6;
     const ProgressPriority prio(niter);
     int it = 6;
-    // The pair-unrolled loop (one window rotation per TWO rows: 569 instead of 580 VALU instructions per row) needs a few registers
-    // more than the 168 a third wave per SIMD leaves: 8-52 bytes of scratch per lane depending on the stage variant.  Round 3, same
-    // call, 4096^2 (gpurun_out -> profiles/r03/ab_rotation.txt): with the vorticity windows in place the pair loop on the variants that
-    // read G- (MODE 3, 7: 8 / 12 B scratch) and the plain loop everywhere (no scratch at all) are equal within the noise -- 388.7 /
-    // 495.8 / 406.5 vs 392.8 / 494.5 / 407.4 us per stage -- while 28 B of scratch cost the last stage 20 % (493 vs 408 us).  Default:
-    // the plain loop for every variant (SW_ROTATE_MODES = 0); the pair loop stays as a build knob (bit MODE).
-#ifndef SW_ROTATE_MODES
-#define SW_ROTATE_MODES 0x00   /* bit MODE set: that stage variant runs the pair-unrolled loop */
-#endif
-    constexpr bool ROTATE = sizeof(T) == 8 && ((SW_ROTATE_MODES >> MODE) & 1);   // (fp32: the pair needs 130 VGPRs, one step above its fourth wave per SIMD)
-    if constexpr (ROTATE) {
-        (void)shift1;
-        for (; it + 1 < niter; it += 2) {
-            prio.at(it);
-            body(it, std::integral_constant<int, 0>{});
-            prio.at(it + 1);
-            body(it + 1, std::integral_constant<int, 1>{});
-            rotate2();
-        }
-        if (it < niter) body(it, std::integral_constant<int, 0>{});   // odd number of rows: the last one alone
-    } else {
-        (void)rotate2;
-        for (; it < niter; ++it) {
-            prio.at(it);
-            body(it, std::integral_constant<int, 0>{});
-            shift1();
-        }
+    // (A pair-unrolled loop -- one window rotation per TWO rows, 569 instead of 580 VALU instructions per row -- needs a few registers
+    // more than the 168 a third wave per SIMD leaves: 8-52 bytes of scratch per lane depending on the stage variant.  Round 3, same call,
+    // 4096^2 (profiles/r03/ab_rotation.txt): on the variants that read G- (MODE 3, 7: 8 / 12 B scratch) it equalled the plain loop within
+    // the noise -- 388.7 / 495.8 / 406.5 vs 392.8 / 494.5 / 407.4 us per stage -- while 28 B of scratch cost the last stage 20 % (493 vs
+    // 408 us).  It was removed after that measurement.)
+    for (; it < niter; ++it) {
+        prio.at(it);
+        body(it);
+        shift1();
     }
 }
 
@@ -341,17 +301,12 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
 //   x-face fluxes (huu @ccc, huv @ffc, tracer flux, Lorentz F1/G1) are computed once in P2 and shared through LDS;
 //   y-face fluxes (hvu, hvv, tracer flux, Lorentz F2/G2) are computed once and carried in registers.
 // ====================================================================================================================
-#ifndef SW_P2_FENCE
-#define SW_P2_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 // Workgroups of 256 per CU (= waves per SIMD) the conservative kernel is compiled for, per stage variant: bit MODE of the mask set =
 // 3, else 2.  At 168 VGPRs the variants need 0 (MODE 7), 12 (MODE 5), 20-60 (others) bytes of scratch per lane.  Measured on MI355X
 // in one call (4096^2 step / 8192x1024 slab step): no variant at 3: 1.514 / 0.758 ms; MODE 7: 1.474 / 0.728; MODE 7+5: 1.452 / 0.721;
 // all fused stages: 1.504 / 0.747 -- a third workgroup pays only where (almost) nothing spills.
-#ifndef SW_CONS_W3_MODES
-#define SW_CONS_W3_MODES ((1 << 7) | (1 << 5) | (1 << 4))
-#endif
-constexpr int cons_minwaves(int mode, int elem_size) { return elem_size == 4 ? 3 : (((SW_CONS_W3_MODES >> mode) & 1) ? 3 : 2); }
+constexpr int CONS_W3_MODES = (1 << 7) | (1 << 5) | (1 << 4);
+constexpr int cons_minwaves(int mode, int elem_size) { return elem_size == 4 ? 3 : (((CONS_W3_MODES >> mode) & 1) ? 3 : 2); }
 template <typename T, int LOR, int NT, int MODE>   // MODE as in k_tendency_vi_march
 __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_tendency_cons_march(TendArgs<T> a, int nstrips, int nseg, int LY) {
     constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0;
@@ -524,7 +479,7 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
             RBy[0][lc] = byw[3];
             RHBy[(jo + 1) & 1][lc] = hby_pub;  // hBy(c, jo+1)
         }
-        SW_TEND_SYNC();
+        __syncthreads();
 
         // ---- P2: x-direction fluxes of row jo (once per face) + Lorentz faces of row jo+2 ----
         const T *su = Ruh[r3o], *sv0 = Rvh[r3o], *sv1 = Rvh[r3p], *sh0 = Rh[r3o], *sh1 = Rh[r3p], *sa0 = RA[jo & 3];
@@ -564,7 +519,7 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
                 RUe[0][lc] = uadv * rhxf;
             }
         }
-        SW_P2_FENCE();
+        __builtin_amdgcn_sched_barrier(0);   // (scheduling fence: P2's phases are scheduled one after the other)
         if constexpr (LOR == 2) {
             // Lorentz x-direction fluxes of row jo from the face rows published in P1 (reference :38-60, :86-108)
             const T *bx0 = RBx[0], *hbx0 = RHBx[jo & 1], *hbxm = RHBx[(jo + 1) & 1], *by0 = RBy[0];
@@ -572,7 +527,7 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
                                                          right3<T>(bx0[lc], bx0[lc + 1], bx0[lc + 2]));
             RG1[0][lc] = g.dy * upwind_biased_product<T>(T(0.5) * (hbxm[lc] + hbx0[lc]), left3<T>(by0[lc - 2], by0[lc - 1], by0[lc]),
                                                          right3<T>(by0[lc - 1], by0[lc], by0[lc + 1]));
-            SW_P2_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             // face quantities of row jf = jo+2 (reference :134-148), once per face
             const T *am = RA[(jf - 1) & 3], *a0 = RA[jf & 3], *ap = RA[(jf + 1) & 3], *shf = Rh[r3m];
             const T m = -(T(0.25) * rdy) * ((ap[lc - 1] - am[lc - 1]) + (aw[5] - aw[3]));
@@ -585,7 +540,7 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
             hby_pub = n;                                               // hBy(c, jo+2): published by the next iteration
             hbx_pub = bxw[3] * (T(0.5) * (sh1[lc - 1] + hw[2]));         // hBx(c, jo+1) = Bx * face-averaged h
         }
-        SW_TEND_SYNC();
+        __syncthreads();
         if constexpr (STEADY && FUSE && HAS_GM) {   // G- of the output row: needed at the very end of the iteration
             const unsigned og = rowb + colb;
             gm0 = LD(a.Gm[0], og); gm1 = LD(a.Gm[1], og); gm2 = LD(a.Gm[2], og); gm3 = LD(a.Gm[3], og);

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march_pk(TendArgs<float> 
         W(RH[jo & 1], Hh[2]);
         W(RA[s4p], Aa[3]);
         W(Rvn[0], V[5]);
-        SW_TEND_SYNC();
+        __syncthreads();
 
         // ---- P2 ----
         VL[5] = P(Rvn[0], -1);
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march_pk(TendArgs<float> 
             W(RFh[0], upwind_weno<T>(uadv, qh));
             W(RFA[0], upwind_weno<T>(uadv, qa));
         }
-        SW_TEND_SYNC();
+        __syncthreads();
         if constexpr (FUSE && HAS_GM) {
             const unsigned og = rowb + colb;
             gm0 = LD(a.Gm[0], og); gm1 = LD(a.Gm[1], og); gm2 = LD(a.Gm[2], og); gm3 = LD(a.Gm[3], og);

@@ -296,12 +296,11 @@ constexpr long SW_MARCH_MIN_CELLS = 330000L;
 #if !SWMHD_STRICT
 // Geometry of the marching tendency kernels.  Vector-invariant kernel: <= 168 VGPRs and 0.19 KB of LDS per lane -> 12 waves per
 // CU, i.e. 3 / 6 workgroups of 256 / 128 threads.  Conservative kernel: 2 workgroups of 256 per CU (69 KB LDS).
-// Knobs (read once): SWMHD_T_LY rows per segment, SWMHD_T_NT workgroup size.
+// Knobs (read once): SWMHD_T_LY rows per segment, SWMHD_T_NT workgroup size (128 or 256).
 // Packed-fp32 kernel (tendency_pk_kernels.inc): vector-invariant model, x read with periodic wrapping, even Nx.  256 lanes = 512
-// columns per strip, 504 of them output; 3 workgroups per CU (<= 168 VGPRs, 46 KB LDS).  SWMHD_T_NOPK=1 keeps the unpacked kernel (A/B).
+// columns per strip, 504 of them output; 3 workgroups per CU (<= 168 VGPRs, 46 KB LDS).
 static bool tendency_uses_packed_fp32(int Nx, int formulation, int wrap) {
-    static int nopk_cache = 0;
-    return formulation == 1 && (wrap & 1) && (Nx % 2 == 0) && Nx >= 8 && env_knob("SWMHD_T_NOPK", nopk_cache) == 0;
+    return formulation == 1 && (wrap & 1) && (Nx % 2 == 0) && Nx >= 8;
 }
 static MarchGeometry packed_fp32_geometry(int Nx, int rows, int leave_room) {
     static int ly_cache = 0;
@@ -325,14 +324,14 @@ static MarchGeometry tendency_march_geometry(int Nx, int rows, int formulation, 
     const int force_ly = env_knob("SWMHD_T_LY", ly_cache), force_nt = env_knob("SWMHD_T_NT", nt_cache);
     if (formulation == 1) {
         // (384-thread workgroups cover 4096 columns with 3 % fewer lanes -- 11 strips instead of 17 -- but measured 37 % SLOWER on
-        //  MI355X, 1.75 vs 1.275 ms per step: six waves per barrier leave each SIMD too little to overlap; selectable with SWMHD_T_NT)
-        static const int nts[3] = {256, 128, 384}, wgs64[3] = {3, 6, 2}, wgs32[3] = {4, 8, 2};   // fp32: <= 128 VGPRs, 4 waves per SIMD
-        return march_geometry(Nx, rows, 3, nts, elem_size == 8 ? wgs64 : wgs32, force_nt == 384 ? 3 : 2, 6, leave_room != 0, force_nt, force_ly);
+        //  MI355X, 1.75 vs 1.275 ms per step: six waves per barrier leave each SIMD too little to overlap; removed after that measurement)
+        static const int nts[2] = {256, 128}, wgs64[2] = {3, 6}, wgs32[2] = {4, 8};   // fp32: <= 128 VGPRs, 4 waves per SIMD
+        return march_geometry(Nx, rows, 3, nts, elem_size == 8 ? wgs64 : wgs32, 2, 6, leave_room != 0, force_nt, force_ly);
     }
     // (128-thread workgroups where they waste >= 5 % fewer lanes in the last strip: 1024 columns = 5 strips of 250 or 9 of 122)
     const int w = cons_minwaves(mode, elem_size);                          // per stage variant (tendency_march_kernels.inc)
     const int nts[2] = {256, 128}, wgs[2] = {w, 2 * w};
-    return march_geometry(Nx, rows, 3, nts, wgs, 2, 6, leave_room != 0, force_nt == 384 ? 0 : force_nt, force_ly);
+    return march_geometry(Nx, rows, 3, nts, wgs, 2, 6, leave_room != 0, force_nt, force_ly);
 }
 #endif
 
@@ -446,7 +445,6 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
 #define SW_VI_MARCH(MODE_)                                                                                                  \
             case MODE_:                                                                                                         \
                 if (mg.nt == 128) SW_VI_GO(128, MODE_);                                                                         \
-                else if (mg.nt == 384) SW_VI_GO(384, MODE_);                                                                    \
                 else SW_VI_GO(256, MODE_);                                                                                      \
                 break;
             switch (mode) { SW_VI_MARCH(4) SW_VI_MARCH(5) SW_VI_MARCH(1) SW_VI_MARCH(7) SW_VI_MARCH(3) default: return hipErrorInvalidValue; }

@@ -16,10 +16,18 @@ from .fields import Field, _SFX, _stream_ptr
 from .grid import Center, Face
 
 VectorInvariantFormulation, ConservativeFormulation = "VectorInvariant", "Conservative"
-import os as _os
-_FROM_STATE = _os.environ.get("SWMHD_FROM_STATE", "1") != "0"      # (A/B knob for the Python-driven stages; the C step drivers always use it in fast builds)
 RK3_GAMMA = (8.0 / 15.0, 5.0 / 12.0, 3.0 / 4.0)
 RK3_ZETA = (0.0, -17.0 / 60.0, -5.0 / 12.0)
+
+
+def rk3_stage(stage, from_state):
+    """(gamma, zeta, store_G, G- from the previous state) of RK3 stage 0, 1 or 2 -- the schedule of the C step drivers (common.hpp
+    Rk3Buffers).  from_state (fast builds, periodic grids): the second stage takes G- = (U1 - U0) / (dt gamma1) from the two states --
+    U0 is still in the buffer that stage writes U2 to -- so the first stage stores no tendencies (swmhd.h SWMHD_GM_IS_PREV_STATE;
+    288 instead of 320 B/cell-step)."""
+    fs = from_state and stage == 1
+    store = 1 if stage == 1 or (stage == 0 and not from_state) else 0
+    return RK3_GAMMA[stage], RK3_ZETA[1] / RK3_GAMMA[0] if fs else RK3_ZETA[stage], store, fs
 
 
 def loopback_rings(nranks, timeout_s=60.0):
@@ -129,11 +137,6 @@ class ShallowWaterModel:
         with torch.cuda.device(dev):
             rc = self._L.swmhd_ring_create(ctypes.byref(ring), rccl, self.decomp.world_size, self.decomp.rank,
                                            (ctypes.c_ubyte * _lib.RING_ID_BYTES).from_buffer_copy(raw))
-        import os
-        if os.environ.get("SWMHD_TEST_RING_CREATE_FAIL_RANK") == str(self.decomp.rank):     # tests: a rank whose communicator failed
-            if rc == 0:
-                self._L.swmhd_ring_destroy(ring)
-            rc = 4
         # every rank learns whether ALL communicators exist: a rank that failed raises, and so do its peers (they destroy theirs
         # first) -- otherwise they would block in the first exchange until the launcher's deadline
         worst = agree_rc(rc, self.group, dev)
@@ -288,22 +291,18 @@ class ShallowWaterModel:
         q = _lib.ptr_array([f.ptr for f in self._raw_fields])
         qn = _lib.ptr_array([self._alt[n].ptr for n in self.names])
         Gn = _lib.ptr_array([f.ptr for f in self.Gn])
-        Gm = _lib.ptr_array([f.ptr for f in self.Gm]) if stage > 0 else None
-        # Fast periodic builds: the second stage takes G- = (U1 - U0) / (dt gamma1) from the two states -- U0 is still in the buffer this
-        # stage writes U2 to -- so the first stage stores no tendencies (swmhd.h SWMHD_GM_IS_PREV_STATE; 288 instead of 320 B/cell-step).
-        from_state = not self.strict and not any(self._bounded) and _FROM_STATE
-        zeta, store = RK3_ZETA[stage], (1 if stage < 2 else 0)
-        if from_state and stage == 0:
-            store = 0
-        if from_state and stage == 1:
-            Gm, zeta, extra_flags = qn, RK3_ZETA[1] / RK3_GAMMA[0], extra_flags | _lib.GM_IS_PREV_STATE
+        gamma, zeta, store, prev_state = rk3_stage(stage, not self.strict and not any(self._bounded))
+        if prev_state:
+            Gm, extra_flags = qn, extra_flags | _lib.GM_IS_PREV_STATE
+        else:
+            Gm = _lib.ptr_array([f.ptr for f in self.Gm]) if stage > 0 else None
         f = getattr(self._L, f"swmhd_tendencies_rk3_{self.sfx}")
         timed = self.tendency_events is not None and 2 * (j1 - j0) > g.Ny    # whole grid, or the interior launch of a slab
         if timed:
             e0, e1 = _lib.TimingEvent(), _lib.TimingEvent()
             e0.record()
         rc = f(q, qn, Gn, Gm, g.Nx, g.Ny, g.Hx, g.Hy, self._raw_fields[0].stride_y, g.dx, g.dy, self.g, self.f, self.form_code,
-               self.lorentz_code, dt, RK3_GAMMA[stage], zeta, store, j0, j1,
+               self.lorentz_code, dt, gamma, zeta, store, j0, j1,
                self._flags | self._rwrap | extra_flags, _stream_ptr())
         if timed:
             e1.record()
@@ -311,32 +310,34 @@ class ShallowWaterModel:
         _lib.check(rc, "swmhd_tendencies_rk3")
 
     # --- time_step!(model, dt): RungeKutta3 ------------------------------------------------------------------
-    def _ring_steps(self, dt, n):
-        """n RK3 steps of this slab through the native ring driver (swmhd_ring_step_rk3_*): one C call enqueues every launch."""
+    def _native_steps(self, dt, n):
+        """n RK3 steps in ONE C call that enqueues every launch: the native ring driver (swmhd_ring_step_rk3_*) on a slab, the step
+        driver (swmhd_step_rk3_*) on one GPU."""
         import ctypes
-        gr = self.grid
-        swapped = ctypes.c_int(0)
-        if self._halo_stale and not (self._rwrap & _lib.WRAP_X):
+        gr, ring = self.grid, self._ring is not None
+        wrap = self._rwrap & _lib.WRAP_X if ring else self._rwrap     # (a slab's y halos come from the ring)
+        if ring and self._halo_stale and not wrap:
             self.update_state()
-        q = _lib.ptr_array([f.ptr for f in self._raw_fields])
-        qa = _lib.ptr_array([self._alt[nm].ptr for nm in self.names])
-        Ga = _lib.ptr_array([f.ptr for f in self.Gn])
-        Gb = _lib.ptr_array([f.ptr for f in self.Gm])
-        f = getattr(self._L, f"swmhd_ring_step_rk3_{self.sfx}")
-        rc = f(self._ring, q, qa, Ga, Gb, gr.Nx, gr.Ny, gr.Hx, gr.Hy, self._raw_fields[0].stride_y, gr.dx, gr.dy, self.g, self.f,
-               self.form_code, self.lorentz_code, dt, n, self._flags | (self._rwrap & _lib.WRAP_X), ctypes.byref(swapped), _stream_ptr())
-        self._ring_check(rc, "swmhd_ring_step_rk3")
+        swapped = ctypes.c_int(0)
+        args = (_lib.ptr_array([f.ptr for f in self._raw_fields]), _lib.ptr_array([self._alt[nm].ptr for nm in self.names]),
+                _lib.ptr_array([f.ptr for f in self.Gn]), _lib.ptr_array([f.ptr for f in self.Gm]), gr.Nx, gr.Ny, gr.Hx, gr.Hy,
+                self._raw_fields[0].stride_y, gr.dx, gr.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
+                self._flags | wrap, ctypes.byref(swapped), _stream_ptr())
+        if ring:
+            self._ring_check(getattr(self._L, f"swmhd_ring_step_rk3_{self.sfx}")(self._ring, *args), "swmhd_ring_step_rk3")
+        else:
+            _lib.check(getattr(self._L, f"swmhd_step_rk3_{self.sfx}")(*args), "swmhd_step_rk3")
         if swapped.value:
             self._state, self._alt = self._alt, self._state
             self.Gn, self.Gm = self.Gm, self.Gn
-        if n > 0 and (self._rwrap & _lib.WRAP_X):
-            self._halo_stale = True       # x halos were not filled; the y exchange of the final state is in flight (see _join)
+        if n > 0 and wrap:
+            self._halo_stale = True       # the wrapped halos were not filled (a slab: the y exchange of the final state is in flight, see _join)
         self.clock_time += n * dt
         self.iteration += n
 
     def time_step(self, dt):
         if self._ring is not None:
-            return self._ring_steps(dt, 1)
+            return self._native_steps(dt, 1)
         g, H = self.grid, 3          # strips and per-stage exchange: the stencil's reach, whatever the grid's halo depth
         multi = self.decomp.ring
         overlap = multi and self.overlap and self._comm_stream is not None and g.Ny > 2 * H
@@ -426,28 +427,8 @@ class ShallowWaterModel:
             self._driver_steps(dt, n)
 
     def _driver_steps(self, dt, n):
-        if self._ring is not None:
-            return self._ring_steps(dt, n)
-        if not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded):
-            gr = self.grid
-            import ctypes
-            swapped = ctypes.c_int(0)
-            q = _lib.ptr_array([f.ptr for f in self._raw_fields])
-            qa = _lib.ptr_array([self._alt[nm].ptr for nm in self.names])
-            Ga = _lib.ptr_array([f.ptr for f in self.Gn])
-            Gb = _lib.ptr_array([f.ptr for f in self.Gm])
-            f = getattr(self._L, f"swmhd_step_rk3_{self.sfx}")
-            rc = f(q, qa, Ga, Gb, gr.Nx, gr.Ny, gr.Hx, gr.Hy, self._raw_fields[0].stride_y, gr.dx, gr.dy, self.g, self.f, self.form_code,
-                   self.lorentz_code, dt, n, self._flags | self._rwrap, ctypes.byref(swapped), _stream_ptr())
-            _lib.check(rc, "swmhd_step_rk3")
-            if swapped.value:
-                self._state, self._alt = self._alt, self._state
-                self.Gn, self.Gm = self.Gm, self.Gn
-            if n > 0 and self._rwrap:
-                self._halo_stale = True
-            self.clock_time += n * dt
-            self.iteration += n
-            return
+        if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)):
+            return self._native_steps(dt, n)
         for _ in range(n):
             self.time_step(dt)
 
