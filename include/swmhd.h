@@ -80,7 +80,14 @@ extern "C" {
                                     stepped from with G- alone (U = U- + dt gamma- G-), not G- itself; pass zeta / gamma- as `zeta`; the kernel
                                     forms Unew = U + dt gamma G + zeta (U - U-).  Gm may then alias qnew (each cell reads its own U- before it
                                     writes Unew): the first RK3 stage need not store its tendencies at all (32 B/cell less HBM traffic per
-                                    step).  Results differ from the G- form by less than one ulp of U.  The step drivers use it.            */
+                                    step).  Results differ from the G- form by less than one ulp of U.                                      */
+#define SWMHD_RK3_ANCHOR 2048 /* swmhd_tendencies_rk3 only (fast builds, periodic): RK3 in anchor form.  With gamma1 + zeta2 = 1/4 and zeta3 = -gamma2
+                                 (Oceananigans' coefficients) a step is exactly U1 = U0 + dt gamma1 G0, W = U0 + (dt/4) G0, U2 = W + dt gamma2 G1,
+                                 U3 = W + dt gamma3 G2.  Gm == NULL (first stage): qnew = q + dt gamma Gn' and Gn[f] RECEIVES W = q + dt zeta Gn'
+                                 (pass zeta = gamma1 + zeta2 = 1/4; Gn' is the tendency, not stored).  Gm set (later stages): Gm[f] holds W and
+                                 qnew = Gm + dt gamma Gn'; zeta is unused and Gn is not written (it may alias Gm).  store_G is ignored.  Every
+                                 stage moves 96 B/cell in fp64.  Results differ from the G- form by rounding only.  The step drivers use it.
+                                 Refused with SWMHD_STRICT or SWMHD_BOUNDED_* (SWMHD_ENOTSUP) and with SWMHD_GM_IS_PREV_STATE (SWMHD_EINVAL). */
 #define SWMHD_LEAVE_ROOM 64   /* tendency entry points: size the row-marching grid ~5 % short of filling the chip, so that kernels of
                                  another stream (the ring's halo exchange and boundary strips) can start while it runs                */
 

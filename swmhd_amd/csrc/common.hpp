@@ -82,18 +82,26 @@ struct TendArgs {
                           // Gm = previous state (gm_prev).  The stage variant that reads Gm AND stores G (the second RK3 stage) uses this form,
                           // so that one compiled kernel serves both operands without a branch (a branch there cost the other variants their
                           // register allocation: 80 B of scratch).
+    int anchor;           // RK3 in anchor form (RK3_ANCHOR below): first stage (first != 0) stores Unew = U + dtg G and W = U + dtw G, the latter
+                          // through G1..GA; later stages read W from Gm and store Unew = W + dtg G.  No G store in either.
+    T dtw;                // dt * (gamma1 + zeta2), formed on the host like dtg (first anchored stage only)
 };
 // ---- RK3 stage schedule of the step drivers (step_common in swmhd_api.hip, both schedules of ring_step in ring.hip) --------------
-// Oceananigans' RungeKutta3 (TimeSteppers): gamma = 8/15, 5/12, 3/4; zeta = -, -17/60, -5/12.  Fast builds (from_state): the second
-// stage takes G- = (U1 - U0) / (dt gamma1) from the two states (GM_IS_PREV_STATE, zeta2 / gamma1) -- U0 lives in the very buffer the
-// stage writes U2 to -- so the first stage stores no tendencies: 288 instead of 320 B/cell-step.
+// Oceananigans' RungeKutta3 (TimeSteppers): gamma = 8/15, 5/12, 3/4; zeta = -, -17/60, -5/12.  Since gamma1 + zeta2 = 1/4 and
+// zeta3 = -gamma2, the step is exactly
+//     U1 = U0 + dt gamma1 G0,   W = U0 + (dt/4) G0,   U2 = W + dt gamma2 G1,   U3 = W + dt gamma3 G2
+// with ONE stored operand, the anchor W.  Fast periodic builds run it in that form (RK3_ANCHOR): stage 1 reads U0 and writes U1 and
+// W, stages 2 and 3 read their state and W and write the new state -- 96 B/cell in every stage (288 B/cell-step, as the from-state
+// G- form had, but split 64 / 128 / 96 there).  Strict builds and Bounded grids keep the classic G- form (store_tendencies!).
 constexpr int GM_IS_PREV_STATE = 1024;   // = SWMHD_GM_IS_PREV_STATE (swmhd.h, which the kernel sources do not include)
+constexpr int RK3_ANCHOR = 2048;         // = SWMHD_RK3_ANCHOR
+constexpr double RK3_ANCHOR_WEIGHT = 0.25;   // gamma1 + zeta2 = 8/15 - 17/60
 template <typename T>
 struct Rk3Stage {
-    T gamma, zeta;
+    T gamma, zeta;        // anchor form: zeta = gamma1 + zeta2 in the first stage (the weight of W), unused later
     int store_G;
-    const T *const *Gm;   // G- operand: none (first stage), the G- buffers, or the new-state buffers, which still hold the previous state
-    int flags;            // GM_IS_PREV_STATE for the from-state stage, else 0
+    const T *const *Gm;   // G- operand: none (first stage), the G- buffers, or (anchor form) the buffers that hold W
+    int flags;            // RK3_ANCHOR for the anchor form, else 0
 };
 template <typename T>
 struct Rk3Buffers {
@@ -106,12 +114,13 @@ struct Rk3Buffers {
         }
         return true;
     }
-    Rk3Stage<T> stage(int st, bool from_state) const {
+    // Stage st of a step.  Anchor form: the first stage writes W into gn; rotate() then moves that buffer to gm (read by the second
+    // stage) and back to gn (read by the third) -- the G roles still swap once per stage, so two steps restore them.
+    Rk3Stage<T> stage(int st, bool anchor) const {
         const T gam[3] = {T(8.0 / 15.0), T(5.0 / 12.0), T(3.0 / 4.0)};
         const T zet[3] = {T(0), T(-17.0 / 60.0), T(-5.0 / 12.0)};
-        const bool fs = from_state && st == 1;
-        return {gam[st], fs ? zet[1] / gam[0] : zet[st], (st == 1 || (st == 0 && !from_state)) ? 1 : 0,
-                st == 0 ? nullptr : (fs ? alt : gm), fs ? GM_IS_PREV_STATE : 0};
+        if (anchor) return {gam[st], st == 0 ? T(RK3_ANCHOR_WEIGHT) : T(0), 0, st == 0 ? nullptr : (st == 1 ? gm : gn), RK3_ANCHOR};
+        return {gam[st], zet[st], st < 2 ? 1 : 0, st == 0 ? nullptr : gm, 0};   // (the last stage's G is never read)
     }
     // after a stage: the new state becomes current, and G- <- G (store_tendencies!: pointer swaps)
     void rotate() {

@@ -251,7 +251,7 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
         r->pending = nullptr;
     }
     hipError_t e;
-    const bool from_state = !(flags & SWMHD_STRICT);   // fast builds: no tendency store in the first stage (common.hpp: Rk3Buffers)
+    const bool anchor = !(flags & SWMHD_STRICT);   // fast builds: the anchor form, 96 B/cell in every stage (common.hpp: Rk3Buffers)
     // whatever the caller enqueued on its stream so far precedes everything this call puts on the comm stream
     if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return hipfail(r, "record", e);
     if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return hipfail(r, "wait", e);
@@ -302,7 +302,7 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
         const int bflags = flags | ((!(flags & (SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL)) && Nx >= 1024) ? SWMHD_MARCH_KERNEL : 0);
         for (int n = 0; n < nsteps; ++n) {
             for (int st = 0; st < 3; ++st) {
-                const swmhd::Rk3Stage<T> g = b.stage(st, from_state);
+                const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
                 if (int rc = run_interior(g, ilo[st], Ny - ilo[st], flags | SWMHD_LEAVE_ROOM)) return bail(rc);
                 if (st < 2) {   // the next boundary launch reads rows of this interior launch
                     if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
@@ -327,7 +327,7 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
     }
     for (int n = 0; n < nsteps; ++n)
         for (int st = 0; st < 3; ++st) {
-            const swmhd::Rk3Stage<T> g = b.stage(st, from_state);
+            const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
             int rc;
             const bool split = r->pending != nullptr;
             // (interior rows: leave a few workgroup slots free, or the exchange and the strips could not start before it ends)

@@ -103,9 +103,13 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
     const int ext = ((flags & (SWMHD_WRAP_Y | SWMHD_BOUNDED_Y)) || Hy < 3) ? 0 : Hy - 3;
     if (j0 < -ext || j1 > Ny + ext || j0 > j1) return SWMHD_EINVAL;
     if (j1b > j0b && (j0b < j1 || j1b > Ny + ext)) return SWMHD_EINVAL;   // (internal: second row range of the slab driver, above the first)
-    if (flags & ~(SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_LEAVE_ROOM | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_GM_IS_PREV_STATE)) return SWMHD_EINVAL;
+    if (flags & ~(SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_LEAVE_ROOM | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR)) return SWMHD_EINVAL;
     if (flags & SWMHD_GM_IS_PREV_STATE) {   // fast, periodic, fused stage with a G- operand only (a Bounded grid's frame launch would read cells the first launch has overwritten)
         if (!rk || !rk->Gm) return SWMHD_EINVAL;
+        if (flags & (SWMHD_STRICT | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;
+    }
+    if (flags & SWMHD_RK3_ANCHOR) {         // fast, periodic, fused stage only; one operand form at a time
+        if (!rk || (flags & SWMHD_GM_IS_PREV_STATE)) return SWMHD_EINVAL;
         if (flags & (SWMHD_STRICT | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;
     }
     if (((flags & SWMHD_BOUNDED_X) && (flags & SWMHD_WRAP_X)) || ((flags & SWMHD_BOUNDED_Y) && (flags & SWMHD_WRAP_Y))) return SWMHD_EINVAL;
@@ -126,7 +130,8 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
     a.dx = dx; a.dy = dy; a.rdx = T(1) / dx; a.rdy = T(1) / dy; a.grav = grav; a.fcor = fcor; a.j0 = j0; a.j1 = j1;
     a.j0b = j1b > j0b ? j0b : 0; a.j1b = j1b > j0b ? j1b : 0;
     a.fuse = 0; a.first = 0; a.store_G = 1; a.drop_G = 0; a.dt = a.gamma = a.zeta = T(0);
-    a.gm_prev = (flags & SWMHD_GM_IS_PREV_STATE) ? 1 : 0; a.cu = a.cg = a.dtg = T(0);
+    a.gm_prev = (flags & SWMHD_GM_IS_PREV_STATE) ? 1 : 0; a.cu = a.cg = a.dtg = a.dtw = T(0);
+    a.anchor = (flags & SWMHD_RK3_ANCHOR) ? 1 : 0;
     a.wrap = ((flags & SWMHD_WRAP_X) ? 1 : 0) | ((flags & SWMHD_WRAP_Y) ? 2 : 0);
     a.leave_room = (flags & SWMHD_LEAVE_ROOM) ? 1 : 0;
     a.edge_cols = 0;
@@ -136,6 +141,10 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
     if (rk) {
         a.fuse = 1; a.first = rk->Gm ? 0 : 1; a.store_G = rk->store_G; a.dt = rk->dt; a.gamma = rk->gamma; a.zeta = rk->zeta;
         a.cu = a.gm_prev ? rk->zeta : T(0); a.cg = a.gm_prev ? -rk->zeta : rk->dt * rk->zeta; a.dtg = rk->dt * rk->gamma;
+        if (a.anchor) {   // no G store: the first stage writes W through the G pointers, later stages only read W
+            a.store_G = 0; a.cu = a.cg = T(0);
+            a.dtw = rk->Gm ? T(0) : rk->dt * rk->zeta;
+        }
         for (int f = 0; f < 4; ++f) { a.Unew[f] = rk->Unew[f] + off; a.Gm[f] = rk->Gm ? rk->Gm[f] + off : nullptr; }
     }
     hipStream_t s = (hipStream_t)stream;
@@ -181,12 +190,12 @@ int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx
     if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // the driver's halo fill is the periodic one
     Rk3Buffers<T> b;
     if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
-    const bool from_state = !(flags & SWMHD_STRICT);   // (common.hpp: Rk3Buffers)
+    const bool anchor = !(flags & SWMHD_STRICT);   // (common.hpp: Rk3Buffers)
     // whatever the kernel does not wrap itself
     const int need = (SWMHD_HALO_X | SWMHD_HALO_Y) & ~(((flags & SWMHD_WRAP_X) ? SWMHD_HALO_X : 0) | ((flags & SWMHD_WRAP_Y) ? SWMHD_HALO_Y : 0));
     for (int n = 0; n < nsteps; ++n)
         for (int st = 0; st < 3; ++st) {
-            const Rk3Stage<T> g = b.stage(st, from_state);
+            const Rk3Stage<T> g = b.stage(st, anchor);
             int rc = tend_rk3_common<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, g.gamma,
                                         g.zeta, g.store_G, 0, Ny, flags | g.flags, stream);
             if (rc) return rc;
@@ -225,6 +234,7 @@ int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy
     return halo_multi_common<T>(f, nf, Nx, Ny, Hx, Hy, (int64_t)sy, which, stream);
 }
 static_assert(GM_IS_PREV_STATE == SWMHD_GM_IS_PREV_STATE, "common.hpp mirrors swmhd.h");
+static_assert(RK3_ANCHOR == SWMHD_RK3_ANCHOR, "common.hpp mirrors swmhd.h");
 #define SW_INST(T)                                                                                                                   \
     template int tendencies_rk3_two_ranges<T>(const T *const *, T *const *, T *const *, const T *const *, int, int, int, int, long, T, \
                                               T, T, T, int, int, T, T, T, int, int, int, int, int, int, void *);                      \

@@ -20,7 +20,9 @@
 // Memory operations are straight-line code (buffer stores with out-of-range offsets for lanes that own no output column,
 // compile-time stage MODE, explicit exact wait): see common.hpp.  Before: 25 % of wave time in s_waitcnt
 // (profiles/r01/tendency_pmc_sq.json), every wave waiting for the stores it had just issued.
-// MODE: bit 0 = fused RK3 substep (writes Unew), bit 1 = the substep reads G- (not the first stage), bit 2 = store G.
+// MODE: bit 0 = fused RK3 substep (writes Unew), bit 1 = the substep reads G- (not the first stage), bit 2 = store G, bit 3 = RK3 in
+// anchor form (common.hpp: Rk3Buffers) -- with bits 0 (9): store Unew = U + dtg G and W = U + dtw G (W through the G descriptors); with
+// bits 0, 1 (11): read W where G- is read otherwise, store Unew = W + dtg G.  Both move 96 B/cell in fp64.
 // A segment starts with a PROLOGUE: the seven rows its windows need are loaded in ONE burst (plus eleven x-neighbour values) and what
 // the steady loop carries in is computed directly -- the two y-face fluxes at the segment's first face, Kh of the row below, two rows
 // of centre B and the LDS rows the first iteration reads but does not write: about half a row's worth of arithmetic, no barrier.
@@ -41,7 +43,8 @@ template <typename TA> __device__ __forceinline__ void segment_rows(const TA &a,
 
 template <typename T, int LOR, int NT, int MODE>
 __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int nstrips, int nseg, int LY) {
-    constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0;
+    constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0, ANCHOR = (MODE & 8) != 0;
+    constexpr bool STORE_W = ANCHOR && FUSE && !HAS_GM;   // first anchored stage: W goes out through the G descriptors
     constexpr int XH = 3, RW = NT + 2 * XH, TXO = NT - 2 * XH;
     __shared__ T Ru[3][RW];    // u rows jo-1, jo (+1: written while the previous row's readers may still run)
     __shared__ T Rvn[1][RW];   // v newest row (to fetch the left neighbour's value for the vl window)
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     auto rowoff = [&](int row) -> unsigned { return (unsigned)((row + a.Hy) * isy) * (unsigned)sizeof(T); };
     const unsigned pbytes = (unsigned)((a.Ny + 2 * a.Hy) * isy) * (unsigned)sizeof(T);
     __amdgpu_buffer_rsrc_t rG[4], rU[4];
-    if constexpr (STORE_G) {
+    if constexpr (STORE_G || STORE_W) {
         rG[0] = out_rsrc(a.G1 - off0, pbytes); rG[1] = out_rsrc(a.G2 - off0, pbytes);
         rG[2] = out_rsrc(a.Gh - off0, pbytes); rG[3] = out_rsrc(a.GA - off0, pbytes);
     }
@@ -155,7 +158,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             const unsigned ob = rowoff(wrap_index(jr + 1, a.Ny, ylo, yhi, wy)) + colb;
             uw[LU] = LD(a.q1, ob); vw[LW] = LD(a.q2, ob); hw[LW] = LD(a.h, ob); aw[LW] = LD(a.A, ob);
         }
-        // G⁻ of the output row is needed only at the very end of the iteration: issue its loads after the second barrier so their
+        // G⁻ (W) of the output row is needed only at the very end of the iteration: issue its loads after the second barrier so their
         // HBM latency hides under the arithmetic in between
         T gm0 = T(0), gm1 = T(0), gm2 = T(0), gm3 = T(0);
         const unsigned rowb = rowoff(jo);
@@ -256,16 +259,22 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             for (int f = 0; f < 4; ++f) {
                 T un;
                 if constexpr (!HAS_GM) un = Us[f] + a.dtg * Gs[f];
+                else if constexpr (ANCHOR) un = fma_<T>(a.dtg, Gs[f], Gms[f]);                                                  // W + dt gamma G
                 else if constexpr (STORE_G) un = fma_<T>(a.cg, Gms[f], fma_<T>(a.dtg, Gs[f], fma_<T>(a.cu, Us[f], Us[f])));   // (common.hpp: cu, cg)
                 else un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * Gms[f]);
                 buffer_store<T>(un, rU[f], o);
             }
         }
+        if constexpr (STORE_W) {
+            const T Us[4] = {U[3], V[2], Hh[2], Aa[2]};
+#pragma unroll
+            for (int f = 0; f < 4; ++f) buffer_store<T>(Us[f] + a.dtw * Gs[f], rG[f], o);
+        }
         fhy = fhy_n; fay = fay_n; km = kc;
         // The prefetched row must have landed; the memory operations issued after it (G- loads, stores) need not.  Stated
         // explicitly because the compiler would place its own wait behind the loop's back edge, where it has to assume the
         // worst over all incoming paths (vmcnt(0)).
-        constexpr int YOUNGER = ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0);
+        constexpr int YOUNGER = ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0) + (STORE_W ? 4 : 0);
         wait_vmem_all_but<YOUNGER>();
     };
     // after each row: shift the windows by one
@@ -304,12 +313,15 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
 // Workgroups of 256 per CU (= waves per SIMD) the conservative kernel is compiled for, per stage variant: bit MODE of the mask set =
 // 3, else 2.  At 168 VGPRs the variants need 0 (MODE 7), 12 (MODE 5), 20-60 (others) bytes of scratch per lane.  Measured on MI355X
 // in one call (4096^2 step / 8192x1024 slab step): no variant at 3: 1.514 / 0.758 ms; MODE 7: 1.474 / 0.728; MODE 7+5: 1.452 / 0.721;
-// all fused stages: 1.504 / 0.747 -- a third workgroup pays only where (almost) nothing spills.
-constexpr int CONS_W3_MODES = (1 << 7) | (1 << 5) | (1 << 4);
+// all fused stages: 1.504 / 0.747 -- a third workgroup pays only where (almost) nothing spills.  The anchor variants (MODE 9, 11) need 0
+// bytes of scratch at two workgroups and 12 at three; 4096^2 step, same call, alternating processes (profiles/rk3_anchor/README.md): two
+// workgroups 1.435 ms (stages 454 / 485 / 480 us), three 1.365 ms (445 / 455 / 451 us) -- three it is.
+constexpr int CONS_W3_MODES = (1 << 7) | (1 << 5) | (1 << 4) | (1 << 9) | (1 << 11);
 constexpr int cons_minwaves(int mode, int elem_size) { return elem_size == 4 ? 3 : (((CONS_W3_MODES >> mode) & 1) ? 3 : 2); }
 template <typename T, int LOR, int NT, int MODE>   // MODE as in k_tendency_vi_march
 __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_tendency_cons_march(TendArgs<T> a, int nstrips, int nseg, int LY) {
-    constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0;
+    constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0, ANCHOR = (MODE & 8) != 0;
+    constexpr bool STORE_W = ANCHOR && FUSE && !HAS_GM;
     constexpr int XH = 3, RW = NT + 2 * XH, TXO = NT - 2 * XH;
     __shared__ T Ruh[3][RW];    // uh rows jo-1, jo (+1: the next row is published while this row's readers may still run)
     __shared__ T Rvh[3][RW];    // vh rows jo, jo+1
@@ -369,7 +381,7 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
     };
     const unsigned pbytes = (unsigned)((a.Ny + 2 * a.Hy) * isy) * (unsigned)sizeof(T);
     __amdgpu_buffer_rsrc_t rG[4], rU[4];
-    if constexpr (STORE_G) {
+    if constexpr (STORE_G || STORE_W) {
         rG[0] = out_rsrc(a.G1 - off0, pbytes); rG[1] = out_rsrc(a.G2 - off0, pbytes);
         rG[2] = out_rsrc(a.Gh - off0, pbytes); rG[3] = out_rsrc(a.GA - off0, pbytes);
     }
@@ -613,15 +625,21 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
                 for (int f = 0; f < 4; ++f) {
                     T un;
                     if constexpr (!HAS_GM) un = Us[f] + a.dtg * Gs[f];
+                    else if constexpr (ANCHOR) un = fma_<T>(a.dtg, Gs[f], Gms[f]);
                     else if constexpr (STORE_G) un = fma_<T>(a.cg, Gms[f], fma_<T>(a.dtg, Gs[f], fma_<T>(a.cu, Us[f], Us[f])));   // (common.hpp: cu, cg)
-                else un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * Gms[f]);
+                    else un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * Gms[f]);
                     buffer_store<T>(un, rU[f], o);
                 }
+            }
+            if constexpr (STORE_W) {
+                const T Us[4] = {uw[2], vw[2], hc, aw[2]};
+#pragma unroll
+                for (int f = 0; f < 4; ++f) buffer_store<T>(Us[f] + a.dtw * Gs[f], rG[f], o);
             }
         }
         d1 = d1n; d2 = d2n; fya_s = fya_n; hff_s = hff_n; vs_ = vn;
         }
-        constexpr int YOUNGER = STEADY ? ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0) : 0;
+        constexpr int YOUNGER = STEADY ? ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0) + (STORE_W ? 4 : 0) : 0;
         wait_vmem_all_but<YOUNGER>();   // the prefetched row is back; younger G- loads and stores need not be
         insert_row(nu, nv, nh, na);
     };

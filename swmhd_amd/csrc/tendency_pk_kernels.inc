@@ -22,7 +22,8 @@ template <int LOR, int NT, int MODE>
 __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march_pk(TendArgs<float> a, int nstrips, int nseg, int LY) {
     using T = sw_f2;
     using S = float;
-    constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0;
+    constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0, ANCHOR = (MODE & 8) != 0;
+    constexpr bool STORE_W = ANCHOR && FUSE && !HAS_GM;   // MODE as in k_tendency_vi_march
     constexpr int XL = 2, PAD = 4, RW = 2 * NT + 2 * PAD, TXO = 2 * (NT - 2 * XL);
     __shared__ __attribute__((aligned(8))) S Ru[3][RW];    // u rows jo-1, jo (+1)
     __shared__ __attribute__((aligned(8))) S Rvn[1][RW];   // v newest row
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march_pk(TendArgs<float> 
     auto rowoff = [&](int row) -> unsigned { return (unsigned)((row + a.Hy) * isy) * (unsigned)sizeof(S); };
     const unsigned pbytes = (unsigned)((a.Ny + 2 * a.Hy) * isy) * (unsigned)sizeof(S);
     __amdgpu_buffer_rsrc_t rG[4], rU[4];
-    if constexpr (STORE_G) {
+    if constexpr (STORE_G || STORE_W) {
         rG[0] = out_rsrc(a.G1 - off0, pbytes); rG[1] = out_rsrc(a.G2 - off0, pbytes);
         rG[2] = out_rsrc(a.Gh - off0, pbytes); rG[3] = out_rsrc(a.GA - off0, pbytes);
     }
@@ -219,13 +220,19 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march_pk(TendArgs<float> 
             for (int f = 0; f < 4; ++f) {
                 T un;
                 if constexpr (!HAS_GM) un = Us[f] + T(a.dtg) * Gs[f];
+                else if constexpr (ANCHOR) un = fma_<T>(T(a.dtg), Gs[f], Gms[f]);
                 else if constexpr (STORE_G) un = fma_<T>(T(a.cg), Gms[f], fma_<T>(T(a.dtg), Gs[f], fma_<T>(T(a.cu), Us[f], Us[f])));
                 else un = Us[f] + T(a.dt) * (T(a.gamma) * Gs[f] + T(a.zeta) * Gms[f]);
                 buffer_store<T>(un, rU[f], o);
             }
         }
+        if constexpr (STORE_W) {
+            const T Us[4] = {U[3], V[2], Hh[2], Aa[2]};
+#pragma unroll
+            for (int f = 0; f < 4; ++f) buffer_store<T>(Us[f] + T(a.dtw) * Gs[f], rG[f], o);
+        }
         fhy = fhy_n; fay = fay_n; km = kc;
-        constexpr int YOUNGER = ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0);
+        constexpr int YOUNGER = ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0) + (STORE_W ? 4 : 0);
         wait_vmem_all_but<YOUNGER>();
         // shift the windows by one row
 #pragma unroll

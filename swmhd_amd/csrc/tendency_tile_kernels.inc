@@ -243,10 +243,18 @@ __global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TendArgs<T> a, int nt
             if (a.fuse) {   // rk3_substep! fused in: the old state of this cell is already in LDS
                 const T Gs[4] = {G1, G2, Gh, GA};
                 const T Us[4] = {U_(i, j), V_(i, j), H_(i, j), A_(i, j)};
+                T *const Gp[4] = {a.G1, a.G2, a.Gh, a.GA};
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
                     T un;
-                    if (a.first) {
+                    if (!STRICT && !BND && a.anchor) {   // anchor form (common.hpp: Rk3Buffers): W out through the G pointers, or W in through Gm
+                        if (a.first) {
+                            un = Us[f] + a.dtg * Gs[f];
+                            Gp[f][o] = Us[f] + a.dtw * Gs[f];
+                        } else {
+                            un = a.Gm[f][o] + a.dtg * Gs[f];
+                        }
+                    } else if (a.first) {
                         if constexpr (STRICT) un = Us[f] + a.dt * a.gamma * Gs[f];
                         else un = Us[f] + (a.dt * a.gamma) * Gs[f];
                     } else if (!STRICT && a.gm_prev) {
@@ -405,7 +413,7 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
             const MarchGeometry mg = packed_fp32_geometry(a.Nx, rows, a.leave_room);
             const int nstrips = mg.nstrips, LY = mg.LY, nseg = two ? two_range_segments(LY) : mg.nseg;
             dim3 mgrid(nstrips * nseg), mblock(256);
-            int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0);
+            int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0) | (a.anchor ? 8 : 0);
             TendArgs<T> ap = a;
             if (a.gm_prev && mode == 3) { mode = 7; ap.drop_G = 1; }
 #define SW_PK_MARCH(MODE_)                                                                                                  \
@@ -413,14 +421,16 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
                 if (lorentz == 1) hipLaunchKernelGGL((k_tendency_vi_march_pk<1, 256, MODE_>), mgrid, mblock, 0, s, ap, nstrips, nseg, LY); \
                 else hipLaunchKernelGGL((k_tendency_vi_march_pk<0, 256, MODE_>), mgrid, mblock, 0, s, ap, nstrips, nseg, LY);            \
                 break;
-            switch (mode) { SW_PK_MARCH(4) SW_PK_MARCH(5) SW_PK_MARCH(1) SW_PK_MARCH(7) SW_PK_MARCH(3) default: return hipErrorInvalidValue; }
+            switch (mode) { SW_PK_MARCH(4) SW_PK_MARCH(5) SW_PK_MARCH(1) SW_PK_MARCH(7) SW_PK_MARCH(3) SW_PK_MARCH(9) SW_PK_MARCH(11)
+                            default: return hipErrorInvalidValue; }
 #undef SW_PK_MARCH
             return hipGetLastError();
         }
     }
     if (march) {
-        // compile-time memory-operation pattern (see the kernel): bit 0 fused substep, bit 1 it reads G-, bit 2 store G
-        int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0);
+        // compile-time memory-operation pattern (see the kernel): bit 0 fused substep, bit 1 it reads G-, bit 2 store G, bit 3 anchor form
+        // (the anchor form stores no G: modes 9 and 11)
+        int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0) | (a.anchor ? 8 : 0);
         TendArgs<T> ax = a;
         // Conservative model: the last RK3 stage (MODE 3) runs on the stage-2 variant (3 workgroups per CU, no scratch) with its G stores
         // dropped by the hardware: 4096^2 step 1.39-1.40 -> 1.36 ms.  (The same substitution bought nothing for the vector-invariant
@@ -447,7 +457,8 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
                 if (mg.nt == 128) SW_VI_GO(128, MODE_);                                                                         \
                 else SW_VI_GO(256, MODE_);                                                                                      \
                 break;
-            switch (mode) { SW_VI_MARCH(4) SW_VI_MARCH(5) SW_VI_MARCH(1) SW_VI_MARCH(7) SW_VI_MARCH(3) default: return hipErrorInvalidValue; }
+            switch (mode) { SW_VI_MARCH(4) SW_VI_MARCH(5) SW_VI_MARCH(1) SW_VI_MARCH(7) SW_VI_MARCH(3) SW_VI_MARCH(9) SW_VI_MARCH(11)
+                            default: return hipErrorInvalidValue; }
 #undef SW_VI_MARCH
 #undef SW_VI_GO
         } else {
@@ -461,7 +472,8 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
                     else hipLaunchKernelGGL((k_tendency_cons_march<T, 0, 256, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY);            \
                 }                                                                                                               \
                 break;
-            switch (mode) { SW_CONS_MARCH(4) SW_CONS_MARCH(5) SW_CONS_MARCH(1) SW_CONS_MARCH(7) SW_CONS_MARCH(3) default: return hipErrorInvalidValue; }
+            switch (mode) { SW_CONS_MARCH(4) SW_CONS_MARCH(5) SW_CONS_MARCH(1) SW_CONS_MARCH(7) SW_CONS_MARCH(3) SW_CONS_MARCH(9) SW_CONS_MARCH(11)
+                            default: return hipErrorInvalidValue; }
 #undef SW_CONS_MARCH
         }
         return hipGetLastError();

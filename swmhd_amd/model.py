@@ -20,14 +20,17 @@ RK3_GAMMA = (8.0 / 15.0, 5.0 / 12.0, 3.0 / 4.0)
 RK3_ZETA = (0.0, -17.0 / 60.0, -5.0 / 12.0)
 
 
-def rk3_stage(stage, from_state):
-    """(gamma, zeta, store_G, G- from the previous state) of RK3 stage 0, 1 or 2 -- the schedule of the C step drivers (common.hpp
-    Rk3Buffers).  from_state (fast builds, periodic grids): the second stage takes G- = (U1 - U0) / (dt gamma1) from the two states --
-    U0 is still in the buffer that stage writes U2 to -- so the first stage stores no tendencies (swmhd.h SWMHD_GM_IS_PREV_STATE;
-    288 instead of 320 B/cell-step)."""
-    fs = from_state and stage == 1
-    store = 1 if stage == 1 or (stage == 0 and not from_state) else 0
-    return RK3_GAMMA[stage], RK3_ZETA[1] / RK3_GAMMA[0] if fs else RK3_ZETA[stage], store, fs
+RK3_ANCHOR_WEIGHT = 0.25    # gamma1 + zeta2 = 8/15 - 17/60
+
+
+def rk3_stage(stage, anchor):
+    """(gamma, zeta, store_G, anchor) of RK3 stage 0, 1 or 2 -- the schedule of the C step drivers (common.hpp Rk3Buffers).
+    anchor (fast builds, periodic grids): gamma1 + zeta2 = 1/4 and zeta3 = -gamma2 make the step exactly U1 = U0 + dt gamma1 G0,
+    W = U0 + (dt/4) G0, U2 = W + dt gamma2 G1, U3 = W + dt gamma3 G2 -- one stored operand W, 96 B/cell in every stage
+    (swmhd.h SWMHD_RK3_ANCHOR; zeta is the weight of W in the first stage).  Otherwise the classic G- form."""
+    if anchor:
+        return RK3_GAMMA[stage], RK3_ANCHOR_WEIGHT if stage == 0 else 0.0, 0, True
+    return RK3_GAMMA[stage], RK3_ZETA[stage], 1 if stage < 2 else 0, False
 
 
 def loopback_rings(nranks, timeout_s=60.0):
@@ -291,9 +294,11 @@ class ShallowWaterModel:
         q = _lib.ptr_array([f.ptr for f in self._raw_fields])
         qn = _lib.ptr_array([self._alt[n].ptr for n in self.names])
         Gn = _lib.ptr_array([f.ptr for f in self.Gn])
-        gamma, zeta, store, prev_state = rk3_stage(stage, not self.strict and not any(self._bounded))
-        if prev_state:
-            Gm, extra_flags = qn, extra_flags | _lib.GM_IS_PREV_STATE
+        gamma, zeta, store, anchor = rk3_stage(stage, not self.strict and not any(self._bounded))
+        if anchor:
+            # stage 0 writes W into Gn; the per-stage swap of Gn and G- (time_step) hands it to stage 1 as G- and to stage 2 as Gn
+            extra_flags |= _lib.RK3_ANCHOR
+            Gm = None if stage == 0 else _lib.ptr_array([f.ptr for f in (self.Gm if stage == 1 else self.Gn)])
         else:
             Gm = _lib.ptr_array([f.ptr for f in self.Gm]) if stage > 0 else None
         f = getattr(self._L, f"swmhd_tendencies_rk3_{self.sfx}")
