@@ -333,12 +333,12 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
     __shared__ T RXv[1][RW];    // huv(c, jo)   momentum_flux_huv @ffc
     __shared__ T RXa[1][RW];    // tracer x-flux at face c (already divided by ℑxᶠ h)
     __shared__ T RUe[1][RW];    // u = uh/ℑxᶠh at face c (for c div U)
-    __shared__ T RBx[1][LOR == 2 ? RW : 1];                   // face Bx row jo   (P2 only)
-    __shared__ T RHBx[LOR == 2 ? 2 : 1][LOR == 2 ? RW : 1];  // face hBx rows jo-1, jo (P2 only)
-    __shared__ T RBy[1][LOR == 2 ? RW : 1];                   // face By row jo   (P2 only)
-    __shared__ T RHBy[LOR == 2 ? 2 : 1][LOR == 2 ? RW : 1];
-    __shared__ T RF1[LOR == 2 ? 1 : 1][LOR == 2 ? RW : 1];   // Lorentz F1(c, jo) @ccc
-    __shared__ T RG1[LOR == 2 ? 1 : 1][LOR == 2 ? RW : 1];   // Lorentz G1(c, jo) @ffc
+    __shared__ T RBx[1][RW];    // face Bx row jo   (P2 only)
+    __shared__ T RHBx[2][RW];   // face hBx rows jo-1, jo (P2 only)
+    __shared__ T RBy[1][RW];    // face By row jo   (P2 only)
+    __shared__ T RHBy[2][RW];
+    __shared__ T RF1[1][RW];    // Lorentz F1(c, jo) @ccc
+    __shared__ T RG1[1][RW];    // Lorentz G1(c, jo) @ffc
 
     const unsigned bid = xcd_remap(blockIdx.x, (unsigned)(nstrips * nseg));
     const int strip = (int)(bid % nstrips), seg = (int)(bid / nstrips);
@@ -471,8 +471,7 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
         RA[jo & 3][lc] = aw[2]; RA[(jo + 1) & 3][lc] = aw[3]; RA[(jo + 2) & 3][lc] = aw[4];   // A(c, jo .. jo+2)
     }
 
-    auto body = [&](const int it, auto steady_tag) {
-        constexpr bool STEADY = decltype(steady_tag)::value;   // it >= 6: a full output row per iteration, no conditions
+    auto body = [&](const int it) {
         const int jr = J0 - 3 + it, jo = jr - 3, jf = jr - 1;   // newest row, output row, Lorentz face row (= jo+2)
         T nu, nv, nh, na;
         ldrow(jr + 1, nu, nv, nh, na);
@@ -553,14 +552,11 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
             hbx_pub = bxw[3] * (T(0.5) * (sh1[lc - 1] + hw[2]));         // hBx(c, jo+1) = Bx * face-averaged h
         }
         __syncthreads();
-        if constexpr (STEADY && FUSE && HAS_GM) {   // G- of the output row: needed at the very end of the iteration
+        if constexpr (FUSE && HAS_GM) {   // G- of the output row: needed at the very end of the iteration
             const unsigned og = rowb + colb;
             gm0 = LD(a.Gm[0], og); gm1 = LD(a.Gm[1], og); gm2 = LD(a.Gm[2], og); gm3 = LD(a.Gm[3], og);
         }
 
-        if (!STEADY && it < 5) {   // nothing carried is valid yet; keep h_ff rolling so that it is valid from it = 5 on
-            hff_s = T(0.25) * ((sh1[lc - 1] + hw[2]) + (hl + hc));
-        } else {
         // ---- P3: y-direction fluxes at the north face (jo+1), carried south-face values, assemble ----
         const T hn1 = hw[2];                                   // h(c, jo+1)
         const T hff_n = T(0.25) * ((hl + hc) + (sh1[lc - 1] + hn1));   // ℑxyᶠᶠh (c, jo+1)
@@ -591,55 +587,52 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
             g2n = g.dx * upwind_biased_product<T>(T(0.5) * (hby_o + hby_n), left3<T>(byw[1], byw[2], byw[3]), right3<T>(byw[2], byw[3], byw[4]));
         }
         const T d1n = f2n - hvu_n, d2n = g2n - hvv_c;
-        if constexpr (STEADY) {
-            const T rAz = rdx * rdy;
-            // x-differences of (Lorentz - momentum) fluxes; the y-differences come from the carried d1, d2
-            T xu = -(RXu[0][lc] - RXu[0][lc - 1]), xv = -(RXv[0][lc + 1] - RXv[0][lc]);
-            if constexpr (LOR == 2) {
-                xu += RF1[0][lc] - RF1[0][lc - 1];
-                xv += RG1[0][lc + 1] - RG1[0][lc];
-            }
-            // uh: −(1/V)(δx huu + δy hvu) − ∂x(½ g h²) + f ℑxyᶠᶜ(vh) + Fx,   Fx = (1/Az)(δx F1 + δy F2)   (reference :162-165)
-            const T vbar = T(0.25) * ((sv0[lc - 1] + vw[2]) + (sv1[lc - 1] + vw[3]));
-            const T G1 = rAz * (xu + (d1n - d1)) - (hg * sq(hc) - hg * sq(hl)) * rdx + a.fcor * vbar;
-            // vh: −(1/V)(δx huv + δy hvv) − ∂y(½ g h²) − f ℑxyᶜᶠ(uh) + Fy,   Fy = (1/Az)(δx G1 + δy G2)   (reference :167-170)
-            const T ubar = T(0.25) * ((uw[1] + Ruh[r3m][lc + 1]) + (uw[2] + su[lc + 1]));
-            const T G2 = rAz * (xv + (d2n - d2)) - (hg * sq(hc) - hg * sq(hw[0])) * rdy - a.fcor * ubar;
-            // h: −(1/Az)(δx(Δy uh) + δy(Δx vh))
-            const T ue_t = su[lc + 1];
-            const T Gh = -((ue_t - uw[2]) * rdx + (vw[3] - vw[2]) * rdy);
-            // A: −(1/Az)(δx fx + δy fy) + A (δx(Δy u) + δy(Δx v))/Az with u = uh/ℑxᶠh, v = vh/ℑyᶠh
-            const T GA = -rAz * ((RXa[0][lc + 1] - RXa[0][lc]) + (fya_n - fya_s))
-                         + aw[2] * ((RUe[0][lc + 1] - RUe[0][lc]) * rdx + (vn - vs_) * rdy);
-            const unsigned o = col_ok ? rowb + colb : SW_OOB;   // lanes without an output column: dropped by the hardware
-            const T Gs[4] = {G1, G2, Gh, GA};
-            if constexpr (STORE_G) {
-                const unsigned oG = a.drop_G ? SW_OOB : o;      // (last RK3 stage running this variant: nothing reads its G)
+        const T rAz = rdx * rdy;
+        // x-differences of (Lorentz - momentum) fluxes; the y-differences come from the carried d1, d2
+        T xu = -(RXu[0][lc] - RXu[0][lc - 1]), xv = -(RXv[0][lc + 1] - RXv[0][lc]);
+        if constexpr (LOR == 2) {
+            xu += RF1[0][lc] - RF1[0][lc - 1];
+            xv += RG1[0][lc + 1] - RG1[0][lc];
+        }
+        // uh: −(1/V)(δx huu + δy hvu) − ∂x(½ g h²) + f ℑxyᶠᶜ(vh) + Fx,   Fx = (1/Az)(δx F1 + δy F2)   (reference :162-165)
+        const T vbar = T(0.25) * ((sv0[lc - 1] + vw[2]) + (sv1[lc - 1] + vw[3]));
+        const T G1 = rAz * (xu + (d1n - d1)) - (hg * sq(hc) - hg * sq(hl)) * rdx + a.fcor * vbar;
+        // vh: −(1/V)(δx huv + δy hvv) − ∂y(½ g h²) − f ℑxyᶜᶠ(uh) + Fy,   Fy = (1/Az)(δx G1 + δy G2)   (reference :167-170)
+        const T ubar = T(0.25) * ((uw[1] + Ruh[r3m][lc + 1]) + (uw[2] + su[lc + 1]));
+        const T G2 = rAz * (xv + (d2n - d2)) - (hg * sq(hc) - hg * sq(hw[0])) * rdy - a.fcor * ubar;
+        // h: −(1/Az)(δx(Δy uh) + δy(Δx vh))
+        const T ue_t = su[lc + 1];
+        const T Gh = -((ue_t - uw[2]) * rdx + (vw[3] - vw[2]) * rdy);
+        // A: −(1/Az)(δx fx + δy fy) + A (δx(Δy u) + δy(Δx v))/Az with u = uh/ℑxᶠh, v = vh/ℑyᶠh
+        const T GA = -rAz * ((RXa[0][lc + 1] - RXa[0][lc]) + (fya_n - fya_s))
+                     + aw[2] * ((RUe[0][lc + 1] - RUe[0][lc]) * rdx + (vn - vs_) * rdy);
+        const unsigned o = col_ok ? rowb + colb : SW_OOB;   // lanes without an output column: dropped by the hardware
+        const T Gs[4] = {G1, G2, Gh, GA};
+        if constexpr (STORE_G) {
+            const unsigned oG = a.drop_G ? SW_OOB : o;      // (last RK3 stage running this variant: nothing reads its G)
 #pragma unroll
-                for (int f = 0; f < 4; ++f) buffer_store<T>(Gs[f], rG[f], oG);
-            }
-            if constexpr (FUSE) {
-                const T Us[4] = {uw[2], vw[2], hc, aw[2]};
-                const T Gms[4] = {gm0, gm1, gm2, gm3};
+            for (int f = 0; f < 4; ++f) buffer_store<T>(Gs[f], rG[f], oG);
+        }
+        if constexpr (FUSE) {
+            const T Us[4] = {uw[2], vw[2], hc, aw[2]};
+            const T Gms[4] = {gm0, gm1, gm2, gm3};
 #pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    T un;
-                    if constexpr (!HAS_GM) un = Us[f] + a.dtg * Gs[f];
-                    else if constexpr (ANCHOR) un = fma_<T>(a.dtg, Gs[f], Gms[f]);
-                    else if constexpr (STORE_G) un = fma_<T>(a.cg, Gms[f], fma_<T>(a.dtg, Gs[f], fma_<T>(a.cu, Us[f], Us[f])));   // (common.hpp: cu, cg)
-                    else un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * Gms[f]);
-                    buffer_store<T>(un, rU[f], o);
-                }
+            for (int f = 0; f < 4; ++f) {
+                T un;
+                if constexpr (!HAS_GM) un = Us[f] + a.dtg * Gs[f];
+                else if constexpr (ANCHOR) un = fma_<T>(a.dtg, Gs[f], Gms[f]);
+                else if constexpr (STORE_G) un = fma_<T>(a.cg, Gms[f], fma_<T>(a.dtg, Gs[f], fma_<T>(a.cu, Us[f], Us[f])));   // (common.hpp: cu, cg)
+                else un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * Gms[f]);
+                buffer_store<T>(un, rU[f], o);
             }
-            if constexpr (STORE_W) {
-                const T Us[4] = {uw[2], vw[2], hc, aw[2]};
+        }
+        if constexpr (STORE_W) {
+            const T Us[4] = {uw[2], vw[2], hc, aw[2]};
 #pragma unroll
-                for (int f = 0; f < 4; ++f) buffer_store<T>(Us[f] + a.dtw * Gs[f], rG[f], o);
-            }
+            for (int f = 0; f < 4; ++f) buffer_store<T>(Us[f] + a.dtw * Gs[f], rG[f], o);
         }
         d1 = d1n; d2 = d2n; fya_s = fya_n; hff_s = hff_n; vs_ = vn;
-        }
-        constexpr int YOUNGER = STEADY ? ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0) + (STORE_W ? 4 : 0) : 0;
+        constexpr int YOUNGER = ((FUSE && HAS_GM) ? 4 : 0) + (STORE_G ? 4 : 0) + (FUSE ? 4 : 0) + (STORE_W ? 4 : 0);
         wait_vmem_all_but<YOUNGER>();   // the prefetched row is back; younger G- loads and stores need not be
         insert_row(nu, nv, nh, na);
     };
@@ -648,6 +641,6 @@ __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_ten
     const ProgressPriority prio(niter);
     for (int it = 6; it < niter; ++it) {
         prio.at(it);
-        body(it, std::true_type{});
+        body(it);
     }
 }

@@ -210,8 +210,9 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march_pk(TendArgs<float> 
         const unsigned o = col_ok ? rowb + colb : SW_OOB;
         const T Gs[4] = {G1, G2, Gh, GA};
         if constexpr (STORE_G) {
+            const unsigned oG = a.drop_G ? SW_OOB : o;      // (last RK3 stage running this variant: nothing reads its G)
 #pragma unroll
-            for (int f = 0; f < 4; ++f) buffer_store<T>(Gs[f], rG[f], o);
+            for (int f = 0; f < 4; ++f) buffer_store<T>(Gs[f], rG[f], oG);
         }
         if constexpr (FUSE) {
             const T Us[4] = {U[3], V[2], Hh[2], Aa[2]};

@@ -312,19 +312,9 @@ static bool tendency_uses_packed_fp32(int Nx, int formulation, int wrap) {
 }
 static MarchGeometry packed_fp32_geometry(int Nx, int rows, int leave_room) {
     static int ly_cache = 0;
-    MarchGeometry g{};
-    g.nt = 256; g.wg_per_cu = 3; g.nstrips = (Nx + 503) / 504;
-    int slots = device_cu_count() * g.wg_per_cu;
-    if (leave_room) slots -= (slots * leave_room_64ths(rows)) / 64;
-    int LY = 32;
-    for (int k = 1; k <= 64; ++k) {
-        const int ns = (slots * k) / g.nstrips;
-        if (ns < 1) continue;
-        const int ly = (rows + ns - 1) / ns;
-        if (ly <= 128) { LY = ly < 6 ? 6 : ly; break; }
-    }
-    if (const int f = env_knob("SWMHD_T_LY", ly_cache)) LY = f;
-    g.LY = LY; g.nseg = (rows + LY - 1) / LY;
+    static const int cols[1] = {512}, wgs[1] = {3};   // in columns: 2 per lane, 4 halo columns a side -> 504 output columns per strip
+    MarchGeometry g = march_geometry(Nx, rows, 4, cols, wgs, 1, 6, leave_room != 0, 0, env_knob("SWMHD_T_LY", ly_cache));
+    g.nt = 256;
     return g;
 }
 static MarchGeometry tendency_march_geometry(int Nx, int rows, int formulation, int leave_room, int elem_size, int mode = 7) {
@@ -341,7 +331,58 @@ static MarchGeometry tendency_march_geometry(int Nx, int rows, int formulation, 
     const int nts[2] = {256, 128}, wgs[2] = {w, 2 * w};
     return march_geometry(Nx, rows, 3, nts, wgs, 2, 6, leave_room != 0, force_nt, force_ly);
 }
+// Compiled stage variant (MODE: bits at k_tendency_vi_march) of the marching kernels for a call; sets a.drop_G where a variant that
+// stores G serves a stage that must not.
+template <typename T> static int march_stage_mode(TendArgs<T> &a, int formulation) {
+    int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0) | (a.anchor ? 8 : 0);
+    const bool cons64 = formulation == 0 && sizeof(T) == 8;
+    // The previous-state operand (gm_prev) lives in the stage-2 variant (coefficient form).  Conservative model: the last RK3 stage
+    // (MODE 3) runs on the stage-2 variant (3 workgroups per CU, no scratch) with its G stores dropped by the hardware: 4096^2 step
+    // 1.39-1.40 -> 1.36 ms.  (The same substitution bought nothing for the vector-invariant kernel, whose MODE 3 already has its third
+    // workgroup: 398-403 vs 403-408 us.)
+    if (mode == 3 && (a.gm_prev || (cons64 && cons_minwaves(7, 8) > cons_minwaves(3, 8)))) { mode = 7; a.drop_G = 1; }
+    // ... and the first stage without a G store (MODE 1, two workgroups per CU) on the MODE-5 variant, likewise
+    if (mode == 1 && cons64 && cons_minwaves(5, 8) > cons_minwaves(1, 8)) { mode = 5; a.drop_G = 1; }
+    return mode;
+}
+template <typename T> using MarchKernel = void (*)(TendArgs<T>, int, int, int);
+template <typename T, int MODE> static MarchKernel<T> march_kernel(int formulation, int lorentz, int nt, bool packed) {
+    if constexpr (std::is_same<T, float>::value) {
+        if (packed) return lorentz == 1 ? k_tendency_vi_march_pk<1, 256, MODE> : k_tendency_vi_march_pk<0, 256, MODE>;
+    }
+    if (formulation == 1) {
+        if (nt == 128) return lorentz == 1 ? k_tendency_vi_march<T, 1, 128, MODE> : k_tendency_vi_march<T, 0, 128, MODE>;
+        return lorentz == 1 ? k_tendency_vi_march<T, 1, 256, MODE> : k_tendency_vi_march<T, 0, 256, MODE>;
+    }
+    if (nt == 128) return lorentz == 2 ? k_tendency_cons_march<T, 2, 128, MODE> : k_tendency_cons_march<T, 0, 128, MODE>;
+    return lorentz == 2 ? k_tendency_cons_march<T, 2, 256, MODE> : k_tendency_cons_march<T, 0, 256, MODE>;
+}
+template <typename T> static MarchKernel<T> march_kernel(int mode, int formulation, int lorentz, int nt, bool packed) {
+    switch (mode) {
+    case 1: return march_kernel<T, 1>(formulation, lorentz, nt, packed);
+    case 3: return march_kernel<T, 3>(formulation, lorentz, nt, packed);
+    case 4: return march_kernel<T, 4>(formulation, lorentz, nt, packed);
+    case 5: return march_kernel<T, 5>(formulation, lorentz, nt, packed);
+    case 7: return march_kernel<T, 7>(formulation, lorentz, nt, packed);
+    case 9: return march_kernel<T, 9>(formulation, lorentz, nt, packed);
+    case 11: return march_kernel<T, 11>(formulation, lorentz, nt, packed);
+    default: return nullptr;
+    }
+}
 #endif
+
+// LDS-tiled kernel, 64 x 4 threads, RY output rows per thread
+template <typename T, int RY, bool BND = false>
+static hipError_t launch_tile(const TendArgs<T> &a, int formulation, int lorentz, int ntx, int nty, hipStream_t s) {
+    constexpr int TX = 64, TYB = 4;
+    const dim3 grid(ntx * nty), block(TX, TYB);
+    if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 
 template <typename T>
 hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int formulation, int lorentz, hipStream_t s) {
@@ -408,74 +449,16 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
     auto two_range_segments = [&](int LY) { return (a.j1 - a.j0 + LY - 1) / LY + (rows_b + LY - 1) / LY; };
     // (one 9-12-row segment per zone instead of two 6-row ones -- a single round of workgroups in the slots the interior launch leaves
     //  free -- measured slower: 4096 x 512 ring-of-one step +22 % over plain instead of +11 %)
-    if constexpr (std::is_same<T, float>::value) {
-        if (march && tendency_uses_packed_fp32(a.Nx, formulation, a.wrap)) {   // two columns per lane, packed arithmetic
-            const MarchGeometry mg = packed_fp32_geometry(a.Nx, rows, a.leave_room);
-            const int nstrips = mg.nstrips, LY = mg.LY, nseg = two ? two_range_segments(LY) : mg.nseg;
-            dim3 mgrid(nstrips * nseg), mblock(256);
-            int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0) | (a.anchor ? 8 : 0);
-            TendArgs<T> ap = a;
-            if (a.gm_prev && mode == 3) { mode = 7; ap.drop_G = 1; }
-#define SW_PK_MARCH(MODE_)                                                                                                  \
-            case MODE_:                                                                                                         \
-                if (lorentz == 1) hipLaunchKernelGGL((k_tendency_vi_march_pk<1, 256, MODE_>), mgrid, mblock, 0, s, ap, nstrips, nseg, LY); \
-                else hipLaunchKernelGGL((k_tendency_vi_march_pk<0, 256, MODE_>), mgrid, mblock, 0, s, ap, nstrips, nseg, LY);            \
-                break;
-            switch (mode) { SW_PK_MARCH(4) SW_PK_MARCH(5) SW_PK_MARCH(1) SW_PK_MARCH(7) SW_PK_MARCH(3) SW_PK_MARCH(9) SW_PK_MARCH(11)
-                            default: return hipErrorInvalidValue; }
-#undef SW_PK_MARCH
-            return hipGetLastError();
-        }
-    }
     if (march) {
-        // compile-time memory-operation pattern (see the kernel): bit 0 fused substep, bit 1 it reads G-, bit 2 store G, bit 3 anchor form
-        // (the anchor form stores no G: modes 9 and 11)
-        int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0) | (a.anchor ? 8 : 0);
         TendArgs<T> ax = a;
-        // Conservative model: the last RK3 stage (MODE 3) runs on the stage-2 variant (3 workgroups per CU, no scratch) with its G stores
-        // dropped by the hardware: 4096^2 step 1.39-1.40 -> 1.36 ms.  (The same substitution bought nothing for the vector-invariant
-        // kernel, whose MODE 3 already has its third workgroup: 398-403 vs 403-408 us.)
-        if (formulation == 0 && mode == 3 && sizeof(T) == 8 && cons_minwaves(7, 8) > cons_minwaves(3, 8)) {
-            mode = 7; ax.drop_G = 1;
-        }
-        if (a.gm_prev && mode == 3) { mode = 7; ax.drop_G = 1; }   // the previous-state operand lives in the stage-2 variant (coefficient form)
-        // ... and the first stage without a G store (MODE 1, two workgroups per CU) on the MODE-5 variant, likewise
-        if (formulation == 0 && mode == 1 && sizeof(T) == 8 && cons_minwaves(5, 8) > cons_minwaves(1, 8)) {
-            mode = 5; ax.drop_G = 1;
-        }
-        const MarchGeometry mg = tendency_march_geometry(a.Nx, rows, formulation, a.leave_room, (int)sizeof(T), mode);
+        const int mode = march_stage_mode(ax, formulation);
+        const bool packed = sizeof(T) == 4 && tendency_uses_packed_fp32(a.Nx, formulation, a.wrap);   // two columns per lane, packed arithmetic
+        const MarchGeometry mg = packed ? packed_fp32_geometry(a.Nx, rows, a.leave_room)
+                                        : tendency_march_geometry(a.Nx, rows, formulation, a.leave_room, (int)sizeof(T), mode);
         const int nstrips = mg.nstrips, LY = mg.LY, nseg = two ? two_range_segments(LY) : mg.nseg;
-        dim3 mgrid(nstrips * nseg), mblock(mg.nt);
-        if (formulation == 1) {
-#define SW_VI_GO(NT_, MODE_)                                                                                                \
-            do {                                                                                                                \
-                if (lorentz == 1) hipLaunchKernelGGL((k_tendency_vi_march<T, 1, NT_, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY); \
-                else hipLaunchKernelGGL((k_tendency_vi_march<T, 0, NT_, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY);            \
-            } while (0)
-#define SW_VI_MARCH(MODE_)                                                                                                  \
-            case MODE_:                                                                                                         \
-                if (mg.nt == 128) SW_VI_GO(128, MODE_);                                                                         \
-                else SW_VI_GO(256, MODE_);                                                                                      \
-                break;
-            switch (mode) { SW_VI_MARCH(4) SW_VI_MARCH(5) SW_VI_MARCH(1) SW_VI_MARCH(7) SW_VI_MARCH(3) SW_VI_MARCH(9) SW_VI_MARCH(11)
-                            default: return hipErrorInvalidValue; }
-#undef SW_VI_MARCH
-#undef SW_VI_GO
-        } else {
-#define SW_CONS_MARCH(MODE_)                                                                                                \
-            case MODE_:                                                                                                         \
-                if (mg.nt == 128) {                                                                                             \
-                    if (lorentz == 2) hipLaunchKernelGGL((k_tendency_cons_march<T, 2, 128, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY); \
-                    else hipLaunchKernelGGL((k_tendency_cons_march<T, 0, 128, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY);            \
-                } else {                                                                                                        \
-                    if (lorentz == 2) hipLaunchKernelGGL((k_tendency_cons_march<T, 2, 256, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY); \
-                    else hipLaunchKernelGGL((k_tendency_cons_march<T, 0, 256, MODE_>), mgrid, mblock, 0, s, ax, nstrips, nseg, LY);            \
-                }                                                                                                               \
-                break;
-            switch (mode) { SW_CONS_MARCH(4) SW_CONS_MARCH(5) SW_CONS_MARCH(1) SW_CONS_MARCH(7) SW_CONS_MARCH(3) SW_CONS_MARCH(9) SW_CONS_MARCH(11)
-                            default: return hipErrorInvalidValue; }
-#undef SW_CONS_MARCH
-        }
+        const MarchKernel<T> k = march_kernel<T>(mode, formulation, lorentz, mg.nt, packed);
+        if (!k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k, dim3(nstrips * nseg), dim3(mg.nt), 0, s, ax, nstrips, nseg, LY);
         return hipGetLastError();
     }
 #endif
@@ -487,30 +470,11 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
     if (!(a.topo_x == 1 || a.topo_y == 1) && (long)a.Nx * rows < SW_MARCH_MIN_CELLS) {
         constexpr int RY1 = 1;
         const int nty1 = (a.j1 - a.j0 + TYB * RY1 - 1) / (TYB * RY1) + (rows_b + TYB * RY1 - 1) / (TYB * RY1);
-        dim3 grid1(ntx * nty1), block1(TX, TYB);
-        if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY1>), grid1, block1, 0, s, a, ntx, nty1);
-        else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY1>), grid1, block1, 0, s, a, ntx, nty1);
-        else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY1>), grid1, block1, 0, s, a, ntx, nty1);
-        else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY1>), grid1, block1, 0, s, a, ntx, nty1);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
+        return launch_tile<T, RY1>(a, formulation, lorentz, ntx, nty1, s);
     }
 #endif
-    dim3 grid(ntx * nty), block(TX, TYB);
-    if (a.topo_x == 1 || a.topo_y == 1) {
-        if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY, true>), grid, block, 0, s, a, ntx, nty);
-        else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY, true>), grid, block, 0, s, a, ntx, nty);
-        else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY, true>), grid, block, 0, s, a, ntx, nty);
-        else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY, true>), grid, block, 0, s, a, ntx, nty);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (a.topo_x == 1 || a.topo_y == 1) return launch_tile<T, RY, true>(a, formulation, lorentz, ntx, nty, s);
+    return launch_tile<T, RY>(a, formulation, lorentz, ntx, nty, s);
 }
 
 template <typename T>

@@ -613,3 +613,36 @@ def test_second_stage_with_the_previous_state_as_operand(swmhd, form, dtype, N):
         assert np.array_equal(ga.numpy()[I], gb.numpy()[I])                 # the tendencies themselves do not depend on the operand
     assert f(P(U1), P(U2b), P(G1b), P(U2b), *args, dt, g2, z2 / g1, 1, 0, g.Ny, flags | L.GM_IS_PREV_STATE | L.STRICT, None) == 3     # SWMHD_ENOTSUP
     assert f(P(U1), P(U2b), P(G1b), None, *args, dt, g2, z2 / g1, 1, 0, g.Ny, flags | L.GM_IS_PREV_STATE, None) == 1                  # no operand: SWMHD_EINVAL
+
+
+@pytest.mark.parametrize("form,dtype", [("VectorInvariant", torch.float32), ("Conservative", torch.float64)])
+def test_previous_state_stage_without_G_store_leaves_Gn_alone(swmhd, form, dtype):
+    """swmhd.h: Gn is written only when store_G != 0.  A SWMHD_GM_IS_PREV_STATE stage with store_G = 0 runs on the G-storing kernel
+    variant with its G stores dropped; at N = 1024 with WRAP_X | WRAP_Y that is the packed-fp32 kernel (fp32 vector invariant) and the
+    fp64 conservative marching kernel.  The Gn buffers must keep their sentinel."""
+    S, L = swmhd, swmhd._lib
+    from test_model_oracle import hf, uf, vf, Af, Lx, Ly
+    N = 1024
+    g = S.RectilinearGrid(size=(N, N), x=(0, Lx), y=(0, Ly))
+    m = S.ShallowWaterModel(g, 9.81, 1.0, formulation=form, dtype=dtype)
+    if form == "VectorInvariant":
+        m.set(u=uf, v=vf, h=hf, A=Af)
+    else:
+        m.set(uh=lambda X, Y: hf(X, Y) * uf(X, Y), vh=lambda X, Y: hf(X, Y) * vf(X, Y), h=hf, A=Af)
+    f = getattr(L.lib(), f"swmhd_tendencies_rk3_{m.sfx}")
+    P = lambda fl: L.ptr_array([x.ptr for x in fl])
+    U = list(m.fields)
+    Unew = [S.Field(g, dtype=dtype, data=x.data.clone()) for x in U]     # holds the previous state (here: U itself) on entry
+    sentinel = 1234.5
+    Gn = [S.Field(g, dtype=dtype) for _ in range(4)]
+    for x in Gn:
+        x.data.fill_(sentinel)
+    args = (g.Nx, g.Ny, g.Hx, g.Hy, U[0].stride_y, g.dx, g.dy, 9.81, 1.0, m.form_code, m.lorentz_code)
+    g2, g3, z3 = 5.0 / 12.0, 3.0 / 4.0, -5.0 / 12.0
+    L.check(f(P(U), P(Unew), P(Gn), P(Unew), *args, 2e-4, g3, z3 / g2, 0, 0, g.Ny, L.WRAP_X | L.WRAP_Y | L.GM_IS_PREV_STATE, None),
+            "last stage, previous state, no G store")
+    torch.cuda.synchronize()
+    for x in Gn:
+        assert np.all(x.numpy() == np.asarray(sentinel, dtype=x.numpy().dtype))
+    for x in Unew:
+        assert np.isfinite(x.numpy()[g.interior]).all()
