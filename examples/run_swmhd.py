@@ -11,6 +11,10 @@ reference's (SWMHD_example.jl:47-61: time, iteration, max|u|, max|A|, min h, wal
 sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the fields incl. halos as .npy (the JLD2 writer's role, :80-84).
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
 
+    python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
+runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
+step): one progress line per member, and --energies gets a leading `member` column.
+
     python examples/run_swmhd.py --plot-case jacobian_formulation/128x128_two_Gaussians_low_B
 re-runs one of the twelve runs behind the reference's committed energy plots (energy_plots/*/*.png; set-up from the scripts' commented
 alternatives, see tests/plot_cases.py) and prints, beside every energy row, the value read off the plot at that time
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--dt", type=float, default=0.01)
     ap.add_argument("--ic", choices=["uniform", "gaussians"], default="uniform")
     ap.add_argument("--amp", type=float, default=None, help="A amplitude (default 0.5 for |y|, 0.1 / 0.5 for the Gaussians)")
+    ap.add_argument("--amps", default=None, help="comma-separated A amplitudes: one ensemble member per amplitude")
     ap.add_argument("--every", type=int, default=100, help="iterations between progress lines / energy rows")
     ap.add_argument("--energies", default=None, help="CSV file for (time, KE, ME, PE, total)")
     ap.add_argument("--dump-every", type=float, default=0.0, help="model time between field dumps (0 = none)")
@@ -36,6 +41,8 @@ def main():
     a = ap.parse_args()
     if a.plot_case:
         return plot_case(a)
+    if a.amps:
+        return run_ensemble(a)
 
     import torch
     import swmhd_amd as S
@@ -82,6 +89,52 @@ def main():
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
+
+
+def run_ensemble(a):
+    """--amps: the same run for several A amplitudes, one ensemble member each."""
+    import torch
+    import swmhd_amd as S
+    from swmhd_amd import configs
+    amps = [float(x) for x in a.amps.split(",") if x.strip()]
+    N, L = a.size, 10.0
+    grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
+    form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
+    ens = S.ShallowWaterEnsemble(grid, len(amps), configs.G, configs.F, formulation=form)
+    A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
+    u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
+    v0 = lambda X, Y: -5 * X * np.exp(-(X ** 2 + Y ** 2))
+    n1, n2 = ens.names[:2]
+    ens.set(**{n1: u0, n2: v0, "h": lambda X, Y: np.ones_like(X), "A": A0})
+    nsteps = int(round(a.stop_time / a.dt))
+    rows = []
+
+    def report(wall):
+        for m, d in enumerate(ens.diagnostics()):
+            print(f"member {m} (amp {amps[m]:g}) Time: {ens.clock_time:9.3f}, iteration: {ens.iteration}, "
+                  f"max(|u|): {max(d['max_abs_u'], d['max_abs_v']):.2e}, max(|A|): {d['max_abs_A']:.2e}, min(h): {d['min_h']:.2e}, "
+                  f"wall time: {wall * 1e3:.1f} ms | KE {d['kinetic_energy']:.6f} ME {d['magnetic_energy']:.6f} "
+                  f"PE {d['potential_energy']:.3e} total {d['total_energy']:.6f}", flush=True)
+            rows.append((m, ens.clock_time, d["kinetic_energy"], d["magnetic_energy"], d["potential_energy"], d["total_energy"]))
+
+    report(0.0)
+    e0 = [r[5] for r in rows]
+    ens.time_step(a.dt)
+    ens.capture_graph(a.dt)
+    t_start = time.perf_counter()
+    while ens.iteration < nsteps:
+        n = min(a.every - ens.iteration % a.every, nsteps - ens.iteration)
+        t0 = time.perf_counter()
+        ens.time_steps(n, a.dt)
+        ens.synchronize()
+        report(time.perf_counter() - t0)
+    total = time.perf_counter() - t_start
+    drift = ", ".join(f"{abs(rows[-len(amps) + m][5] - e0[m]) * 100:.4f}" for m in range(len(amps)))
+    print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations of {len(amps)} members, "
+          f"{len(amps) * N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); energy drift abs(E - E0) * 100 per member = {drift}")
+    if a.energies:
+        with open(a.energies, "w", newline="") as f:
+            w = csv.writer(f); w.writerow(["member", "time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
 
 
 def plot_case(a):

@@ -405,6 +405,67 @@ int swmhd_diagnostics_f32(const float *q1, const float *q2, const float *h, cons
                           float g, float h_ref, int formulation, int j_begin, int j_end,
                           double *workspace, double *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ensembles: `members` independent runs of ONE periodic grid stepped together -- the reference's runs are sweeps of small grids
+ * (64^2, 128^2; initial conditions that differ in the amplitude of A), where one grid fills a few percent of the chip.  Every
+ * member has the same Nx, Ny, Hx, Hy, stride_y, dx, dy, g, f, formulation, forcing, precision and dt; members differ in their state.
+ * Layout: field f of member m is the halo-padded parent (conventions above) at  ptr[f] + m * stride_m  (elements), for every pointer
+ * argument; stride_m >= (Ny + 2Hy) * stride_y.  A larger stride_m (pitched members) is allowed: nothing between two members is read
+ * or written.  1 <= members <= SWMHD_ENSEMBLE_MAX_MEMBERS.  All members of a call run in one launch per kernel.
+ * Every argument is checked before any HIP call.  Besides the single-grid checks of the corresponding call:
+ *   SWMHD_EINVAL   members out of range, stride_m too small, unknown flags
+ *   SWMHD_ENOTSUP  SWMHD_BOUNDED_X / _Y, SWMHD_MARCH_KERNEL, SWMHD_GM_IS_PREV_STATE, SWMHD_LEAVE_ROOM (periodic members on the
+ *                  LDS-tiled kernel only)
+ * Accepted flags: SWMHD_STRICT, SWMHD_TILE_KERNEL (the only kernel), SWMHD_WRAP_X, SWMHD_WRAP_Y, SWMHD_RK3_ANCHOR (tendencies only).
+ * Results: each member gets exactly the arithmetic of the single-grid call on that member: SWMHD_STRICT members are bit-identical to
+ * the oracle; fast members below ~0.33 Mcell (the reference's grids) are bit-identical to swmhd_tendencies_rk3 / swmhd_step_rk3 on
+ * the member alone (same tile shape, same compiled body); larger fast members run the LDS-tiled kernel where a single grid would
+ * march, within the fast tolerances above.  A non-finite member does not affect the others.
+ * ---------------------------------------------------------------------------------------------- */
+#define SWMHD_ENSEMBLE_MAX_MEMBERS 65535
+/* swmhd_ensemble_tendencies_rk3: swmhd_tendencies_rk3 over all rows of every member (q, qnew, Gn, Gm: HOST arrays of 4 device pointers
+ * to member 0's parents).  Semantics of store_G, Gm == NULL, SWMHD_RK3_ANCHOR and the WRAP flags as there. */
+int swmhd_ensemble_tendencies_rk3_f64(const double *const *q, double *const *qnew, double *const *Gn, const double *const *Gm,
+                                      int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                      double dx, double dy, double g, double f, int formulation, int lorentz,
+                                      double dt, double gamma, double zeta, int store_G, int flags, void *stream);
+int swmhd_ensemble_tendencies_rk3_f32(const float *const *q, float *const *qnew, float *const *Gn, const float *const *Gm,
+                                      int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                      float dx, float dy, float g, float f, int formulation, int lorentz,
+                                      float dt, float gamma, float zeta, int store_G, int flags, void *stream);
+/* swmhd_ensemble_step_rk3: swmhd_step_rk3 for every member -- the same stage schedule (anchor form in fast builds, G- form with
+ * SWMHD_STRICT), the same buffer rotation and *state_in_alt, and with WRAP flags the same stale halos, for all members at once:
+ * 3 launches per step with SWMHD_WRAP_X | SWMHD_WRAP_Y, 6 without (stage + one periodic fill of every member). */
+int swmhd_ensemble_step_rk3_f64(double *const *q, double *const *q_alt, double *const *Ga, double *const *Gb,
+                                int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                double dx, double dy, double g, double f, int formulation, int lorentz, double dt, int nsteps,
+                                int flags, int *state_in_alt, void *stream);
+int swmhd_ensemble_step_rk3_f32(float *const *q, float *const *q_alt, float *const *Ga, float *const *Gb,
+                                int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                float dx, float dy, float g, float f, int formulation, int lorentz, float dt, int nsteps,
+                                int flags, int *state_in_alt, void *stream);
+/* swmhd_ensemble_fill_halo_periodic: swmhd_fill_halo_periodic_multi (1..4 fields, `which` = SWMHD_HALO_X | SWMHD_HALO_Y) of every
+ * member, one launch.  flags: none. */
+int swmhd_ensemble_fill_halo_periodic_f64(double *const *fields, int nfields, int members, int64_t stride_m, int Nx, int Ny,
+                                          int Hx, int Hy, int64_t stride_y, int which, void *stream);
+int swmhd_ensemble_fill_halo_periodic_f32(float *const *fields, int nfields, int members, int64_t stride_m, int Nx, int Ny,
+                                          int Hx, int Hy, int64_t stride_y, int which, void *stream);
+/* swmhd_ensemble_diagnostics: swmhd_diagnostics over all rows of every member, two launches for the whole ensemble.
+ *   out = members x 7 doubles (member m at out + 7m, order as swmhd_diagnostics), DEVICE memory; no host synchronisation.
+ *   workspace: >= SWMHD_ENSEMBLE_DIAG_WORKSPACE(members, Nx, Ny) doubles of DEVICE memory.
+ * Each member's 7 values are bitwise equal to swmhd_diagnostics_* on that member alone (same partition of the cells, same fold
+ * order; partial blocks that would own no cell are not launched and enter the fold as the exact identity element). */
+#define SWMHD_ENSEMBLE_DIAG_WORKSPACE(members, Nx, Ny) \
+    ((int64_t)(members) * 7 * ((int64_t)(Nx) * (Ny) >= 1024 * 256 ? 1024 : ((int64_t)(Nx) * (Ny) + 255) / 256))
+int swmhd_ensemble_diagnostics_f64(const double *q1, const double *q2, const double *h, const double *A,
+                                   int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                   double dx, double dy, double g, double h_ref, int formulation,
+                                   double *workspace, double *out, void *stream);
+int swmhd_ensemble_diagnostics_f32(const float *q1, const float *q2, const float *h, const float *A,
+                                   int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                   float dx, float dy, float g, float h_ref, int formulation,
+                                   double *workspace, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,8 @@ from .fields import Field
 from .operators import lorentz_force_func, div_lorentz
 from .model import ShallowWaterModel, loopback_rings, VectorInvariantFormulation, ConservativeFormulation
 from .distributed import SlabDecomposition, exchange_y_halos
+from .ensemble import ShallowWaterEnsemble
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
-           "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "_lib"]
+           "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble", "_lib"]

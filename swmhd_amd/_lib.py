@@ -20,6 +20,13 @@ KERNEL_FLAGS = {None: 0, "auto": 0, "tile": 2, "march": 4}
 PERIODIC, BOUNDED = 0, 1
 HALO_X, HALO_Y = 1, 2
 DIAG_NOUT, DIAG_WORKSPACE = 7, 1024 * 7
+ENSEMBLE_MAX_MEMBERS = 65535
+
+
+def ensemble_diag_workspace(members, Nx, Ny):
+    """SWMHD_ENSEMBLE_DIAG_WORKSPACE(members, Nx, Ny): doubles of device workspace swmhd_ensemble_diagnostics_* needs."""
+    cells = Nx * Ny
+    return members * 7 * (1024 if cells >= 1024 * 256 else (cells + 255) // 256)
 CONSERVATIVE, VECTOR_INVARIANT = 0, 1
 LORENTZ_NONE, LORENTZ_JACOBIAN, LORENTZ_DIVERGENCE = 0, 1, 2
 
@@ -83,6 +90,18 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_rk3_substep_{sfx}")
         f.argtypes = [C.POINTER(p), C.POINTER(p), C.POINTER(p), i, i, i, i, i64, ft, ft, ft, i, i, i, p]
         f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_tendencies_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, ft, ft, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_step_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, i, i, C.POINTER(i), p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_fill_halo_periodic_{sfx}")
+        f.argtypes = [C.POINTER(p), i, i, i64, i, i, i, i, i64, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_diagnostics_{sfx}")
+        f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, ft, ft, i, p, p, p]
+        f.restype = i
         f = getattr(lib, f"swmhd_ring_exchange_y_{sfx}")
         f.argtypes = [p, C.POINTER(p), i, i, i, i, i, i64, p]
         f.restype = i
@@ -118,7 +137,8 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
     f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in (
         "lorentz_jacobian", "lorentz_jacobian_rows", "lorentz_divergence", "lorentz_divergence_rows",
         "fill_halo", "fill_halo_periodic", "fill_halo_periodic_multi", "tendencies", "tendencies_rk3", "rk3_substep", "step_rk3", "diagnostics",
-        "ring_exchange_y", "ring_step_rk3")] + [
+        "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
+        "ensemble_diagnostics")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace swmhd {
 
@@ -35,9 +36,10 @@ template <typename T> hipError_t launch_lorentz_divergence_strict(const OpArgs<T
 template <typename T>
 hipError_t launch_fill_halo_periodic(T *interior, int Nx, int Ny, int Hx, int Hy, long sy, int which, hipStream_t s);
 // up to 4 fields in one launch; corners resolved by wrapping both coordinates, so x and y halos need no ordering
+// members > 0: an ensemble -- the same fill for each of `members` copies at interiors[k] + m * stride_m, in one launch
 template <typename T>
 hipError_t launch_fill_halo_periodic_multi(T *const *interiors, int nfields, int Nx, int Ny, int Hx, int Hy, long sy,
-                                           int which, hipStream_t s);
+                                           int which, hipStream_t s, int members = 0, long stride_m = 0);
 // fill_halo_regions! for any (Periodic | Bounded) topology pair with Oceananigans' default boundary conditions or gradient BCs
 // (oracle_fill_halo): west/east pass, then south/north pass over the padded width.  face_x/face_y: bit f set = field f is
 // located at Face in that direction; grad[f][4] = west, east, south, north GradientBoundaryCondition values (NaN = default).
@@ -86,6 +88,16 @@ struct TendArgs {
                           // through G1..GA; later stages read W from Gm and store Unew = W + dtg G.  No G store in either.
     T dtw;                // dt * (gamma1 + zeta2), formed on the host like dtg (first anchored stage only)
 };
+// Ensemble launches (swmhd_ensemble_*): `members` copies of one periodic grid stepped together, member m of every parent at
+// ptr + m * stride_m (elements).  The tile kernel's ENS variant adds that offset to all of its field pointers.
+template <typename T>
+struct EnsTendArgs : TendArgs<T> {
+    long stride_m;
+    int members;
+    int fold;             // 1: the member is folded into blockIdx.x (XCD-remapped over all tiles of all members, so a member's tiles
+                          // share an XCD); 0: the member is blockIdx.y and the remap runs over the tiles of one member
+};
+template <typename T, bool ENS> using TileArgs = std::conditional_t<ENS, EnsTendArgs<T>, TendArgs<T>>;
 // ---- RK3 stage schedule of the step drivers (step_common in swmhd_api.hip, both schedules of ring_step in ring.hip) --------------
 // Oceananigans' RungeKutta3 (TimeSteppers): gamma = 8/15, 5/12, 3/4; zeta = -, -17/60, -5/12.  Since gamma1 + zeta2 = 1/4 and
 // zeta3 = -gamma2, the step is exactly
@@ -260,6 +272,10 @@ template <typename T> hipError_t launch_tendency_fast(const TendArgs<T> &a, int 
 int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, int kernel_variant, int leave_room, int wrap, int out[8]);
 template <typename T> hipError_t launch_tendency_strict(const TendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_rk3_substep_fast(const Rk3Args<T> &a, hipStream_t s);
+// ensemble stage: every tile of every member in one launch of the LDS-tiled kernel (rows [a.j0, a.j1) of each member; no second range,
+// no Bounded frame).  The launcher sets a.fold.
+template <typename T> hipError_t launch_tendency_ensemble_fast(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
+template <typename T> hipError_t launch_tendency_ensemble_strict(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 // internal twins of swmhd_tendencies_rk3_* and swmhd_fill_halo_periodic_multi_* for the slab driver (ring.hip), same argument checks
 // and return codes; the first serves rows [j0, j1) and [j0b, j1b) of one RK3 stage in ONE launch where the kernel chosen supports it
 // (an empty second range: exactly the exported call)
@@ -271,10 +287,11 @@ template <typename T>
 int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which, void *stream);
 template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, hipStream_t s);
 
-// energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory)
+// energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
+// rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE
 template <typename T>
 hipError_t launch_diagnostics(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int j0, int j1, long sy, T dx, T dy,
-                              T grav, T href, int form, double *workspace, double *out, hipStream_t s);
+                              T grav, T href, int form, double *workspace, double *out, hipStream_t s, int members = 0, long stride_m = 0);
 
 // Periodic "gather on read": with TendArgs::wrap the tendency kernels map a halo index to its periodic image in the interior when
 // they LOAD (one integer select per row / per lane, outside the arithmetic), so the state needs no halo-fill launch between RK3

@@ -31,6 +31,16 @@ struct DiagArgs {
     double *out;    // [NQ]
 };
 
+// Ensemble: member blockIdx.y (partials) / blockIdx.x (final) at ptr + member * stride_m.  Only the nb partial blocks that own cells
+// run (nb = ceil(cells / NT) <= NB); the final fold takes the identity element in place of every empty block's partial -- exactly what
+// an empty block of the single-grid launch writes -- so each member's 7 values are bitwise those of swmhd_diagnostics on it alone.
+template <typename T>
+struct DiagArgsEns : DiagArgs<T> {
+    long stride_m;
+    int nb;
+};
+template <typename T, bool ENS> using DiagArgsT = std::conditional_t<ENS, DiagArgsEns<T>, DiagArgs<T>>;
+
 __device__ __forceinline__ void fold(double *acc, const double *v) {
     acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2];
     acc[3] = fmax(acc[3], v[3]); acc[4] = fmax(acc[4], v[4]); acc[5] = fmax(acc[5], v[5]); acc[6] = fmin(acc[6], v[6]);
@@ -54,9 +64,14 @@ __device__ void block_reduce(double *acc, double (*sm)[NQ]) {
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NT) void k_diag_partial(DiagArgs<T> a) {
+template <typename T, bool ENS = false>
+__global__ __launch_bounds__(NT) void k_diag_partial(DiagArgsT<T, ENS> a) {
     __shared__ double sm[NT][NQ];
+    if constexpr (ENS) {
+        const long o = (long)blockIdx.y * a.stride_m;
+        a.q1 += o; a.q2 += o; a.h += o; a.A += o;
+        a.part += (long)blockIdx.y * a.nb * NQ;
+    }
     double acc[NQ] = {0, 0, 0, 0, 0, 0, 1e300};
     const double rdx = 1.0 / (double)a.dx, rdy = 1.0 / (double)a.dy;
     const long ncell = (long)a.Nx * (a.j1 - a.j0);
@@ -98,11 +113,21 @@ __global__ __launch_bounds__(NT) void k_diag_partial(DiagArgs<T> a) {
         for (int q = 0; q < NQ; ++q) a.part[(long)blockIdx.x * NQ + q] = sm[0][q];
 }
 
-template <typename T>
-__global__ __launch_bounds__(NT) void k_diag_final(DiagArgs<T> a) {
+template <typename T, bool ENS = false>
+__global__ __launch_bounds__(NT) void k_diag_final(DiagArgsT<T, ENS> a) {
     __shared__ double sm[NT][NQ];
     double acc[NQ] = {0, 0, 0, 0, 0, 0, 1e300};
-    for (int b = threadIdx.x; b < NB; b += NT) fold(acc, a.part + (long)b * NQ);
+    if constexpr (ENS) {
+        a.part += (long)blockIdx.x * a.nb * NQ;
+        a.out += (long)blockIdx.x * NQ;
+        const double id[NQ] = {0, 0, 0, 0, 0, 0, 1e300};
+        for (int b = threadIdx.x; b < NB; b += NT) {
+            if (b < a.nb) fold(acc, a.part + (long)b * NQ);
+            else fold(acc, id);
+        }
+    } else {
+        for (int b = threadIdx.x; b < NB; b += NT) fold(acc, a.part + (long)b * NQ);
+    }
     block_reduce(acc, sm);
     if (threadIdx.x == 0) {
         const double cell = (double)a.dx * (double)a.dy;
@@ -115,16 +140,27 @@ __global__ __launch_bounds__(NT) void k_diag_final(DiagArgs<T> a) {
 
 template <typename T>
 hipError_t launch_diagnostics(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int j0, int j1, long sy, T dx, T dy,
-                              T grav, T href, int form, double *workspace, double *out, hipStream_t s) {
+                              T grav, T href, int form, double *workspace, double *out, hipStream_t s, int members, long stride_m) {
     DiagArgs<T> a{q1, q2, h, A, Nx, Ny, j0, j1, sy, dx, dy, grav, href, form, workspace, out};
+    if (members > 0) {
+        DiagArgsEns<T> e;
+        static_cast<DiagArgs<T> &>(e) = a;
+        e.stride_m = stride_m;
+        const long ncell = (long)Nx * (j1 - j0);
+        e.nb = ncell >= (long)NB * NT ? NB : (int)((ncell + NT - 1) / NT);
+        if (e.nb < 1) e.nb = 1;
+        hipLaunchKernelGGL((k_diag_partial<T, true>), dim3(e.nb, members), dim3(NT), 0, s, e);
+        hipLaunchKernelGGL((k_diag_final<T, true>), dim3(members), dim3(NT), 0, s, e);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((k_diag_partial<T>), dim3(NB), dim3(NT), 0, s, a);
     hipLaunchKernelGGL((k_diag_final<T>), dim3(1), dim3(NT), 0, s, a);
     return hipGetLastError();
 }
 template hipError_t launch_diagnostics<double>(const double *, const double *, const double *, const double *, int, int, int, int, long,
-                                               double, double, double, double, int, double *, double *, hipStream_t);
+                                               double, double, double, double, int, double *, double *, hipStream_t, int, long);
 template hipError_t launch_diagnostics<float>(const float *, const float *, const float *, const float *, int, int, int, int, long, float,
-                                              float, float, float, int, double *, double *, hipStream_t);
+                                              float, float, float, int, double *, double *, hipStream_t, int, long);
 
 }  // namespace swmhd
 

@@ -38,7 +38,11 @@ struct HaloMulti {
     long sy;
 };
 template <typename T>
-__global__ void k_halo_multi(HaloMulti<T> a) {
+struct HaloMultiEns : HaloMulti<T> {
+    long stride_m;   // ensemble: member blockIdx.y at f[k] + blockIdx.y * stride_m
+};
+template <typename T, bool ENS = false>
+__global__ void k_halo_multi(std::conditional_t<ENS, HaloMultiEns<T>, HaloMulti<T>> a) {
     // cells are enumerated as: [south+north strips: 2*Hy rows x (Nx+2Hx)] then [west+east strips: Ny rows x 2*Hx]
     const int W = a.Nx + 2 * a.Hx;
     const long nsn = (a.which & 2) ? (long)2 * a.Hy * W : 0;
@@ -61,7 +65,8 @@ __global__ void k_halo_multi(HaloMulti<T> a) {
     int sy_ = y < 0 ? y + a.Ny : (y >= a.Ny ? y - a.Ny : y);
     if (!(a.which & 2)) sy_ = y;
     if (!(a.which & 1)) sx = x;
-    const long dst = (long)y * a.sy + x, src = (long)sy_ * a.sy + sx;
+    long dst = (long)y * a.sy + x, src = (long)sy_ * a.sy + sx;
+    if constexpr (ENS) { dst += (long)blockIdx.y * a.stride_m; src += (long)blockIdx.y * a.stride_m; }
     for (int k = 0; k < a.nf; ++k) a.f[k][dst] = a.f[k][src];
 }
 
@@ -107,17 +112,18 @@ template hipError_t launch_fill_halo_bc<float>(const HaloBc<float> &, hipStream_
 
 template <typename T>
 hipError_t launch_fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which,
-                                           hipStream_t s) {
-    HaloMulti<T> a;
+                                           hipStream_t s, int members, long stride_m) {
+    HaloMultiEns<T> a;
     for (int k = 0; k < 4; ++k) a.f[k] = k < nf ? f[k] : nullptr;
-    a.nf = nf; a.Nx = Nx; a.Ny = Ny; a.Hx = Hx; a.Hy = Hy; a.which = which; a.sy = sy;
+    a.nf = nf; a.Nx = Nx; a.Ny = Ny; a.Hx = Hx; a.Hy = Hy; a.which = which; a.sy = sy; a.stride_m = stride_m;
     long n = ((which & 2) ? (long)2 * Hy * (Nx + 2 * Hx) : 0) + ((which & 1) ? (long)Ny * 2 * Hx : 0);
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL((k_halo_multi<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    if (members > 0) hipLaunchKernelGGL((k_halo_multi<T, true>), dim3((unsigned)((n + 255) / 256), members), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_halo_multi<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, static_cast<const HaloMulti<T> &>(a));
     return hipGetLastError();
 }
-template hipError_t launch_fill_halo_periodic_multi<double>(double *const *, int, int, int, int, int, long, int, hipStream_t);
-template hipError_t launch_fill_halo_periodic_multi<float>(float *const *, int, int, int, int, int, long, int, hipStream_t);
+template hipError_t launch_fill_halo_periodic_multi<double>(double *const *, int, int, int, int, int, long, int, hipStream_t, int, long);
+template hipError_t launch_fill_halo_periodic_multi<float>(float *const *, int, int, int, int, int, long, int, hipStream_t, int, long);
 
 template <typename T>
 hipError_t launch_fill_halo_periodic(T *f, int Nx, int Ny, int Hx, int Hy, long sy, int which, hipStream_t s) {

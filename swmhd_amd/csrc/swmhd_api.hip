@@ -10,6 +10,23 @@ namespace {
 
 inline int hiprc(hipError_t e) { return e == hipSuccess ? SWMHD_OK : -(int)e; }
 
+// Ensemble calls (swmhd_ensemble_*): `members` copies of one periodic grid, member m of every parent at ptr + m * stride_m.  The
+// single-grid helpers below take it as an optional last argument and check everything else exactly as for one grid.
+struct Ens {
+    int members;
+    int64_t stride_m;
+};
+constexpr int ENS_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_RK3_ANCHOR;
+constexpr int ENS_NOTSUP = SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_LEAVE_ROOM;
+// the checks of the ensemble itself (the caller's single-grid checks follow): member count, member stride, flags
+inline int ens_check(const Ens &e, int Ny, int Hy, int64_t sy, int flags) {
+    if (e.members < 1 || e.members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
+    if (Ny <= 0 || Hy < 0 || sy <= 0 || e.stride_m < ((int64_t)Ny + 2 * Hy) * sy) return SWMHD_EINVAL;
+    if (flags & ~(ENS_FLAGS | ENS_NOTSUP)) return SWMHD_EINVAL;
+    if (flags & ENS_NOTSUP) return SWMHD_ENOTSUP;
+    return SWMHD_OK;
+}
+
 template <typename T>
 int lorentz_common(bool divergence, const T *A, const T *h, T *Fx, T *Fy, int Nx, int Ny, int Hx, int Hy,
                    int64_t sy, T dx, T dy, int topo_x, int topo_y, int j_begin, int j_end, int flags, void *stream) {
@@ -49,7 +66,11 @@ int halo_common(T *f, int Nx, int Ny, int Hx, int Hy, int64_t sy, int which, voi
 }
 
 template <typename T>
-int halo_multi_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int which, void *stream) {
+int halo_multi_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int which, void *stream, const Ens *ens = nullptr) {
+    if (ens) {
+        const int rc = ens_check(*ens, Ny, Hy, sy, 0);
+        if (rc) return rc;
+    }
     if (!f || nf < 1 || nf > 4 || Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
     if (Hx > Nx || Hy > Ny) return SWMHD_EHALO;
     if (which & ~(SWMHD_HALO_X | SWMHD_HALO_Y)) return SWMHD_EINVAL;
@@ -58,7 +79,8 @@ int halo_multi_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64
         if (!f[k]) return SWMHD_EINVAL;
         p[k] = f[k] + (long)Hy * sy + Hx;
     }
-    return hiprc(launch_fill_halo_periodic_multi<T>(p, nf, Nx, Ny, Hx, Hy, (long)sy, which, (hipStream_t)stream));
+    return hiprc(launch_fill_halo_periodic_multi<T>(p, nf, Nx, Ny, Hx, Hy, (long)sy, which, (hipStream_t)stream, ens ? ens->members : 0,
+                                                    ens ? (long)ens->stride_m : 0));
 }
 
 template <typename T>
@@ -94,7 +116,11 @@ struct FuseRk3 {
 template <typename T>
 int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, T *Gh, T *GA, int Nx, int Ny, int Hx, int Hy,
                 int64_t sy, T dx, T dy, T grav, T fcor, int formulation, int lorentz, int j0, int j1, int flags, void *stream,
-                const FuseRk3<T> *rk = nullptr, int j0b = 0, int j1b = 0) {
+                const FuseRk3<T> *rk = nullptr, int j0b = 0, int j1b = 0, const Ens *ens = nullptr) {
+    if (ens) {
+        const int rc = ens_check(*ens, Ny, Hy, sy, flags);
+        if (rc) return rc;
+    }
     if (!q1 || !q2 || !h || !A || !G1 || !G2 || !Gh || !GA) return SWMHD_EINVAL;
     if (Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
     if (!(dx > T(0)) || !(dy > T(0))) return SWMHD_EINVAL;
@@ -148,6 +174,13 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
         for (int f = 0; f < 4; ++f) { a.Unew[f] = rk->Unew[f] + off; a.Gm[f] = rk->Gm ? rk->Gm[f] + off : nullptr; }
     }
     hipStream_t s = (hipStream_t)stream;
+    if (ens) {
+        EnsTendArgs<T> e;
+        static_cast<TendArgs<T> &>(e) = a;
+        e.stride_m = (long)ens->stride_m; e.members = ens->members; e.fold = 1;
+        return hiprc((flags & SWMHD_STRICT) ? launch_tendency_ensemble_strict<T>(e, formulation, lorentz, s)
+                                            : launch_tendency_ensemble_fast<T>(e, formulation, lorentz, s));
+    }
     return hiprc((flags & SWMHD_STRICT) ? launch_tendency_strict<T>(a, formulation, lorentz, s)
                                         : launch_tendency_fast<T>(a, formulation, lorentz, s));
 }
@@ -155,7 +188,11 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
 template <typename T>
 int tend_rk3_common(const T *const *q, T *const *qnew, T *const *Gn, const T *const *Gm, int Nx, int Ny, int Hx, int Hy, int64_t sy,
                     T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, T gamma, T zeta, int store_G, int j0, int j1,
-                    int flags, void *stream, int j0b = 0, int j1b = 0) {
+                    int flags, void *stream, int j0b = 0, int j1b = 0, const Ens *ens = nullptr) {
+    if (ens) {
+        const int rc = ens_check(*ens, Ny, Hy, sy, flags);
+        if (rc) return rc;
+    }
     if (!q || !qnew || !Gn) return SWMHD_EINVAL;
     for (int f = 0; f < 4; ++f) {
         if (!q[f] || !qnew[f] || !Gn[f] || (Gm && !Gm[f])) return SWMHD_EINVAL;
@@ -164,7 +201,7 @@ int tend_rk3_common(const T *const *q, T *const *qnew, T *const *Gn, const T *co
     }
     FuseRk3<T> rk{{qnew[0], qnew[1], qnew[2], qnew[3]}, Gm, dt, gamma, zeta, store_G ? 1 : 0};
     return tend_common<T>(q[0], q[1], q[2], q[3], Gn[0], Gn[1], Gn[2], Gn[3], Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation,
-                          lorentz, j0, j1, flags, stream, &rk, j0b, j1b);
+                          lorentz, j0, j1, flags, stream, &rk, j0b, j1b, ens);
 }
 
 template <typename T>
@@ -185,7 +222,12 @@ int rk3_common(T *const *U, const T *const *Gn, const T *const *Gm, int Nx, int 
 
 template <typename T>
 int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, T grav,
-                T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt, void *stream) {
+                T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt, void *stream,
+                const Ens *ens = nullptr) {
+    if (ens) {
+        const int rc = ens_check(*ens, Ny, Hy, sy, flags);
+        if (rc) return rc;
+    }
     if (!q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
     if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // the driver's halo fill is the periodic one
     Rk3Buffers<T> b;
@@ -197,10 +239,10 @@ int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx
         for (int st = 0; st < 3; ++st) {
             const Rk3Stage<T> g = b.stage(st, anchor);
             int rc = tend_rk3_common<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, g.gamma,
-                                        g.zeta, g.store_G, 0, Ny, flags | g.flags, stream);
+                                        g.zeta, g.store_G, 0, Ny, flags | g.flags, stream, 0, 0, ens);
             if (rc) return rc;
             b.rotate();
-            if (need && (rc = halo_multi_common<T>(b.cur, 4, Nx, Ny, Hx, Hy, sy, need, stream))) return rc;
+            if (need && (rc = halo_multi_common<T>(b.cur, 4, Nx, Ny, Hx, Hy, sy, need, stream, ens))) return rc;
         }
     if (state_in_alt) *state_in_alt = b.swaps & 1;
     return SWMHD_OK;
@@ -208,7 +250,11 @@ int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx
 
 template <typename T>
 int diag_common(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, T grav,
-                T href, int form, int j0, int j1, double *ws, double *out, void *stream) {
+                T href, int form, int j0, int j1, double *ws, double *out, void *stream, const Ens *ens = nullptr) {
+    if (ens) {
+        const int rc = ens_check(*ens, Ny, Hy, sy, 0);
+        if (rc) return rc;
+    }
     if (!q1 || !q2 || !h || !A || !ws || !out) return SWMHD_EINVAL;
     if (Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx || !(dx > T(0)) || !(dy > T(0))) return SWMHD_EINVAL;
     if (j0 < 0 || j1 > Ny || j0 > j1) return SWMHD_EINVAL;
@@ -216,7 +262,7 @@ int diag_common(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny
     if (Hx < 1 || Hy < 1) return SWMHD_EHALO;
     const long off = (long)Hy * sy + Hx;
     return hiprc(launch_diagnostics<T>(q1 + off, q2 + off, h + off, A + off, Nx, Ny, j0, j1, (long)sy, dx, dy, grav, href, form, ws,
-                                       out, (hipStream_t)stream));
+                                       out, (hipStream_t)stream, ens ? ens->members : 0, ens ? (long)ens->stride_m : 0));
 }
 
 }  // namespace
@@ -341,6 +387,33 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
     int swmhd_rk3_substep_##sfx(T *const *U, const T *const *Gn, const T *const *Gm, int Nx, int Ny, int Hx, int Hy,   \
                                 int64_t sy, T dt, T gamma, T zeta, int j0, int j1, int flags, void *stream) {          \
         return rk3_common<T>(U, Gn, Gm, Nx, Ny, Hx, Hy, sy, dt, gamma, zeta, j0, j1, flags, stream);                   \
+    }                                                                                                                  \
+    int swmhd_ensemble_tendencies_rk3_##sfx(const T *const *q, T *const *qnew, T *const *Gn, const T *const *Gm,       \
+                                            int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy,  \
+                                            T dx, T dy, T g, T f, int formulation, int lorentz, T dt, T gamma, T zeta,  \
+                                            int store_G, int flags, void *stream) {                                     \
+        const Ens e{members, stride_m};                                                                                \
+        return tend_rk3_common<T>(q, qnew, Gn, Gm, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, gamma,   \
+                                  zeta, store_G, 0, Ny, flags, stream, 0, 0, &e);                                       \
+    }                                                                                                                  \
+    int swmhd_ensemble_step_rk3_##sfx(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int members,           \
+                                      int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, T g, T f, \
+                                      int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt,     \
+                                      void *stream) {                                                                  \
+        const Ens e{members, stride_m};                                                                                \
+        return step_common<T>(q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, nsteps, flags, \
+                              state_in_alt, stream, &e);                                                               \
+    }                                                                                                                  \
+    int swmhd_ensemble_fill_halo_periodic_##sfx(T *const *f, int nf, int members, int64_t stride_m, int Nx, int Ny,     \
+                                                int Hx, int Hy, int64_t sy, int which, void *stream) {                  \
+        const Ens e{members, stride_m};                                                                                \
+        return halo_multi_common<T>(f, nf, Nx, Ny, Hx, Hy, sy, which, stream, &e);                                     \
+    }                                                                                                                  \
+    int swmhd_ensemble_diagnostics_##sfx(const T *q1, const T *q2, const T *h, const T *A, int members, int64_t stride_m, \
+                                         int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, T g, T href, int form,   \
+                                         double *ws, double *out, void *stream) {                                       \
+        const Ens e{members, stride_m};                                                                                \
+        return diag_common<T>(q1, q2, h, A, Nx, Ny, Hx, Hy, sy, dx, dy, g, href, form, 0, Ny, ws, out, stream, &e);    \
     }
 
 SWMHD_DEF_LORENTZ(f64, double)

@@ -24,12 +24,34 @@ constexpr bool STRICT = (SWMHD_STRICT != 0);
 #include "lorentz_device.inc"
 #include "sw_device.inc"
 
+// Ensemble workgroup (ENS variant): pick the member, point every field of `a` at it, return the tile index within the member.
+template <typename T>
+__device__ __forceinline__ unsigned ens_member(EnsTendArgs<T> &a, unsigned ntiles) {
+    unsigned m, t;
+    if (a.fold) {
+        const unsigned L = xcd_remap(blockIdx.x, ntiles * (unsigned)a.members);
+        m = L / ntiles; t = L - m * ntiles;
+    } else {
+        m = blockIdx.y; t = xcd_remap(blockIdx.x, ntiles);
+    }
+    const long o = (long)m * a.stride_m;
+    a.q1 += o; a.q2 += o; a.h += o; a.A += o;
+    a.G1 += o; a.G2 += o; a.Gh += o; a.GA += o;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        if (a.Unew[f]) a.Unew[f] += o;
+        if (a.Gm[f]) a.Gm[f] += o;
+    }
+    return t;
+}
+
 // FORM: 0 conservative, 1 vector invariant.  LOR: 0 none, 1 Jacobian (FORM 1 only), 2 divergence (FORM 0 only).
 // BND: at least one direction is Bounded -- reconstructions near walls drop to the boundary schemes (sw_device.inc) and the divergence-
 // form Lorentz fluxes take the reference's wall branches (sw_mhd_divergence_functions.jl:42-53,66-77,90-101,114-125).  With
 // BND = false every order is the compile-time constant 5 and the code is the periodic kernel.
-template <typename T, int FORM, int LOR, int TX, int TYB, int RY, bool BND = false>
-__global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TendArgs<T> a, int ntx, int nty) {
+// ENS: ensemble launch (EnsTendArgs) -- the workgroup's member offsets every field pointer; otherwise the body is the same.
+template <typename T, int FORM, int LOR, int TX, int TYB, int RY, bool BND = false, bool ENS = false>
+__global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS> a, int ntx, int nty) {
     constexpr int TY = TYB * RY, NT = TX * TYB;
     constexpr int W = TX + 6, HH = TY + 6;
     __shared__ T s1[HH][W];   // u | uh   (Face, Center)
@@ -44,7 +66,9 @@ __global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TendArgs<T> a, int nt
     __shared__ T sL2[LOR == 2 ? LH : 1][LOR == 2 ? LW : 1];
     __shared__ T sL3[LOR == 2 ? LH : 1][LOR == 2 ? LW : 1];
 
-    const unsigned bid = xcd_remap(blockIdx.x, (unsigned)(ntx * nty));
+    unsigned bid;
+    if constexpr (ENS) bid = ens_member<T>(a, (unsigned)(ntx * nty));
+    else bid = xcd_remap(blockIdx.x, (unsigned)(ntx * nty));
     // tile rows of the optional second row range follow those of the first
     const int tyi = (int)(bid / ntx), ntya = (a.j1 - a.j0 + TY - 1) / TY;
     const bool second = tyi >= ntya;
@@ -371,15 +395,17 @@ template <typename T> static MarchKernel<T> march_kernel(int mode, int formulati
 }
 #endif
 
-// LDS-tiled kernel, 64 x 4 threads, RY output rows per thread
-template <typename T, int RY, bool BND = false>
-static hipError_t launch_tile(const TendArgs<T> &a, int formulation, int lorentz, int ntx, int nty, hipStream_t s) {
+// LDS-tiled kernel, 64 x 4 threads, RY output rows per thread; ENS: every tile of a.members members (grid folded or 2-D, see EnsTendArgs)
+template <typename T, int RY, bool BND = false, bool ENS = false>
+static hipError_t launch_tile(const TileArgs<T, ENS> &a, int formulation, int lorentz, int ntx, int nty, hipStream_t s) {
     constexpr int TX = 64, TYB = 4;
-    const dim3 grid(ntx * nty), block(TX, TYB);
-    if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY, BND>), grid, block, 0, s, a, ntx, nty);
+    dim3 grid(ntx * nty);
+    const dim3 block(TX, TYB);
+    if constexpr (ENS) grid = a.fold ? dim3(ntx * nty * a.members) : dim3(ntx * nty, a.members);
+    if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -477,6 +503,29 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
     return launch_tile<T, RY>(a, formulation, lorentz, ntx, nty, s);
 }
 
+// Ensemble stage: the LDS-tiled kernel over every tile of every member (periodic members, one row range).  Tile height as a single
+// model of the member's size would take it: 64 x 4 tiles (RY = 1) below SW_MARCH_MIN_CELLS cells per member in fast builds -- the
+// same compiled body as that model's launch, so a member's results are bitwise those of the single model -- and 64 x 8 otherwise
+// (strict builds, and members the single model would march over).  Members are folded into blockIdx.x by default.  Both choices were
+// measured (tools/time_ensemble.py, profiles/ensemble/).  Knobs (read once; measurement only): SWMHD_ENS_RY = 1 | 2 forces the tile
+// height, SWMHD_ENS_MAP = 1 folds the member into blockIdx.x, 2 makes it blockIdx.y.
+template <typename T>
+hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s) {
+    constexpr int TX = 64, TYB = 4;
+    static int ry_cache = 0, map_cache = 0;
+    const int rows = a.j1 - a.j0;
+    if (rows <= 0 || a.members <= 0) return hipSuccess;
+    const int force_ry = env_knob("SWMHD_ENS_RY", ry_cache), map = env_knob("SWMHD_ENS_MAP", map_cache);
+    const int ry = force_ry == 1 || force_ry == 2 ? force_ry : ((!STRICT && (long)a.Nx * rows < SW_MARCH_MIN_CELLS) ? 1 : 2);
+    const int ntx = (a.Nx + TX - 1) / TX, nty = (rows + TYB * ry - 1) / (TYB * ry);
+    const long blocks = (long)ntx * nty * a.members;
+    if (blocks >= (1L << 31) || (map == 2 && a.members > 65535)) return hipErrorInvalidConfiguration;
+    EnsTendArgs<T> e = a;
+    e.fold = map == 2 ? 0 : 1;
+    return ry == 1 ? launch_tile<T, 1, false, true>(e, formulation, lorentz, ntx, nty, s)
+                   : launch_tile<T, 2, false, true>(e, formulation, lorentz, ntx, nty, s);
+}
+
 template <typename T>
 hipError_t LAUNCH_NAME(launch_rk3_substep_, LAUNCH_SFX)(const Rk3Args<T> &a, hipStream_t s) {
     if (a.j1 <= a.j0) return hipSuccess;
@@ -504,6 +553,8 @@ int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, i
 
 template hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)<double>(const TendArgs<double> &, int, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)<float>(const TendArgs<float> &, int, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)<double>(const EnsTendArgs<double> &, int, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)<float>(const EnsTendArgs<float> &, int, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_rk3_substep_, LAUNCH_SFX)<double>(const Rk3Args<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_rk3_substep_, LAUNCH_SFX)<float>(const Rk3Args<float> &, hipStream_t);
 

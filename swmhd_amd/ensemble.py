@@ -1,0 +1,230 @@
+"""Ensembles: B independent runs of one periodic grid stepped together on one GPU (swmhd_ensemble_* in include/swmhd.h).
+
+The reference's runs are sweeps of small grids -- 64^2 and 128^2, two formulations, initial conditions that differ in the amplitude of A
+(SWMHD_example.jl:11,35-37; divergence_sw_mhd.jl:11,32-34; its twelve energy_plots/*).  A 64^2 grid gives the chip 16 workgroups per
+stage; an ensemble of B members gives it 16 B, in the same three launches per RK3 step.  Every member has the grid, physics, precision
+and dt of the ensemble; members differ only in their state.  Member m of field f is row m of a (members, Ny+2Hy, Nx+2Hx) tensor: the
+halo-padded parent a ShallowWaterModel would hold.  `member(m)` hands one member to the single-grid tools (checkpoints, inspection).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .fields import _SFX, _stream_ptr
+from .grid import Center, Face
+from .model import ShallowWaterModel, VectorInvariantFormulation
+
+LOCS = ((Face, Center), (Center, Face), (Center, Center), (Center, Center))
+
+
+class ShallowWaterEnsemble:
+    """`members` ShallowWaterModels of one periodic grid in one set of tensors.  Arguments as ShallowWaterModel's; `member_stride`
+    (elements, >= (Ny+2Hy)(Nx+2Hx)) pitches the members apart inside one allocation (the gaps are never read or written).
+    fuse_halo=False fills every member's halos after each stage instead of reading the periodic images (ShallowWaterModel's option)."""
+
+    def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
+                 lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
+                 fuse_halo=True):
+        if decomp is not None or grid.Ny_global != grid.Ny or grid.j_offset != 0:
+            raise _lib.SwmhdError("ShallowWaterEnsemble runs on one GPU: no slab decomposition")
+        if grid.topo_codes() != (_lib.PERIODIC, _lib.PERIODIC):
+            raise _lib.SwmhdError("ShallowWaterEnsemble supports (Periodic, Periodic) grids only (SWMHD_ENOTSUP): run Bounded members "
+                                  "as separate ShallowWaterModels")
+        if torch.device(device).type != "cuda":
+            raise _lib.SwmhdError("ShallowWaterEnsemble runs on the GPU only (no CPU fallback)")
+        if dtype not in _SFX:
+            raise _lib.SwmhdError(f"dtype {dtype}: float64 or float32")
+        self.members = int(members)
+        if not 1 <= self.members <= _lib.ENSEMBLE_MAX_MEMBERS:
+            raise _lib.SwmhdError(f"members = {members}: 1 .. {_lib.ENSEMBLE_MAX_MEMBERS}")
+        self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
+        self.formulation, self.strict, self.dtype = formulation, strict, dtype
+        self.lorentz_forcing = lorentz_forcing
+        self.form_code = _lib.VECTOR_INVARIANT if formulation == VectorInvariantFormulation else _lib.CONSERVATIVE
+        if not lorentz_forcing:
+            self.lorentz_code = _lib.LORENTZ_NONE
+        else:
+            self.lorentz_code = _lib.LORENTZ_JACOBIAN if self.form_code == _lib.VECTOR_INVARIANT else _lib.LORENTZ_DIVERGENCE
+        self.names = ("u", "v", "h", "A") if self.form_code == _lib.VECTOR_INVARIANT else ("uh", "vh", "h", "A")
+        self.sfx = _SFX[dtype]
+        self._flags = _lib.STRICT if strict else _lib.FAST
+        # periodic "gather on read", as in ShallowWaterModel: no halo fill between stages, halos filled lazily (_ensure_halos)
+        self._rwrap = (_lib.WRAP_X | _lib.WRAP_Y) if (fuse_halo and grid.Nx >= grid.Hx and grid.Ny >= grid.Hy) else 0
+        self._halo_stale = False
+        Py, Px = grid.parent_shape
+        self.stride_m = int(member_stride) if member_stride is not None else Py * Px
+        if self.stride_m < Py * Px:
+            raise _lib.SwmhdError(f"member_stride {member_stride} < (Ny+2Hy)(Nx+2Hx) = {Py * Px}")
+
+        def mk():
+            if self.stride_m == Py * Px:
+                return torch.zeros((self.members, Py, Px), dtype=dtype, device=device)
+            flat = torch.zeros(self.members * self.stride_m, dtype=dtype, device=device)
+            return flat.as_strided((self.members, Py, Px), (self.stride_m, Px, 1))
+        self._state, self._alt = [mk() for _ in LOCS], [mk() for _ in LOCS]
+        self.Gn, self.Gm = [mk() for _ in LOCS], [mk() for _ in LOCS]
+        self.clock_time, self.iteration = 0.0, 0
+        self._L = _lib.lib()
+
+    # --- state ---------------------------------------------------------------------------------------------------
+    def set(self, **kw):
+        """set!(model, ...) for every member.  Each value: a callable (X, Y) used for every member, a list of `members` callables,
+        or an array of shape (members, Ny, Nx) (interiors) or (members, Ny+2Hy, Nx+2Hx) (parents)."""
+        g = self.grid
+        B = self.members
+        for k, v in kw.items():
+            idx = self.names.index(k)
+            X, Y = g.nodes(LOCS[idx])
+            evaluate = lambda fn: np.asarray(fn(X, Y), dtype=np.float64) + np.zeros(g.parent_shape)
+            if callable(v):
+                full = np.repeat(evaluate(v)[None], B, axis=0)
+            elif isinstance(v, (list, tuple)) and all(callable(fn) for fn in v):
+                if len(v) != B:
+                    raise ValueError(f"{k}: {len(v)} callables for {B} members")
+                full = np.stack([evaluate(fn) for fn in v])
+            else:
+                arr = np.asarray(v, dtype=np.float64)
+                if arr.shape == (B, g.Ny, g.Nx):
+                    full = np.zeros((B,) + g.parent_shape)
+                    full[(slice(None),) + g.interior] = arr
+                elif arr.shape == (B,) + g.parent_shape:
+                    full = arr
+                else:
+                    raise ValueError(f"{k}: shape {arr.shape}, expected ({B}, {g.Ny}, {g.Nx}) or ({B}, {g.parent_shape[0]}, {g.parent_shape[1]})")
+            self._state[idx].copy_(torch.from_numpy(np.ascontiguousarray(full)).to(self.dtype))
+        self.update_state()
+        return self
+
+    @property
+    def fields(self):
+        """The four prognostic tensors (members, Ny+2Hy, Nx+2Hx) in the order of `names`, halos current."""
+        self._ensure_halos()
+        return list(self._state)
+
+    @property
+    def solution(self):
+        self._ensure_halos()
+        return dict(zip(self.names, self._state))
+
+    def _ptrs(self, ts):
+        return _lib.ptr_array([t.data_ptr() for t in ts])
+
+    def _ensure_halos(self):
+        if self._halo_stale:
+            self.update_state()
+
+    def update_state(self):
+        """fill_halo_regions! of every member (one launch for all four fields of all members)."""
+        g = self.grid
+        self._halo_stale = False
+        f = getattr(self._L, f"swmhd_ensemble_fill_halo_periodic_{self.sfx}")
+        _lib.check(f(self._ptrs(self._state), 4, self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1),
+                     _lib.HALO_X | _lib.HALO_Y, _stream_ptr()), "swmhd_ensemble_fill_halo_periodic")
+
+    # --- time stepping (the native ensemble step driver: 3 launches per RK3 step for all members) ---------------------
+    def _native_steps(self, dt, n):
+        g = self.grid
+        swapped = ctypes.c_int(0)
+        f = getattr(self._L, f"swmhd_ensemble_step_rk3_{self.sfx}")
+        rc = f(self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(self.Gm), self.members, self.stride_m,
+               g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
+               self._flags | self._rwrap, ctypes.byref(swapped), _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_step_rk3")
+        if swapped.value:
+            self._state, self._alt = self._alt, self._state
+            self.Gn, self.Gm = self.Gm, self.Gn
+        if n > 0 and self._rwrap:
+            self._halo_stale = True
+        self.clock_time += n * dt
+        self.iteration += n
+
+    def time_step(self, dt):
+        self._native_steps(dt, 1)
+
+    def capture_graph(self, dt):
+        """Capture TWO RK3 steps of every member into one HIP graph (ShallowWaterModel.capture_graph: same role tracking)."""
+        self._ensure_halos()
+        keep = [t.clone() for t in self._state] + [t.clone() for t in self.Gm]
+        t0, i0 = self.clock_time, self.iteration
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self.time_step(dt); self.time_step(dt)
+        torch.cuda.current_stream().wait_stream(side)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self.time_step(dt); self.time_step(dt)
+        self._graph_dt = dt
+        self._graph_roles = self._roles()
+        for t, k in zip(self._state + self.Gm, keep):
+            t.copy_(k)
+        self._halo_stale = False
+        self.clock_time, self.iteration = t0, i0
+        return self
+
+    def _roles(self):
+        return tuple(t.data_ptr() for t in self._state) + tuple(t.data_ptr() for t in self.Gn)
+
+    def time_steps(self, n, dt):
+        """n RK3 steps of every member: graph replays (2 steps each) when a graph was captured for this dt, else the step driver."""
+        gr = getattr(self, "_graph", None)
+        if gr is not None and self._graph_dt == dt and n >= 2 and self._roles() != self._graph_roles:
+            self._native_steps(dt, 1)           # an odd number of steps since capture: one eager step restores the captured roles
+            n -= 1
+        if gr is not None and self._graph_dt == dt and self._roles() == self._graph_roles:
+            for _ in range(n // 2):
+                gr.replay()
+                self._halo_stale = self._halo_stale or bool(self._rwrap)
+                self.clock_time += 2 * dt
+                self.iteration += 2
+            n = n % 2
+        if n > 0:
+            self._native_steps(dt, n)
+
+    # --- diagnostics (SWMHD_example.jl:47-77) ------------------------------------------------------------------------
+    def diagnostics_into(self, out, h_ref=1.0):
+        """Enqueue every member's 7 diagnostics (KE, ME, PE, max|u|, max|v|, max|A|, min h; ShallowWaterModel.diagnostics order)
+        into `out`, a contiguous float64 device tensor of shape (members, 7).  No host synchronisation."""
+        g = self.grid
+        if not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (self.members, _lib.DIAG_NOUT) and out.is_contiguous()):
+            raise _lib.SwmhdError(f"diagnostics_into: need a contiguous float64 CUDA tensor of shape ({self.members}, {_lib.DIAG_NOUT})")
+        self._ensure_halos()
+        if not hasattr(self, "_diag_ws"):
+            self._diag_ws = torch.empty(_lib.ensemble_diag_workspace(self.members, g.Nx, g.Ny), dtype=torch.float64, device=out.device)
+        q = self._state
+        f = getattr(self._L, f"swmhd_ensemble_diagnostics_{self.sfx}")
+        rc = f(q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), q[3].data_ptr(), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy,
+               q[0].stride(1), g.dx, g.dy, self.g, h_ref, self.form_code, self._diag_ws.data_ptr(), out.data_ptr(), _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_diagnostics")
+        return out
+
+    def diagnostics(self, h_ref=1.0):
+        """One dict per member with the keys of ShallowWaterModel.diagnostics."""
+        out = self.diagnostics_into(torch.empty((self.members, _lib.DIAG_NOUT), dtype=torch.float64, device=self._state[0].device), h_ref)
+        res = []
+        for v in out.cpu().tolist():
+            res.append(dict(kinetic_energy=v[0], magnetic_energy=v[1], potential_energy=v[2], total_energy=v[0] + v[1] + v[2],
+                            max_abs_u=v[3], max_abs_v=v[4], max_abs_A=v[5], min_h=v[6]))
+        return res
+
+    # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
+    def member(self, m):
+        """A ShallowWaterModel holding a copy of member m (state with halos, G-, clock and iteration)."""
+        if not 0 <= m < self.members:
+            raise IndexError(f"member {m} of {self.members}")
+        self._ensure_halos()
+        model = ShallowWaterModel(self.grid, self.g, self.f, formulation=self.formulation, lorentz_forcing=self.lorentz_forcing,
+                                  dtype=self.dtype, device=self._state[0].device, strict=self.strict)
+        for fld, t in zip(model._raw_fields, self._state):
+            fld.data.copy_(t[m])
+        for fld, t in zip(model.Gm, self.Gm):
+            fld.data.copy_(t[m])
+        model.clock_time, model.iteration = self.clock_time, self.iteration
+        return model
+
+    def synchronize(self):
+        """Wait for everything enqueued; afterwards the halos of every member are current."""
+        self._ensure_halos()
+        torch.cuda.synchronize()
