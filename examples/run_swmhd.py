@@ -15,6 +15,11 @@ The step loop runs through HIP-graph replays (two RK3 steps per replay).
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
 step): one progress line per member, and --energies gets a leading `member` column.
 
+    python examples/run_swmhd.py --channel --gradients -0.01,-0.05,-0.1 [other options as above]
+runs the reference's commented channel experiment (SWMHD_example.jl:18-22, divergence_sw_mhd.jl:17-21,34) as a sweep over the
+gradient g, one member of a swmhd_amd.BoundedShallowWaterEnsemble per value: topology (Periodic, Bounded, Flat), A = g y with
+GradientBoundaryCondition(g) on A north and south (an imposed uniform B_x = -g / h), h = 1 and the vortex above.  Output as for --amps.
+
     python examples/run_swmhd.py --plot-case jacobian_formulation/128x128_two_Gaussians_low_B
 re-runs one of the twelve runs behind the reference's committed energy plots (energy_plots/*/*.png; set-up from the scripts' commented
 alternatives, see tests/plot_cases.py) and prints, beside every energy row, the value read off the plot at that time
@@ -33,15 +38,26 @@ def main():
     ap.add_argument("--ic", choices=["uniform", "gaussians"], default="uniform")
     ap.add_argument("--amp", type=float, default=None, help="A amplitude (default 0.5 for |y|, 0.1 / 0.5 for the Gaussians)")
     ap.add_argument("--amps", default=None, help="comma-separated A amplitudes: one ensemble member per amplitude")
+    ap.add_argument("--channel", action="store_true", help="(Periodic, Bounded) channel with gradient boundary conditions on A")
+    ap.add_argument("--gradients", default=None, help="with --channel: comma-separated gradients of A, one ensemble member each")
     ap.add_argument("--every", type=int, default=100, help="iterations between progress lines / energy rows")
     ap.add_argument("--energies", default=None, help="CSV file for (time, KE, ME, PE, total)")
     ap.add_argument("--dump-every", type=float, default=0.0, help="model time between field dumps (0 = none)")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
-    a = ap.parse_args()
+    argv = sys.argv[1:]
+    for k in range(len(argv) - 1):   # "--gradients -0.01,-0.05": argparse would read the negative list as an option
+        if argv[k] == "--gradients":
+            argv[k:k + 2] = ["--gradients=" + argv[k + 1]]
+            break
+    a = ap.parse_args(argv)
     if a.plot_case:
         return plot_case(a)
-    if a.amps:
+    if a.channel != (a.gradients is not None):
+        ap.error("--channel and --gradients go together")
+    if a.channel and a.amps:
+        ap.error("--channel sweeps --gradients, not --amps")
+    if a.amps or a.channel:
         return run_ensemble(a)
 
     import torch
@@ -92,16 +108,23 @@ def main():
 
 
 def run_ensemble(a):
-    """--amps: the same run for several A amplitudes, one ensemble member each."""
+    """--amps: the same run for several A amplitudes, one ensemble member each.  --channel: one member per gradient of A."""
     import torch
     import swmhd_amd as S
     from swmhd_amd import configs
-    amps = [float(x) for x in a.amps.split(",") if x.strip()]
+    amps = [float(x) for x in (a.gradients if a.channel else a.amps).split(",") if x.strip()]
     N, L = a.size, 10.0
-    grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
     form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
-    ens = S.ShallowWaterEnsemble(grid, len(amps), configs.G, configs.F, formulation=form)
-    A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
+    if a.channel:
+        grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2), topology=("Periodic", "Bounded", "Flat"))
+        bcs = [{"A": S.FieldBoundaryConditions(north=S.GradientBoundaryCondition(gr), south=S.GradientBoundaryCondition(gr))} for gr in amps]
+        ens = S.BoundedShallowWaterEnsemble(grid, len(amps), configs.G, configs.F, formulation=form, boundary_conditions=bcs)
+        A0 = [lambda X, Y, gr=gr: gr * Y for gr in amps]
+    else:
+        grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
+        ens = S.ShallowWaterEnsemble(grid, len(amps), configs.G, configs.F, formulation=form)
+        A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
+    label = "gradient" if a.channel else "amp"
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
     v0 = lambda X, Y: -5 * X * np.exp(-(X ** 2 + Y ** 2))
     n1, n2 = ens.names[:2]
@@ -111,7 +134,7 @@ def run_ensemble(a):
 
     def report(wall):
         for m, d in enumerate(ens.diagnostics()):
-            print(f"member {m} (amp {amps[m]:g}) Time: {ens.clock_time:9.3f}, iteration: {ens.iteration}, "
+            print(f"member {m} ({label} {amps[m]:g}) Time: {ens.clock_time:9.3f}, iteration: {ens.iteration}, "
                   f"max(|u|): {max(d['max_abs_u'], d['max_abs_v']):.2e}, max(|A|): {d['max_abs_A']:.2e}, min(h): {d['min_h']:.2e}, "
                   f"wall time: {wall * 1e3:.1f} ms | KE {d['kinetic_energy']:.6f} ME {d['magnetic_energy']:.6f} "
                   f"PE {d['potential_energy']:.3e} total {d['total_energy']:.6f}", flush=True)

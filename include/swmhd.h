@@ -466,6 +466,47 @@ int swmhd_ensemble_diagnostics_f32(const float *q1, const float *q2, const float
                                    float dx, float dy, float g, float h_ref, int formulation,
                                    double *workspace, double *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bounded ensembles: members of a grid with at least one Bounded direction (topology (Periodic | Bounded, Periodic | Bounded, Flat)),
+ * each with its own GradientBoundaryCondition values -- the reference's commented channel experiment (A_bcs with
+ * GradientBoundaryCondition(-0.05) north and south, SWMHD_example.jl:18-22, divergence_sw_mhd.jl:17-21,34) swept over the gradient.
+ * Layout, member limits and the ensemble checks as for the periodic ensemble calls above.  The periodic calls
+ * (swmhd_ensemble_tendencies_rk3, swmhd_ensemble_step_rk3, swmhd_ensemble_fill_halo_periodic) keep refusing SWMHD_BOUNDED_X / _Y.
+ * gradient: a DEVICE table, member m's values at gradient + m * 4 * nf: (west, east, south, north) of field 0, then field 1, ...
+ * (NaN = the default condition of that side), or NULL for defaults everywhere.
+ * Results: SWMHD_STRICT members are bit-identical to the oracle's time_step with that member's gradients (and so to the single-grid
+ * Bounded schedule, swmhd_tendencies_rk3 with the BOUNDED flags + swmhd_fill_halo per stage, as ShallowWaterModel.time_step runs it).
+ * Fast members run the single grid's 64 x 8 wall-tile kernel body in its ensemble instantiation, within the fast tolerances of that
+ * schedule but not bitwise: the compiler groups the uniform factors of the fused substep differently there (last-bit differences in
+ * a few cells per stage).  Larger fast members run that kernel where a single grid takes the marching kernel plus a wall frame.
+ * The boundary-condition fill is bitwise swmhd_fill_halo in both builds.  A non-finite member does not affect the others.
+ * ---------------------------------------------------------------------------------------------- */
+/* swmhd_ensemble_fill_halo: swmhd_fill_halo of every member (two launches for all members), with the checks of that call and of the
+ * ensemble. */
+int swmhd_ensemble_fill_halo_f64(double *const *fields, int nf, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy,
+                                 int64_t stride_y, int topo_x, int topo_y, int face_x, int face_y,
+                                 const double *gradient, double dx, double dy, void *stream);
+int swmhd_ensemble_fill_halo_f32(float *const *fields, int nf, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy,
+                                 int64_t stride_y, int topo_x, int topo_y, int face_x, int face_y,
+                                 const float *gradient, float dx, float dy, void *stream);
+/* swmhd_ensemble_step_rk3_bc: nsteps RK3 steps of every member on the Bounded schedule: per stage the fused stage kernel in G- form
+ * (no anchor form), then swmhd_fill_halo of the four fields (face_x = 0b0001, face_y = 0b0010): 9 launches per step for all members
+ * (3 stages, 3 x 2 fill passes).  gradient: members x 16 values (fields q1, q2, h, A) or NULL.
+ * Buffer rotation and *state_in_alt as swmhd_step_rk3.  Halos are current on return.
+ *   flags: SWMHD_BOUNDED_X and/or SWMHD_BOUNDED_Y (at least one, else SWMHD_EINVAL: periodic ensembles use swmhd_ensemble_step_rk3),
+ *          SWMHD_STRICT, SWMHD_TILE_KERNEL, SWMHD_WRAP_X / _Y on a Periodic direction only (SWMHD_EINVAL on a Bounded one)
+ *   SWMHD_ENOTSUP  SWMHD_MARCH_KERNEL, SWMHD_GM_IS_PREV_STATE, SWMHD_LEAVE_ROOM, SWMHD_RK3_ANCHOR
+ *   SWMHD_EHALO    halo < 3 (the stencil), or a Bounded direction with halo < 1
+ * Every check precedes the first HIP call; nsteps = 0 enqueues nothing. */
+int swmhd_ensemble_step_rk3_bc_f64(double *const *q, double *const *q_alt, double *const *Ga, double *const *Gb,
+                                   int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                   double dx, double dy, double g, double f, int formulation, int lorentz, double dt, int nsteps,
+                                   const double *gradient, int flags, int *state_in_alt, void *stream);
+int swmhd_ensemble_step_rk3_bc_f32(float *const *q, float *const *q_alt, float *const *Ga, float *const *Gb,
+                                   int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                   float dx, float dy, float g, float f, int formulation, int lorentz, float dt, int nsteps,
+                                   const float *gradient, int flags, int *state_in_alt, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

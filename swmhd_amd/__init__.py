@@ -9,8 +9,9 @@ from .fields import Field
 from .operators import lorentz_force_func, div_lorentz
 from .model import ShallowWaterModel, loopback_rings, VectorInvariantFormulation, ConservativeFormulation
 from .distributed import SlabDecomposition, exchange_y_halos
-from .ensemble import ShallowWaterEnsemble
+from .ensemble import ShallowWaterEnsemble, BoundedShallowWaterEnsemble
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
-           "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble", "_lib"]
+           "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble",
+           "BoundedShallowWaterEnsemble", "_lib"]

@@ -102,6 +102,12 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_diagnostics_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, ft, ft, i, p, p, p]
         f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_fill_halo_{sfx}")
+        f.argtypes = [C.POINTER(p), i, i, i64, i, i, i, i, i64, i, i, i, i, p, ft, ft, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_step_rk3_bc_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, i, p, i, C.POINTER(i), p]
+        f.restype = i
         f = getattr(lib, f"swmhd_ring_exchange_y_{sfx}")
         f.argtypes = [p, C.POINTER(p), i, i, i, i, i, i64, p]
         f.restype = i
@@ -138,7 +144,7 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "lorentz_jacobian", "lorentz_jacobian_rows", "lorentz_divergence", "lorentz_divergence_rows",
         "fill_halo", "fill_halo_periodic", "fill_halo_periodic_multi", "tendencies", "tendencies_rk3", "rk3_substep", "step_rk3", "diagnostics",
         "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
-        "ensemble_diagnostics")] + [
+        "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

@@ -52,6 +52,15 @@ struct HaloBc {
     T dx, dy;
 };
 template <typename T> hipError_t launch_fill_halo_bc(const HaloBc<T> &a, hipStream_t s);
+// The same fill for an ensemble (swmhd_ensemble_fill_halo_*): member blockIdx.y at f[k] + m * stride_m, its gradient values in a
+// DEVICE table gtab[m * 4 * nf + 4 * f + side] (NaN = default; gtab == nullptr: defaults everywhere).  HaloBc::grad is not read.
+template <typename T>
+struct HaloBcEns : HaloBc<T> {
+    long stride_m;
+    int members;
+    const T *gtab;
+};
+template <typename T> hipError_t launch_fill_halo_bc_ensemble(const HaloBcEns<T> &a, hipStream_t s);
 
 // Arguments of the fused tendency kernels; pointers address interior cell (1,1) like OpArgs.
 template <typename T>
@@ -273,7 +282,7 @@ int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, i
 template <typename T> hipError_t launch_tendency_strict(const TendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_rk3_substep_fast(const Rk3Args<T> &a, hipStream_t s);
 // ensemble stage: every tile of every member in one launch of the LDS-tiled kernel (rows [a.j0, a.j1) of each member; no second range,
-// no Bounded frame).  The launcher sets a.fold.
+// no Bounded frame: Bounded members run the wall kernel on every tile).  The launcher sets a.fold.
 template <typename T> hipError_t launch_tendency_ensemble_fast(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_tendency_ensemble_strict(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 // internal twins of swmhd_tendencies_rk3_* and swmhd_fill_halo_periodic_multi_* for the slab driver (ring.hip), same argument checks

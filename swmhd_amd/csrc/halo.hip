@@ -70,21 +70,31 @@ __global__ void k_halo_multi(std::conditional_t<ENS, HaloMultiEns<T>, HaloMulti<
     for (int k = 0; k < a.nf; ++k) a.f[k][dst] = a.f[k][src];
 }
 
+// Gradient value `side` (west, east, south, north) of field fld: from the kernel arguments (one grid), or from the ensemble's device
+// table at member blockIdx.y (HaloBcEns; no table: NaN, the default condition).
+template <typename T>
+__device__ __forceinline__ T bc_gradient(const HaloBc<T> &a, int fld, int side) { return a.grad[fld][side]; }
+template <typename T>
+__device__ __forceinline__ T bc_gradient(const HaloBcEns<T> &a, int fld, int side) {
+    return a.gtab ? a.gtab[((long)blockIdx.y * a.nf + fld) * 4 + side] : T(__builtin_nan(""));
+}
+
 // fill_halo_regions! with boundary conditions, one pass per direction (x pass over interior rows, then y pass over the padded
 // width, like the oracle and like Oceananigans' west/east-then-south/north order).  One thread per (field, line): the line's halo
-// cells are few (<= 2 Hx) and the passes are launch-latency bound anyway.
-template <typename T, int DIR>
-__global__ void k_halo_bc(HaloBc<T> a) {
+// cells are few (<= 2 Hx) and the passes are launch-latency bound anyway.  ENS: member blockIdx.y of an ensemble (HaloBcEns).
+template <typename T, int DIR, bool ENS = false>
+__global__ void k_halo_bc(std::conditional_t<ENS, HaloBcEns<T>, HaloBc<T>> a) {
     const int nlines = DIR == 0 ? a.Ny : a.Nx + 2 * a.Hx;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nlines * a.nf) return;
     const int fld = t / nlines, line = t - fld * nlines;
     T *f = a.f[fld];
+    if constexpr (ENS) f += (long)blockIdx.y * a.stride_m;
     const int N = DIR == 0 ? a.Nx : a.Ny, H = DIR == 0 ? a.Hx : a.Hy;
     const int topo = DIR == 0 ? a.topo_x : a.topo_y;
     const bool face = ((DIR == 0 ? a.face_x : a.face_y) >> fld) & 1;
     const T d = DIR == 0 ? a.dx : a.dy;
-    const T glo = a.grad[fld][DIR == 0 ? 0 : 2], ghi = a.grad[fld][DIR == 0 ? 1 : 3];
+    const T glo = bc_gradient<T>(a, fld, DIR == 0 ? 0 : 2), ghi = bc_gradient<T>(a, fld, DIR == 0 ? 1 : 3);
     // element k (0-based along the direction, halo cells have k < 0 or k >= N) of this line
     auto at = [&](int k) -> T & { return DIR == 0 ? f[(long)line * a.sy + k] : f[(long)k * a.sy + (line - a.Hx)]; };
     if (topo == 0) {
@@ -109,6 +119,16 @@ hipError_t launch_fill_halo_bc(const HaloBc<T> &a, hipStream_t s) {
 }
 template hipError_t launch_fill_halo_bc<double>(const HaloBc<double> &, hipStream_t);
 template hipError_t launch_fill_halo_bc<float>(const HaloBc<float> &, hipStream_t);
+
+template <typename T>
+hipError_t launch_fill_halo_bc_ensemble(const HaloBcEns<T> &a, hipStream_t s) {
+    const int nx = a.Ny * a.nf, ny = (a.Nx + 2 * a.Hx) * a.nf;
+    hipLaunchKernelGGL((k_halo_bc<T, 0, true>), dim3((nx + 127) / 128, a.members), dim3(128), 0, s, a);
+    hipLaunchKernelGGL((k_halo_bc<T, 1, true>), dim3((ny + 127) / 128, a.members), dim3(128), 0, s, a);
+    return hipGetLastError();
+}
+template hipError_t launch_fill_halo_bc_ensemble<double>(const HaloBcEns<double> &, hipStream_t);
+template hipError_t launch_fill_halo_bc_ensemble<float>(const HaloBcEns<float> &, hipStream_t);
 
 template <typename T>
 hipError_t launch_fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which,

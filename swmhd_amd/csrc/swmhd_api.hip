@@ -10,20 +10,26 @@ namespace {
 
 inline int hiprc(hipError_t e) { return e == hipSuccess ? SWMHD_OK : -(int)e; }
 
-// Ensemble calls (swmhd_ensemble_*): `members` copies of one periodic grid, member m of every parent at ptr + m * stride_m.  The
-// single-grid helpers below take it as an optional last argument and check everything else exactly as for one grid.
+// Ensemble calls (swmhd_ensemble_*): `members` copies of one grid, member m of every parent at ptr + m * stride_m.  The single-grid
+// helpers below take it as an optional last argument and check everything else exactly as for one grid.  `bc`: a call of the
+// boundary-condition family (swmhd_ensemble_fill_halo, swmhd_ensemble_step_rk3_bc), which accepts Bounded directions and runs the
+// stage in G- form; the periodic family refuses them.
 struct Ens {
     int members;
     int64_t stride_m;
+    bool bc = false;
 };
 constexpr int ENS_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_RK3_ANCHOR;
 constexpr int ENS_NOTSUP = SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_LEAVE_ROOM;
+constexpr int ENS_BC_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y;
+constexpr int ENS_BC_NOTSUP = SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_LEAVE_ROOM | SWMHD_RK3_ANCHOR;
 // the checks of the ensemble itself (the caller's single-grid checks follow): member count, member stride, flags
 inline int ens_check(const Ens &e, int Ny, int Hy, int64_t sy, int flags) {
+    const int ok = e.bc ? ENS_BC_FLAGS : ENS_FLAGS, notsup = e.bc ? ENS_BC_NOTSUP : ENS_NOTSUP;
     if (e.members < 1 || e.members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
     if (Ny <= 0 || Hy < 0 || sy <= 0 || e.stride_m < ((int64_t)Ny + 2 * Hy) * sy) return SWMHD_EINVAL;
-    if (flags & ~(ENS_FLAGS | ENS_NOTSUP)) return SWMHD_EINVAL;
-    if (flags & ENS_NOTSUP) return SWMHD_ENOTSUP;
+    if (flags & ~(ok | notsup)) return SWMHD_EINVAL;
+    if (flags & notsup) return SWMHD_ENOTSUP;
     return SWMHD_OK;
 }
 
@@ -83,26 +89,41 @@ int halo_multi_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64
                                                     ens ? (long)ens->stride_m : 0));
 }
 
+// the checks of swmhd_fill_halo (and of the ensemble); sets every field of `a` but the gradient values
 template <typename T>
-int halo_bc_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int topo_x, int topo_y, int face_x, int face_y,
-                   const T *gradient, T dx, T dy, void *stream) {
+int halo_bc_args(HaloBc<T> &a, T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int topo_x, int topo_y, int face_x,
+                 int face_y, T dx, T dy, const Ens *ens = nullptr) {
+    if (ens) {
+        const int rc = ens_check(*ens, Ny, Hy, sy, 0);
+        if (rc) return rc;
+    }
     if (!f || nf < 1 || nf > 4 || Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
     if ((topo_x != SWMHD_BOUNDED && topo_x != SWMHD_PERIODIC) || (topo_y != SWMHD_BOUNDED && topo_y != SWMHD_PERIODIC)) return SWMHD_EINVAL;
     if (Hx > Nx || Hy > Ny) return SWMHD_EHALO;
     if ((topo_x == SWMHD_BOUNDED && Hx < 1) || (topo_y == SWMHD_BOUNDED && Hy < 1)) return SWMHD_EHALO;   // the far wall lives in the first halo line
     if (!(dx > T(0)) || !(dy > T(0))) return SWMHD_EINVAL;
-    HaloBc<T> a;
-    for (int k = 0; k < 4; ++k) {
-        a.f[k] = nullptr;
-        for (int e = 0; e < 4; ++e) a.grad[k][e] = (gradient && k < nf) ? gradient[4 * k + e] : T(NAN);
-    }
+    for (int k = 0; k < 4; ++k) a.f[k] = nullptr;
     for (int k = 0; k < nf; ++k) {
         if (!f[k]) return SWMHD_EINVAL;
         a.f[k] = f[k] + (long)Hy * sy + Hx;
     }
     a.nf = nf; a.Nx = Nx; a.Ny = Ny; a.Hx = Hx; a.Hy = Hy; a.topo_x = topo_x; a.topo_y = topo_y; a.face_x = face_x; a.face_y = face_y;
     a.sy = (long)sy; a.dx = dx; a.dy = dy;
-    return hiprc(launch_fill_halo_bc<T>(a, (hipStream_t)stream));
+    return SWMHD_OK;
+}
+
+// gradient: HOST array of 4 nf values (one grid), or with `ens` a DEVICE table of members x 4 nf values; NULL = defaults everywhere
+template <typename T>
+int halo_bc_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int topo_x, int topo_y, int face_x, int face_y,
+                   const T *gradient, T dx, T dy, void *stream, const Ens *ens = nullptr) {
+    HaloBcEns<T> a;
+    const int rc = halo_bc_args<T>(a, f, nf, Nx, Ny, Hx, Hy, sy, topo_x, topo_y, face_x, face_y, dx, dy, ens);
+    if (rc) return rc;
+    for (int k = 0; k < 4; ++k)
+        for (int e = 0; e < 4; ++e) a.grad[k][e] = (!ens && gradient && k < nf) ? gradient[4 * k + e] : T(NAN);
+    if (!ens) return hiprc(launch_fill_halo_bc<T>(a, (hipStream_t)stream));
+    a.stride_m = (long)ens->stride_m; a.members = ens->members; a.gtab = gradient;
+    return hiprc(launch_fill_halo_bc_ensemble<T>(a, (hipStream_t)stream));
 }
 
 template <typename T>
@@ -220,19 +241,32 @@ int rk3_common(T *const *U, const T *const *Gn, const T *const *Gm, int Nx, int 
     return hiprc((flags & SWMHD_STRICT) ? launch_rk3_substep_strict<T>(a, s) : launch_rk3_substep_fast<T>(a, s));
 }
 
+// The RK3 step driver.  Periodic: stages in anchor form (fast) and a periodic fill of whatever the kernel does not wrap.  With `bc`
+// (Bounded ensembles, swmhd_ensemble_step_rk3_bc): ShallowWaterModel.time_step's Bounded schedule -- every stage in G- form, then the
+// boundary-condition fill of the four fields (u|uh at Face in x, v|vh at Face in y), gradient values from the DEVICE table bc_gradient.
 template <typename T>
 int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, T grav,
                 T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt, void *stream,
-                const Ens *ens = nullptr) {
+                const Ens *ens = nullptr, bool bc = false, const T *bc_gradient = nullptr) {
     if (ens) {
         const int rc = ens_check(*ens, Ny, Hy, sy, flags);
         if (rc) return rc;
     }
     if (!q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
-    if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // the driver's halo fill is the periodic one
+    const int bounded = flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y);
+    if (!bc && bounded) return SWMHD_ENOTSUP;   // the periodic driver's halo fill is the periodic one
+    if (bc && !bounded) return SWMHD_EINVAL;    // periodic grids have the periodic driver
+    if (((flags & SWMHD_BOUNDED_X) && (flags & SWMHD_WRAP_X)) || ((flags & SWMHD_BOUNDED_Y) && (flags & SWMHD_WRAP_Y))) return SWMHD_EINVAL;
     Rk3Buffers<T> b;
     if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
-    const bool anchor = !(flags & SWMHD_STRICT);   // (common.hpp: Rk3Buffers)
+    const int topo_x = (flags & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC, topo_y = (flags & SWMHD_BOUNDED_Y) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
+    constexpr int FACE_X = 0b0001, FACE_Y = 0b0010;
+    if (bc) {   // the fill's own checks, before the first launch
+        HaloBc<T> a;
+        const int rc = halo_bc_args<T>(a, b.cur, 4, Nx, Ny, Hx, Hy, sy, topo_x, topo_y, FACE_X, FACE_Y, dx, dy, ens);
+        if (rc) return rc;
+    }
+    const bool anchor = !(flags & SWMHD_STRICT) && !bc;   // (common.hpp: Rk3Buffers)
     // whatever the kernel does not wrap itself
     const int need = (SWMHD_HALO_X | SWMHD_HALO_Y) & ~(((flags & SWMHD_WRAP_X) ? SWMHD_HALO_X : 0) | ((flags & SWMHD_WRAP_Y) ? SWMHD_HALO_Y : 0));
     for (int n = 0; n < nsteps; ++n)
@@ -242,7 +276,9 @@ int step_common(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx
                                         g.zeta, g.store_G, 0, Ny, flags | g.flags, stream, 0, 0, ens);
             if (rc) return rc;
             b.rotate();
-            if (need && (rc = halo_multi_common<T>(b.cur, 4, Nx, Ny, Hx, Hy, sy, need, stream, ens))) return rc;
+            if (bc) rc = halo_bc_common<T>(b.cur, 4, Nx, Ny, Hx, Hy, sy, topo_x, topo_y, FACE_X, FACE_Y, bc_gradient, dx, dy, stream, ens);
+            else if (need) rc = halo_multi_common<T>(b.cur, 4, Nx, Ny, Hx, Hy, sy, need, stream, ens);
+            if (rc) return rc;
         }
     if (state_in_alt) *state_in_alt = b.swaps & 1;
     return SWMHD_OK;
@@ -414,6 +450,21 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
                                          double *ws, double *out, void *stream) {                                       \
         const Ens e{members, stride_m};                                                                                \
         return diag_common<T>(q1, q2, h, A, Nx, Ny, Hx, Hy, sy, dx, dy, g, href, form, 0, Ny, ws, out, stream, &e);    \
+    }                                                                                                                  \
+    int swmhd_ensemble_fill_halo_##sfx(T *const *f, int nf, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, \
+                                       int64_t sy, int topo_x, int topo_y, int face_x, int face_y, const T *gradient,   \
+                                       T dx, T dy, void *stream) {                                                      \
+        const Ens e{members, stride_m, true};                                                                          \
+        return halo_bc_common<T>(f, nf, Nx, Ny, Hx, Hy, sy, topo_x, topo_y, face_x, face_y, gradient, dx, dy, stream,  \
+                                 &e);                                                                                  \
+    }                                                                                                                  \
+    int swmhd_ensemble_step_rk3_bc_##sfx(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int members,        \
+                                         int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, T g, \
+                                         T f, int formulation, int lorentz, T dt, int nsteps, const T *gradient,        \
+                                         int flags, int *state_in_alt, void *stream) {                                  \
+        const Ens e{members, stride_m, true};                                                                          \
+        return step_common<T>(q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, nsteps, flags, \
+                              state_in_alt, stream, &e, true, gradient);                                               \
     }
 
 SWMHD_DEF_LORENTZ(f64, double)

@@ -509,19 +509,25 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
 // (strict builds, and members the single model would march over).  Members are folded into blockIdx.x by default.  Both choices were
 // measured (tools/time_ensemble.py, profiles/ensemble/).  Knobs (read once; measurement only): SWMHD_ENS_RY = 1 | 2 forces the tile
 // height, SWMHD_ENS_MAP = 1 folds the member into blockIdx.x, 2 makes it blockIdx.y.
+// Bounded members (a.topo_x or a.topo_y = 1) always take the wall kernel with 64 x 8 tiles, the tile a single Bounded model takes
+// below SW_MARCH_MIN_CELLS; larger members run it where a single model takes the marching kernel plus the wall frame.  SWMHD_ENS_RY does
+// not apply to them.  Strict members are bitwise single models.  Fast members are not: with reassociation the compiler groups the
+// uniform factors of the fused substep differently in this instantiation (an ulp in a few cells per stage), within the fast tolerances.
 template <typename T>
 hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s) {
     constexpr int TX = 64, TYB = 4;
     static int ry_cache = 0, map_cache = 0;
     const int rows = a.j1 - a.j0;
     if (rows <= 0 || a.members <= 0) return hipSuccess;
-    const int force_ry = env_knob("SWMHD_ENS_RY", ry_cache), map = env_knob("SWMHD_ENS_MAP", map_cache);
-    const int ry = force_ry == 1 || force_ry == 2 ? force_ry : ((!STRICT && (long)a.Nx * rows < SW_MARCH_MIN_CELLS) ? 1 : 2);
+    const bool bnd = a.topo_x == 1 || a.topo_y == 1;
+    const int force_ry = bnd ? 0 : env_knob("SWMHD_ENS_RY", ry_cache), map = env_knob("SWMHD_ENS_MAP", map_cache);
+    const int ry = bnd ? 2 : (force_ry == 1 || force_ry == 2 ? force_ry : ((!STRICT && (long)a.Nx * rows < SW_MARCH_MIN_CELLS) ? 1 : 2));
     const int ntx = (a.Nx + TX - 1) / TX, nty = (rows + TYB * ry - 1) / (TYB * ry);
     const long blocks = (long)ntx * nty * a.members;
     if (blocks >= (1L << 31) || (map == 2 && a.members > 65535)) return hipErrorInvalidConfiguration;
     EnsTendArgs<T> e = a;
     e.fold = map == 2 ? 0 : 1;
+    if (bnd) return launch_tile<T, 2, true, true>(e, formulation, lorentz, ntx, nty, s);
     return ry == 1 ? launch_tile<T, 1, false, true>(e, formulation, lorentz, ntx, nty, s)
                    : launch_tile<T, 2, false, true>(e, formulation, lorentz, ntx, nty, s);
 }

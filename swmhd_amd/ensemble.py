@@ -5,6 +5,10 @@ The reference's runs are sweeps of small grids -- 64^2 and 128^2, two formulatio
 stage; an ensemble of B members gives it 16 B, in the same three launches per RK3 step.  Every member has the grid, physics, precision
 and dt of the ensemble; members differ only in their state.  Member m of field f is row m of a (members, Ny+2Hy, Nx+2Hx) tensor: the
 halo-padded parent a ShallowWaterModel would hold.  `member(m)` hands one member to the single-grid tools (checkpoints, inspection).
+
+BoundedShallowWaterEnsemble does the same for a grid with Bounded directions, each member with its own boundary conditions: the
+reference's commented channel experiment (A_bcs = GradientBoundaryCondition(-0.05) north and south, SWMHD_example.jl:18-22,
+divergence_sw_mhd.jl:17-21,34) as a sweep over the gradient.
 """
 import ctypes
 
@@ -13,7 +17,7 @@ import torch
 
 from . import _lib
 from .fields import _SFX, _stream_ptr
-from .grid import Center, Face
+from .grid import Center, Face, FieldBoundaryConditions
 from .model import ShallowWaterModel, VectorInvariantFormulation
 
 LOCS = ((Face, Center), (Center, Face), (Center, Center), (Center, Center))
@@ -29,9 +33,7 @@ class ShallowWaterEnsemble:
                  fuse_halo=True):
         if decomp is not None or grid.Ny_global != grid.Ny or grid.j_offset != 0:
             raise _lib.SwmhdError("ShallowWaterEnsemble runs on one GPU: no slab decomposition")
-        if grid.topo_codes() != (_lib.PERIODIC, _lib.PERIODIC):
-            raise _lib.SwmhdError("ShallowWaterEnsemble supports (Periodic, Periodic) grids only (SWMHD_ENOTSUP): run Bounded members "
-                                  "as separate ShallowWaterModels")
+        self._check_topology(grid)
         if torch.device(device).type != "cuda":
             raise _lib.SwmhdError("ShallowWaterEnsemble runs on the GPU only (no CPU fallback)")
         if dtype not in _SFX:
@@ -67,6 +69,11 @@ class ShallowWaterEnsemble:
         self.Gn, self.Gm = [mk() for _ in LOCS], [mk() for _ in LOCS]
         self.clock_time, self.iteration = 0.0, 0
         self._L = _lib.lib()
+
+    def _check_topology(self, grid):
+        if grid.topo_codes() != (_lib.PERIODIC, _lib.PERIODIC):
+            raise _lib.SwmhdError("ShallowWaterEnsemble supports (Periodic, Periodic) grids only (SWMHD_ENOTSUP): use "
+                                  "BoundedShallowWaterEnsemble for Bounded grids")
 
     # --- state ---------------------------------------------------------------------------------------------------
     def set(self, **kw):
@@ -215,8 +222,7 @@ class ShallowWaterEnsemble:
         if not 0 <= m < self.members:
             raise IndexError(f"member {m} of {self.members}")
         self._ensure_halos()
-        model = ShallowWaterModel(self.grid, self.g, self.f, formulation=self.formulation, lorentz_forcing=self.lorentz_forcing,
-                                  dtype=self.dtype, device=self._state[0].device, strict=self.strict)
+        model = self._member_model(m)
         for fld, t in zip(model._raw_fields, self._state):
             fld.data.copy_(t[m])
         for fld, t in zip(model.Gm, self.Gm):
@@ -224,7 +230,91 @@ class ShallowWaterEnsemble:
         model.clock_time, model.iteration = self.clock_time, self.iteration
         return model
 
+    def _member_model(self, m):
+        return ShallowWaterModel(self.grid, self.g, self.f, formulation=self.formulation, lorentz_forcing=self.lorentz_forcing,
+                                 dtype=self.dtype, device=self._state[0].device, strict=self.strict)
+
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
         self._ensure_halos()
         torch.cuda.synchronize()
+
+
+class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
+    """`members` ShallowWaterModels of one grid with at least one Bounded direction, each with its own boundary conditions.
+    `boundary_conditions`: one dict {name: FieldBoundaryConditions} for every member (ShallowWaterModel's argument), or a list of
+    `members` such dicts (None entries: defaults).  Other arguments as ShallowWaterEnsemble's; fuse_halo=True lets the stage read the
+    periodic images of a Periodic direction (the boundary-condition fill after every stage writes all halos either way).
+
+    Every RK3 stage is one launch of the wall kernel for all members (G- form, as ShallowWaterModel.time_step runs a Bounded grid),
+    followed by one boundary-condition fill of all members (swmhd_ensemble_step_rk3_bc).  Halos are always current."""
+
+    def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
+                 lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
+                 fuse_halo=True, boundary_conditions=None):
+        tx, ty = grid.topo_codes()
+        self._bounded = (tx == _lib.BOUNDED, ty == _lib.BOUNDED)
+        if not any(self._bounded):
+            raise _lib.SwmhdError("BoundedShallowWaterEnsemble needs a Bounded direction: use ShallowWaterEnsemble for (Periodic, Periodic)")
+        vi = formulation == VectorInvariantFormulation
+        names = ("u", "v", "h", "A") if vi else ("uh", "vh", "h", "A")
+        B = int(members)
+        if isinstance(boundary_conditions, (list, tuple)):
+            if len(boundary_conditions) != B:
+                raise _lib.SwmhdError(f"boundary_conditions: {len(boundary_conditions)} entries for {members} members")
+            per_member = [dict(bc or {}) for bc in boundary_conditions]
+        else:
+            per_member = [dict(boundary_conditions or {})] * max(B, 0)
+        for bcs in per_member:
+            for name, bc in bcs.items():
+                if name not in names:
+                    raise _lib.SwmhdError(f"boundary condition for {name!r}: the fields are {names}")
+                if not isinstance(bc, FieldBoundaryConditions):
+                    raise _lib.SwmhdError(f"boundary condition for {name!r}: a FieldBoundaryConditions, not {type(bc).__name__}")
+                sides = [(bc.west, 0), (bc.east, 0), (bc.south, 1), (bc.north, 1)]
+                if any(b is not None and not self._bounded[d] for b, d in sides):
+                    raise _lib.SwmhdError(f"boundary condition on a Periodic side of {name} (Oceananigans rejects it as well)")
+        super().__init__(grid, members, gravitational_acceleration, coriolis_f, formulation, lorentz_forcing, dtype, strict, device,
+                         member_stride, decomp, fuse_halo)
+        self._member_bcs = per_member
+        # (members, 4 fields, 4 sides: west, east, south, north), NaN = default; in the ensemble's dtype (f32: rounded to nearest as the
+        # single model's ctypes.c_float values are)
+        table = [[(bcs[n].gradients() if n in bcs else [float("nan")] * 4) for n in self.names] for bcs in per_member]
+        self.gradients = torch.tensor(table, dtype=torch.float64).to(device=self._state[0].device, dtype=dtype)
+        # the kernel reads the periodic images of a Periodic direction, as ShallowWaterModel sets _rwrap; halos never go stale
+        self._kwrap = 0
+        if fuse_halo and grid.Nx >= grid.Hx and grid.Ny >= grid.Hy:
+            self._kwrap = (0 if self._bounded[0] else _lib.WRAP_X) | (0 if self._bounded[1] else _lib.WRAP_Y)
+        self._rwrap = 0
+        self._flags |= (_lib.BOUNDED_X if self._bounded[0] else 0) | (_lib.BOUNDED_Y if self._bounded[1] else 0)
+
+    def _check_topology(self, grid):
+        pass   # (checked in __init__)
+
+    def update_state(self):
+        """fill_halo_regions! of every member with its boundary conditions (swmhd_ensemble_fill_halo: two launches for all)."""
+        g = self.grid
+        self._halo_stale = False
+        tx, ty = g.topo_codes()
+        f = getattr(self._L, f"swmhd_ensemble_fill_halo_{self.sfx}")
+        _lib.check(f(self._ptrs(self._state), 4, self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), tx, ty,
+                     0b0001, 0b0010, self.gradients.data_ptr(), g.dx, g.dy, _stream_ptr()), "swmhd_ensemble_fill_halo")
+
+    def _native_steps(self, dt, n):
+        g = self.grid
+        swapped = ctypes.c_int(0)
+        f = getattr(self._L, f"swmhd_ensemble_step_rk3_bc_{self.sfx}")
+        rc = f(self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(self.Gm), self.members, self.stride_m,
+               g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
+               self.gradients.data_ptr(), self._flags | self._kwrap, ctypes.byref(swapped), _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_step_rk3_bc")
+        if swapped.value:
+            self._state, self._alt = self._alt, self._state
+            self.Gn, self.Gm = self.Gm, self.Gn
+        self.clock_time += n * dt
+        self.iteration += n
+
+    def _member_model(self, m):
+        return ShallowWaterModel(self.grid, self.g, self.f, formulation=self.formulation, lorentz_forcing=self.lorentz_forcing,
+                                 dtype=self.dtype, device=self._state[0].device, strict=self.strict,
+                                 boundary_conditions=self._member_bcs[m])
