@@ -85,6 +85,7 @@ struct TendArgs {
     int topo_x, topo_y;   // 0 Periodic, 1 Bounded (wall orders of the reconstructions; the LDS-tiled kernel implements them)
     int leave_room;       // marching kernels: leave ~5 % of the workgroup slots free for another stream's kernels
     int edge_cols;        // LDS-tiled kernel: only the first and the last (narrow last: last two) 64-column tile columns -- the x-wall frame of a Bounded grid
+    int fold_last;        // vector-invariant marching kernel: the last column strip is folded (MarchGeometry::fold; set by the launcher)
     T *Unew[4];
     const T *Gm[4];
     T dt, gamma, zeta;
@@ -212,10 +213,14 @@ struct ProgressPriority {
 
 // ---- launch geometry of the row-marching kernels --------------------------------------------------------------------------
 // One workgroup = a strip of nt - 2*xh output columns x LY rows; the grid is a whole number of rounds of resident workgroups.
+// Folded last strip (fold = 1): where the last strip has at most nt/2 - 2*xh output columns, each of its workgroups runs two
+// half-width sub-strips of nt/2 lanes on two segments, so a segment row costs nstrips - 1/2 workgroups instead of nstrips.
 struct MarchGeometry {
     int nt;        // threads per workgroup (strip width incl. 2*xh halo lanes)
     int nstrips, nseg, LY;
     int wg_per_cu; // resident workgroups per CU the kernel is built for
+    int fold;      // 1: the last strip is folded (nstrips still counts it as one strip)
+    int blocks() const { return fold ? (nstrips - 1) * nseg + (nseg + 1) / 2 : nstrips * nseg; }
 };
 // Compute units of the current device (hipDeviceAttributeMultiprocessorCount; 256 on MI355X), cached per process.
 inline int device_cu_count() {
@@ -240,7 +245,8 @@ inline int env_knob(const char *name, int &cache) {   // cache: 0 = not read yet
 // Strip width: the FIRST candidate workgroup size unless a later one covers Nx with at least 5 % fewer lanes (1024 columns: 5 strips x
 // 256 lanes = 1280, but 9 x 128 = 1152).  Rows per segment: the smallest whole number of rounds of resident workgroups
 // (wg_per_cu x CUs slots; ~5 % fewer with leave_room, so that another stream's kernels find room) whose segments are at most
-// 128 rows, but never shorter than ly_min rows.
+// 128 rows, but never shorter than ly_min rows.  fold_nt: the workgroup size whose kernel can fold its last strip (0: none); the strip
+// width is chosen first, and folding then only changes how many workgroups a segment row costs.
 // Share of the workgroup slots an interior launch of the slab driver leaves free for the comm stream's kernels, in 64ths: 3 (4.7 %),
 // and 1 (1.6 %) for slabs of 3072 rows and more -- the boundary work per step is fixed, a long interior launch gives it time enough in
 // few slots, and every slot costs the interior launch its share of the chip (4096 x 4096 ring-of-one step: +1.4-1.9 % over the plain
@@ -251,7 +257,7 @@ inline int leave_room_64ths(int rows) {
     return v > 0 ? (v < 32 ? v : 32) : (rows >= 3072 ? 1 : 3);
 }
 inline MarchGeometry march_geometry(int Nx, int rows, int xh, const int *nts, const int *wgs, int ncand, int ly_min, bool leave_room,
-                                    int force_nt, int force_ly) {
+                                    int force_nt, int force_ly, int fold_nt = 0) {
     MarchGeometry g{};
     long best = -1;
     for (int k = 0; k < ncand; ++k) {
@@ -261,11 +267,13 @@ inline MarchGeometry march_geometry(int Nx, int rows, int xh, const int *nts, co
         if (take) { best = lanes; g.nt = nts[k]; g.nstrips = ns; g.wg_per_cu = wgs[k]; }
     }
     if (best < 0) { g.nt = nts[0]; g.nstrips = (Nx + nts[0] - 2 * xh - 1) / (nts[0] - 2 * xh); g.wg_per_cu = wgs[0]; }
+    g.fold = fold_nt && g.nt == fold_nt && g.nstrips > 1 && Nx - (g.nstrips - 1) * (g.nt - 2 * xh) <= g.nt / 2 - 2 * xh ? 1 : 0;
+    const int halves = 2 * g.nstrips - g.fold;   // half-workgroups per segment row
     int slots = device_cu_count() * g.wg_per_cu;
     if (leave_room) slots -= (slots * leave_room_64ths(rows)) / 64;
     int LY = 32;
     for (int k = 1; k <= 64; ++k) {
-        const int ns = (slots * k) / g.nstrips;
+        const int ns = (2 * slots * k) / halves;
         if (ns < 1) continue;
         const int ly = (rows + ns - 1) / ns;
         if (ly <= 128) { LY = ly < ly_min ? ly_min : ly; break; }

@@ -41,11 +41,19 @@ template <typename TA> __device__ __forceinline__ void segment_rows(const TA &a,
     J1 = base + LY < end ? base + LY : end;
 }
 
+// Folded last strip (TendArgs::fold_last, fp64 with 256 lanes): where the last strip has at most NT/2 - 2 XH output columns (4096 columns:
+// 16 strips of 250 and one of 96), its workgroups run waves 0-1 and waves 2-3 as two independent 128-lane sub-strips of that strip, each
+// with its own halo lanes and its own LDS columns, on two segments.  A segment row then costs 16.5 workgroups instead of 17.  Block ids:
+// per pair of segments, the full strips of the first, then those of the second, then one folded workgroup for both.  The halves share the
+// barriers, so both run as many iterations as the longer segment; the shorter half (last segment, or none at an odd segment count) runs
+// its extra iterations with every store dropped and its G- loads on its own last row.
 template <typename T, int LOR, int NT, int MODE>
 __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int nstrips, int nseg, int LY) {
     constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0, ANCHOR = (MODE & 8) != 0;
     constexpr bool STORE_W = ANCHOR && FUSE && !HAS_GM;   // first anchored stage: W goes out through the G descriptors
-    constexpr int XH = 3, RW = NT + 2 * XH, TXO = NT - 2 * XH;
+    constexpr bool FOLDS = NT == 256 && sizeof(T) == 8;  // built with the folded layout (the launcher folds nothing else)
+    constexpr int XH = 3, NH = NT / 2, TXO = NT - 2 * XH;
+    constexpr int RW = FOLDS ? 2 * (NH + 2 * XH) : NT + 2 * XH;   // LDS columns: a full strip, or two sub-strips side by side
     __shared__ T Ru[3][RW];    // u rows jo-1, jo (+1: written while the previous row's readers may still run)
     __shared__ T Rvn[1][RW];   // v newest row (to fetch the left neighbour's value for the vl window)
     __shared__ __attribute__((aligned(16))) T RHA[4][RW][2];   // per column (A, h): A rows jo-1 .. jo+1 (+1 being written), h row jo --
@@ -58,19 +66,35 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     __shared__ T RZUV[RW][3];  // per column: zeta(c, jo) and the velocities uf, vf at the vorticity point, for the x-direction stencil
                                // (interleaved: one LDS address per stencil point serves all three; 24-B stride is conflict-free)
 
-    const unsigned bid = xcd_remap(blockIdx.x, (unsigned)(nstrips * nseg));
-    const int strip = (int)(bid % nstrips), seg = (int)(bid / nstrips);
+    const bool fold = FOLDS && a.fold_last;
+    const int nfull = fold ? nstrips - 1 : nstrips;   // full strips
+    const unsigned bid = xcd_remap(blockIdx.x, (unsigned)(fold ? nfull * nseg + (nseg + 1) / 2 : nstrips * nseg));
+    int strip = (int)(bid % nstrips), seg = (int)(bid / nstrips);
+    bool half_wg = false;   // a folded workgroup
+    int hf = 0;             // this wave's sub-strip in it
+    if (fold) {
+        const int pr = (int)bid / (2 * nfull + 1), r = (int)bid - pr * (2 * nfull + 1);   // segments 2 pr, 2 pr + 1
+        half_wg = r >= (2 * pr + 1 < nseg ? 2 : 1) * nfull;                              // (after the pair's full-strip workgroups)
+        if (half_wg) hf = __builtin_amdgcn_readfirstlane((int)threadIdx.x / NH);         // (wave-uniform: the row arithmetic stays scalar)
+        strip = half_wg ? nfull : r % nfull;
+        seg = 2 * pr + (half_wg ? hf : r / nfull);
+    }
+    int J0, J1, niter;
+    segment_rows(a, seg - hf, LY, J0, J1);   // a folded workgroup iterates over its first segment, the longer one
+    niter = (J1 - J0) + 6;
+    if (hf) {
+        if (seg < nseg) segment_rows(a, seg, LY, J0, J1);
+        else J0 = J1 = a.j1;                 // (odd segment count: the last folded workgroup's second half has no rows)
+    }
     const int x0 = strip * TXO;
-    int J0, J1;
-    segment_rows(a, seg, LY, J0, J1);
-    const int c = threadIdx.x, lc = c + XH;
+    const int c = threadIdx.x - hf * NH, lc = c + XH + hf * (NH + 2 * XH);   // lane and LDS column within the (sub-)strip
     const int gx = x0 - XH + c;
     const bool wx = (a.wrap & 1) != 0, wy = (a.wrap & 2) != 0;   // periodic images instead of halo cells (common.hpp)
     const int gxc = wrap_index(gx, a.Nx, -a.Hx, a.Nx + a.Hx - 1, wx);
     const int ylo = -a.Hy, yhi = a.Ny + a.Hy - 1;
     const T rdx = a.rdx, rdy = a.rdy;
     const Geo<T> g{a.dx, a.dy, a.rdx, a.rdy};
-    const bool col_ok = (c >= XH) && (c < NT - XH) && (gx < a.Nx);
+    const bool col_ok = (c >= XH) && (c < (half_wg ? NH : NT) - XH) && (gx < a.Nx);
 
     // register windows of this lane's column, one element longer than the stencils (see above): element k holds row jo-3+k (uw) /
     // jo-2+k (the others).
@@ -90,6 +114,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     const unsigned colb = (unsigned)(gxc + a.Hx) * (unsigned)sizeof(T);
     auto rowoff = [&](int row) -> unsigned { return (unsigned)((row + a.Hy) * isy) * (unsigned)sizeof(T); };
     const unsigned pbytes = (unsigned)((a.Ny + 2 * a.Hy) * isy) * (unsigned)sizeof(T);
+    const unsigned rowlast = rowoff(J1 - 1);
     __amdgpu_buffer_rsrc_t rG[4], rU[4];
     if constexpr (STORE_G || STORE_W) {
         rG[0] = out_rsrc(a.G1 - off0, pbytes); rG[1] = out_rsrc(a.G2 - off0, pbytes);
@@ -161,7 +186,11 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         // G⁻ (W) of the output row is needed only at the very end of the iteration: issue its loads after the second barrier so their
         // HBM latency hides under the arithmetic in between
         T gm0 = T(0), gm1 = T(0), gm2 = T(0), gm3 = T(0);
-        const unsigned rowb = rowoff(jo);
+        // Rows without an output (the extra iterations of a folded workgroup's shorter half): stores at pbytes + colb, beyond the
+        // parent (dropped by the hardware); G- loads on the half's last row.  (Clamping the row itself instead cost 16-164 B of scratch.)
+        const bool live = jo < J1;
+        const unsigned rowb = live ? rowoff(jo) : pbytes;
+        const unsigned og = (live ? rowb : rowlast) + colb;
 
         const int s3o = ((jo % 3) + 3) % 3, s3m = (s3o + 2) % 3, s3p = (s3o + 1) % 3;   // ring slots of rows jo, jo-1, jo+1
         const int s4o = jo & 3, s4p = (jo + 1) & 3;
@@ -206,7 +235,6 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         }
         __syncthreads();
         if constexpr (FUSE && HAS_GM) {   // G- of the output row: needed at the very end, ~2/3 of an iteration away
-            const unsigned og = rowb + colb;
             gm0 = LD(a.Gm[0], og); gm1 = LD(a.Gm[1], og); gm2 = LD(a.Gm[2], og); gm3 = LD(a.Gm[3], og);
         }
 
@@ -245,7 +273,8 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         const T Gh = -((RFh[0][lc + 1] - RFh[0][lc]) * rdx + (fhy_n - fhy) * rdy);
         const T GA = -((RFA[0][lc + 1] - RFA[0][lc]) * rdx + (fay_n - fay) * rdy)
                      + Aa[2] * ((ue - U[3]) * rdx + (V[3] - V[2]) * rdy);
-        const unsigned o = col_ok ? rowb + colb : SW_OOB;   // lanes without an output column: dropped by the hardware
+        // lanes / rows without an output: dropped by the hardware (the G- offset serves where there is one: one VALU add less)
+        const unsigned o = FUSE && HAS_GM ? (col_ok && live ? og : SW_OOB) : (col_ok ? rowb + colb : SW_OOB);
         const T Gs[4] = {G1, G2, Gh, GA};
         if constexpr (STORE_G) {
             const unsigned oG = a.drop_G ? SW_OOB : o;      // (last RK3 stage running this variant: nothing reads its G)
@@ -287,7 +316,6 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         for (int k = 0; k < 5; ++k) { zw[k] = zw[k + 1]; svw[k] = svw[k + 1]; }
     };
 
-    const int niter = (J1 - J0) + 6;
     const ProgressPriority prio(niter);
     int it = 6;
     // (A pair-unrolled loop -- one window rotation per TWO rows, 569 instead of 580 VALU instructions per row -- needs a few registers

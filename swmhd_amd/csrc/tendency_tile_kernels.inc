@@ -328,7 +328,9 @@ constexpr long SW_MARCH_MIN_CELLS = 330000L;
 #if !SWMHD_STRICT
 // Geometry of the marching tendency kernels.  Vector-invariant kernel: <= 168 VGPRs and 0.19 KB of LDS per lane -> 12 waves per
 // CU, i.e. 3 / 6 workgroups of 256 / 128 threads.  Conservative kernel: 2 workgroups of 256 per CU (69 KB LDS).
-// Knobs (read once): SWMHD_T_LY rows per segment, SWMHD_T_NT workgroup size (128 or 256).
+// Knobs (read once): SWMHD_T_LY rows per segment, SWMHD_T_NT workgroup size (128 or 256), SWMHD_T_FOLD=0 no folded last strip (A/B).
+// Folded last strip (fp64 vector-invariant kernel, 256 lanes, last strip <= 122 output columns; tendency_march_kernels.inc): 4096
+// columns run 16 full workgroups and half a folded one per segment row instead of 17 -- LY 90 instead of 92 in one round.
 // Packed-fp32 kernel (tendency_pk_kernels.inc): vector-invariant model, x read with periodic wrapping, even Nx.  256 lanes = 512
 // columns per strip, 504 of them output; 3 workgroups per CU (<= 168 VGPRs, 46 KB LDS).
 static bool tendency_uses_packed_fp32(int Nx, int formulation, int wrap) {
@@ -341,14 +343,21 @@ static MarchGeometry packed_fp32_geometry(int Nx, int rows, int leave_room) {
     g.nt = 256;
     return g;
 }
-static MarchGeometry tendency_march_geometry(int Nx, int rows, int formulation, int leave_room, int elem_size, int mode = 7) {
+static bool tendency_fold_enabled() {
+    static const bool on = [] { const char *e = getenv("SWMHD_T_FOLD"); return !e || atoi(e) != 0; }();
+    return on;
+}
+// fold_ok: the launch may fold its last strip (one row range: the slab driver's two-range launches keep full strips)
+static MarchGeometry tendency_march_geometry(int Nx, int rows, int formulation, int leave_room, int elem_size, int mode = 7,
+                                             bool fold_ok = true) {
     static int ly_cache = 0, nt_cache = 0;
     const int force_ly = env_knob("SWMHD_T_LY", ly_cache), force_nt = env_knob("SWMHD_T_NT", nt_cache);
     if (formulation == 1) {
         // (384-thread workgroups cover 4096 columns with 3 % fewer lanes -- 11 strips instead of 17 -- but measured 37 % SLOWER on
         //  MI355X, 1.75 vs 1.275 ms per step: six waves per barrier leave each SIMD too little to overlap; removed after that measurement)
         static const int nts[2] = {256, 128}, wgs64[2] = {3, 6}, wgs32[2] = {4, 8};   // fp32: <= 128 VGPRs, 4 waves per SIMD
-        return march_geometry(Nx, rows, 3, nts, elem_size == 8 ? wgs64 : wgs32, 2, 6, leave_room != 0, force_nt, force_ly);
+        const int fold_nt = elem_size == 8 && fold_ok && tendency_fold_enabled() ? 256 : 0;
+        return march_geometry(Nx, rows, 3, nts, elem_size == 8 ? wgs64 : wgs32, 2, 6, leave_room != 0, force_nt, force_ly, fold_nt);
     }
     // (128-thread workgroups where they waste >= 5 % fewer lanes in the last strip: 1024 columns = 5 strips of 250 or 9 of 122)
     const int w = cons_minwaves(mode, elem_size);                          // per stage variant (tendency_march_kernels.inc)
@@ -479,12 +488,15 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
         TendArgs<T> ax = a;
         const int mode = march_stage_mode(ax, formulation);
         const bool packed = sizeof(T) == 4 && tendency_uses_packed_fp32(a.Nx, formulation, a.wrap);   // two columns per lane, packed arithmetic
-        const MarchGeometry mg = packed ? packed_fp32_geometry(a.Nx, rows, a.leave_room)
-                                        : tendency_march_geometry(a.Nx, rows, formulation, a.leave_room, (int)sizeof(T), mode);
-        const int nstrips = mg.nstrips, LY = mg.LY, nseg = two ? two_range_segments(LY) : mg.nseg;
+        // (a folded workgroup's rows without an output store one row beyond the parent: that offset must fit 32 bits too)
+        const bool fold_ok = !two && (long)(a.Ny + 2 * a.Hy + 1) * a.sy * (long)sizeof(T) < (1L << 32) - 64;
+        MarchGeometry mg = packed ? packed_fp32_geometry(a.Nx, rows, a.leave_room)
+                                  : tendency_march_geometry(a.Nx, rows, formulation, a.leave_room, (int)sizeof(T), mode, fold_ok);
+        if (two) mg.nseg = two_range_segments(mg.LY);
+        ax.fold_last = mg.fold;
         const MarchKernel<T> k = march_kernel<T>(mode, formulation, lorentz, mg.nt, packed);
         if (!k) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k, dim3(nstrips * nseg), dim3(mg.nt), 0, s, ax, nstrips, nseg, LY);
+        hipLaunchKernelGGL(k, dim3(mg.blocks()), dim3(mg.nt), 0, s, ax, mg.nstrips, mg.nseg, mg.LY);
         return hipGetLastError();
     }
 #endif
