@@ -88,6 +88,11 @@ extern "C" {
                                  qnew = Gm + dt gamma Gn'; zeta is unused and Gn is not written (it may alias Gm).  store_G is ignored.  Every
                                  stage moves 96 B/cell in fp64.  Results differ from the G- form by rounding only.  The step drivers use it.
                                  Refused with SWMHD_STRICT or SWMHD_BOUNDED_* (SWMHD_ENOTSUP) and with SWMHD_GM_IS_PREV_STATE (SWMHD_EINVAL). */
+#define SWMHD_OPEN_SOUTH 4096 /* tendency entry points, with SWMHD_BOUNDED_Y only (else SWMHD_EINVAL): the south / north side of these rows is a  */
+#define SWMHD_OPEN_NORTH 8192 /*   cut to a neighbouring y-slab of a Bounded-y chain, not a wall.  Its halo holds the neighbour's rows; rows next
+                                   to it keep WENO5 / the centred 4th order and the divergence forcing takes no wall branch there -- exactly what
+                                   the whole domain computes for those rows.  Rank 0 of a chain passes OPEN_NORTH, the last rank OPEN_SOUTH, every
+                                   other rank both (swmhd_ring_step_rk3_bc sets them itself).                                                  */
 #define SWMHD_LEAVE_ROOM 64   /* tendency entry points: size the row-marching grid ~5 % short of filling the chip, so that kernels of
                                  another stream (the ring's halo exchange and boundary strips) can start while it runs                */
 
@@ -204,6 +209,16 @@ int swmhd_fill_halo_f64(double *const *fields, int nf, int Nx, int Ny, int Hx, i
 int swmhd_fill_halo_f32(float *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t stride_y, int topo_x, int topo_y,
                         int face_x, int face_y, const float *gradient, float dx, float dy, void *stream);
 
+/* swmhd_fill_halo for one y-slab of a chain (a Bounded y direction cut into slabs, swmhd_ring_step_rk3_bc): x halos as topo_x says,
+ * y halos as a Bounded direction but only on the sides that ARE walls -- walls_y bit 0 = south wall (rank 0), bit 1 = north wall (the
+ * last rank); a cut side (its halo comes from the neighbour; its first interior line is not a wall either) is left untouched.  walls_y = 3
+ * is bitwise swmhd_fill_halo with topo_y = SWMHD_BOUNDED; walls_y = 0 fills x only (a slab of a Periodic-y ring with Bounded x).
+ * Other bits of walls_y: SWMHD_EINVAL.  Other arguments and checks as swmhd_fill_halo. */
+int swmhd_fill_halo_walls_f64(double *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t stride_y, int topo_x, int walls_y,
+                              int face_x, int face_y, const double *gradient, double dx, double dy, void *stream);
+int swmhd_fill_halo_walls_f32(float *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t stride_y, int topo_x, int walls_y,
+                              int face_x, int face_y, const float *gradient, float dx, float dy, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused tendency evaluation: the whole-field form of Oceananigans' ShallowWaterModel tendency kernels
  * (calculate_tendencies!) WITH the reference's forcing callback fused in -- one pass over the four
@@ -225,7 +240,8 @@ int swmhd_fill_halo_f32(float *const *fields, int nf, int Nx, int Ny, int Hx, in
  * wall-normal velocity ON the wall (index 1) is whatever the stencil gives: the caller's halo fill resets that line to zero, as
  * Oceananigans' does.  Bounded grids run on the LDS-tiled kernel; from ~0.3 Mcell on, the row-marching kernel computes every row with
  * the periodic formulas first and the LDS-tiled kernel then overwrites the frame of cells near the walls (same results to rounding).
- * A direction cannot be both Bounded and SWMHD_WRAP-ped.
+ * A direction cannot be both Bounded and SWMHD_WRAP-ped.  SWMHD_OPEN_SOUTH / SWMHD_OPEN_NORTH (with SWMHD_BOUNDED_Y): these rows are a
+ * y-slab of a Bounded-y chain and that side is a cut -- no wall frame along it, periodic formulas next to it.
  * ---------------------------------------------------------------------------------------------- */
 #define SWMHD_CONSERVATIVE 0
 #define SWMHD_VECTOR_INVARIANT 1
@@ -312,7 +328,8 @@ int swmhd_step_rk3_f32(float *const *q, float *const *q_alt, float *const *Ga, f
 int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, int flags, int out[8]);
 
 /* ------------------------------------------------------------------------------------------------
- * Multi-GPU: one process per GPU, the domain cut into y-slabs (rank r owns global rows [r*Ny, (r+1)*Ny), all x).
+ * Multi-GPU: one process per GPU, the domain cut into y-slabs (rank r owns global rows [r*Ny, (r+1)*Ny), all x).  A Periodic y
+ * direction makes the slabs a ring; a Bounded one a chain with walls at its two ends (swmhd_ring_step_rk3_bc).
  * The reference is single-process -- its periodic y boundary is the in-memory halo copy of Oceananigans'
  * fill_halo_regions! (topology = (Periodic, Periodic, Flat), SWMHD_example.jl:16, divergence_sw_mhd.jl:14); here that
  * copy becomes a ring of RCCL sends/receives between y-neighbours.  A swmhd_ring owns the RCCL
@@ -379,6 +396,40 @@ int swmhd_ring_step_rk3_f32(swmhd_ring *ring, float *const *q, float *const *q_a
                             float g, float f, int formulation, int lorentz, float dt, int nsteps,
                             int flags, int *state_in_alt, void *stream);
 int swmhd_ring_join(swmhd_ring *ring, void *stream);   /* order `stream` behind the exchange in flight (no-op if none) */
+/* Flags SWMHD_BOUNDED_X / SWMHD_BOUNDED_Y: swmhd_ring_step_rk3 refuses them (SWMHD_ENOTSUP); Bounded slabs step with the call below. */
+
+/* swmhd_ring_exchange_y restricted to some sides: sides bit 0 = the south neighbour, bit 1 = the north neighbour (3: the full
+ * exchange).  A chain (Bounded y) exchanges nothing across its two walls: rank 0 passes 2, the last rank 1, the others 3, a chain of
+ * one 0 (nothing is enqueued).  Both ends of every pair must name it. */
+int swmhd_ring_exchange_y_sides_f64(swmhd_ring *ring, double *const *fields, int nfields, int Nx, int Ny, int Hx, int Hy,
+                                    int64_t stride_y, int sides, void *stream);
+int swmhd_ring_exchange_y_sides_f32(swmhd_ring *ring, float *const *fields, int nfields, int Nx, int Ny, int Hx, int Hy,
+                                    int64_t stride_y, int sides, void *stream);
+
+/* swmhd_ring_step_rk3 for Bounded slabs.  flags must carry SWMHD_BOUNDED_X and/or SWMHD_BOUNDED_Y (else SWMHD_EINVAL).
+ *   SWMHD_BOUNDED_Y: the ring is a CHAIN -- rank 0 holds the south wall, rank nranks-1 the north wall (a ring of one: both), every other
+ *     side is a cut whose halo rows come from the neighbour; nothing travels between the last rank and rank 0.  The driver passes
+ *     SWMHD_OPEN_SOUTH / _NORTH for the cut sides itself (a caller's OPEN flags: SWMHD_EINVAL).
+ *   SWMHD_BOUNDED_X alone: a periodic-y ring of slabs whose x walls are local to every slab.
+ * Stages in G- form (as the single Bounded model; no anchor form), the per-stage schedule only (also for Hy >= 9): rows that need no
+ * remote data -- the interior and a wall side's strip -- run on `stream` while the exchange is in flight; the Hy-row strip of each cut
+ * side follows the exchange on the comm stream; then the boundary-condition fill (swmhd_fill_halo_walls: x, and the wall sides) of the
+ * new state on `stream`, and its exchange (swmhd_ring_exchange_y_sides) on the comm stream.  gradient: DEVICE table of 16 values
+ * (west, east, south, north of q1, q2, h, A; NaN = default) or NULL.  Entry / exit conditions, buffers and state_in_alt as
+ * swmhd_ring_step_rk3 (entry: halos current, i.e. filled and exchanged).
+ *   SWMHD_ENOTSUP  SWMHD_MARCH_KERNEL, SWMHD_GM_IS_PREV_STATE, SWMHD_RK3_ANCHOR (as the single Bounded grid)
+ *   SWMHD_EINVAL   ring NULL, no Bounded flag, SWMHD_WRAP_Y, SWMHD_OPEN_*, unknown flags, a wrapped Bounded direction, Ny < 2 Hy + 1
+ * Flag checks precede the ring check; every check precedes the first HIP call.  Results: SWMHD_STRICT slabs are bit-identical to the
+ * single-domain Bounded model (every row is the same arithmetic); fast slabs are within the fast tolerances of it (a row may be
+ * computed by another kernel variant), deterministic from run to run. */
+int swmhd_ring_step_rk3_bc_f64(swmhd_ring *ring, double *const *q, double *const *q_alt, double *const *Ga, double *const *Gb,
+                               int Nx, int Ny, int Hx, int Hy, int64_t stride_y, double dx, double dy,
+                               double g, double f, int formulation, int lorentz, double dt, int nsteps,
+                               const double *gradient, int flags, int *state_in_alt, void *stream);
+int swmhd_ring_step_rk3_bc_f32(swmhd_ring *ring, float *const *q, float *const *q_alt, float *const *Ga, float *const *Gb,
+                               int Nx, int Ny, int Hx, int Hy, int64_t stride_y, float dx, float dy,
+                               float g, float f, int formulation, int lorentz, float dt, int nsteps,
+                               const float *gradient, int flags, int *state_in_alt, void *stream);
 
 /* Measurement hook: record HIP events around the next `max_launches` interior launches of swmhd_ring_step_rk3 (0 = off);
  * swmhd_ring_launch_times waits for them and returns how many (ms, rows) pairs it wrote. */

@@ -16,6 +16,7 @@ LEAVE_ROOM = 64
 GM_IS_PREV_STATE = 1024
 RK3_ANCHOR = 2048
 BOUNDED_X, BOUNDED_Y = 256, 512
+OPEN_SOUTH, OPEN_NORTH = 4096, 8192    # with BOUNDED_Y: that side of a y-slab of a Bounded-y chain is a cut, not a wall
 KERNEL_FLAGS = {None: 0, "auto": 0, "tile": 2, "march": 4}
 PERIODIC, BOUNDED = 0, 1
 HALO_X, HALO_Y = 1, 2
@@ -114,6 +115,15 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ring_step_rk3_{sfx}")
         f.argtypes = [p] + [C.POINTER(p)] * 4 + [i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, i, i, C.POINTER(i), p]
         f.restype = i
+        f = getattr(lib, f"swmhd_ring_exchange_y_sides_{sfx}")
+        f.argtypes = [p, C.POINTER(p), i, i, i, i, i, i64, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ring_step_rk3_bc_{sfx}")
+        f.argtypes = [p] + [C.POINTER(p)] * 4 + [i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, i, p, i, C.POINTER(i), p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_fill_halo_walls_{sfx}")
+        f.argtypes = [C.POINTER(p), i, i, i, i, i, i64, i, i, i, i, p, ft, ft, p]
+        f.restype = i
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
     lib.swmhd_tendency_launch_geometry.restype = i
     lib.swmhd_ring_available.argtypes = [C.c_char_p]
@@ -144,7 +154,7 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "lorentz_jacobian", "lorentz_jacobian_rows", "lorentz_divergence", "lorentz_divergence_rows",
         "fill_halo", "fill_halo_periodic", "fill_halo_periodic_multi", "tendencies", "tendencies_rk3", "rk3_substep", "step_rk3", "diagnostics",
         "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
-        "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc")] + [
+        "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc", "fill_halo_walls", "ring_exchange_y_sides", "ring_step_rk3_bc")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

@@ -43,6 +43,13 @@ hipError_t launch_fill_halo_periodic_multi(T *const *interiors, int nfields, int
 // fill_halo_regions! for any (Periodic | Bounded) topology pair with Oceananigans' default boundary conditions or gradient BCs
 // (oracle_fill_halo): west/east pass, then south/north pass over the padded width.  face_x/face_y: bit f set = field f is
 // located at Face in that direction; grad[f][4] = west, east, south, north GradientBoundaryCondition values (NaN = default).
+// A Bounded y direction cut into y-slabs (swmhd_ring_step_rk3_bc, SWMHD_OPEN_SOUTH / _NORTH): bits above the topology code 1 in
+// TendArgs::topo_y and HaloBc::topo_y mark a side that is a cut to a neighbouring slab, not a wall.  Reconstructions see the rows next to
+// it as far from any wall (order 5 / centred 4th, no wall branch of the divergence forcing); the boundary-condition fill leaves its halo
+// rows alone (they come from the neighbour).  topo_y == 1 is the whole Bounded direction, both sides walls.
+constexpr int TOPO_OPEN_SOUTH = 2, TOPO_OPEN_NORTH = 4;
+// index offset that puts an open side's rows out of reach of every wall test (left_order / right_order / sym_fourth / wall_code)
+constexpr int TOPO_FAR = 1 << 20;
 template <typename T>
 struct HaloBc {
     T *f[4];
@@ -82,7 +89,8 @@ struct TendArgs {
     int wrap;             // periodic index wrapping of the READS: bit0 = x, bit1 = y -- the kernel takes (x mod Nx, y mod Ny) instead of the
                           // halo cells, so the caller need not have filled those halos (no halo-fill launch between RK3 stages)
     int kernel_variant;   // 0 = by size, 1 = LDS-tiled kernel, 2 = row-marching kernel
-    int topo_x, topo_y;   // 0 Periodic, 1 Bounded (wall orders of the reconstructions; the LDS-tiled kernel implements them)
+    int topo_x, topo_y;   // 0 Periodic, 1 Bounded (wall orders of the reconstructions; the LDS-tiled kernel implements them); topo_y of a
+                          // y-slab of a Bounded-y chain also carries TOPO_OPEN_SOUTH / TOPO_OPEN_NORTH: that side is a cut, not a wall
     int leave_room;       // marching kernels: leave ~5 % of the workgroup slots free for another stream's kernels
     int edge_cols;        // LDS-tiled kernel: only the first and the last (narrow last: last two) 64-column tile columns -- the x-wall frame of a Bounded grid
     int fold_last;        // vector-invariant marching kernel: the last column strip is folded (MarchGeometry::fold; set by the launcher)
@@ -302,6 +310,11 @@ int tendencies_rk3_two_ranges(const T *const *q, T *const *qnew, T *const *Gn, c
                               int j0b, int j1b, int flags, void *stream);
 template <typename T>
 int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which, void *stream);
+// boundary-condition fill of one slab (swmhd_fill_halo_walls with a DEVICE gradient table of 4 nf values, NULL = defaults): x in the
+// grid's x topology, y walls only on the sides of walls_y (bit 0 south, bit 1 north); same checks and return codes
+template <typename T>
+int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int topo_x, int walls_y, int face_x, int face_y,
+                        const T *gtab, T dx, T dy, void *stream);
 template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, hipStream_t s);
 
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,

@@ -97,14 +97,16 @@ __global__ void k_halo_bc(std::conditional_t<ENS, HaloBcEns<T>, HaloBc<T>> a) {
     const T glo = bc_gradient<T>(a, fld, DIR == 0 ? 0 : 2), ghi = bc_gradient<T>(a, fld, DIR == 0 ? 1 : 3);
     // element k (0-based along the direction, halo cells have k < 0 or k >= N) of this line
     auto at = [&](int k) -> T & { return DIR == 0 ? f[(long)line * a.sy + k] : f[(long)k * a.sy + (line - a.Hx)]; };
+    // a side marked open (TOPO_OPEN_SOUTH / _NORTH: a y-slab's cut to its neighbour) is left alone: its halo comes from the neighbour
+    const bool lo = !(topo & TOPO_OPEN_SOUTH), hi = !(topo & TOPO_OPEN_NORTH);
     if (topo == 0) {
         for (int m = 1; m <= H; ++m) { at(-m) = at(N - m); at(N + m - 1) = at(m - 1); }
     } else if (face) {                                      // impenetrable walls at Julia indices 1 and N+1; zeros beyond them
-        at(0) = T(0);
-        for (int m = 1; m <= H; ++m) { at(-m) = T(0); at(N + m - 1) = T(0); }
+        if (lo) at(0) = T(0);
+        for (int m = 1; m <= H; ++m) { if (lo) at(-m) = T(0); if (hi) at(N + m - 1) = T(0); }
     } else {                                                // gradient side: first halo point extrapolated, the others zero
-        for (int m = 1; m <= H; ++m) at(-m) = (glo == glo) ? (m == 1 ? at(0) - glo * d : T(0)) : at(m - 1);
-        for (int m = 1; m <= H; ++m) at(N + m - 1) = (ghi == ghi) ? (m == 1 ? at(N - 1) + ghi * d : T(0)) : at(N - m);
+        if (lo) for (int m = 1; m <= H; ++m) at(-m) = (glo == glo) ? (m == 1 ? at(0) - glo * d : T(0)) : at(m - 1);
+        if (hi) for (int m = 1; m <= H; ++m) at(N + m - 1) = (ghi == ghi) ? (m == 1 ? at(N - 1) + ghi * d : T(0)) : at(N - m);
     }
 }
 

@@ -126,8 +126,10 @@ template <> constexpr ncclDataType_t nccl_type<float>() { return ncclFloat32; }
 // neighbour's north halo.  Issue order (send_n, recv_s, send_s, recv_n per field) is what makes the 1- and 2-rank rings,
 // where both neighbours are the same peer, pair up correctly: RCCL matches sends and receives of a peer in issue order.
 // The same exchange through the loopback hub (see LoopHub): post my edge rows, copy my neighbours' into my halos, wait until mine were taken.
+// sides: bit 0 = the south neighbour, bit 1 = the north neighbour (a chain's end ranks post and take one side only; the other ranks
+// count exchanges all the same, so exchange k of a rank always pairs with exchange k of its neighbours).
 int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *const *send_n, char *const *recv_s, char *const *recv_n,
-                      int nf, size_t bytes, hipStream_t s) {
+                      int nf, size_t bytes, int sides, hipStream_t s) {
     LoopHub &h = *r->hub;
     if (nf > LoopHub::MAXF) return SWMHD_EINVAL;
     hipError_t e;
@@ -158,6 +160,7 @@ int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *cons
     // (2) receives: my south halo <- the south neighbour's northern edge rows; my north halo <- the north neighbour's southern ones
     const int peers[2] = {r->south, r->north};
     for (int side = 0; side < 2; ++side) {
+        if (!((sides >> side) & 1)) continue;
         const int p = peers[side];
         if (!wait_for([&] { return h.post[p].seq >= k; }, "a neighbour did not reach its matching exchange")) return SWMHD_ECOMM;
         hipEvent_t ready; const char *src[LoopHub::MAXF]; size_t pbytes; int pnf;
@@ -182,6 +185,7 @@ int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *cons
     h.cv.notify_all();
     // (4) my sends complete when both neighbours have taken my rows: later work on s may overwrite them
     for (int side = 0; side < 2; ++side) {
+        if (!((sides >> side) & 1)) continue;
         const int p = peers[side];
         if (!wait_for([&] { return h.post[p].done >= k; }, "a neighbour did not take the rows sent to it")) return SWMHD_ECOMM;
         hipEvent_t consumed;
@@ -191,10 +195,14 @@ int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *cons
     return SWMHD_OK;
 }
 
+// sides: bit 0 = with the south neighbour, bit 1 = with the north one (3: the ring's full exchange; a chain leaves out its walls)
 template <typename T>
-int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, hipStream_t s) {
-    if (!r || !fields || nf <= 0) return SWMHD_EINVAL;
+int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, hipStream_t s, int sides = 3) {
+    if (!r || !fields || nf <= 0 || (sides & ~3)) return SWMHD_EINVAL;
     if (Nx <= 0 || Ny < Hy || Hy <= 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
+    for (int f = 0; f < nf; ++f)
+        if (!fields[f]) return SWMHD_EINVAL;
+    if (!sides) return SWMHD_OK;
     const size_t count = (size_t)Hy * (size_t)sy;   // Hy full rows (the pitch padding of the last row travels too: harmless)
     if (r->hub) {
         if (nf > LoopHub::MAXF) return SWMHD_EINVAL;
@@ -205,7 +213,7 @@ int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, in
             ss[f] = (const char *)(p + (size_t)Hy * sy); sn[f] = (const char *)(p + (size_t)Ny * sy);
             rs[f] = (char *)p; rn[f] = (char *)(p + (size_t)(Ny + Hy) * sy);
         }
-        return loopback_exchange(r, ss, sn, rs, rn, nf, count * sizeof(T), s);
+        return loopback_exchange(r, ss, sn, rs, rn, nf, count * sizeof(T), sides, s);
     }
     ncclResult_t rc = r->api.GroupStart();
     if (rc != ncclSuccess) return fail(r, "ncclGroupStart", rc);
@@ -214,10 +222,11 @@ int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, in
         if (!p) { r->api.GroupEnd(); return SWMHD_EINVAL; }
         T *send_s = p + (size_t)Hy * sy, *send_n = p + (size_t)Ny * sy;
         T *recv_s = p, *recv_n = p + (size_t)(Ny + Hy) * sy;
-        if ((rc = r->api.Send(send_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
-        if ((rc = r->api.Recv(recv_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
-        if ((rc = r->api.Send(send_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
-        if ((rc = r->api.Recv(recv_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
+        const bool n = sides & 2, so = sides & 1;
+        if (n && (rc = r->api.Send(send_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
+        if (so && (rc = r->api.Recv(recv_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
+        if (so && (rc = r->api.Send(send_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
+        if (n && (rc = r->api.Recv(recv_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
     }
     ncclResult_t rc2 = r->api.GroupEnd();
     if (rc != ncclSuccess) return fail(r, "ncclSend/ncclRecv", rc);
@@ -239,6 +248,7 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
               T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt,
               void *stream) {
     if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
+    if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // walls: swmhd_ring_step_rk3_bc (its fill is the BC fill)
     if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;   // y images belong to the neighbours (x may be wrapped on read: no x-halo kernel then)
     if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;                          // a slab needs interior rows between its two strips
     hipStream_t s = (hipStream_t)stream, c = r->comm_stream;
@@ -354,6 +364,91 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
             if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
             if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
             if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
+            r->pending = b.cur[0];
+        }
+    if (state_in_alt) *state_in_alt = b.swaps & 1;
+    return SWMHD_OK;
+}
+
+// nsteps RK3 steps of a Bounded slab (swmhd_ring_step_rk3_bc): with SWMHD_BOUNDED_Y the ranks form a CHAIN -- rank 0 holds the south
+// wall, the last rank the north wall, every other side is a cut to a neighbour -- with SWMHD_BOUNDED_X alone a periodic-y ring whose x
+// walls are local to every slab.  The per-stage schedule of ring_step, in G- form, with the boundary-condition fill in place of the
+// x-halo kernel (X = current state, Y = the other buffer set):
+//   main stream : rows of X that need no remote data -> Y: the interior, plus the Hy-row strip of a WALL side (its halo is local)
+//   comm stream : ... exchange of X (cut sides only) ... ; the Hy-row strips of the CUT sides of X -> Y   (one launch)
+//   main        : wait(comm) ; swmhd_fill_halo_walls of Y (x, and the wall sides in y) ; record ; comm waits ; comm: exchange of Y
+// The fill precedes the exchange because x halos live in memory and the corners travel with the rows.  A chain of one has no cut: all
+// rows of every stage on the main stream, nothing exchanged.  The first stage of a call finds the caller's halos current.
+template <typename T>
+int ring_step_bc(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy,
+                 T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, const T *gradient, int flags,
+                 int *state_in_alt, void *stream) {
+    constexpr int KNOWN = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_BOUNDED_X |
+                          SWMHD_BOUNDED_Y | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR | SWMHD_LEAVE_ROOM;
+    if (flags & ~KNOWN) return SWMHD_EINVAL;                                   // (SWMHD_OPEN_*: the chain decides its walls)
+    if (!(flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y))) return SWMHD_EINVAL;   // periodic slabs: swmhd_ring_step_rk3
+    if (flags & (SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR)) return SWMHD_ENOTSUP;
+    if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;
+    if ((flags & SWMHD_BOUNDED_X) && (flags & SWMHD_WRAP_X)) return SWMHD_EINVAL;
+    if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
+    if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;
+    swmhd::Rk3Buffers<T> b;
+    if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
+    const bool chain = flags & SWMHD_BOUNDED_Y;
+    const bool south_wall = chain && r->rank == 0, north_wall = chain && r->rank == r->nranks - 1;
+    const int walls_y = (south_wall ? 1 : 0) | (north_wall ? 2 : 0), cuts = 3 & ~walls_y;
+    const int fl = flags | (chain && !south_wall ? SWMHD_OPEN_SOUTH : 0) | (chain && !north_wall ? SWMHD_OPEN_NORTH : 0);
+    const int topo_x = (flags & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
+    constexpr int FACE_X = 0b0001, FACE_Y = 0b0010;
+    // rows that need no remote data, and the cut-side strips
+    const int lo = (cuts & 1) ? Hy : 0, hi = (cuts & 2) ? Ny - Hy : Ny;
+    const int s0 = 0, s1 = (cuts & 1) ? Hy : 0, n0 = (cuts & 2) ? Ny - Hy : Ny, n1 = Ny;
+    // the argument checks of the stage and of the fill, before the first HIP call (an empty row range checks without launching)
+    if (int rc = swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, b.gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
+                                                     lorentz, dt, T(0), T(0), 1, 0, 0, 0, 0, fl, nullptr))
+        return rc;
+    if (Hx > Nx || Hy > Ny) return SWMHD_EHALO;   // (the fill's own check; the stage's are above)
+    if (nsteps == 0) { if (state_in_alt) *state_in_alt = 0; return SWMHD_OK; }
+    hipStream_t s = (hipStream_t)stream, c = r->comm_stream;
+    hipError_t e;
+    if (r->pending && r->pending != (const void *)b.cur[0]) {   // an exchange of some other state is in flight: drain it first
+        e = hipEventRecord(r->ev_comm, c);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, r->ev_comm, 0);
+        if (e != hipSuccess) return hipfail(r, "join", e);
+        r->pending = nullptr;
+    }
+    if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return hipfail(r, "record", e);
+    if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return hipfail(r, "wait", e);
+    auto bail = [&](int code) {
+        if (hipEventRecord(r->ev_comm, c) == hipSuccess) (void)hipStreamWaitEvent(s, r->ev_comm, 0);
+        r->pending = nullptr;
+        if (state_in_alt) *state_in_alt = b.swaps & 1;
+        return code;
+    };
+    auto run = [&](const swmhd::Rk3Stage<T> &g, int j0, int j1, int j0b, int j1b, int f, hipStream_t on) {
+        return swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
+                                                   lorentz, dt, g.gamma, g.zeta, g.store_G, j0, j1, j0b, j1b, f, (void *)on);
+    };
+    for (int n = 0; n < nsteps; ++n)
+        for (int st = 0; st < 3; ++st) {
+            const swmhd::Rk3Stage<T> g = b.stage(st, false);
+            int rc;
+            const bool split = r->pending != nullptr;
+            if ((rc = split ? run(g, lo, hi, 0, 0, fl | SWMHD_LEAVE_ROOM, s) : run(g, 0, Ny, 0, 0, fl, s))) return bail(rc);
+            if (split) {   // the cut strips, one launch behind the exchange; the main stream then waits for them
+                if ((rc = s1 > s0 ? run(g, s0, s1, n0, n1, fl, c) : run(g, n0, n1, 0, 0, fl, c))) return bail(rc);
+                if ((e = hipEventRecord(r->ev_comm, c)) != hipSuccess) return bail(hipfail(r, "record", e));
+                if ((e = hipStreamWaitEvent(s, r->ev_comm, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
+            }
+            b.rotate();
+            r->pending = nullptr;
+            if ((rc = swmhd::fill_halo_walls_dev<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, topo_x, chain ? walls_y : 0, FACE_X, FACE_Y,
+                                                    gradient, dx, dy, (void *)s)))
+                return bail(rc);
+            if (!cuts) continue;   // a chain of one: both walls local, nothing to exchange
+            if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
+            if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
+            if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c, cuts))) return bail(rc);
             r->pending = b.cur[0];
         }
     if (state_in_alt) *state_in_alt = b.swaps & 1;
@@ -490,7 +585,21 @@ int swmhd_ring_launch_times(swmhd_ring *r, float *ms, int *rows, int capacity) {
                             state_in_alt, stream);                                                                               \
     }
 
+#define SWMHD_DEF_RING_BC(sfx, T)                                                                                                \
+    int swmhd_ring_exchange_y_sides_##sfx(swmhd_ring *r, T *const *fields, int nfields, int Nx, int Ny, int Hx, int Hy,          \
+                                          int64_t sy, int sides, void *stream) {                                                 \
+        return exchange<T>(r, fields, nfields, Nx, Ny, Hx, Hy, sy, (hipStream_t)stream, sides);                                  \
+    }                                                                                                                            \
+    int swmhd_ring_step_rk3_bc_##sfx(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny,    \
+                                     int Hx, int Hy, int64_t sy, T dx, T dy, T g, T f, int formulation, int lorentz, T dt,       \
+                                     int nsteps, const T *gradient, int flags, int *state_in_alt, void *stream) {               \
+        return ring_step_bc<T>(r, q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, nsteps, gradient, \
+                               flags, state_in_alt, stream);                                                                     \
+    }
+
 SWMHD_DEF_RING(f64, double)
 SWMHD_DEF_RING(f32, float)
+SWMHD_DEF_RING_BC(f64, double)
+SWMHD_DEF_RING_BC(f32, float)
 
 }  // extern "C"

@@ -126,6 +126,23 @@ int halo_bc_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t 
     return hiprc(launch_fill_halo_bc_ensemble<T>(a, (hipStream_t)stream));
 }
 
+// swmhd_fill_halo_walls: swmhd_fill_halo of one y-slab -- x as topo_x says, y walls only on the sides of walls_y (bit 0 south, bit 1
+// north), the other y sides untouched.  gradient: HOST array of 4 nf values (gtab == nullptr), or gtab: a DEVICE table of 4 nf values.
+template <typename T>
+int halo_walls_common(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int topo_x, int walls_y, int face_x, int face_y,
+                      const T *gradient, const T *gtab, T dx, T dy, void *stream) {
+    if (walls_y & ~3) return SWMHD_EINVAL;
+    HaloBcEns<T> a;
+    const int rc = halo_bc_args<T>(a, f, nf, Nx, Ny, Hx, Hy, sy, topo_x, SWMHD_BOUNDED, face_x, face_y, dx, dy);
+    if (rc) return rc;
+    a.topo_y = SWMHD_BOUNDED | ((walls_y & 1) ? 0 : TOPO_OPEN_SOUTH) | ((walls_y & 2) ? 0 : TOPO_OPEN_NORTH);
+    for (int k = 0; k < 4; ++k)
+        for (int e = 0; e < 4; ++e) a.grad[k][e] = (gradient && k < nf) ? gradient[4 * k + e] : T(NAN);
+    if (!gtab) return hiprc(launch_fill_halo_bc<T>(a, (hipStream_t)stream));
+    a.stride_m = 0; a.members = 1; a.gtab = gtab;   // (the ensemble fill of one member reads its values from the device table)
+    return hiprc(launch_fill_halo_bc_ensemble<T>(a, (hipStream_t)stream));
+}
+
 template <typename T>
 struct FuseRk3 {
     T *Unew[4];
@@ -150,7 +167,8 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
     const int ext = ((flags & (SWMHD_WRAP_Y | SWMHD_BOUNDED_Y)) || Hy < 3) ? 0 : Hy - 3;
     if (j0 < -ext || j1 > Ny + ext || j0 > j1) return SWMHD_EINVAL;
     if (j1b > j0b && (j0b < j1 || j1b > Ny + ext)) return SWMHD_EINVAL;   // (internal: second row range of the slab driver, above the first)
-    if (flags & ~(SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_LEAVE_ROOM | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR)) return SWMHD_EINVAL;
+    if (flags & ~(SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_LEAVE_ROOM | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR | SWMHD_OPEN_SOUTH | SWMHD_OPEN_NORTH)) return SWMHD_EINVAL;
+    if ((flags & (SWMHD_OPEN_SOUTH | SWMHD_OPEN_NORTH)) && (!(flags & SWMHD_BOUNDED_Y) || ens)) return SWMHD_EINVAL;   // a cut of a Bounded y direction
     if (flags & SWMHD_GM_IS_PREV_STATE) {   // fast, periodic, fused stage with a G- operand only (a Bounded grid's frame launch would read cells the first launch has overwritten)
         if (!rk || !rk->Gm) return SWMHD_EINVAL;
         if (flags & (SWMHD_STRICT | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;
@@ -183,6 +201,7 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
     a.leave_room = (flags & SWMHD_LEAVE_ROOM) ? 1 : 0;
     a.edge_cols = 0; a.fold_last = 0;
     a.topo_x = (flags & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC; a.topo_y = (flags & SWMHD_BOUNDED_Y) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
+    a.topo_y |= ((flags & SWMHD_OPEN_SOUTH) ? TOPO_OPEN_SOUTH : 0) | ((flags & SWMHD_OPEN_NORTH) ? TOPO_OPEN_NORTH : 0);
     a.kernel_variant = (flags & SWMHD_TILE_KERNEL) ? 1 : ((flags & SWMHD_MARCH_KERNEL) ? 2 : 0);
     for (int f = 0; f < 4; ++f) { a.Unew[f] = nullptr; a.Gm[f] = nullptr; }
     if (rk) {
@@ -315,12 +334,18 @@ template <typename T>
 int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which, void *stream) {
     return halo_multi_common<T>(f, nf, Nx, Ny, Hx, Hy, (int64_t)sy, which, stream);
 }
+template <typename T>
+int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int topo_x, int walls_y, int face_x, int face_y,
+                        const T *gtab, T dx, T dy, void *stream) {
+    return halo_walls_common<T>(f, nf, Nx, Ny, Hx, Hy, (int64_t)sy, topo_x, walls_y, face_x, face_y, nullptr, gtab, dx, dy, stream);
+}
 static_assert(GM_IS_PREV_STATE == SWMHD_GM_IS_PREV_STATE, "common.hpp mirrors swmhd.h");
 static_assert(RK3_ANCHOR == SWMHD_RK3_ANCHOR, "common.hpp mirrors swmhd.h");
 #define SW_INST(T)                                                                                                                   \
     template int tendencies_rk3_two_ranges<T>(const T *const *, T *const *, T *const *, const T *const *, int, int, int, int, long, T, \
                                               T, T, T, int, int, T, T, T, int, int, int, int, int, int, void *);                      \
-    template int fill_halo_periodic_multi<T>(T *const *, int, int, int, int, int, long, int, void *);
+    template int fill_halo_periodic_multi<T>(T *const *, int, int, int, int, int, long, int, void *);                              \
+    template int fill_halo_walls_dev<T>(T *const *, int, int, int, int, int, long, int, int, int, int, const T *, T, T, void *);
 SW_INST(double)
 SW_INST(float)
 #undef SW_INST
@@ -392,6 +417,11 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
     int swmhd_fill_halo_##sfx(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int topo_x, int topo_y,  \
                               int face_x, int face_y, const T *gradient, T dx, T dy, void *stream) {                       \
         return halo_bc_common<T>(f, nf, Nx, Ny, Hx, Hy, sy, topo_x, topo_y, face_x, face_y, gradient, dx, dy, stream);     \
+    }                                                                                                                  \
+    int swmhd_fill_halo_walls_##sfx(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, int topo_x, int walls_y, \
+                                    int face_x, int face_y, const T *gradient, T dx, T dy, void *stream) {             \
+        return halo_walls_common<T>(f, nf, Nx, Ny, Hx, Hy, sy, topo_x, walls_y, face_x, face_y, gradient, nullptr, dx, dy, \
+                                    stream);                                                                           \
     }                                                                                                                  \
     int swmhd_fill_halo_periodic_multi_##sfx(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy,          \
                                              int which, void *stream) {                                                \

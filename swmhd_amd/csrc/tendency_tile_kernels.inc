@@ -122,13 +122,17 @@ __global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS> a, i
         for (int m = 0; m < 6; ++m) q[m] = F(ii, f - 3 + m);
     };
     // orders of the interpolant of tile-local index (ii | jj) in x | y: its 1-based index is x0 + ii + 1 | y0 + jj + 1
-    const bool bx = BND && a.topo_x == 1, by = BND && a.topo_y == 1;
+    const bool bx = BND && a.topo_x == 1, by = BND && (a.topo_y & 1);
+    // y-slab of a Bounded-y chain (TOPO_OPEN_*): an open side moves the slab's row indices TOPO_FAR away from that wall position, so
+    // the wall tests below see the rows next to a cut as interior rows; (0, Ny) for a whole Bounded direction
+    const int yb = BND && (a.topo_y & TOPO_OPEN_SOUTH) ? TOPO_FAR : 0;
+    const int yN = BND ? a.Ny + yb + ((a.topo_y & TOPO_OPEN_NORTH) ? TOPO_FAR : 0) : a.Ny;
     auto oLx = [&](int ii) -> int { return BND ? left_order(bx, x0 + ii + 1, a.Nx) : 5; };
     auto oRx = [&](int ii) -> int { return BND ? right_order(bx, x0 + ii + 1, a.Nx) : 5; };
-    auto oLy = [&](int jj) -> int { return BND ? left_order(by, y0 + jj + 1, a.Ny) : 5; };
-    auto oRy = [&](int jj) -> int { return BND ? right_order(by, y0 + jj + 1, a.Ny) : 5; };
+    auto oLy = [&](int jj) -> int { return BND ? left_order(by, yb + y0 + jj + 1, yN) : 5; };
+    auto oRy = [&](int jj) -> int { return BND ? right_order(by, yb + y0 + jj + 1, yN) : 5; };
     auto s4x = [&](int ii) -> bool { return BND ? sym_fourth(bx, x0 + ii + 1, a.Nx) : true; };
-    auto s4y = [&](int jj) -> bool { return BND ? sym_fourth(by, y0 + jj + 1, a.Ny) : true; };
+    auto s4y = [&](int jj) -> bool { return BND ? sym_fourth(by, yb + y0 + jj + 1, yN) : true; };
     // advective_tracer_flux_x/y(U, c) = A_face * upwind(U[i,j], cL, cR)   (face interpolants: index = the face's)
     auto tflux_x = [&](auto &Uf, auto &C, int ii, int jj) -> T { T q[6]; gx6(C, ii, jj, q); return g.dy * upwind_recon<T>(Uf(ii, jj), q, oLx(ii), oRx(ii)); };
     auto tflux_y = [&](auto &Vf, auto &C, int ii, int jj) -> T { T q[6]; gy6(C, ii, jj, q); return g.dx * upwind_recon<T>(Vf(ii, jj), q, oLy(jj), oRy(jj)); };
@@ -230,11 +234,11 @@ __global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS> a, i
             if constexpr (LOR == 2) {
                 const T rAzs = T(1) / (g.dx * g.dy);
                 // wall codes of the reference's Bounded branches (0 on periodic grids); Julia indices of this cell: (gxi+1, gyj+1)
-                const int iJ = gxi + 1, jJ = gyj + 1;
+                const int iJ = gxi + 1, jJ = yb + gyj + 1;
                 const int cF1 = BND ? wall_code(bx, iJ, 0, a.Nx) : 0, cF1m = BND ? wall_code(bx, iJ - 1, 0, a.Nx) : 0;
                 const int cG1 = BND ? wall_code(bx, iJ, 1, a.Nx + 1) : 0, cG1p = BND ? wall_code(bx, iJ + 1, 1, a.Nx + 1) : 0;
-                const int cF2 = BND ? wall_code(by, jJ, 1, a.Ny + 1) : 0, cF2p = BND ? wall_code(by, jJ + 1, 1, a.Ny + 1) : 0;
-                const int cG2 = BND ? wall_code(by, jJ, 0, a.Ny) : 0, cG2m = BND ? wall_code(by, jJ - 1, 0, a.Ny) : 0;
+                const int cF2 = BND ? wall_code(by, jJ, 1, yN + 1) : 0, cF2p = BND ? wall_code(by, jJ + 1, 1, yN + 1) : 0;
+                const int cG2 = BND ? wall_code(by, jJ, 0, yN) : 0, cG2m = BND ? wall_code(by, jJ - 1, 0, yN) : 0;
                 Fx = rAzs * ((div_F1<T>(L0_, L1_, i, j, g, cF1) - div_F1<T>(L0_, L1_, i - 1, j, g, cF1m)) + (div_F2<T>(L2_, L1_, i, j + 1, g, cF2p) - div_F2<T>(L2_, L1_, i, j, g, cF2)));
                 Fy = rAzs * ((div_G1<T>(L0_, L3_, i + 1, j, g, cG1p) - div_G1<T>(L0_, L3_, i, j, g, cG1)) + (div_G2<T>(L2_, L3_, i, j, g, cG2) - div_G2<T>(L2_, L3_, i, j - 1, g, cG2m)));
             }
@@ -448,7 +452,7 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
     // chip matters more than the warm-up overhead (1024^2: 42 us/stage at LY = 7, 54 at 16).
     // (the marching kernels address memory with 32-bit byte offsets: fields of 4 GiB or more stay on the tile kernel)
     const bool fits32 = (long)(a.Ny + 2 * a.Hy) * a.sy * (long)sizeof(T) < (1L << 32) - 64;
-    const bool bnd = a.topo_x == 1 || a.topo_y == 1;   // Bounded: LDS-tiled kernel only
+    const bool bnd = a.topo_x == 1 || a.topo_y != 0;   // Bounded: LDS-tiled kernel only
     const bool march = !bnd && fits32 && (a.kernel_variant == 2 || (a.kernel_variant == 0 && (long)a.Nx * rows >= SW_MARCH_MIN_CELLS));
     // Large Bounded grids: a cell further than a few cells from a wall has exactly the periodic formulas (every reconstruction at full
     // order, no wall branch of the Lorentz fluxes).  So the row-marching kernel computes ALL rows as if the grid were periodic, reading
@@ -465,9 +469,12 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
         if (e != hipSuccess) return e;
         TendArgs<T> f = a;
         f.kernel_variant = 1;
-        if (a.topo_y == 1) {
+        if (a.topo_y != 0) {   // a frame along each actual y wall (a y-slab's cut side has none: TOPO_OPEN_*)
             const int a0 = a.j0, a1 = a.j1 < FW ? a.j1 : FW, b0 = a.j0 > a.Ny - FW ? a.j0 : a.Ny - FW, b1 = a.j1;
             f.j0 = a0; f.j1 = a1 > a0 ? a1 : a0; f.j0b = b0; f.j1b = b1 > b0 ? b1 : b0;
+            if (a.topo_y & TOPO_OPEN_SOUTH) f.j1 = f.j0;
+            if (a.topo_y & TOPO_OPEN_NORTH) f.j1b = f.j0b;
+            if (f.j1 <= f.j0 && f.j1b > f.j0b) { f.j0 = f.j0b; f.j1 = f.j1b; f.j0b = f.j1b = 0; }
             if (f.j1 > f.j0 || f.j1b > f.j0b) {
                 e = LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)<T>(f, formulation, lorentz, s);
                 if (e != hipSuccess) return e;
@@ -505,13 +512,13 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
     // strips: there are at most a few tiles per CU, so the launch lasts about as long as ONE tile takes; one output row per lane
     // (64 x 4 tiles) instead of two halves the dependent arithmetic of that tile (64^2 .. 256^2: 41 -> 27 us per RK3 step,
     // 512^2: 60 -> 52).  Larger grids forced onto the tile kernel keep 64 x 8 tiles (less halo per cell).
-    if (!(a.topo_x == 1 || a.topo_y == 1) && (long)a.Nx * rows < SW_MARCH_MIN_CELLS) {
+    if (!(a.topo_x == 1 || a.topo_y != 0) && (long)a.Nx * rows < SW_MARCH_MIN_CELLS) {
         constexpr int RY1 = 1;
         const int nty1 = (a.j1 - a.j0 + TYB * RY1 - 1) / (TYB * RY1) + (rows_b + TYB * RY1 - 1) / (TYB * RY1);
         return launch_tile<T, RY1>(a, formulation, lorentz, ntx, nty1, s);
     }
 #endif
-    if (a.topo_x == 1 || a.topo_y == 1) return launch_tile<T, RY, true>(a, formulation, lorentz, ntx, nty, s);
+    if (a.topo_x == 1 || a.topo_y != 0) return launch_tile<T, RY, true>(a, formulation, lorentz, ntx, nty, s);
     return launch_tile<T, RY>(a, formulation, lorentz, ntx, nty, s);
 }
 

@@ -62,8 +62,16 @@ class ShallowWaterModel:
         self._bounded = (tx == _lib.BOUNDED, ty == _lib.BOUNDED)
         self._flags |= (_lib.BOUNDED_X if self._bounded[0] else 0) | (_lib.BOUNDED_Y if self._bounded[1] else 0)
         self.decomp = decomp or SlabDecomposition(grid.Ny_global, 1, 0)
-        if any(self._bounded) and self.decomp.ring:
-            raise _lib.SwmhdError("y-slab decomposition (ring halo exchange) supports (Periodic, Periodic) grids only (SWMHD_ENOTSUP)")
+        # y-slabs: a Periodic y direction is a ring (periodic decomposition; x may be Bounded, its walls are local to every slab), a
+        # Bounded one a chain (SlabDecomposition(..., periodic=False)) with the south wall on rank 0 and the north wall on rank P-1
+        self._chain = not self.decomp.periodic
+        if self._bounded[1] and self.decomp.ring and not self._chain:
+            raise _lib.SwmhdError("y-slab decomposition (ring halo exchange) of a Bounded-y grid needs a chain: "
+                                  "SlabDecomposition(..., periodic=False) (SWMHD_ENOTSUP)")
+        if self._chain and not self._bounded[1]:
+            raise _lib.SwmhdError("a chain decomposition (SlabDecomposition(..., periodic=False)) needs a Bounded y direction")
+        if self._chain:   # the cut sides of this slab: reconstructions next to them are those of the whole domain's interior rows
+            self._flags |= (_lib.OPEN_SOUTH if self.decomp.south is not None else 0) | (_lib.OPEN_NORTH if self.decomp.north is not None else 0)
         # boundary_conditions = {"A": FieldBoundaryConditions(north = GradientBoundaryCondition(-0.05), ...)}  (SWMHD_example.jl:18-22)
         self.boundary_conditions = dict(boundary_conditions or {})
         for name, bc in self.boundary_conditions.items():
@@ -216,18 +224,28 @@ class ShallowWaterModel:
             self.update_state()
 
     # --- update_state!: fill halos (periodic x locally; y locally or by ring exchange) --------------------------
+    def _gradients(self):
+        """The 16 GradientBoundaryCondition values of the fill: (west, east, south, north) of each field, NaN = default."""
+        grads = []
+        for n in self.names:
+            bc = self.boundary_conditions.get(n)
+            grads += bc.gradients() if bc is not None else [float("nan")] * 4
+        return grads
+
     def _fill_bc(self, stream=None):
         """fill_halo_regions! with boundary conditions (at least one Bounded direction): swmhd_fill_halo."""
         import ctypes
         g = self.grid
         q = self._raw_fields
         ct = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
-        grads = []
-        for n in self.names:
-            bc = self.boundary_conditions.get(n)
-            grads += bc.gradients() if bc is not None else [float("nan")] * 4
-        f = getattr(self._L, f"swmhd_fill_halo_{self.sfx}")
+        grads = self._gradients()
         tx, ty = g.topo_codes()
+        if self.decomp.ring:   # a slab: y walls only where this slab has them (none on a ring); cut sides come from the neighbours
+            f = getattr(self._L, f"swmhd_fill_halo_walls_{self.sfx}")
+            rc = f(_lib.ptr_array([x.ptr for x in q]), 4, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride_y, tx, self.decomp.walls_y(), 0b0001, 0b0010,
+                   (ct * 16)(*grads), g.dx, g.dy, _stream_ptr(stream))
+            return _lib.check(rc, "swmhd_fill_halo_walls")
+        f = getattr(self._L, f"swmhd_fill_halo_{self.sfx}")
         rc = f(_lib.ptr_array([x.ptr for x in q]), 4, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride_y, tx, ty, 0b0001, 0b0010,
                (ct * 16)(*grads), g.dx, g.dy, _stream_ptr(stream))
         _lib.check(rc, "swmhd_fill_halo")
@@ -249,8 +267,13 @@ class ShallowWaterModel:
         q = self._raw_fields
         if self._ring is not None:
             g = self.grid
-            f = getattr(self._L, f"swmhd_ring_exchange_y_{self.sfx}")
-            rc = f(self._ring, _lib.ptr_array([x.ptr for x in q]), 4, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride_y, _stream_ptr())
+            if self._chain:      # nothing travels across the chain's walls
+                f = getattr(self._L, f"swmhd_ring_exchange_y_sides_{self.sfx}")
+                rc = f(self._ring, _lib.ptr_array([x.ptr for x in q]), 4, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride_y, self.decomp.cuts(),
+                       _stream_ptr())
+            else:
+                f = getattr(self._L, f"swmhd_ring_exchange_y_{self.sfx}")
+                rc = f(self._ring, _lib.ptr_array([x.ptr for x in q]), 4, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride_y, _stream_ptr())
             self._ring_check(rc, "swmhd_ring_exchange_y")
         elif self.decomp.ring:
             exchange_y_halos([f.data for f in q], self.grid.Ny, self.grid.Hy, self.decomp, self.group)
@@ -321,6 +344,8 @@ class ShallowWaterModel:
         import ctypes
         gr, ring = self.grid, self._ring is not None
         wrap = self._rwrap & _lib.WRAP_X if ring else self._rwrap     # (a slab's y halos come from the ring)
+        if ring and any(self._bounded):
+            wrap = 0                  # (the Bounded slab driver fills every halo between the stages: its state's halos stay current)
         if ring and self._halo_stale and not wrap:
             self.update_state()
         swapped = ctypes.c_int(0)
@@ -328,7 +353,15 @@ class ShallowWaterModel:
                 _lib.ptr_array([f.ptr for f in self.Gn]), _lib.ptr_array([f.ptr for f in self.Gm]), gr.Nx, gr.Ny, gr.Hx, gr.Hy,
                 self._raw_fields[0].stride_y, gr.dx, gr.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
                 self._flags | wrap, ctypes.byref(swapped), _stream_ptr())
-        if ring:
+        if ring and any(self._bounded):
+            # Bounded slabs (a chain, or Bounded x on a ring): the driver decides the cut sides itself and fills the boundary conditions
+            # from a device table of the 16 gradient values
+            if getattr(self, "_grad_dev", None) is None:
+                self._grad_dev = torch.tensor(self._gradients(), dtype=self._raw_fields[0].data.dtype, device=self._raw_fields[0].data.device)
+            fl = self._flags & ~(_lib.OPEN_SOUTH | _lib.OPEN_NORTH)
+            args = args[:-3] + (self._grad_dev.data_ptr(), fl) + args[-2:]
+            self._ring_check(getattr(self._L, f"swmhd_ring_step_rk3_bc_{self.sfx}")(self._ring, *args), "swmhd_ring_step_rk3_bc")
+        elif ring:
             self._ring_check(getattr(self._L, f"swmhd_ring_step_rk3_{self.sfx}")(self._ring, *args), "swmhd_ring_step_rk3")
         else:
             _lib.check(getattr(self._L, f"swmhd_step_rk3_{self.sfx}")(*args), "swmhd_step_rk3")
