@@ -349,7 +349,7 @@ int swmhd_ring_create(swmhd_ring **ring, const char *rccl_path, int nranks, int 
 /* Loopback transport for rehearsals and tests on ONE GPU (RCCL refuses two ranks on one device): creates `nranks` rings in this
  * process, rings[k] = rank k with neighbours (k-1, k+1) mod nranks, whose exchanges copy the neighbours' edge rows device-to-device
  * on the comm streams with RCCL's rendezvous semantics (a receive waits for the sender's matching exchange, a send for the
- * receiver to have taken the rows).  Everything else -- swmhd_ring_step_rk3's two schedules, streams, events -- is the code the
+ * receiver to have taken the rows).  Everything else -- the slab drivers' schedules, streams, events -- is the code the
  * RCCL ring runs.  Drive every ring from its OWN host thread (an exchange blocks on the host until the neighbours have enqueued
  * theirs, at most `timeout_s` seconds (<= 0: 60), then SWMHD_ECOMM).  Each ring is destroyed with swmhd_ring_destroy. */
 int swmhd_ring_create_loopback(swmhd_ring **rings, int nranks, double timeout_s);
@@ -375,6 +375,7 @@ int swmhd_ring_exchange_y_f32(swmhd_ring *ring, float *const *fields, int nfield
  *          anything but swmhd_ring_step_rk3 reads the y halos (or reuses the buffers) on `stream`
  * flags must not carry SWMHD_WRAP_Y (y images belong to the neighbours); with SWMHD_WRAP_X no x-halo kernel runs between a stage and
  * its exchange and the x halos of the returned state are stale.  Ny >= 2*Hy+1.  Other arguments and state_in_alt as swmhd_step_rk3.
+ * Every check precedes the first HIP call; nsteps == 0 enqueues nothing and leaves the ring as it is (*state_in_alt = 0).
  * Deep-halo schedule (taken when Hy >= 9, Ny >= 32 and SWMHD_WRAP_X is set): ONE exchange of Hy rows per step instead of one of 3
  * rows per stage.  The slab evaluates the rows of its neighbours that stages 2 and 3 need inside its own halo (18 redundant rows
  * per step): stage k computes interior rows [3,9,12][k] .. Ny - [3,9,12][k] on `stream` and the boundary zones
@@ -411,17 +412,18 @@ int swmhd_ring_exchange_y_sides_f32(swmhd_ring *ring, float *const *fields, int 
  *     side is a cut whose halo rows come from the neighbour; nothing travels between the last rank and rank 0.  The driver passes
  *     SWMHD_OPEN_SOUTH / _NORTH for the cut sides itself (a caller's OPEN flags: SWMHD_EINVAL).
  *   SWMHD_BOUNDED_X alone: a periodic-y ring of slabs whose x walls are local to every slab.
- * Stages in G- form (as the single Bounded model; no anchor form), the per-stage schedule only (also for Hy >= 9): rows that need no
- * remote data -- the interior and a wall side's strip -- run on `stream` while the exchange is in flight; the Hy-row strip of each cut
- * side follows the exchange on the comm stream; then the boundary-condition fill (swmhd_fill_halo_walls: x, and the wall sides) of the
- * new state on `stream`, and its exchange (swmhd_ring_exchange_y_sides) on the comm stream.  gradient: DEVICE table of 16 values
+ * Stages in G- form (as the single Bounded model; no anchor form), the per-stage schedule of swmhd_ring_step_rk3 only (also for
+ * Hy >= 9), with the wall sides left out of the exchange: rows that need no remote data -- the interior and a wall side's strip -- run
+ * on `stream` while the exchange is in flight; the Hy-row strip of each cut side follows the exchange on the comm stream; then the
+ * boundary-condition fill (swmhd_fill_halo_walls: x, and the wall sides) of the new state on `stream`, and its exchange
+ * (swmhd_ring_exchange_y_sides) on the comm stream.  gradient: DEVICE table of 16 values
  * (west, east, south, north of q1, q2, h, A; NaN = default) or NULL.  Entry / exit conditions, buffers and state_in_alt as
  * swmhd_ring_step_rk3 (entry: halos current, i.e. filled and exchanged).
  *   SWMHD_ENOTSUP  SWMHD_MARCH_KERNEL, SWMHD_GM_IS_PREV_STATE, SWMHD_RK3_ANCHOR (as the single Bounded grid)
  *   SWMHD_EINVAL   ring NULL, no Bounded flag, SWMHD_WRAP_Y, SWMHD_OPEN_*, unknown flags, a wrapped Bounded direction, Ny < 2 Hy + 1
- * Flag checks precede the ring check; every check precedes the first HIP call.  Results: SWMHD_STRICT slabs are bit-identical to the
- * single-domain Bounded model (every row is the same arithmetic); fast slabs are within the fast tolerances of it (a row may be
- * computed by another kernel variant), deterministic from run to run. */
+ * Flag checks precede the ring check; every check precedes the first HIP call and any read of the ring; nsteps == 0 enqueues
+ * nothing.  Results: SWMHD_STRICT slabs are bit-identical to the single-domain Bounded model (every row is the same arithmetic); fast
+ * slabs are within the fast tolerances of it (a row may be computed by another kernel variant), deterministic from run to run. */
 int swmhd_ring_step_rk3_bc_f64(swmhd_ring *ring, double *const *q, double *const *q_alt, double *const *Ga, double *const *Gb,
                                int Nx, int Ny, int Hx, int Hy, int64_t stride_y, double dx, double dy,
                                double g, double f, int formulation, int lorentz, double dt, int nsteps,
@@ -431,7 +433,7 @@ int swmhd_ring_step_rk3_bc_f32(swmhd_ring *ring, float *const *q, float *const *
                                float g, float f, int formulation, int lorentz, float dt, int nsteps,
                                const float *gradient, int flags, int *state_in_alt, void *stream);
 
-/* Measurement hook: record HIP events around the next `max_launches` interior launches of swmhd_ring_step_rk3 (0 = off);
+/* Measurement hook: record HIP events around the next `max_launches` interior launches of either slab driver (0 = off);
  * swmhd_ring_launch_times waits for them and returns how many (ms, rows) pairs it wrote. */
 int swmhd_ring_time_launches(swmhd_ring *ring, int max_launches);
 int swmhd_ring_launch_times(swmhd_ring *ring, float *ms, int *rows, int capacity);

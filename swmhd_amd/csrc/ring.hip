@@ -65,7 +65,7 @@ bool load_rccl(const char *path, RcclApi &api, std::string &err) {
 // into its own halo rows with hipMemcpyAsync on its comm stream, with the rendezvous semantics RCCL gives a grouped send/recv:
 //   a receive completes only after the sender has reached the matching exchange   (wait for the peer's "rows ready" event)
 //   a send completes only after the receiver has taken the rows                     (wait for the peer's "consumed" event)
-// so that the real driver (ring_step) runs with north != south, every ring on its own pair of streams.  Events can only be waited
+// so that the real slab drivers run with north != south, every ring on its own pair of streams.  Events can only be waited
 // for once they have been recorded, hence a HOST-side rendezvous as well: exchange number k of a ring blocks until its neighbours
 // have enqueued theirs -- the rings must be driven from one host thread each, as RCCL ranks are driven from one process each.  A
 // neighbour that does not arrive within the hub's timeout ends the exchange with SWMHD_ECOMM instead of blocking for ever.
@@ -122,16 +122,22 @@ template <typename T> constexpr ncclDataType_t nccl_type();
 template <> constexpr ncclDataType_t nccl_type<double>() { return ncclFloat64; }
 template <> constexpr ncclDataType_t nccl_type<float>() { return ncclFloat32; }
 
-// One grouped launch: for every field, northern edge rows -> north neighbour's south halo, southern edge rows -> south
-// neighbour's north halo.  Issue order (send_n, recv_s, send_s, recv_n per field) is what makes the 1- and 2-rank rings,
-// where both neighbours are the same peer, pair up correctly: RCCL matches sends and receives of a peer in issue order.
-// The same exchange through the loopback hub (see LoopHub): post my edge rows, copy my neighbours' into my halos, wait until mine were taken.
+// The Hy-row runs of one field that an exchange moves (x-fastest: each is ONE contiguous run of full padded rows): the southern and
+// northern edge rows it sends, the south and north halo rows it receives.
+struct EdgeRows {
+    const char *send_s, *send_n;
+    char *recv_s, *recv_n;
+};
+template <typename T> EdgeRows edge_rows(T *p, int Ny, int Hy, int64_t sy) {
+    return {(const char *)(p + (size_t)Hy * sy), (const char *)(p + (size_t)Ny * sy), (char *)p, (char *)(p + (size_t)(Ny + Hy) * sy)};
+}
+
+// The exchange through the loopback hub (see LoopHub): post my edge rows, copy my neighbours' into my halos, wait until mine were taken.
 // sides: bit 0 = the south neighbour, bit 1 = the north neighbour (a chain's end ranks post and take one side only; the other ranks
-// count exchanges all the same, so exchange k of a rank always pairs with exchange k of its neighbours).
-int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *const *send_n, char *const *recv_s, char *const *recv_n,
-                      int nf, size_t bytes, int sides, hipStream_t s) {
+// count exchanges all the same, so exchange k of a rank always pairs with exchange k of its neighbours).  rows(f): field f's EdgeRows.
+template <class Rows>
+int loopback_exchange(swmhd_ring *r, const Rows &rows, int nf, size_t bytes, int sides, hipStream_t s) {
     LoopHub &h = *r->hub;
-    if (nf > LoopHub::MAXF) return SWMHD_EINVAL;
     hipError_t e;
     unsigned long k;
     int slot;
@@ -142,7 +148,7 @@ int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *cons
         if (!me.ready[slot] && (e = hipEventCreateWithFlags(&me.ready[slot], hipEventDisableTiming)) != hipSuccess) return hipfail(r, "loopback event", e);
         if (!me.consumed[slot] && (e = hipEventCreateWithFlags(&me.consumed[slot], hipEventDisableTiming)) != hipSuccess) return hipfail(r, "loopback event", e);
         if ((e = hipEventRecord(me.ready[slot], s)) != hipSuccess) return hipfail(r, "loopback record", e);
-        for (int f = 0; f < nf; ++f) { me.send_s[slot][f] = send_s[f]; me.send_n[slot][f] = send_n[f]; }
+        for (int f = 0; f < nf; ++f) { me.send_s[slot][f] = rows(f).send_s; me.send_n[slot][f] = rows(f).send_n; }
         me.bytes[slot] = bytes; me.nf[slot] = nf;
         me.seq = k;
     }
@@ -173,7 +179,7 @@ int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *cons
         if (pbytes != bytes || pnf != nf) { r->err = "loopback exchange: neighbour posted a different message (fields / bytes)"; return SWMHD_ECOMM; }
         if ((e = hipStreamWaitEvent(s, ready, 0)) != hipSuccess) return hipfail(r, "loopback wait", e);
         for (int f = 0; f < nf; ++f)
-            if ((e = hipMemcpyAsync(side == 0 ? recv_s[f] : recv_n[f], src[f], bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
+            if ((e = hipMemcpyAsync(side == 0 ? rows(f).recv_s : rows(f).recv_n, src[f], bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess)
                 return hipfail(r, "loopback copy", e);
     }
     {   // (3) rows consumed
@@ -195,7 +201,11 @@ int loopback_exchange(swmhd_ring *r, const char *const *send_s, const char *cons
     return SWMHD_OK;
 }
 
-// sides: bit 0 = with the south neighbour, bit 1 = with the north one (3: the ring's full exchange; a chain leaves out its walls)
+// One exchange of the Hy edge rows of every field, enqueued on s.  sides: bit 0 = with the south neighbour, bit 1 = with the north
+// one (3: the ring's full exchange; a chain leaves out its walls).  RCCL: one grouped launch -- for every field, northern edge rows ->
+// north neighbour's south halo, southern edge rows -> south neighbour's north halo.  Issue order (send_n, recv_s, send_s, recv_n per
+// field) is what makes the 1- and 2-rank rings, where both neighbours are the same peer, pair up correctly: RCCL matches sends and
+// receives of a peer in issue order.
 template <typename T>
 int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, hipStream_t s, int sides = 3) {
     if (!r || !fields || nf <= 0 || (sides & ~3)) return SWMHD_EINVAL;
@@ -203,30 +213,19 @@ int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, in
     for (int f = 0; f < nf; ++f)
         if (!fields[f]) return SWMHD_EINVAL;
     if (!sides) return SWMHD_OK;
+    if (r->hub && nf > LoopHub::MAXF) return SWMHD_EINVAL;
     const size_t count = (size_t)Hy * (size_t)sy;   // Hy full rows (the pitch padding of the last row travels too: harmless)
-    if (r->hub) {
-        if (nf > LoopHub::MAXF) return SWMHD_EINVAL;
-        const char *ss[LoopHub::MAXF], *sn[LoopHub::MAXF]; char *rs[LoopHub::MAXF], *rn[LoopHub::MAXF];
-        for (int f = 0; f < nf; ++f) {
-            T *p = fields[f];
-            if (!p) return SWMHD_EINVAL;
-            ss[f] = (const char *)(p + (size_t)Hy * sy); sn[f] = (const char *)(p + (size_t)Ny * sy);
-            rs[f] = (char *)p; rn[f] = (char *)(p + (size_t)(Ny + Hy) * sy);
-        }
-        return loopback_exchange(r, ss, sn, rs, rn, nf, count * sizeof(T), sides, s);
-    }
+    auto rows = [&](int f) { return edge_rows(fields[f], Ny, Hy, sy); };
+    if (r->hub) return loopback_exchange(r, rows, nf, count * sizeof(T), sides, s);
     ncclResult_t rc = r->api.GroupStart();
     if (rc != ncclSuccess) return fail(r, "ncclGroupStart", rc);
+    const bool so = sides & 1, n = sides & 2;
     for (int f = 0; f < nf; ++f) {
-        T *p = fields[f];
-        if (!p) { r->api.GroupEnd(); return SWMHD_EINVAL; }
-        T *send_s = p + (size_t)Hy * sy, *send_n = p + (size_t)Ny * sy;
-        T *recv_s = p, *recv_n = p + (size_t)(Ny + Hy) * sy;
-        const bool n = sides & 2, so = sides & 1;
-        if (n && (rc = r->api.Send(send_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
-        if (so && (rc = r->api.Recv(recv_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
-        if (so && (rc = r->api.Send(send_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
-        if (n && (rc = r->api.Recv(recv_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
+        const EdgeRows e = rows(f);
+        if (n && (rc = r->api.Send(e.send_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
+        if (so && (rc = r->api.Recv(e.recv_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
+        if (so && (rc = r->api.Send(e.send_s, count, nccl_type<T>(), r->south, r->comm, s)) != ncclSuccess) break;
+        if (n && (rc = r->api.Recv(e.recv_n, count, nccl_type<T>(), r->north, r->comm, s)) != ncclSuccess) break;
     }
     ncclResult_t rc2 = r->api.GroupEnd();
     if (rc != ncclSuccess) return fail(r, "ncclSend/ncclRecv", rc);
@@ -234,57 +233,83 @@ int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, in
     return SWMHD_OK;
 }
 
-// nsteps RK3 steps of one y-slab.  Two schedules: the deep-halo one (Hy >= 9, x wrapped on read: ONE exchange per step, described
-// where it is implemented below) and the per-stage one.  Per stage (X = current state, Y = the other buffer set):
-//   main stream : rows [Hy, Ny-Hy) of X -> Y          (need no remote data; the exchange of X is still in flight)
-//   comm stream : ... exchange of X ... ; rows [0,Hy) and [Ny-Hy,Ny) of X -> Y     (one launch, queued behind the exchange)
-//   x wrapped on read : comm: exchange of Y straight after the strips ; comm waits for main's interior ; main waits for the strips
-//   x halos in memory : main: wait(comm) ; x-halo fill of Y ; record ; comm waits ; comm: exchange of Y
-// Either way the exchange of Y overlaps the next stage's interior rows.  A thin slab is bound by the chain exchange -> strips ->
-// exchange on the comm stream (tools/ring_rehearsal.py), which is why that chain has no hop through the main stream.
-// The first stage of the first call finds no exchange in flight and the caller's halos current: it runs all rows at once.
+// Stream `to` waits for what stream `from` has enqueued so far, through the ring's event of that direction (ev_main: main -> comm,
+// ev_comm: comm -> main).
+hipError_t follow(hipStream_t to, hipStream_t from, hipEvent_t ev) {
+    const hipError_t e = hipEventRecord(ev, from);
+    return e == hipSuccess ? hipStreamWaitEvent(to, ev, 0) : e;
+}
+
+// Drain the exchange in flight (if any): `s` waits for the comm stream.
+int join(swmhd_ring *r, hipStream_t s) {
+    if (!r->pending) return SWMHD_OK;
+    if (hipError_t e = follow(s, r->comm_stream, r->ev_comm)) return hipfail(r, "join", e);
+    r->pending = nullptr;
+    return SWMHD_OK;
+}
+
+// One call of a slab driver (swmhd_ring_step_rk3 and _bc): nsteps RK3 steps of one y-slab by one of two schedules, the deep-halo one
+// (described below) or the per-stage one.  Per stage (X = current state, Y = the other buffer set; cut sides: those whose halo rows
+// come from a neighbour -- both of a ring's slab, the sides without a wall of a chain's):
+//   main stream : rows of X that need no remote data -> Y: the interior, and the Hy-row strip of a wall side (the exchange of X is
+//                 still in flight)
+//   comm stream : ... exchange of X ... ; the Hy-row strips of the cut sides of X -> Y     (one launch, queued behind the exchange)
+//   no fill     : comm: exchange of Y straight after the strips ; comm waits for main's interior ; main waits for the strips
+//   a fill      : main: wait(comm) ; fill of Y ; comm waits ; comm: exchange of Y   (x halos live in memory: corners travel with rows)
+// The fill is none (periodic, x wrapped on read), the periodic x fill, or a Bounded slab's boundary-condition fill (x, and the wall
+// sides).  Either way the exchange of Y overlaps the next stage's interior rows.  A thin slab is bound by the chain exchange -> strips
+// -> exchange on the comm stream (tools/ring_rehearsal.py), which is why that chain has no hop through the main stream when no fill
+// runs.  A chain of one has no cut and exchanges nothing.  The first stage of a call that finds no exchange in flight (the caller's
+// halos current) runs all rows at once on the main stream.
 template <typename T>
-int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy,
-              T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt,
-              void *stream) {
-    if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
-    if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // walls: swmhd_ring_step_rk3_bc (its fill is the BC fill)
-    if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;   // y images belong to the neighbours (x may be wrapped on read: no x-halo kernel then)
-    if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;                          // a slab needs interior rows between its two strips
-    hipStream_t s = (hipStream_t)stream, c = r->comm_stream;
+struct Slab {
+    swmhd_ring *r;
+    hipStream_t s, c;   // the caller's stream (main) and, from begin() on, the ring's comm stream
     swmhd::Rk3Buffers<T> b;
-    if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
-    if (r->pending && r->pending != (const void *)b.cur[0]) {   // an exchange of some other state is in flight: drain it first
-        hipError_t e = hipEventRecord(r->ev_comm, c);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, r->ev_comm, 0);
-        if (e != hipSuccess) return hipfail(r, "join", e);
-        r->pending = nullptr;
-    }
-    hipError_t e;
-    const bool anchor = !(flags & SWMHD_STRICT);   // fast builds: the anchor form, 96 B/cell in every stage (common.hpp: Rk3Buffers)
-    // whatever the caller enqueued on its stream so far precedes everything this call puts on the comm stream
-    if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return hipfail(r, "record", e);
-    if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return hipfail(r, "wait", e);
-    // Error exit from the middle of a step: whatever was enqueued stays enqueued, so order the caller's stream behind the comm
-    // stream and forget the in-flight exchange -- `pending` must never describe an exchange that was not (fully) issued -- and
-    // tell the caller which buffer set holds the newest completed stage.
-    auto bail = [&](int code) {
-        if (hipEventRecord(r->ev_comm, c) == hipSuccess) (void)hipStreamWaitEvent(s, r->ev_comm, 0);
-        r->pending = nullptr;
-        if (state_in_alt) *state_in_alt = b.swaps & 1;
-        return code;
-    };
+    int Nx, Ny, Hx, Hy; int64_t sy; T dx, dy, grav, fcor; int formulation, lorentz; T dt;   // the grid and physics of every stage
+    bool anchor;   // fast periodic slabs: the anchor form, 96 B/cell in every stage (common.hpp: Rk3Buffers); else the G- form
+    int *state_in_alt;
+
     // rows [j0, j1) and [j0b, j1b) of stage g on stream `on`
-    auto run = [&](const swmhd::Rk3Stage<T> &g, int j0, int j1, int j0b, int j1b, int fl, hipStream_t on) {
+    int run(const swmhd::Rk3Stage<T> &g, int j0, int j1, int j0b, int j1b, int fl, hipStream_t on) {
         return swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
                                                    lorentz, dt, g.gamma, g.zeta, g.store_G, j0, j1, j0b, j1b, fl | g.flags, (void *)on);
-    };
+    }
+    // checks of both drivers, before any HIP call or read of the ring: the first stage's over an empty row range, and the fill's own
+    int check(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int flags) {
+        if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;   // a slab needs interior rows between its two strips
+        if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
+        if (int rc = run(b.stage(0, anchor), 0, 0, 0, 0, flags, s)) return rc;
+        return Hx > Nx ? SWMHD_EHALO : SWMHD_OK;
+    }
+    // drain an exchange in flight for another state; what the caller enqueued so far precedes all this call puts on the comm stream
+    int begin() {
+        c = r->comm_stream;
+        if (r->pending != (const void *)b.cur[0])
+            if (int rc = join(r, s)) return rc;
+        return comm_waits();
+    }
+    // exit: after an error whatever was enqueued stays enqueued, so order the caller's stream behind the comm stream and forget the
+    // exchange in flight (`pending` never describes one not fully issued); tell the caller which set holds the newest completed stage
+    int end(int rc) {
+        if (rc) { (void)follow(s, c, r->ev_comm); r->pending = nullptr; }
+        if (state_in_alt) *state_in_alt = b.swaps & 1;
+        return rc;
+    }
+    int comm_waits() { const hipError_t e = follow(c, s, r->ev_main); return e == hipSuccess ? SWMHD_OK : hipfail(r, "comm waits for main", e); }
+    int main_waits() { const hipError_t e = follow(s, c, r->ev_comm); return e == hipSuccess ? SWMHD_OK : hipfail(r, "main waits for comm", e); }
+    int exchange_cur(int cuts) {
+        const int rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c, cuts);
+        if (!rc) r->pending = b.cur[0];
+        return rc;
+    }
     // the interior launch of a stage on the main stream, between two timing events while swmhd_ring_time_launches asks for them
     // (timing-only events: without the system-scope fence a default event performs when it is recorded -- with the comm stream's
     //  kernels running beside the interior launch that fence cost 16 % of the step, 1.53 vs 1.32 ms)
-    auto run_interior = [&](const swmhd::Rk3Stage<T> &g, int j0, int j1, int fl) {
+    int run_interior(const swmhd::Rk3Stage<T> &g, int j0, int j1, int fl) {
         if (r->t0.size() >= r->tcap) return run(g, j0, j1, 0, 0, fl, s);
         hipEvent_t t0 = nullptr, t1 = nullptr;
+        hipError_t e;
         if ((e = hipEventCreateWithFlags(&t0, hipEventDisableSystemFence)) != hipSuccess) return hipfail(r, "hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&t1, hipEventDisableSystemFence)) != hipSuccess) { (void)hipEventDestroy(t0); return hipfail(r, "hipEventCreate", e); }
         (void)hipEventRecord(t0, s);
@@ -292,93 +317,100 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
         if (rc) { (void)hipEventDestroy(t0); (void)hipEventDestroy(t1); return rc; }
         (void)hipEventRecord(t1, s);
         r->t0.push_back(t0); r->t1.push_back(t1); r->trows.push_back(j1 - j0);
-        return 0;
-    };
-    if ((flags & SWMHD_WRAP_X) && Hy >= 9 && Ny >= 32) {
-        // ---- deep-halo schedule: ONE exchange per step instead of one per stage ------------------------------------------------
-        // With Hy >= 9 a slab evaluates the rows of its neighbours it needs for stages 2 and 3 itself (redundantly: 18 extra rows
-        // per step) from the 9 halo rows exchanged once per step.  Rows per stage (north side mirrored):
-        //     stage 1   interior [3, Ny-3)     boundary [-6, 3)      stage 2   interior [9, Ny-9)    boundary [-3, 9)
-        //     stage 3   interior [12, Ny-12)   boundary [0, 12)
-        // Interior launches (main stream) read only what earlier interior launches of the same step wrote -- plus, for stage 1,
-        // the boundary rows of the previous step's last stage: ONE wait of the main stream per step.  Boundary launches (comm
-        // stream, behind the exchange) read rows of the previous interior launch: the comm stream waits twice, off the critical
-        // path.  Stage 2's interior starts at row 9, not 6, because it overwrites the buffer whose rows [0, 9) the exchange in
-        // flight is still sending.  A thin slab (strong scaling) is then bound by its interior launches, not by the chain
-        // exchange -> strips -> exchange of the per-stage schedule below (tools/ring_rehearsal.py).
+        return SWMHD_OK;
+    }
+
+    // ---- per-stage schedule.  cuts: bit 0 south, bit 1 north.  The fill follows from the flags: Bounded slabs the boundary-
+    //      condition fill (gradient: device table of 16 values, or NULL), x halos in memory the periodic x fill, x wrapped on read none
+    int per_stage(int nsteps, int fl, int cuts, const T *gradient) {
+        const bool walls = fl & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y), fill = walls || !(fl & SWMHD_WRAP_X);
+        const int topo_x = (fl & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
+        constexpr int FACE_X = 0b0001, FACE_Y = 0b0010;
+        const int lo = (cuts & 1) ? Hy : 0, hi = (cuts & 2) ? Ny - Hy : Ny;   // rows [lo, hi) need no remote data
+        for (int n = 0; n < nsteps; ++n)
+            for (int st = 0; st < 3; ++st) {
+                const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
+                const bool split = r->pending != nullptr;
+                int rc;
+                // (interior rows: leave a few workgroup slots free, or the exchange and the strips could not start before it ends)
+                if ((rc = split ? run_interior(g, lo, hi, fl | SWMHD_LEAVE_ROOM) : run_interior(g, 0, Ny, fl))) return rc;
+                // the cut strips in one launch: they sit on the exchange -> strips -> exchange chain that bounds a thin slab
+                if (split && ((rc = lo > 0 ? run(g, 0, lo, hi, Ny, fl, c) : run(g, hi, Ny, 0, 0, fl, c)) || (rc = main_waits()))) return rc;
+                b.rotate();
+                r->pending = nullptr;   // the exchange of the OLD state has been consumed; none of the new state is in flight yet
+                if (split && !fill) {
+                    // The rows the exchange sends are exactly the strips' output and no fill touches them: the exchange of the new
+                    // state follows the strips on the comm stream directly, without a round trip through the main stream; only the
+                    // NEXT stage's strips wait for this stage's interior rows.
+                    if ((rc = exchange_cur(cuts)) || (rc = comm_waits())) return rc;
+                    continue;
+                }
+                if (walls && (rc = swmhd::fill_halo_walls_dev<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, topo_x, 3 & ~cuts, FACE_X, FACE_Y, gradient,
+                                                                 dx, dy, (void *)s)))
+                    return rc;
+                if (!walls && fill && (rc = swmhd::fill_halo_periodic_multi<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, SWMHD_HALO_X, (void *)s)))
+                    return rc;
+                if (!cuts) continue;   // a chain of one: both walls local, nothing to exchange
+                if ((rc = comm_waits()) || (rc = exchange_cur(cuts))) return rc;
+            }
+        return SWMHD_OK;
+    }
+
+    // ---- deep-halo schedule: ONE exchange per step instead of one per stage (periodic rings) ------------------------------------
+    // With Hy >= 9 a slab evaluates the rows of its neighbours it needs for stages 2 and 3 itself (redundantly: 18 extra rows
+    // per step) from the 9 halo rows exchanged once per step.  Rows per stage (north side mirrored):
+    //     stage 1   interior [3, Ny-3)     boundary [-6, 3)      stage 2   interior [9, Ny-9)    boundary [-3, 9)
+    //     stage 3   interior [12, Ny-12)   boundary [0, 12)
+    // Interior launches (main stream) read only what earlier interior launches of the same step wrote -- plus, for stage 1,
+    // the boundary rows of the previous step's last stage: ONE wait of the main stream per step.  Boundary launches (comm
+    // stream, behind the exchange) read rows of the previous interior launch: the comm stream waits twice, off the critical
+    // path.  Stage 2's interior starts at row 9, not 6, because it overwrites the buffer whose rows [0, 9) the exchange in
+    // flight is still sending.  A thin slab (strong scaling) is then bound by its interior launches, not by the chain
+    // exchange -> strips -> exchange of the per-stage schedule (tools/ring_rehearsal.py).
+    int deep_halo(int nsteps, int flags) {
         const int ilo[3] = {3, 9, 12}, blo[3] = {-6, -3, 0};
         // boundary zones of a wide slab take the row-marching kernel too (both zones in one launch, a few dozen workgroups beside the
         // interior launch); the LDS-tiled kernel re-loads a 10-row halo per 4-row tile and costs ten times as much per row
         const int bflags = flags | ((!(flags & (SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL)) && Nx >= 1024) ? SWMHD_MARCH_KERNEL : 0);
+        int rc;
         for (int n = 0; n < nsteps; ++n) {
             for (int st = 0; st < 3; ++st) {
                 const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
-                if (int rc = run_interior(g, ilo[st], Ny - ilo[st], flags | SWMHD_LEAVE_ROOM)) return bail(rc);
-                if (st < 2) {   // the next boundary launch reads rows of this interior launch
-                    if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
-                }
+                if ((rc = run_interior(g, ilo[st], Ny - ilo[st], flags | SWMHD_LEAVE_ROOM))) return rc;
                 // boundary rows of this stage, both sides in one launch, behind the exchange (stage 1) / the previous boundary launch
-                if (int rc = run(g, blo[st], ilo[st], Ny - ilo[st], Ny - blo[st], bflags, c)) return bail(rc);
-                if (st < 2) {
-                    if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-                }
+                if ((rc = run(g, blo[st], ilo[st], Ny - ilo[st], Ny - blo[st], bflags, c))) return rc;
+                if (st < 2 && (rc = comm_waits())) return rc;   // the next boundary launch reads rows of this interior launch
                 b.rotate();
             }
             // end of the step: the main stream's next interior launch reads the last boundary rows; the exchange of the new state
             // (its 9 edge rows are exactly those boundary rows) follows them on the comm stream
             r->pending = nullptr;
-            if ((e = hipEventRecord(r->ev_comm, c)) != hipSuccess) return bail(hipfail(r, "record", e));
-            if ((e = hipStreamWaitEvent(s, r->ev_comm, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            if (int rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c)) return bail(rc);
-            r->pending = b.cur[0];
+            if ((rc = main_waits()) || (rc = exchange_cur(3))) return rc;
         }
-        if (state_in_alt) *state_in_alt = b.swaps & 1;
         return SWMHD_OK;
     }
-    for (int n = 0; n < nsteps; ++n)
-        for (int st = 0; st < 3; ++st) {
-            const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
-            int rc;
-            const bool split = r->pending != nullptr;
-            // (interior rows: leave a few workgroup slots free, or the exchange and the strips could not start before it ends)
-            if ((rc = split ? run_interior(g, Hy, Ny - Hy, flags | SWMHD_LEAVE_ROOM) : run_interior(g, 0, Ny, flags))) return bail(rc);
-            if (split) {   // both strips in one launch: they sit on the exchange -> strips -> exchange chain that bounds a thin slab
-                if ((rc = run(g, 0, Hy, Ny - Hy, Ny, flags, c))) return bail(rc);
-                if ((e = hipEventRecord(r->ev_comm, c)) != hipSuccess) return bail(hipfail(r, "record", e));
-                if ((e = hipStreamWaitEvent(s, r->ev_comm, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            }
-            b.rotate();
-            r->pending = nullptr;   // the exchange of the OLD state has been consumed; none of the new state is in flight yet
-            if (split && (flags & SWMHD_WRAP_X)) {
-                // The rows the exchange sends are exactly the strips' output and (x wrapped on read) no x-halo kernel touches them:
-                // the exchange of the new state follows the strips on the comm stream directly, without a round trip through the
-                // main stream; only the NEXT stage's strips wait for this stage's interior rows.
-                if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
-                r->pending = b.cur[0];
-                if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
-                if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-                continue;
-            }
-            if (!(flags & SWMHD_WRAP_X) && (rc = swmhd::fill_halo_periodic_multi<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, SWMHD_HALO_X, (void *)s)))
-                return bail(rc);
-            if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
-            if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c))) return bail(rc);
-            r->pending = b.cur[0];
-        }
-    if (state_in_alt) *state_in_alt = b.swaps & 1;
-    return SWMHD_OK;
+};
+
+// swmhd_ring_step_rk3: a periodic ring -- both sides cut, stages in anchor form (fast) or G- form (strict)
+template <typename T>
+int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy,
+              T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt,
+              void *stream) {
+    if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
+    if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // walls: swmhd_ring_step_rk3_bc (its fill is the BC fill)
+    if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;   // y images belong to the neighbours (x may be wrapped on read: no x-halo kernel then)
+    Slab<T> x{r, (hipStream_t)stream, nullptr, {}, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt,
+              !(flags & SWMHD_STRICT), state_in_alt};
+    if (int rc = x.check(q, q_alt, Ga, Gb, flags)) return rc;
+    if (nsteps == 0) return x.end(SWMHD_OK);
+    if (int rc = x.begin()) return rc;
+    const bool deep = (flags & SWMHD_WRAP_X) && Hy >= 9 && Ny >= 32;
+    return x.end(deep ? x.deep_halo(nsteps, flags) : x.per_stage(nsteps, flags, 3, nullptr));
 }
 
-// nsteps RK3 steps of a Bounded slab (swmhd_ring_step_rk3_bc): with SWMHD_BOUNDED_Y the ranks form a CHAIN -- rank 0 holds the south
-// wall, the last rank the north wall, every other side is a cut to a neighbour -- with SWMHD_BOUNDED_X alone a periodic-y ring whose x
-// walls are local to every slab.  The per-stage schedule of ring_step, in G- form, with the boundary-condition fill in place of the
-// x-halo kernel (X = current state, Y = the other buffer set):
-//   main stream : rows of X that need no remote data -> Y: the interior, plus the Hy-row strip of a WALL side (its halo is local)
-//   comm stream : ... exchange of X (cut sides only) ... ; the Hy-row strips of the CUT sides of X -> Y   (one launch)
-//   main        : wait(comm) ; swmhd_fill_halo_walls of Y (x, and the wall sides in y) ; record ; comm waits ; comm: exchange of Y
-// The fill precedes the exchange because x halos live in memory and the corners travel with the rows.  A chain of one has no cut: all
-// rows of every stage on the main stream, nothing exchanged.  The first stage of a call finds the caller's halos current.
+// swmhd_ring_step_rk3_bc: Bounded slabs, stages in G- form (as the single Bounded model), the per-stage schedule with the boundary-
+// condition fill.  With SWMHD_BOUNDED_Y the ranks form a CHAIN -- rank 0 holds the south wall, the last rank the north wall, every
+// other side is a cut to a neighbour; with SWMHD_BOUNDED_X alone a periodic-y ring whose x walls are local to every slab.
 template <typename T>
 int ring_step_bc(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy,
                  T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, const T *gradient, int flags,
@@ -391,68 +423,26 @@ int ring_step_bc(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *c
     if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;
     if ((flags & SWMHD_BOUNDED_X) && (flags & SWMHD_WRAP_X)) return SWMHD_EINVAL;
     if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
-    if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;
-    swmhd::Rk3Buffers<T> b;
-    if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
+    Slab<T> x{r, (hipStream_t)stream, nullptr, {}, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, false, state_in_alt};
+    if (int rc = x.check(q, q_alt, Ga, Gb, flags)) return rc;   // (the SWMHD_OPEN_* bits set below change none of its checks)
+    if (nsteps == 0) return x.end(SWMHD_OK);
     const bool chain = flags & SWMHD_BOUNDED_Y;
-    const bool south_wall = chain && r->rank == 0, north_wall = chain && r->rank == r->nranks - 1;
-    const int walls_y = (south_wall ? 1 : 0) | (north_wall ? 2 : 0), cuts = 3 & ~walls_y;
-    const int fl = flags | (chain && !south_wall ? SWMHD_OPEN_SOUTH : 0) | (chain && !north_wall ? SWMHD_OPEN_NORTH : 0);
-    const int topo_x = (flags & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
-    constexpr int FACE_X = 0b0001, FACE_Y = 0b0010;
-    // rows that need no remote data, and the cut-side strips
-    const int lo = (cuts & 1) ? Hy : 0, hi = (cuts & 2) ? Ny - Hy : Ny;
-    const int s0 = 0, s1 = (cuts & 1) ? Hy : 0, n0 = (cuts & 2) ? Ny - Hy : Ny, n1 = Ny;
-    // the argument checks of the stage and of the fill, before the first HIP call (an empty row range checks without launching)
-    if (int rc = swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, b.gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
-                                                     lorentz, dt, T(0), T(0), 1, 0, 0, 0, 0, fl, nullptr))
-        return rc;
-    if (Hx > Nx || Hy > Ny) return SWMHD_EHALO;   // (the fill's own check; the stage's are above)
-    if (nsteps == 0) { if (state_in_alt) *state_in_alt = 0; return SWMHD_OK; }
-    hipStream_t s = (hipStream_t)stream, c = r->comm_stream;
-    hipError_t e;
-    if (r->pending && r->pending != (const void *)b.cur[0]) {   // an exchange of some other state is in flight: drain it first
-        e = hipEventRecord(r->ev_comm, c);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, r->ev_comm, 0);
-        if (e != hipSuccess) return hipfail(r, "join", e);
-        r->pending = nullptr;
-    }
-    if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return hipfail(r, "record", e);
-    if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return hipfail(r, "wait", e);
-    auto bail = [&](int code) {
-        if (hipEventRecord(r->ev_comm, c) == hipSuccess) (void)hipStreamWaitEvent(s, r->ev_comm, 0);
-        r->pending = nullptr;
-        if (state_in_alt) *state_in_alt = b.swaps & 1;
-        return code;
-    };
-    auto run = [&](const swmhd::Rk3Stage<T> &g, int j0, int j1, int j0b, int j1b, int f, hipStream_t on) {
-        return swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
-                                                   lorentz, dt, g.gamma, g.zeta, g.store_G, j0, j1, j0b, j1b, f, (void *)on);
-    };
-    for (int n = 0; n < nsteps; ++n)
-        for (int st = 0; st < 3; ++st) {
-            const swmhd::Rk3Stage<T> g = b.stage(st, false);
-            int rc;
-            const bool split = r->pending != nullptr;
-            if ((rc = split ? run(g, lo, hi, 0, 0, fl | SWMHD_LEAVE_ROOM, s) : run(g, 0, Ny, 0, 0, fl, s))) return bail(rc);
-            if (split) {   // the cut strips, one launch behind the exchange; the main stream then waits for them
-                if ((rc = s1 > s0 ? run(g, s0, s1, n0, n1, fl, c) : run(g, n0, n1, 0, 0, fl, c))) return bail(rc);
-                if ((e = hipEventRecord(r->ev_comm, c)) != hipSuccess) return bail(hipfail(r, "record", e));
-                if ((e = hipStreamWaitEvent(s, r->ev_comm, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            }
-            b.rotate();
-            r->pending = nullptr;
-            if ((rc = swmhd::fill_halo_walls_dev<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, topo_x, chain ? walls_y : 0, FACE_X, FACE_Y,
-                                                    gradient, dx, dy, (void *)s)))
-                return bail(rc);
-            if (!cuts) continue;   // a chain of one: both walls local, nothing to exchange
-            if ((e = hipEventRecord(r->ev_main, s)) != hipSuccess) return bail(hipfail(r, "record", e));
-            if ((e = hipStreamWaitEvent(c, r->ev_main, 0)) != hipSuccess) return bail(hipfail(r, "wait", e));
-            if ((rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c, cuts))) return bail(rc);
-            r->pending = b.cur[0];
-        }
-    if (state_in_alt) *state_in_alt = b.swaps & 1;
-    return SWMHD_OK;
+    const int walls_y = chain ? (r->rank == 0 ? 1 : 0) | (r->rank == r->nranks - 1 ? 2 : 0) : 0, cuts = 3 & ~walls_y;
+    const int fl = flags | (chain && (cuts & 1) ? SWMHD_OPEN_SOUTH : 0) | (chain && (cuts & 2) ? SWMHD_OPEN_NORTH : 0);
+    if (int rc = x.begin()) return rc;
+    return x.end(x.per_stage(nsteps, fl, cuts, gradient));
+}
+
+// rank `rank` of `nranks` with its neighbours, its comm stream (the device's highest priority) and its two events
+hipError_t init_ring(swmhd_ring *r, int nranks, int rank) {
+    r->nranks = nranks; r->rank = rank;
+    r->south = (rank + nranks - 1) % nranks; r->north = (rank + 1) % nranks;
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // hi = numerically lowest = highest priority
+    hipError_t e = hipStreamCreateWithPriority(&r->comm_stream, hipStreamNonBlocking, hi);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_main, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_comm, hipEventDisableTiming);
+    return e;
 }
 
 }  // namespace
@@ -482,18 +472,10 @@ int swmhd_ring_create(swmhd_ring **out, const char *rccl_path, int nranks, int r
     swmhd_ring *r = new (std::nothrow) swmhd_ring;
     if (!r) return SWMHD_EINVAL;
     if (!load_rccl(rccl_path, r->api, r->err)) { delete r; return SWMHD_ENOTSUP; }
-    r->nranks = nranks; r->rank = rank;
-    r->south = (rank + nranks - 1) % nranks;
-    r->north = (rank + 1) % nranks;
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     if (r->api.CommInitRank(&r->comm, nranks, id, rank) != ncclSuccess) { delete r; return SWMHD_ECOMM; }
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // hi = numerically lowest = highest priority
-    hipError_t e = hipStreamCreateWithPriority(&r->comm_stream, hipStreamNonBlocking, hi);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_main, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_comm, hipEventDisableTiming);
-    if (e != hipSuccess) { swmhd_ring_destroy(r); return -(int)e; }
+    if (hipError_t e = init_ring(r, nranks, rank)) { swmhd_ring_destroy(r); return -(int)e; }
     *out = r;
     return SWMHD_OK;
 }
@@ -503,19 +485,11 @@ int swmhd_ring_create_loopback(swmhd_ring **out, int nranks, double timeout_s) {
     std::shared_ptr<LoopHub> hub;
     try { hub = std::make_shared<LoopHub>(nranks); } catch (...) { return SWMHD_EINVAL; }
     if (timeout_s > 0) hub->timeout_s = timeout_s;
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
     for (int k = 0; k < nranks; ++k) out[k] = nullptr;
     for (int k = 0; k < nranks; ++k) {
         swmhd_ring *r = new (std::nothrow) swmhd_ring;
-        hipError_t e = r ? hipSuccess : hipErrorOutOfMemory;
-        if (r) {
-            r->hub = hub; r->nranks = nranks; r->rank = k;
-            r->south = (k + nranks - 1) % nranks; r->north = (k + 1) % nranks;
-            e = hipStreamCreateWithPriority(&r->comm_stream, hipStreamNonBlocking, hi);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_main, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_comm, hipEventDisableTiming);
-        }
+        hipError_t e = hipErrorOutOfMemory;
+        if (r) { r->hub = hub; e = init_ring(r, nranks, k); }
         if (e != hipSuccess) {
             if (r) swmhd_ring_destroy(r);
             for (int j = 0; j < k; ++j) { swmhd_ring_destroy(out[j]); out[j] = nullptr; }
@@ -543,15 +517,7 @@ const char *swmhd_ring_last_error(const swmhd_ring *r) { return r ? r->err.c_str
 
 void *swmhd_ring_comm_stream(const swmhd_ring *r) { return r ? (void *)r->comm_stream : nullptr; }
 
-int swmhd_ring_join(swmhd_ring *r, void *stream) {
-    if (!r) return SWMHD_EINVAL;
-    if (!r->pending) return SWMHD_OK;
-    hipError_t e = hipEventRecord(r->ev_comm, r->comm_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, r->ev_comm, 0);
-    if (e != hipSuccess) return hipfail(r, "join", e);
-    r->pending = nullptr;
-    return SWMHD_OK;
-}
+int swmhd_ring_join(swmhd_ring *r, void *stream) { return r ? join(r, (hipStream_t)stream) : SWMHD_EINVAL; }
 
 int swmhd_ring_time_launches(swmhd_ring *r, int max_launches) {
     if (!r || max_launches < 0) return SWMHD_EINVAL;

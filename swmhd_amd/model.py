@@ -342,29 +342,31 @@ class ShallowWaterModel:
         """n RK3 steps in ONE C call that enqueues every launch: the native ring driver (swmhd_ring_step_rk3_*) on a slab, the step
         driver (swmhd_step_rk3_*) on one GPU."""
         import ctypes
-        gr, ring = self.grid, self._ring is not None
+        gr, ring, bounded = self.grid, self._ring is not None, any(self._bounded)
         wrap = self._rwrap & _lib.WRAP_X if ring else self._rwrap     # (a slab's y halos come from the ring)
-        if ring and any(self._bounded):
+        if ring and bounded:
             wrap = 0                  # (the Bounded slab driver fills every halo between the stages: its state's halos stay current)
         if ring and self._halo_stale and not wrap:
             self.update_state()
         swapped = ctypes.c_int(0)
-        args = (_lib.ptr_array([f.ptr for f in self._raw_fields]), _lib.ptr_array([self._alt[nm].ptr for nm in self.names]),
+        # the arguments the three drivers share: up to nsteps, and state_in_alt, stream after the flags
+        head = (_lib.ptr_array([f.ptr for f in self._raw_fields]), _lib.ptr_array([self._alt[nm].ptr for nm in self.names]),
                 _lib.ptr_array([f.ptr for f in self.Gn]), _lib.ptr_array([f.ptr for f in self.Gm]), gr.Nx, gr.Ny, gr.Hx, gr.Hy,
-                self._raw_fields[0].stride_y, gr.dx, gr.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
-                self._flags | wrap, ctypes.byref(swapped), _stream_ptr())
-        if ring and any(self._bounded):
+                self._raw_fields[0].stride_y, gr.dx, gr.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n)
+        tail = (ctypes.byref(swapped), _stream_ptr())
+        if ring and bounded:
             # Bounded slabs (a chain, or Bounded x on a ring): the driver decides the cut sides itself and fills the boundary conditions
             # from a device table of the 16 gradient values
             if getattr(self, "_grad_dev", None) is None:
                 self._grad_dev = torch.tensor(self._gradients(), dtype=self._raw_fields[0].data.dtype, device=self._raw_fields[0].data.device)
             fl = self._flags & ~(_lib.OPEN_SOUTH | _lib.OPEN_NORTH)
-            args = args[:-3] + (self._grad_dev.data_ptr(), fl) + args[-2:]
-            self._ring_check(getattr(self._L, f"swmhd_ring_step_rk3_bc_{self.sfx}")(self._ring, *args), "swmhd_ring_step_rk3_bc")
+            step = getattr(self._L, f"swmhd_ring_step_rk3_bc_{self.sfx}")
+            self._ring_check(step(self._ring, *head, self._grad_dev.data_ptr(), fl, *tail), "swmhd_ring_step_rk3_bc")
         elif ring:
-            self._ring_check(getattr(self._L, f"swmhd_ring_step_rk3_{self.sfx}")(self._ring, *args), "swmhd_ring_step_rk3")
+            step = getattr(self._L, f"swmhd_ring_step_rk3_{self.sfx}")
+            self._ring_check(step(self._ring, *head, self._flags | wrap, *tail), "swmhd_ring_step_rk3")
         else:
-            _lib.check(getattr(self._L, f"swmhd_step_rk3_{self.sfx}")(*args), "swmhd_step_rk3")
+            _lib.check(getattr(self._L, f"swmhd_step_rk3_{self.sfx}")(*head, self._flags | wrap, *tail), "swmhd_step_rk3")
         if swapped.value:
             self._state, self._alt = self._alt, self._state
             self.Gn, self.Gm = self.Gm, self.Gn

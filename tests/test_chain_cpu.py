@@ -136,6 +136,42 @@ def test_ring_step_bc_refusals(swmhd, sfx):
 
 
 @pytest.mark.parametrize("sfx", ["f64", "f32"])
+def test_slab_drivers_check_everything_before_touching_the_ring(swmhd, sfx):
+    """both slab drivers check every stage argument, and return on nsteps == 0, before any HIP call and any read of the ring"""
+    B = swmhd._lib
+    L = B.lib()
+    _b1, p, arr = _bufs(sfx)
+    _b2, _p2, alt = _bufs(sfx)
+    _b3, _p3, ga = _bufs(sfx)
+    _b4, _p4, gb = _bufs(sfx)
+    ring_step = getattr(L, f"swmhd_ring_step_rk3_{sfx}")
+    ring_step_bc = getattr(L, f"swmhd_ring_step_rk3_bc_{sfx}")
+    fake = ctypes.c_void_p(1)    # never dereferenced
+    for strict in (0, B.STRICT):
+        def step(form=1, lorentz=1, q_alt=alt, nsteps=1, Hx=H, flags=0):
+            return ring_step(fake, arr, q_alt, ga, gb, Nx, Ny, Hx, H, Nx + 2 * Hx, 0.1, 0.1, 9.81, 1.0, form, lorentz, 1e-3, nsteps,
+                             strict | flags, None, None)
+
+        assert step(form=7) == 1                                   # unknown formulation
+        assert step(form=B.CONSERVATIVE, lorentz=B.LORENTZ_JACOBIAN) == 1
+        assert step(q_alt=arr) == 1                                # the new state aliases the state read through halos
+        assert step(Hx=Nx + 1) == 2                                # the x fill's halo check (x halos in memory)
+        assert step(Hx=Nx + 1, flags=B.WRAP_X) == 2                # the stage's own (x wrapped on read)
+        for fl in (0, B.WRAP_X):
+            alt_flag = ctypes.c_int(7)
+            assert ring_step(fake, arr, alt, ga, gb, Nx, Ny, H, H, SY, 0.1, 0.1, 9.81, 1.0, 1, 1, 1e-3, 0, strict | fl,
+                             ctypes.byref(alt_flag), None) == 0
+            assert alt_flag.value == 0
+        for fl in (B.BOUNDED_X, B.BOUNDED_Y, B.BOUNDED_X | B.BOUNDED_Y):
+            alt_flag = ctypes.c_int(7)
+            assert ring_step_bc(fake, arr, alt, ga, gb, Nx, Ny, H, H, SY, 0.1, 0.1, 9.81, 1.0, 1, 1, 1e-3, 0, None, strict | fl,
+                                ctypes.byref(alt_flag), None) == 0
+            assert alt_flag.value == 0
+            assert ring_step_bc(fake, arr, arr, ga, gb, Nx, Ny, H, H, SY, 0.1, 0.1, 9.81, 1.0, 1, 1, 1e-3, 1, None, strict | fl,
+                                None, None) == 1
+
+
+@pytest.mark.parametrize("sfx", ["f64", "f32"])
 def test_open_flags_and_wall_fill_refusals(swmhd, sfx):
     B = swmhd._lib
     L = B.lib()
