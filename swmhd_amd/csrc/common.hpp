@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 namespace swmhd {
@@ -43,11 +42,7 @@ hipError_t launch_fill_halo_periodic_multi(T *const *interiors, int nfields, int
 // fill_halo_regions! for any (Periodic | Bounded) topology pair with Oceananigans' default boundary conditions or gradient BCs
 // (oracle_fill_halo): west/east pass, then south/north pass over the padded width.  face_x/face_y: bit f set = field f is
 // located at Face in that direction; grad[f][4] = west, east, south, north GradientBoundaryCondition values (NaN = default).
-// A Bounded y direction cut into y-slabs (swmhd_ring_step_rk3_bc, SWMHD_OPEN_SOUTH / _NORTH): bits above the topology code 1 in
-// TendArgs::topo_y and HaloBc::topo_y mark a side that is a cut to a neighbouring slab, not a wall.  Reconstructions see the rows next to
-// it as far from any wall (order 5 / centred 4th, no wall branch of the divergence forcing); the boundary-condition fill leaves its halo
-// rows alone (they come from the neighbour).  topo_y == 1 is the whole Bounded direction, both sides walls.
-constexpr int TOPO_OPEN_SOUTH = 2, TOPO_OPEN_NORTH = 4;
+// topo_y may carry TOPO_OPEN_SOUTH / TOPO_OPEN_NORTH (launch_plan.hpp): that side of a y-slab is a cut to its neighbour, not a wall.
 // index offset that puts an open side's rows out of reach of every wall test (left_order / right_order / sym_fourth / wall_code)
 constexpr int TOPO_FAR = 1 << 20;
 template <typename T>
@@ -219,82 +214,8 @@ struct ProgressPriority {
 //  beside it at the top level was measured and dropped -- the ring-of-one step got 2-8 % SLOWER at every slab height: the falling
 //  priorities are what keeps the interior's own workgroups in step.)
 
-// ---- launch geometry of the row-marching kernels --------------------------------------------------------------------------
-// One workgroup = a strip of nt - 2*xh output columns x LY rows; the grid is a whole number of rounds of resident workgroups.
-// Folded last strip (fold = 1): where the last strip has at most nt/2 - 2*xh output columns, each of its workgroups runs two
-// half-width sub-strips of nt/2 lanes on two segments, so a segment row costs nstrips - 1/2 workgroups instead of nstrips.
-struct MarchGeometry {
-    int nt;        // threads per workgroup (strip width incl. 2*xh halo lanes)
-    int nstrips, nseg, LY;
-    int wg_per_cu; // resident workgroups per CU the kernel is built for
-    int fold;      // 1: the last strip is folded (nstrips still counts it as one strip)
-    int blocks() const { return fold ? (nstrips - 1) * nseg + (nseg + 1) / 2 : nstrips * nseg; }
-};
-// Compute units of the current device (hipDeviceAttributeMultiprocessorCount; 256 on MI355X), cached per process.
-inline int device_cu_count() {
-    static int cus = 0;
-    if (cus <= 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        cus = n;
-    }
-    return cus;
-}
-// Tuning knobs are read from the environment ONCE per process (not on every launch).
-inline int env_knob(const char *name, int &cache) {   // cache: 0 = not read yet, -1 = unset, > 0 = value
-    if (cache == 0) {
-        const char *e = getenv(name);
-        const int v = e ? atoi(e) : 0;
-        cache = v > 0 ? v : -1;
-    }
-    return cache > 0 ? cache : 0;
-}
-// Strip width: the FIRST candidate workgroup size unless a later one covers Nx with at least 5 % fewer lanes (1024 columns: 5 strips x
-// 256 lanes = 1280, but 9 x 128 = 1152).  Rows per segment: the smallest whole number of rounds of resident workgroups
-// (wg_per_cu x CUs slots; ~5 % fewer with leave_room, so that another stream's kernels find room) whose segments are at most
-// 128 rows, but never shorter than ly_min rows.  fold_nt: the workgroup size whose kernel can fold its last strip (0: none); the strip
-// width is chosen first, and folding then only changes how many workgroups a segment row costs.
-// Share of the workgroup slots an interior launch of the slab driver leaves free for the comm stream's kernels, in 64ths: 3 (4.7 %),
-// and 1 (1.6 %) for slabs of 3072 rows and more -- the boundary work per step is fixed, a long interior launch gives it time enough in
-// few slots, and every slot costs the interior launch its share of the chip (4096 x 4096 ring-of-one step: +1.4-1.9 % over the plain
-// step with 1, +3.7-4.0 % with 3; 4096 x 2048: +4.8-5.2 % vs +4.6-4.7 %; three alternating runs each).  SWMHD_RING_ROOM overrides (tuning).
-inline int leave_room_64ths(int rows) {
-    static int cache = 0;
-    const int v = env_knob("SWMHD_RING_ROOM", cache);
-    return v > 0 ? (v < 32 ? v : 32) : (rows >= 3072 ? 1 : 3);
-}
-inline MarchGeometry march_geometry(int Nx, int rows, int xh, const int *nts, const int *wgs, int ncand, int ly_min, bool leave_room,
-                                    int force_nt, int force_ly, int fold_nt = 0) {
-    MarchGeometry g{};
-    long best = -1;
-    for (int k = 0; k < ncand; ++k) {
-        const int txo = nts[k] - 2 * xh, ns = (Nx + txo - 1) / txo;
-        const long lanes = (long)ns * nts[k];
-        const bool take = force_nt ? nts[k] == force_nt : (best < 0 || lanes * 20 <= best * 19);
-        if (take) { best = lanes; g.nt = nts[k]; g.nstrips = ns; g.wg_per_cu = wgs[k]; }
-    }
-    if (best < 0) { g.nt = nts[0]; g.nstrips = (Nx + nts[0] - 2 * xh - 1) / (nts[0] - 2 * xh); g.wg_per_cu = wgs[0]; }
-    g.fold = fold_nt && g.nt == fold_nt && g.nstrips > 1 && Nx - (g.nstrips - 1) * (g.nt - 2 * xh) <= g.nt / 2 - 2 * xh ? 1 : 0;
-    const int halves = 2 * g.nstrips - g.fold;   // half-workgroups per segment row
-    int slots = device_cu_count() * g.wg_per_cu;
-    if (leave_room) slots -= (slots * leave_room_64ths(rows)) / 64;
-    int LY = 32;
-    for (int k = 1; k <= 64; ++k) {
-        const int ns = (2 * slots * k) / halves;
-        if (ns < 1) continue;
-        const int ly = (rows + ns - 1) / ns;
-        if (ly <= 128) { LY = ly < ly_min ? ly_min : ly; break; }
-    }
-    if (force_ly > 0) LY = force_ly;
-    g.LY = LY;
-    g.nseg = (rows + LY - 1) / LY;
-    return g;
-}
-
+// (launch geometry and kernel choice of the tendency kernels: launch_plan.hpp, host only)
 template <typename T> hipError_t launch_tendency_fast(const TendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
-// geometry the fast tendency launcher would use (kind: 1 = LDS-tiled kernel, 2 = row-marching kernel); for bench.py's VALU floor
-int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, int kernel_variant, int leave_room, int wrap, int out[8]);
 template <typename T> hipError_t launch_tendency_strict(const TendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_rk3_substep_fast(const Rk3Args<T> &a, hipStream_t s);
 // ensemble stage: every tile of every member in one launch of the LDS-tiled kernel (rows [a.j0, a.j1) of each member; no second range,

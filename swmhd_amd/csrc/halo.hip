@@ -1,6 +1,7 @@
 // Periodic halo fill: the stand-alone engine's counterpart of Oceananigans' fill_halo_regions! for
 // topology = (Periodic, Periodic, Flat) (reference: jacobian_formulation/SWMHD_example.jl:16).
 #include "common.hpp"
+#include "launch_plan.hpp"   // TOPO_OPEN_*
 // (gradient boundary values are formed as c - g*d in two roundings, like the oracle: the Makefile builds this file -ffp-contract=off)
 
 namespace swmhd {

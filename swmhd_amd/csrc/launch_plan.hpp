@@ -1,0 +1,309 @@
+// Host-only launch planning of the fused tendency kernels: what a call will enqueue, decided as data before anything is launched.
+// No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
+// compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdlib.h>
+
+namespace swmhd {
+
+// ---- topology codes of TendArgs / OpArgs / HaloBc -------------------------------------------------------------------------------
+// 0 Periodic, 1 Bounded.  A Bounded y direction cut into y-slabs (swmhd_ring_step_rk3_bc, SWMHD_OPEN_SOUTH / _NORTH): bits above the
+// topology code 1 in TendArgs::topo_y and HaloBc::topo_y mark a side that is a cut to a neighbouring slab, not a wall.  Reconstructions
+// see the rows next to it as far from any wall (order 5 / centred 4th, no wall branch of the divergence forcing); the boundary-condition
+// fill leaves its halo rows alone (they come from the neighbour).  topo_y == 1 is the whole Bounded direction, both sides walls.
+constexpr int TOPO_OPEN_SOUTH = 2, TOPO_OPEN_NORTH = 4;
+// THE test for "this grid has a wall kernel to run" (topo_y != 0, not == 1: a slab's topo_y carries the open-side bits)
+constexpr bool is_bounded(int topo_x, int topo_y) { return topo_x == 1 || topo_y != 0; }
+
+// Frame of a Bounded grid that the wall kernels recompute after a periodic-formula kernel has run over rows [j0, j1): FRAME_ROWS rows
+// along each y wall that is a real wall (empty ranges along open sides and on a Periodic y direction), and the outermost tile columns
+// along the x walls.  A cell further from a wall has exactly the periodic formulas.
+constexpr int TILE_X = 64, FRAME_ROWS = 8;
+// tile columns of the x-wall frame (TendArgs / OpArgs::edge_cols): the first and the last; the last two where the last one is narrower
+// than 8 columns
+inline int frame_tile_columns(int Nx) {
+    const int ntx = (Nx + TILE_X - 1) / TILE_X, ne = (Nx % TILE_X == 0 || Nx % TILE_X >= 8) ? 2 : 3;
+    return ntx < ne ? ntx : ne;
+}
+struct BoundedFrame {
+    int s0, s1, n0, n1;   // south rows [s0, s1), north rows [n0, n1); s1 <= s0 / n1 <= n0: none
+    bool x_walls;         // the x direction is Bounded: frame_tile_columns() tile columns over rows [j0, j1)
+};
+inline BoundedFrame bounded_frame(int Ny, int j0, int j1, int topo_x, int topo_y) {
+    BoundedFrame f{j0, j0, j1, j1, topo_x == 1};
+    if (topo_y != 0 && !(topo_y & TOPO_OPEN_SOUTH)) f.s1 = j1 < FRAME_ROWS ? j1 : FRAME_ROWS;
+    if (topo_y != 0 && !(topo_y & TOPO_OPEN_NORTH)) f.n0 = j0 > Ny - FRAME_ROWS ? j0 : Ny - FRAME_ROWS;
+    return f;
+}
+
+// ---- launch geometry of the row-marching kernels --------------------------------------------------------------------------
+// One workgroup = a strip of nt - 2*xh output columns x LY rows; the grid is a whole number of rounds of resident workgroups.
+// Folded last strip (fold = 1): where the last strip has at most nt/2 - 2*xh output columns, each of its workgroups runs two
+// half-width sub-strips of nt/2 lanes on two segments, so a segment row costs nstrips - 1/2 workgroups instead of nstrips.
+struct MarchGeometry {
+    int nt;        // threads per workgroup (strip width incl. 2*xh halo lanes)
+    int nstrips, nseg, LY;
+    int wg_per_cu; // resident workgroups per CU the kernel is built for
+    int fold;      // 1: the last strip is folded (nstrips still counts it as one strip)
+    int blocks() const { return fold ? (nstrips - 1) * nseg + (nseg + 1) / 2 : nstrips * nseg; }
+};
+// Compute units of the current device (hipDeviceAttributeMultiprocessorCount; 256 on MI355X), cached per process.
+inline int device_cu_count() {
+    static int cus = 0;
+    if (cus <= 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        cus = n;
+    }
+    return cus;
+}
+// Tuning knobs are read from the environment ONCE per process (not on every launch).
+inline int env_knob(const char *name, int &cache) {   // cache: 0 = not read yet, -1 = unset, > 0 = value
+    if (cache == 0) {
+        const char *e = getenv(name);
+        const int v = e ? atoi(e) : 0;
+        cache = v > 0 ? v : -1;
+    }
+    return cache > 0 ? cache : 0;
+}
+// Share of the workgroup slots an interior launch of the slab driver leaves free for the comm stream's kernels, in 64ths: 3 (4.7 %),
+// and 1 (1.6 %) for slabs of 3072 rows and more -- the boundary work per step is fixed, a long interior launch gives it time enough in
+// few slots, and every slot costs the interior launch its share of the chip (4096 x 4096 ring-of-one step: +1.4-1.9 % over the plain
+// step with 1, +3.7-4.0 % with 3; 4096 x 2048: +4.8-5.2 % vs +4.6-4.7 %; three alternating runs each).  SWMHD_RING_ROOM overrides (tuning).
+inline int leave_room_64ths(int rows) {
+    static int cache = 0;
+    const int v = env_knob("SWMHD_RING_ROOM", cache);
+    return v > 0 ? (v < 32 ? v : 32) : (rows >= 3072 ? 1 : 3);
+}
+// Strip width: the FIRST candidate workgroup size unless a later one covers Nx with at least 5 % fewer lanes (1024 columns: 5 strips x
+// 256 lanes = 1280, but 9 x 128 = 1152).  Rows per segment: the smallest whole number of rounds of resident workgroups
+// (wg_per_cu x CUs slots; ~5 % fewer with leave_room, so that another stream's kernels find room) whose segments are at most
+// 128 rows, but never shorter than ly_min rows.  fold_nt: the workgroup size whose kernel can fold its last strip (0: none); the strip
+// width is chosen first, and folding then only changes how many workgroups a segment row costs.
+inline MarchGeometry march_geometry(int Nx, int rows, int xh, const int *nts, const int *wgs, int ncand, int ly_min, bool leave_room,
+                                    int force_nt, int force_ly, int fold_nt = 0) {
+    MarchGeometry g{};
+    long best = -1;
+    for (int k = 0; k < ncand; ++k) {
+        const int txo = nts[k] - 2 * xh, ns = (Nx + txo - 1) / txo;
+        const long lanes = (long)ns * nts[k];
+        const bool take = force_nt ? nts[k] == force_nt : (best < 0 || lanes * 20 <= best * 19);
+        if (take) { best = lanes; g.nt = nts[k]; g.nstrips = ns; g.wg_per_cu = wgs[k]; }
+    }
+    if (best < 0) { g.nt = nts[0]; g.nstrips = (Nx + nts[0] - 2 * xh - 1) / (nts[0] - 2 * xh); g.wg_per_cu = wgs[0]; }
+    g.fold = fold_nt && g.nt == fold_nt && g.nstrips > 1 && Nx - (g.nstrips - 1) * (g.nt - 2 * xh) <= g.nt / 2 - 2 * xh ? 1 : 0;
+    const int halves = 2 * g.nstrips - g.fold;   // half-workgroups per segment row
+    int slots = device_cu_count() * g.wg_per_cu;
+    if (leave_room) slots -= (slots * leave_room_64ths(rows)) / 64;
+    int LY = 32;
+    for (int k = 1; k <= 64; ++k) {
+        const int ns = (2 * slots * k) / halves;
+        if (ns < 1) continue;
+        const int ly = (rows + ns - 1) / ns;
+        if (ly <= 128) { LY = ly < ly_min ? ly_min : ly; break; }
+    }
+    if (force_ly > 0) LY = force_ly;
+    g.LY = LY;
+    g.nseg = (rows + LY - 1) / LY;
+    return g;
+}
+
+// Workgroups per CU of the conservative marching kernel, per stage variant (MODE: bits at k_tendency_vi_march).  ONE definition for the
+// kernel's __launch_bounds__ and for the geometry that fills the slots it implies.  fp64: the variants of CONS_W3_MODES fit three
+// workgroups of 256 (measurements at k_tendency_cons_march, tendency_march_kernels.inc), the others two; fp32: three throughout.
+constexpr int CONS_W3_MODES = (1 << 7) | (1 << 5) | (1 << 4) | (1 << 9) | (1 << 11);
+constexpr int cons_minwaves(int mode, int elem_size) { return elem_size == 4 ? 3 : (((CONS_W3_MODES >> mode) & 1) ? 3 : 2); }
+
+// Geometry of the marching tendency kernels.  Vector-invariant kernel: <= 168 VGPRs and 0.19 KB of LDS per lane -> 12 waves per
+// CU, i.e. 3 / 6 workgroups of 256 / 128 threads.  Conservative kernel: 2 or 3 workgroups of 256 per CU (cons_minwaves).
+// Knobs (read once): SWMHD_T_LY rows per segment, SWMHD_T_NT workgroup size (128 or 256), SWMHD_T_FOLD=0 no folded last strip (A/B).
+// Folded last strip (fp64 vector-invariant kernel, 256 lanes, last strip <= 122 output columns; tendency_march_kernels.inc): 4096
+// columns run 16 full workgroups and half a folded one per segment row instead of 17 -- LY 90 instead of 92 in one round.
+// Packed-fp32 kernel (tendency_pk_kernels.inc): vector-invariant model, x read with periodic wrapping, even Nx.  256 lanes = 512
+// columns per strip, 504 of them output; 3 workgroups per CU (<= 168 VGPRs, 46 KB LDS).
+inline bool tendency_uses_packed_fp32(int Nx, int formulation, int wrap) {
+    return formulation == 1 && (wrap & 1) && (Nx % 2 == 0) && Nx >= 8;
+}
+inline int tendency_force_ly() {
+    static int cache = 0;
+    return env_knob("SWMHD_T_LY", cache);
+}
+inline MarchGeometry packed_fp32_geometry(int Nx, int rows, int leave_room) {
+    static const int cols[1] = {512}, wgs[1] = {3};   // in columns: 2 per lane, 4 halo columns a side -> 504 output columns per strip
+    MarchGeometry g = march_geometry(Nx, rows, 4, cols, wgs, 1, 6, leave_room != 0, 0, tendency_force_ly());
+    g.nt = 256;
+    return g;
+}
+inline bool tendency_fold_enabled() {
+    static const bool on = [] { const char *e = getenv("SWMHD_T_FOLD"); return !e || atoi(e) != 0; }();
+    return on;
+}
+// fold_ok: the launch may fold its last strip (one row range: the slab driver's two-range launches keep full strips)
+inline MarchGeometry tendency_march_geometry(int Nx, int rows, int formulation, int leave_room, int elem_size, int mode, bool fold_ok) {
+    static int nt_cache = 0;
+    const int force_ly = tendency_force_ly(), force_nt = env_knob("SWMHD_T_NT", nt_cache);
+    if (formulation == 1) {
+        // (384-thread workgroups cover 4096 columns with 3 % fewer lanes -- 11 strips instead of 17 -- but measured 37 % SLOWER on
+        //  MI355X, 1.75 vs 1.275 ms per step: six waves per barrier leave each SIMD too little to overlap; removed after that measurement)
+        static const int nts[2] = {256, 128}, wgs64[2] = {3, 6}, wgs32[2] = {4, 8};   // fp32: <= 128 VGPRs, 4 waves per SIMD
+        const int fold_nt = elem_size == 8 && fold_ok && tendency_fold_enabled() ? 256 : 0;
+        return march_geometry(Nx, rows, 3, nts, elem_size == 8 ? wgs64 : wgs32, 2, 6, leave_room != 0, force_nt, force_ly, fold_nt);
+    }
+    // (128-thread workgroups where they waste >= 5 % fewer lanes in the last strip: 1024 columns = 5 strips of 250 or 9 of 122)
+    const int w = cons_minwaves(mode, elem_size);
+    const int nts[2] = {256, 128}, wgs[2] = {w, 2 * w};
+    return march_geometry(Nx, rows, 3, nts, wgs, 2, 6, leave_room != 0, force_nt, force_ly);
+}
+
+// ---- the plan of one tendency call ------------------------------------------------------------------------------------------------
+constexpr long SW_MARCH_MIN_CELLS = 330000L;
+
+// What the decision depends on: the fields of TendArgs of the same names, plus the build and, for an ensemble, the member count.
+struct TendPlanIn {
+    int Nx, Ny, Hy;
+    long sy;              // 0: no parent known (the geometry query) -- taken to lie below 4 GiB
+    int elem_size;
+    int j0, j1, j0b, j1b;
+    int formulation;
+    bool strict;
+    int kernel_variant, wrap, leave_room, topo_x, topo_y, edge_cols;
+    int fuse, first, store_G, gm_prev, anchor;
+    int members;          // > 0: an ensemble stage (LDS-tiled kernel, one row range, no frame); 0: a single grid
+};
+enum class TendKernel { TILE_RY1, TILE_RY2, TILE_BOUNDED, MARCH, MARCH_PACKED };   // 64 x 4 tiles | 64 x 8 | 64 x 8 wall kernel | row-marching | packed fp32
+// One launch: the kernel family, its grid, and the arguments it runs with where they differ from the caller's.
+struct TendLaunch {
+    TendKernel kernel;
+    int ntx, nty;             // tile kernels: tile columns, tile rows (both row ranges)
+    MarchGeometry mg;         // marching kernels (mg.fold becomes TendArgs::fold_last)
+    int mode, drop_G;         // marching kernels: compiled stage variant (MODE bits at k_tendency_vi_march); its G stores are to be dropped
+    int j0, j1, j0b, j1b;     // row ranges of this launch
+    int topo_x, topo_y;       // topology the kernel sees (0, 0 for the periodic body of a hybrid launch)
+    int edge_cols;
+    bool tile() const { return kernel != TendKernel::MARCH && kernel != TendKernel::MARCH_PACKED; }
+};
+struct TendPlan {
+    int n = 0;
+    TendLaunch e[3];
+};
+
+// Compiled stage variant of the marching kernels for a stage, and whether that variant stores a G the stage must not (drop_G: the
+// stores are issued with an out-of-range offset).
+inline int march_stage_mode(const TendPlanIn &a, int &drop_G) {
+    int mode = (a.fuse ? 1 : 0) | ((a.fuse && !a.first) ? 2 : 0) | ((a.store_G || !a.fuse) ? 4 : 0) | (a.anchor ? 8 : 0);
+    const bool cons64 = a.formulation == 0 && a.elem_size == 8;
+    drop_G = 0;
+    // The previous-state operand (gm_prev) lives in the stage-2 variant (coefficient form).  Conservative model: the last RK3 stage
+    // (MODE 3) runs on the stage-2 variant (3 workgroups per CU, no scratch) with its G stores dropped by the hardware: 4096^2 step
+    // 1.39-1.40 -> 1.36 ms.  (The same substitution bought nothing for the vector-invariant kernel, whose MODE 3 already has its third
+    // workgroup: 398-403 vs 403-408 us.)
+    if (mode == 3 && (a.gm_prev || (cons64 && cons_minwaves(7, 8) > cons_minwaves(3, 8)))) { mode = 7; drop_G = 1; }
+    // ... and the first stage without a G store (MODE 1, two workgroups per CU) on the MODE-5 variant, likewise
+    if (mode == 1 && cons64 && cons_minwaves(5, 8) > cons_minwaves(1, 8)) { mode = 5; drop_G = 1; }
+    return mode;
+}
+
+inline TendLaunch tile_launch(TendKernel k, int ntx, int j0, int j1, int j0b, int j1b, int topo_x, int topo_y, int edge_cols) {
+    const int ty = k == TendKernel::TILE_RY1 ? 4 : 8, rows_b = j1b > j0b ? j1b - j0b : 0;
+    TendLaunch l{};
+    l.kernel = k; l.ntx = ntx; l.nty = (j1 - j0 + ty - 1) / ty + (rows_b + ty - 1) / ty;
+    l.j0 = j0; l.j1 = j1; l.j0b = j0b; l.j1b = j1b; l.topo_x = topo_x; l.topo_y = topo_y; l.edge_cols = edge_cols;
+    return l;
+}
+
+// The launches of one tendency call, in order (none: nothing to compute).
+// Kernel choice, fast builds: the row-marching kernels overtake the tile kernel between 512^2 and 640^2 cells for both formulations
+// (tools/crossover.py: 640^2 82 vs 111 us/step, 1024^2 119 vs 184, 1280^2 161 vs 276; at 512^2 the tile kernel with its fused halo fill
+// wins 60 : 80); small grids and the 3-row boundary strips of the overlapped multi-GPU step take the tile kernel.  kernel_variant 1 / 2
+// force tile / marching.  Strict builds and ensembles have the tile kernel only.
+inline TendPlan plan_tendency(TendPlanIn a) {
+    TendPlan p;
+    if (a.j1b <= a.j0b) a.j0b = a.j1b = 0;
+    if (a.j1 <= a.j0 && a.j1b > a.j0b) { a.j0 = a.j0b; a.j1 = a.j1b; a.j0b = a.j1b = 0; }   // an empty first range: the second alone
+    if (a.Nx <= 0 || a.j1 <= a.j0) return p;
+    const bool two = a.j1b > a.j0b, bnd = is_bounded(a.topo_x, a.topo_y), fast = !a.strict && a.members <= 0;
+    const int rows = a.j1 - a.j0 + (a.j1b - a.j0b);
+    const bool big = (long)a.Nx * rows >= SW_MARCH_MIN_CELLS;
+    const int ntx = a.edge_cols ? frame_tile_columns(a.Nx) : (a.Nx + TILE_X - 1) / TILE_X;
+    // (the marching kernels address memory with 32-bit byte offsets: fields of 4 GiB or more stay on the tile kernel)
+    const long parent_bytes = (long)(a.Ny + 2 * a.Hy) * a.sy * a.elem_size, row_bytes = a.sy * a.elem_size, lim32 = (1L << 32) - 64;
+    const bool fits32 = parent_bytes < lim32;
+    auto march = [&](int topo_x, int topo_y) {
+        TendLaunch l{};
+        const bool packed = a.elem_size == 4 && tendency_uses_packed_fp32(a.Nx, a.formulation, a.wrap);   // two columns per lane
+        l.kernel = packed ? TendKernel::MARCH_PACKED : TendKernel::MARCH;
+        l.mode = march_stage_mode(a, l.drop_G);
+        // (a folded workgroup's rows without an output store one row beyond the parent: that offset must fit 32 bits too)
+        const bool fold_ok = !two && parent_bytes + row_bytes < lim32;
+        // Segments may be as short as 6 rows (as many warm-up rows as output rows): on mid-size grids filling the chip matters more
+        // than the warm-up overhead (1024^2: 42 us/stage at LY = 7, 54 at 16).
+        l.mg = packed ? packed_fp32_geometry(a.Nx, rows, a.leave_room)
+                      : tendency_march_geometry(a.Nx, rows, a.formulation, a.leave_room, a.elem_size, l.mode, fold_ok);
+        // (two ranges: the segments of the second range follow those of the first, same LY.  One 9-12-row segment per zone instead of
+        //  two 6-row ones -- a single round of workgroups in the slots the interior launch leaves free -- measured slower: 4096 x 512
+        //  ring-of-one step +22 % over plain instead of +11 %)
+        if (two) l.mg.nseg = (a.j1 - a.j0 + l.mg.LY - 1) / l.mg.LY + (a.j1b - a.j0b + l.mg.LY - 1) / l.mg.LY;
+        l.j0 = a.j0; l.j1 = a.j1; l.j0b = a.j0b; l.j1b = a.j1b; l.topo_x = topo_x; l.topo_y = topo_y; l.edge_cols = a.edge_cols;
+        return l;
+    };
+    if (fast && !bnd && fits32 && (a.kernel_variant == 2 || (a.kernel_variant == 0 && big))) {
+        p.e[p.n++] = march(0, 0);
+        return p;
+    }
+    // Large Bounded grids: a cell further than a few cells from a wall has exactly the periodic formulas (every reconstruction at full
+    // order, no wall branch of the Lorentz fluxes).  So the row-marching kernel computes ALL rows as if the grid were periodic, reading
+    // the boundary-condition halos from memory, and the LDS-tiled Bounded kernel then overwrites the frame (bounded_frame; fused
+    // substep included: all launches compute from the same old state).  A y-slab's cut side has no frame rows (TOPO_OPEN_*).
+    // 4096^2 (Bounded, Bounded), RK3 step incl. the boundary-condition fills: 3.12 -> 1.49 ms (vector-invariant), 4.34 -> 1.67
+    // (conservative); periodic 1.31 / 1.36 in the same call (tools/time_bounded.py).
+    if (fast && bnd && !two && !a.edge_cols && fits32 && a.kernel_variant == 0 && big && a.Nx >= 4 * TILE_X && a.Ny >= 48) {
+        p.e[p.n++] = march(0, 0);
+        BoundedFrame f = bounded_frame(a.Ny, a.j0, a.j1, a.topo_x, a.topo_y);
+        if (f.s1 <= f.s0) { f.s0 = f.n0; f.s1 = f.n1; f.n0 = f.n1 = 0; }
+        if (f.n1 <= f.n0) f.n0 = f.n1 = 0;
+        if (f.s1 > f.s0) p.e[p.n++] = tile_launch(TendKernel::TILE_BOUNDED, ntx, f.s0, f.s1, f.n0, f.n1, a.topo_x, a.topo_y, 0);
+        if (f.x_walls) p.e[p.n++] = tile_launch(TendKernel::TILE_BOUNDED, frame_tile_columns(a.Nx), a.j0, a.j1, 0, 0, a.topo_x, a.topo_y, 1);
+        return p;
+    }
+    // Tile height.  Bounded grids: the wall kernel, 64 x 8.  Small grids of fast builds (the reference's own 64^2 .. 128^2,
+    // SWMHD_example.jl:11, up to where the marching kernels take over) and thin strips: there are at most a few tiles per CU, so the
+    // launch lasts about as long as ONE tile takes; one output row per lane (64 x 4 tiles) instead of two halves the dependent
+    // arithmetic of that tile (64^2 .. 256^2: 41 -> 27 us per RK3 step, 512^2: 60 -> 52).  Larger grids forced onto the tile kernel
+    // keep 64 x 8 tiles (less halo per cell), as do strict builds.  An ensemble's members take the tile a single model of the member's
+    // size would take; SWMHD_ENS_RY = 1 | 2 forces the height for periodic members (read once; measurement only).
+    TendKernel k = bnd ? TendKernel::TILE_BOUNDED : (!a.strict && !big ? TendKernel::TILE_RY1 : TendKernel::TILE_RY2);
+    if (a.members > 0 && !bnd) {
+        static int ry_cache = 0;
+        const int force_ry = env_knob("SWMHD_ENS_RY", ry_cache);
+        if (force_ry == 1 || force_ry == 2) k = force_ry == 1 ? TendKernel::TILE_RY1 : TendKernel::TILE_RY2;
+    }
+    p.e[p.n++] = tile_launch(k, ntx, a.j0, a.j1, a.j0b, a.j1b, a.topo_x, a.topo_y, a.edge_cols);
+    return p;
+}
+
+// swmhd_tendency_launch_geometry: the first launch of the plan of a periodic single-range stage of MODE 7 (a fused middle stage that
+// stores G) on a parent below 4 GiB.  out: kind (1 LDS-tiled, 2 row-marching, 3 packed fp32), threads, strips | tile columns, segments |
+// tile rows, rows per segment | tile, workgroups per CU (0: tiles), halo lanes a side, CUs.
+inline int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, bool strict, int kernel_variant, int leave_room,
+                                    int wrap, int out[8]) {
+    TendPlanIn in{};
+    in.Nx = Nx; in.Ny = rows; in.elem_size = elem_size; in.j1 = rows; in.formulation = formulation; in.strict = strict;
+    in.kernel_variant = kernel_variant; in.wrap = wrap; in.leave_room = leave_room;
+    in.fuse = 1; in.store_G = 1;
+    const TendPlan p = plan_tendency(in);
+    if (p.n < 1) return 1;
+    const TendLaunch &l = p.e[0];
+    if (l.tile()) {
+        out[0] = 1; out[1] = 256; out[2] = l.ntx; out[3] = l.nty; out[4] = l.kernel == TendKernel::TILE_RY1 ? 4 : 8; out[5] = 0; out[6] = 3;
+    } else {
+        const bool packed = l.kernel == TendKernel::MARCH_PACKED;
+        out[0] = packed ? 3 : 2; out[1] = l.mg.nt; out[2] = l.mg.nstrips; out[3] = l.mg.nseg; out[4] = l.mg.LY; out[5] = l.mg.wg_per_cu;
+        out[6] = packed ? 2 : 3;
+    }
+    out[7] = device_cu_count();
+    return 0;
+}
+
+}  // namespace swmhd

@@ -190,8 +190,8 @@ hipError_t LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)(const OpArgs<T> &
     if (ntx <= 0 || nty <= 0) return hipSuccess;
 #if !SWMHD_STRICT
     // (cross-over with the tile kernel near 1000^2: 1024^2 17 vs 20 us, 1448^2 27 vs 41 us; the Jacobian form's is at ~2 Mcell)
-    if ((a.kernel_variant == 2 || (a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 900000L)) && a.topo_x == 0 &&
-        a.topo_y == 0) {   // the marching kernel implements the periodic branch only
+    if ((a.kernel_variant == 2 || (a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 900000L)) &&
+        !is_bounded(a.topo_x, a.topo_y)) {   // the marching kernel implements the periodic branch only
         constexpr int NT = 256, PF = 2, TXO = NT - 6;
         const int rows = a.j1 - a.j0, nstrips = (a.Nx + TXO - 1) / TXO;
         const int LY = march_rows_per_segment(rows, nstrips, 5), nseg = (rows + LY - 1) / LY;
@@ -199,34 +199,29 @@ hipError_t LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)(const OpArgs<T> &
         return hipGetLastError();
     }
     // Large Bounded grids: the marching kernel (periodic branch) over every row, then the LDS-tiled kernel with the reference's wall
-    // branches over the frame of cells near the walls (8 rows along y walls, the outer tile columns along x walls) -- the hybrid
-    // launch of the fused tendency kernels (tendency_tile_kernels.inc)
-    if ((a.topo_x == 1 || a.topo_y == 1) && !a.edge_cols && a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 900000L && a.Nx >= 4 * TX &&
+    // branches over the frame of cells near the walls (bounded_frame, launch_plan.hpp: the frame of the fused tendency kernels' hybrid
+    // launch); the two y strips are two launches here
+    if (is_bounded(a.topo_x, a.topo_y) && !a.edge_cols && a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 900000L && a.Nx >= 4 * TX &&
         a.Ny >= 48) {
-        constexpr int FW = 8;
+        const BoundedFrame fr = bounded_frame(a.Ny, a.j0, a.j1, a.topo_x, a.topo_y);
         OpArgs<T> p = a;
         p.topo_x = p.topo_y = 0;
         hipError_t e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(p, s);
         if (e != hipSuccess) return e;
         OpArgs<T> f = a;
         f.kernel_variant = 1;
-        if (a.topo_y == 1) {
-            f.j0 = a.j0; f.j1 = a.j1 < FW ? a.j1 : FW;
-            if (f.j1 > f.j0 && (e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
-            f.j0 = a.j0 > a.Ny - FW ? a.j0 : a.Ny - FW; f.j1 = a.j1;
-            if (f.j1 > f.j0 && (e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
-        }
-        if (a.topo_x == 1) {
+        f.j0 = fr.s0; f.j1 = fr.s1;
+        if (f.j1 > f.j0 && (e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
+        f.j0 = fr.n0; f.j1 = fr.n1;
+        if (f.j1 > f.j0 && (e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
+        if (fr.x_walls) {
             f.j0 = a.j0; f.j1 = a.j1; f.edge_cols = 1;
             if ((e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
         }
         return hipSuccess;
     }
 #endif
-    if (a.edge_cols) {   // first and last tile column; the last two where the last one is narrower than 8 columns
-        const int ne = (a.Nx % TX == 0 || a.Nx % TX >= 8) ? 2 : 3;
-        ntx = ntx < ne ? ntx : ne;
-    }
+    if (a.edge_cols) ntx = frame_tile_columns(a.Nx);
     hipLaunchKernelGGL((k_lorentz_divergence<T, TX, TYB, RY>), dim3(ntx * nty), dim3(TX, TYB), 0, s, a, ntx, nty);
     return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 // global state; every call only enqueues work on the caller's stream.
 #include "../../include/swmhd.h"
 #include "common.hpp"
+#include "launch_plan.hpp"
 #include <math.h>
 
 using namespace swmhd;
@@ -389,7 +390,7 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
     if (!out || Nx <= 0 || rows <= 0 || (elem_size != 4 && elem_size != 8)) return SWMHD_EINVAL;
     if (formulation != SWMHD_CONSERVATIVE && formulation != SWMHD_VECTOR_INVARIANT) return SWMHD_EINVAL;
     const int variant = (flags & SWMHD_TILE_KERNEL) ? 1 : ((flags & SWMHD_MARCH_KERNEL) ? 2 : 0);
-    return tendency_launch_geometry(Nx, rows, formulation, elem_size, (flags & SWMHD_STRICT) ? 1 : variant, (flags & SWMHD_LEAVE_ROOM) ? 1 : 0,
+    return tendency_launch_geometry(Nx, rows, formulation, elem_size, (flags & SWMHD_STRICT) != 0, variant, (flags & SWMHD_LEAVE_ROOM) ? 1 : 0,
                                     ((flags & SWMHD_WRAP_X) ? 1 : 0) | ((flags & SWMHD_WRAP_Y) ? 2 : 0), out);
 }
 

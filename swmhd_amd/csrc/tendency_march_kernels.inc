@@ -344,8 +344,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
 // all fused stages: 1.504 / 0.747 -- a third workgroup pays only where (almost) nothing spills.  The anchor variants (MODE 9, 11) need 0
 // bytes of scratch at two workgroups and 12 at three; 4096^2 step, same call, alternating processes (profiles/rk3_anchor/README.md): two
 // workgroups 1.435 ms (stages 454 / 485 / 480 us), three 1.365 ms (445 / 455 / 451 us) -- three it is.
-constexpr int CONS_W3_MODES = (1 << 7) | (1 << 5) | (1 << 4) | (1 << 9) | (1 << 11);
-constexpr int cons_minwaves(int mode, int elem_size) { return elem_size == 4 ? 3 : (((CONS_W3_MODES >> mode) & 1) ? 3 : 2); }
+// (CONS_W3_MODES and cons_minwaves are defined in launch_plan.hpp: the launch geometry reads the same table)
 template <typename T, int LOR, int NT, int MODE>   // MODE as in k_tendency_vi_march
 __global__ __launch_bounds__(NT, cons_minwaves(MODE, (int)sizeof(T))) void k_tendency_cons_march(TendArgs<T> a, int nstrips, int nseg, int LY) {
     constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0, ANCHOR = (MODE & 8) != 0;
