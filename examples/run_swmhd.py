@@ -9,6 +9,8 @@ g = 9.81, f = 1, RK3, A = 0.5|y| ("uniform B_x") or the two Gaussians, h = 1, th
 (multiplied by h for the conservative variables), dt = 0.01, stop time 30.  Every --every iterations one progress line like the
 reference's (SWMHD_example.jl:47-61: time, iteration, max|u|, max|A|, min h, wall time) and one row of the energies the reference
 sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the fields incl. halos as .npy (the JLD2 writer's role, :80-84).
+--frames T collects the reference's output frames on the device (swmhd_amd.FieldTimeSeries: the fields (u, v, A, s) every T time units,
+:80-84, or those of --frame-fields out of u v h A s B_x B_y, as --frame-dtype f32|f64) and writes them to <out>/frames.npz at the end.
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
@@ -43,6 +45,9 @@ def main():
     ap.add_argument("--every", type=int, default=100, help="iterations between progress lines / energy rows")
     ap.add_argument("--energies", default=None, help="CSV file for (time, KE, ME, PE, total)")
     ap.add_argument("--dump-every", type=float, default=0.0, help="model time between field dumps (0 = none)")
+    ap.add_argument("--frames", type=float, default=0.0, help="model time between output frames (0 = none); written to <out>/frames.npz")
+    ap.add_argument("--frame-fields", default="u,v,A,s", help="comma-separated fields of a frame: u v h A s B_x B_y")
+    ap.add_argument("--frame-dtype", choices=["f32", "f64"], default="f32")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -85,16 +90,27 @@ def main():
 
     report(0.0)
     e0 = rows[0][4]
+    series, fevery = frame_writer(a, model, nsteps)
     model.time_step(a.dt)
+    if fevery == 1:
+        series.write()
     model.capture_graph(a.dt)
     next_dump = a.dump_every
     t_start = time.perf_counter()
+    t0 = None
     while model.iteration < nsteps:
+        t0 = time.perf_counter() if t0 is None else t0      # wall time of one progress interval
         n = min(a.every - model.iteration % a.every, nsteps - model.iteration)
-        t0 = time.perf_counter()
+        if fevery:
+            n = min(n, fevery - model.iteration % fevery)
         model.time_steps(n, a.dt)
+        if fevery and model.iteration % fevery == 0:
+            series.write(time=model.iteration * a.dt)         # one launch, no synchronisation
+        if model.iteration % a.every != 0 and model.iteration != nsteps:
+            continue
         model.synchronize()
         report(time.perf_counter() - t0)
+        t0 = None
         if a.dump_every > 0 and model.clock_time + 1e-12 >= next_dump:
             os.makedirs(a.out, exist_ok=True)
             model.save_checkpoint(os.path.join(a.out, f"fields_{model.iteration:07d}"))
@@ -102,9 +118,31 @@ def main():
     total = time.perf_counter() - t_start
     print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations, {N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); "
           f"energy drift abs(E - E0) * 100 = {abs(rows[-1][4] - e0) * 100:.4f}")
+    save_frames(a, series)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
+
+
+def frame_writer(a, model, nsteps):
+    """--frames: (FieldTimeSeries, steps between frames), or (None, 0)"""
+    if a.frames <= 0:
+        return None, 0
+    import torch
+    import swmhd_amd as S
+    sched = S.TimeInterval(a.frames)
+    every = sched.steps(a.dt)
+    series = S.FieldTimeSeries(model, names=tuple(n.strip() for n in a.frame_fields.split(",") if n.strip()), schedule=sched,
+                               capacity=nsteps // every + 1, array_type=torch.float32 if a.frame_dtype == "f32" else torch.float64)
+    series.write()          # the initial state, as Oceananigans' writers do at iteration 0
+    return series, every
+
+
+def save_frames(a, series):
+    if series is not None:
+        os.makedirs(a.out, exist_ok=True)
+        series.save(os.path.join(a.out, "frames.npz"))
+        print(f"{len(series)} frames of ({', '.join(series.names)}) -> {os.path.join(a.out, 'frames.npz')}")
 
 
 def run_ensemble(a):
@@ -142,19 +180,31 @@ def run_ensemble(a):
 
     report(0.0)
     e0 = [r[5] for r in rows]
+    series, fevery = frame_writer(a, ens, nsteps)
     ens.time_step(a.dt)
+    if fevery == 1:
+        series.write()
     ens.capture_graph(a.dt)
     t_start = time.perf_counter()
+    t0 = None
     while ens.iteration < nsteps:
+        t0 = time.perf_counter() if t0 is None else t0      # wall time of one progress interval
         n = min(a.every - ens.iteration % a.every, nsteps - ens.iteration)
-        t0 = time.perf_counter()
+        if fevery:
+            n = min(n, fevery - ens.iteration % fevery)
         ens.time_steps(n, a.dt)
+        if fevery and ens.iteration % fevery == 0:
+            series.write(time=ens.iteration * a.dt)           # all members in one launch, no synchronisation
+        if ens.iteration % a.every != 0 and ens.iteration != nsteps:
+            continue
         ens.synchronize()
         report(time.perf_counter() - t0)
+        t0 = None
     total = time.perf_counter() - t_start
     drift = ", ".join(f"{abs(rows[-len(amps) + m][5] - e0[m]) * 100:.4f}" for m in range(len(amps)))
     print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations of {len(amps)} members, "
           f"{len(amps) * N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); energy drift abs(E - E0) * 100 per member = {drift}")
+    save_frames(a, series)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["member", "time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)

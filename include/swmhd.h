@@ -560,6 +560,59 @@ int swmhd_ensemble_step_rk3_bc_f32(float *const *q, float *const *q_alt, float *
                                    float dx, float dy, float g, float f, int formulation, int lorentz, float dt, int nsteps,
                                    const float *gradient, int flags, int *state_in_alt, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Output frames: the fields an output writer stores, made on the device in ONE pass over the four prognostic parents -- derived
+ * fields included, halo-stripped, in the writer's element type.  The reference writes (u, v, A, s), s = sqrt(u^2 + v^2), every 0.1
+ * time units (JLD2OutputWriter, SWMHD_example.jl:67-68,80-84; divergence_sw_mhd.jl:64-66,75-82 with u = uh / h, v = vh / h) and looks
+ * at B_x = -dA/dy / h, B_y = dA/dx / h (MHD_visualize.jl:55-65).  Definitions (operand-location rule of swmhd_diagnostics: first
+ * operand's location, the second interpolated there, a divisor field interpolated; all arithmetic in double):
+ *   SWMHD_OUT_U     @(f,c)  q1 (vector-invariant) | q1 / ℑxᶠh (conservative)        SWMHD_OUT_H, SWMHD_OUT_A  @(c,c)  copies
+ *   SWMHD_OUT_V     @(c,f)  q2                    | q2 / ℑyᶠh
+ *   SWMHD_OUT_SPEED @(f,c)  sqrt(U² + ℑxyᶠᶜ(V²))  -- Σ ½ h ℑxᶜ(s²) Δx Δy is the kinetic energy of the Jacobian driver
+ *   SWMHD_OUT_BX    @(c,f)  −((A(j) − A(j−1)) / Δy) / ℑyᶠh        SWMHD_OUT_BY  @(f,c)  ((A(i) − A(i−1)) / Δx) / ℑxᶠh
+ * Points written: i = 1..Nx, rows j_begin+1..j_end, for every field, Bounded directions included (the far-wall line of a face field is a
+ * boundary value, not part of a frame).  The frame is compact: field number k of `which` (counting set bits from bit 0) starts at
+ * out + k * out_stride_f, its row j (0-based) at + (j - j_begin) * out_stride_y, x contiguous -- strides in ELEMENTS of out_elem_size
+ * bytes (4: float, 8: double; values are computed in double and rounded once).  out_stride_y >= Nx, out_stride_f >= (j_end - j_begin)
+ * * out_stride_y.  Reach: one cell; needs halo >= 1, filled (SWMHD_EHALO) -- except that with SWMHD_WRAP_X / SWMHD_WRAP_Y the kernel reads
+ * (x mod Nx, y mod Ny) instead of the halo cell of that direction, as the tendency kernels do: on a periodic grid a frame is one launch on
+ * the stale halos that swmhd_step_rk3 with the WRAP flags leaves.  WRAP on a Bounded direction is the caller's error.  flags: only those two.
+ * One launch, enqueue-only; an empty row range enqueues nothing.
+ *   SWMHD_EINVAL  null pointer, bad extents / spacing / formulation / rows, `which` empty or with unknown bits, out_elem_size not 4 or 8,
+ *                 a stride smaller than the compact extent, unknown flags; ensemble: members out of range, stride_m < (Ny+2Hy) stride_y,
+ *                 out_stride_m < (number of fields) * out_stride_f.   Every check precedes the first HIP call.
+ * Ensemble form: all members in one launch, member m's parents at ptr + m * stride_m, its frame at out + m * out_stride_m.
+ * Tolerances: none -- the object is compiled without FMA contraction and with IEEE divide and sqrt, so every value is bitwise that of
+ *   the same expression evaluated in IEEE double in the order written above (tests/output_cases.py is that restatement in numpy;
+ *   tests/test_output_gpu.py compares bitwise, float frames against the restatement rounded to float).
+ * ---------------------------------------------------------------------------------------------- */
+#define SWMHD_OUT_U 1
+#define SWMHD_OUT_V 2
+#define SWMHD_OUT_H 4
+#define SWMHD_OUT_A 8
+#define SWMHD_OUT_SPEED 16
+#define SWMHD_OUT_BX 32
+#define SWMHD_OUT_BY 64
+#define SWMHD_OUT_ALL 127
+int swmhd_output_fields_f64(const double *q1, const double *q2, const double *h, const double *A,
+                            int Nx, int Ny, int Hx, int Hy, int64_t stride_y, double dx, double dy, int formulation,
+                            int j_begin, int j_end, int which, void *out, int out_elem_size,
+                            int64_t out_stride_y, int64_t out_stride_f, int flags, void *stream);
+int swmhd_output_fields_f32(const float *q1, const float *q2, const float *h, const float *A,
+                            int Nx, int Ny, int Hx, int Hy, int64_t stride_y, float dx, float dy, int formulation,
+                            int j_begin, int j_end, int which, void *out, int out_elem_size,
+                            int64_t out_stride_y, int64_t out_stride_f, int flags, void *stream);
+int swmhd_ensemble_output_fields_f64(const double *q1, const double *q2, const double *h, const double *A,
+                                     int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                     double dx, double dy, int formulation, int j_begin, int j_end, int which,
+                                     void *out, int out_elem_size, int64_t out_stride_y, int64_t out_stride_f,
+                                     int64_t out_stride_m, int flags, void *stream);
+int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const float *h, const float *A,
+                                     int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                     float dx, float dy, int formulation, int j_begin, int j_end, int which,
+                                     void *out, int out_elem_size, int64_t out_stride_y, int64_t out_stride_f,
+                                     int64_t out_stride_m, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

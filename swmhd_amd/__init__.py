@@ -10,8 +10,9 @@ from .operators import lorentz_force_func, div_lorentz
 from .model import ShallowWaterModel, loopback_rings, VectorInvariantFormulation, ConservativeFormulation
 from .distributed import SlabDecomposition, exchange_y_halos
 from .ensemble import ShallowWaterEnsemble, BoundedShallowWaterEnsemble
+from .output import FieldTimeSeries, TimeInterval, IterationInterval, run
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
            "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble",
-           "BoundedShallowWaterEnsemble", "_lib"]
+           "BoundedShallowWaterEnsemble", "FieldTimeSeries", "TimeInterval", "IterationInterval", "run", "_lib"]

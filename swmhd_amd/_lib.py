@@ -21,6 +21,8 @@ KERNEL_FLAGS = {None: 0, "auto": 0, "tile": 2, "march": 4}
 PERIODIC, BOUNDED = 0, 1
 HALO_X, HALO_Y = 1, 2
 DIAG_NOUT, DIAG_WORKSPACE = 7, 1024 * 7
+# SWMHD_OUT_*: the output fields of swmhd_output_fields_*, by the names of the reference's writer, in bit (= frame) order
+OUT_BITS = {"u": 1, "v": 2, "h": 4, "A": 8, "s": 16, "B_x": 32, "B_y": 64}
 ENSEMBLE_MAX_MEMBERS = 65535
 
 
@@ -124,6 +126,12 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_fill_halo_walls_{sfx}")
         f.argtypes = [C.POINTER(p), i, i, i, i, i, i64, i, i, i, i, p, ft, ft, p]
         f.restype = i
+        f = getattr(lib, f"swmhd_output_fields_{sfx}")
+        f.argtypes = [p, p, p, p, i, i, i, i, i64, ft, ft, i, i, i, i, p, i, i64, i64, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_output_fields_{sfx}")
+        f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, i, i, i, p, i, i64, i64, i64, i, p]
+        f.restype = i
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
     lib.swmhd_tendency_launch_geometry.restype = i
     lib.swmhd_ring_available.argtypes = [C.c_char_p]
@@ -154,7 +162,8 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "lorentz_jacobian", "lorentz_jacobian_rows", "lorentz_divergence", "lorentz_divergence_rows",
         "fill_halo", "fill_halo_periodic", "fill_halo_periodic_multi", "tendencies", "tendencies_rk3", "rk3_substep", "step_rk3", "diagnostics",
         "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
-        "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc", "fill_halo_walls", "ring_exchange_y_sides", "ring_step_rk3_bc")] + [
+        "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc", "fill_halo_walls", "ring_exchange_y_sides", "ring_step_rk3_bc",
+        "output_fields", "ensemble_output_fields")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

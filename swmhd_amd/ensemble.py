@@ -216,6 +216,13 @@ class ShallowWaterEnsemble:
                             max_abs_u=v[3], max_abs_v=v[4], max_abs_A=v[5], min_h=v[6]))
         return res
 
+    # --- output frames of all members in one launch (swmhd_ensemble_output_fields_*) ---------------------------------
+    def output_fields(self, names=("u", "v", "A", "s"), out=None, array_type=torch.float32):
+        """ShallowWaterModel.output_fields for every member: the device tensor (members, len(names), Ny, Nx); member m of it is
+        bitwise member(m).output_fields(...).  One launch, no host synchronisation."""
+        from .output import enqueue_frame
+        return enqueue_frame(self, names, out, array_type)
+
     # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
     def member(self, m):
         """A ShallowWaterModel holding a copy of member m (state with halos, G-, clock and iteration)."""

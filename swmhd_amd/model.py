@@ -500,6 +500,15 @@ class ShallowWaterModel:
         return dict(kinetic_energy=v[0], magnetic_energy=v[1], potential_energy=v[2], total_energy=v[0] + v[1] + v[2],
                     max_abs_u=v[3], max_abs_v=v[4], max_abs_A=v[5], min_h=v[6])
 
+    # --- output frames (the reference's field writer, SWMHD_example.jl:80-84): one launch, no host synchronisation -------
+    def output_fields(self, names=("u", "v", "A", "s"), out=None, array_type=torch.float32):
+        """Enqueue one frame of the current state: the device tensor (len(names), Ny, Nx) of the named fields -- u v h A s B_x B_y,
+        s = sqrt(u^2 + v^2), B = (-dA/dy, dA/dx) / h (swmhd_output_fields_* in include/swmhd.h) -- halo-stripped, in `array_type` (or
+        into `out`, float32 or float64 of that shape).  On a y-slab: this rank's rows.  Reads the periodic images where the step leaves
+        the halos stale, so no halo fill runs in front of it.  See swmhd_amd.output for the writer (FieldTimeSeries, run)."""
+        from .output import enqueue_frame
+        return enqueue_frame(self, names, out, array_type)
+
     # --- checkpoint: prognostic fields with halos + G⁻ + clock, one .npz per rank ---------------------------------
     def save_checkpoint(self, path):
         import numpy as np

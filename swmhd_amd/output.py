@@ -1,0 +1,213 @@
+"""Output frames and the writer that collects them on the device.
+
+The reference's run loop does three things per iteration: it steps the model, writes the energies, and every 0.1 time units writes
+the FIELDS (u, v, A, s), s = sqrt(u^2 + v^2):
+    JLD2OutputWriter(model, (; u, v, A = model.tracers.A, s), schedule = TimeInterval(0.1))   jacobian_formulation/SWMHD_example.jl:67-68,80-84
+    the same with u = uh / h, v = vh / h                                                      divergence_formulation/divergence_sw_mhd.jl:64-66,75-82
+Its movies are made of those frames, and MHD_visualize.jl:55-65 looks at B_x = -dA/dy / h, B_y = dA/dx / h.
+
+`output_fields` (a method of ShallowWaterModel and of the ensembles) enqueues ONE kernel (swmhd_output_fields_*, include/swmhd.h) that
+writes the selected fields -- derived ones included, halo-stripped, in the writer's element type, for all members of an ensemble --
+into a device tensor, without a host synchronisation.  FieldTimeSeries + run() are the writer and the run loop around it.  File
+formats and plotting stay out of scope: `FieldTimeSeries.save` writes one .npz.
+"""
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib
+from .fields import _stream_ptr
+
+DEFAULT_NAMES = ("u", "v", "A", "s")    # the reference's writer
+_ELEM = {torch.float32: 4, torch.float64: 8}
+
+
+def _runs(names):
+    """The frame's fields as launches: the kernel writes the fields of a mask in bit order (u v h A s B_x B_y), so `names` is cut into
+    runs that ascend in that order -- one launch for the default frame, and any order or repetition of names is honoured."""
+    runs = []
+    for n in names:
+        if n not in _lib.OUT_BITS:
+            raise _lib.SwmhdError(f"output field {n!r}: one of {' '.join(_lib.OUT_BITS)} (velocities u, v also for the conservative model)")
+        bit = _lib.OUT_BITS[n]
+        if runs and bit > runs[-1][-1]:
+            runs[-1].append(bit)
+        else:
+            runs.append([bit])
+    if not runs:
+        raise _lib.SwmhdError("output_fields: no field names")
+    return runs
+
+
+def frame_shape(model, names):
+    g, members = model.grid, getattr(model, "members", None)
+    return ((members,) if members is not None else ()) + (len(names), g.Ny, g.Nx)
+
+
+def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32):
+    """ShallowWaterModel.output_fields / ShallowWaterEnsemble.output_fields: see there."""
+    names = tuple(names)
+    runs = _runs(names)
+    ens = getattr(model, "members", None) is not None
+    g = model.grid
+    if ens:
+        q = model._state                  # (whichever set of tensors is the state NOW: the ping-pong roles flip every stage)
+        ptrs, sy, dev = [t.data_ptr() for t in q], q[0].stride(1), q[0].device
+    else:
+        model._join()                     # a ring exchange of this state may still be in flight
+        q = model._raw_fields
+        ptrs, sy, dev = [f.ptr for f in q], q[0].stride_y, q[0].data.device
+    shape = frame_shape(model, names)
+    if out is None:
+        if array_type not in _ELEM:
+            raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
+        out = torch.empty(shape, dtype=array_type, device=dev)
+    elif not (out.is_cuda and out.dtype in _ELEM and tuple(out.shape) == shape and out.stride(-1) == 1):
+        raise _lib.SwmhdError(f"output_fields: out must be a float32 / float64 CUDA tensor of shape {shape} with unit stride in x")
+    # The model steps with SWMHD_WRAP_* exactly where its halos may be stale (_rwrap): the kernel then reads the periodic image
+    # itself, so a frame needs no halo fill in front of it.  Everywhere else the halos are kept current by the step.
+    flags = model._rwrap
+    sfx = model.sfx
+    k = 0
+    for bits in runs:
+        which = sum(bits)
+        first = out.select(-3, k)
+        if ens:
+            f = getattr(model._L, f"swmhd_ensemble_output_fields_{sfx}")
+            rc = f(*ptrs, model.members, model.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, sy, g.dx, g.dy, model.form_code, 0, g.Ny, which,
+                   first.data_ptr(), out.element_size(), out.stride(-2), out.stride(-3), out.stride(0), flags, _stream_ptr())
+        else:
+            f = getattr(model._L, f"swmhd_output_fields_{sfx}")
+            rc = f(*ptrs, g.Nx, g.Ny, g.Hx, g.Hy, sy, g.dx, g.dy, model.form_code, 0, g.Ny, which,
+                   first.data_ptr(), out.element_size(), out.stride(-2), out.stride(-3), flags, _stream_ptr())
+        _lib.check(rc, "swmhd_output_fields")
+        k += len(bits)
+    return out
+
+
+# --- schedules (Oceananigans.Utils: TimeInterval, IterationInterval) ----------------------------------------------------------
+def _whole(ratio, what):
+    n = round(ratio)
+    if n < 1 or abs(ratio - n) > 1e-9 * max(1.0, abs(ratio)):
+        raise _lib.SwmhdError(f"{what} = {ratio!r} is not a whole number of time steps: this engine runs a fixed dt "
+                              "(Oceananigans would shorten a step to land on the time; choose an interval that dt divides)")
+    return int(n)
+
+
+@dataclass(frozen=True)
+class IterationInterval:
+    interval: int
+
+    def steps(self, dt):
+        if int(self.interval) != self.interval or self.interval < 1:
+            raise _lib.SwmhdError(f"IterationInterval({self.interval!r}): a positive whole number of iterations")
+        return int(self.interval)
+
+
+@dataclass(frozen=True)
+class TimeInterval:
+    """TimeInterval(T) with the fixed dt of this engine is IterationInterval(round(T / dt)); T / dt must be whole to 1e-9."""
+    interval: float
+
+    def steps(self, dt):
+        return _whole(self.interval / dt, f"TimeInterval({self.interval!r}) / dt")
+
+
+def frame_iterations(schedule, dt, nsteps):
+    """Iterations (counted from the start of a run of `nsteps` steps) at which `schedule` writes: 0, n, 2n, ... <= nsteps."""
+    n = schedule.steps(dt)
+    return list(range(0, nsteps + 1, n))
+
+
+class FieldTimeSeries:
+    """The reference's field writer on the device: `capacity` frames of `names` in one tensor, plus the host lists `times` and
+    `iterations`.  frames: (capacity, len(names), Ny, Nx); for an ensemble (capacity, members, len(names), Ny, Nx); on a y-slab the
+    rank's own rows.  Names: u v h A s B_x B_y (velocities also for the conservative model, which stores uh, vh).
+
+    array_type defaults to float32.  That default is this library's: the reference's field writer was given no array type and its
+    NetCDF writer (the energies) is the one that asks for Array{Float64}; what Oceananigans' JLD2 writer stores unasked is
+    library-internal and unpinned here, like the rest of assumption A9.  Pass torch.float64 for exact frames.
+
+    The tensor (capacity x frame bytes: 268 MB per 4096^2 float32 frame of four fields) is allocated when the first frame is written.
+    `write` only enqueues; `numpy` and `save` are the calls that synchronise."""
+
+    def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None, array_type=torch.float32):
+        self.model, self.names, self.schedule = model, tuple(names), schedule
+        _runs(self.names)
+        if array_type not in _ELEM:
+            raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
+        if capacity is None or int(capacity) < 1:
+            raise _lib.SwmhdError("FieldTimeSeries: capacity (frames) must be given: the frames stay on the device")
+        self.capacity, self.array_type = int(capacity), array_type
+        self.times, self.iterations = [], []
+        self._frames = None
+
+    def __len__(self):
+        return len(self.times)
+
+    @property
+    def frames(self):
+        """The device tensor of all `capacity` slots; the first len(self) hold frames."""
+        if self._frames is None:
+            m = self.model
+            dev = m._state[0].device if getattr(m, "members", None) is not None else m._raw_fields[0].data.device
+            self._frames = torch.empty((self.capacity,) + frame_shape(m, self.names), dtype=self.array_type, device=dev)
+        return self._frames
+
+    def write(self, time=None):
+        """Enqueue one frame of the model's current state into the next slot."""
+        k = len(self.times)
+        if k >= self.capacity:
+            raise _lib.SwmhdError(f"FieldTimeSeries: all {self.capacity} slots are written")
+        enqueue_frame(self.model, self.names, out=self.frames[k])
+        self.times.append(self.model.clock_time if time is None else time)
+        self.iterations.append(self.model.iteration)
+
+    def numpy(self):
+        """The frames written so far as a host array (synchronises)."""
+        return self.frames[:len(self.times)].cpu().numpy()
+
+    def save(self, path):
+        """One .npz: frames, names, times, iterations and the grid extents (synchronises)."""
+        import numpy as np
+        g = self.model.grid
+        np.savez(path, frames=self.numpy(), names=np.array(self.names), times=np.array(self.times, dtype=np.float64),
+                 iterations=np.array(self.iterations, dtype=np.int64), size=np.array([g.Nx, g.Ny]),
+                 x=np.array(g.x, dtype=np.float64), y=np.array(g.y, dtype=np.float64), j_offset=g.j_offset, Ny_global=g.Ny_global)
+
+
+def run(model, dt, stop_time=None, stop_iteration=None, writers=()):
+    """run!(simulation): step `model` (a ShallowWaterModel or an ensemble) to stop_time or stop_iteration with the writers attached.
+    Every writer gets a frame of the state the run starts from (as Oceananigans' writers do at iteration 0) and then one whenever its
+    schedule is due: model.time_steps(n, dt) -- graph replays when a graph was captured for dt -- followed by one output_fields launch.
+    Nothing here synchronises with the device.  Refuses up front (SwmhdError, before any step) when a writer's capacity is too small."""
+    if (stop_time is None) == (stop_iteration is None):
+        raise _lib.SwmhdError("run: give stop_time or stop_iteration")
+    it0, t0 = model.iteration, model.clock_time
+    if stop_iteration is not None:
+        nsteps = int(stop_iteration) - it0
+    else:
+        ratio = (stop_time - t0) / dt
+        nsteps = 0 if abs(ratio) <= 1e-9 else _whole(ratio, "(stop_time - time) / dt")
+    if nsteps < 0:
+        raise _lib.SwmhdError("run: the model is already past the stop")
+    plans = []
+    for w in writers:
+        due = frame_iterations(w.schedule, dt, nsteps)
+        if w.iterations and w.iterations[-1] == it0:
+            due = due[1:]                               # a continued run: this state is in the series already
+        if len(w) + len(due) > w.capacity:
+            raise _lib.SwmhdError(f"FieldTimeSeries capacity {w.capacity} < {len(w) + len(due)} frames: this run writes {len(due)} "
+                                  f"({nsteps} steps, one frame every {w.schedule.steps(dt)}) on top of {len(w)}")
+        plans.append((w, set(due)))
+    done = 0
+    while True:
+        for w, due in plans:
+            if done in due:
+                w.write(time=t0 + done * dt)
+        if done == nsteps:
+            break
+        nxt = min([min((k for k in due if k > done), default=nsteps) for _, due in plans] + [nsteps])
+        model.time_steps(nxt - done, dt)
+        done = nxt
+    return model
