@@ -41,7 +41,7 @@
  *       conservative uh, vh   :  max( (|uh|+|vh|)(|u|+|v|)(1/dx+1/dy),  g max|h|^2/2 (1/dx+1/dy),  f (|uh|+|vh|),  max|F_Lorentz| )
  *       h                     :  (|u|/dx + |v|/dy) max|h|        (conservative: |uh|/dx + |vh|/dy)
  *       A                     :  (|u|/dx + |v|/dy) max|A|
- *     (maxima over the field; tests/test_fullsize_gpu.py::term_scales).  Achieved on MI355X at every BASELINE size: <= 5e-15 of
+ *     (maxima over the field; tests/helpers.py::term_scales).  Achieved on MI355X at every BASELINE size: <= 5e-15 of
  *     max(max|G|, S) in fp64, <= 5e-7 in fp32.  Measured against max|G| ALONE the same errors are as large as 2e-9 (fp64: config 2's
  *     vh, 7.9e-10 for config 3's h) because at those resolutions the tendency is orders of magnitude smaller than the terms it is the
  *     difference of.  fp32 CAVEAT: where the terms cancel strongly the fp32 tendency carries no significant digits relative to its own

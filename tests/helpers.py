@@ -51,3 +51,32 @@ def two_gaussians(X, Y, amp=0.5):
 
 def interior(a, Nx, Ny, Hx, Hy):
     return a[Hy:Hy + Ny, Hx:Hx + Nx]
+
+
+def poison_halo(a, Nx, Ny, Hx, Hy, x=True, y=True):
+    """NaN in the halo cells of the x and / or y direction of a parent, in place (corners belong to both): what a call that reads the
+    periodic images instead of the halo cells (SWMHD_WRAP_X / SWMHD_WRAP_Y) must never touch."""
+    if x:
+        a[:, :Hx] = np.nan
+        a[:, Hx + Nx:] = np.nan
+    if y:
+        a[:Hy, :] = np.nan
+        a[Hy + Ny:, :] = np.nan
+    return a
+
+
+G, F = 9.81, 1.0   # gravity and Coriolis parameter of the tendency tests
+
+
+def term_scales(form, q, dx, dy, force):
+    """Magnitude of the largest term summed into each of the four tendencies (the S of the tolerances in include/swmhd.h)."""
+    q1, q2, h, A = (np.abs(a).max() for a in q)
+    hmin = q[2].min()
+    rd = 1.0 / dx + 1.0 / dy
+    if form == "VectorInvariant":
+        zeta = 2 * (q2 / dx + q1 / dy)
+        mom = max((q1 + q2) * zeta, 0.5 * (q1 ** 2 + q2 ** 2) * rd, G * h * rd, F * (q1 + q2), force)
+        return [mom, mom, (q1 / dx + q2 / dy) * h, (q1 / dx + q2 / dy) * A]
+    u, v = q1 / hmin, q2 / hmin
+    mom = max((q1 + q2) * (u + v) * rd, 0.5 * G * h * h * rd, F * (q1 + q2), force)
+    return [mom, mom, q1 / dx + q2 / dy, (u / dx + v / dy) * A]

@@ -1,0 +1,481 @@
+"""Reference of ONE call of the fused tendency entry points (swmhd_tendencies_*, swmhd_tendencies_rk3_* in include/swmhd.h) and the
+matrix of calls that tests/test_stage_matrix_gpu.py, its forced-layout child processes and tools/stage_matrix_report.py run through the
+row-marching kernels (k_tendency_vi_march, k_tendency_cons_march, k_tendency_vi_march_pk).
+
+The tendencies G come from the CPU oracle in float64 (fp32 inputs widened exactly); the substep is evaluated in np.longdouble from the
+formulas of the header.  The reference part (reference_stage, stage_bounds, StageData) is numpy only; run_stage / check_case need a GPU.
+
+Variants, at the level of the call (which compiled stage MODE a call lands on is launch_plan.hpp's business, pinned by
+tests/launch_plan_check.cpp):
+    T          swmhd_tendencies                                   Gn = G
+    S1g / S1n  first stage (Gm == NULL), store_G 1 / 0            qnew = q + dt gamma G                       Gn = G iff store_G
+    S2g / S3n  stage with Gm, store_G 1 / 0                       qnew = q + dt (gamma G + zeta Gm)           Gn = G iff store_G
+    P2g / P3n  SWMHD_GM_IS_PREV_STATE, store_G 1 / 0              qnew = q + dt gamma G + zeta' (q - Uprev)   Gn = G iff store_G
+               (Gm is passed as the buffers of qnew, which hold Uprev on entry)
+    A1         SWMHD_RK3_ANCHOR, Gm == NULL                       qnew = q + dt gamma G                       Gn = W = q + dt zeta G
+    A2 / A2a   SWMHD_RK3_ANCHOR with Gm = W                       qnew = W + dt gamma G                       Gn not written
+               (A2: Gn is a buffer of its own; A2a: Gn aliases Gm)
+
+Tolerances (all from include/swmhd.h and the tests that precede this one, none fitted to what the kernels give):
+    tendencies  max|dG| <= tol * max(max|G|, S), tol = 1e-12 (fp64, rough random fields) / 1e-4 (fp32), S = helpers.term_scales
+    new state   max|dqnew| <= dt c (tendency bound) + 4 eps max|operands of the update|: c is the weight G enters with -- |gamma|, and
+                |gamma| + |zeta| for the stages that also add zeta Gm -- and 4 eps is the rounding allowance of
+                test_second_stage_with_the_previous_state_as_operand.  The operands are the addends of the update (q or W, dt gamma G,
+                dt zeta Gm or zeta' (q - Uprev)); the maximum also runs over the result, which is no operand: that is the precedent
+                of the test named above (4 eps max|result|), and the result is at most the sum of the addends.  W: the same with zeta.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+import helpers as Hh
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+H = 3                               # halo width in x and y
+DX, DY = 0.11, 0.13                 # dx != dy
+GRAV, FCOR = Hh.G, Hh.F
+SENTINEL = -555.5                   # exact in fp32
+KEEP = "must keep its sentinel"
+FORM = {0: "Conservative", 1: "VectorInvariant"}
+FORMS = [(1, 1), (1, 0), (0, 2), (0, 0)]      # (formulation, lorentz)
+DTYPES = [np.float64, np.float32]
+TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.float32): 1e-4}
+MARCH_KERNEL, WRAP_X, WRAP_Y, GM_IS_PREV_STATE, RK3_ANCHOR = 4, 16, 32, 1024, 2048      # include/swmhd.h
+NTHREADS = max(1, min(len(os.sched_getaffinity(0)), 8))
+
+# variant: fused substep, operand (None | "Gm" | "Uprev" | "W"), store_G, anchor form, Gn aliases the operand
+VARIANTS = {
+    "T": dict(fused=False, operand=None, store_G=1, anchor=False, alias=False),
+    "S1g": dict(fused=True, operand=None, store_G=1, anchor=False, alias=False),
+    "S1n": dict(fused=True, operand=None, store_G=0, anchor=False, alias=False),
+    "S2g": dict(fused=True, operand="Gm", store_G=1, anchor=False, alias=False),
+    "S3n": dict(fused=True, operand="Gm", store_G=0, anchor=False, alias=False),
+    "P2g": dict(fused=True, operand="Uprev", store_G=1, anchor=False, alias=False),
+    "P3n": dict(fused=True, operand="Uprev", store_G=0, anchor=False, alias=False),
+    "A1": dict(fused=True, operand=None, store_G=0, anchor=True, alias=False),
+    "A2": dict(fused=True, operand="W", store_G=1, anchor=True, alias=False),     # (store_G is ignored in anchor form: Gn stays)
+    "A2a": dict(fused=True, operand="W", store_G=0, anchor=True, alias=True),
+}
+# (gamma, zeta) as the call receives them.  "rk3": Oceananigans' values, stage by stage; for P* zeta' = zeta / gamma-, for A1 the weight of
+# W.  "generic": one pair without the identities gamma1 + zeta2 = 1/4 and zeta3 = -gamma2 that could hide a wrong operand -- also
+# passed where the header says zeta is unused (first stages, A2), which must then ignore it.
+_G1, _G2, _G3, _Z2, _Z3 = 8.0 / 15.0, 5.0 / 12.0, 3.0 / 4.0, -17.0 / 60.0, -5.0 / 12.0
+COEFFS = {
+    "rk3": {"T": (0.0, 0.0), "S1g": (_G1, 0.0), "S1n": (_G1, 0.0), "S2g": (_G2, _Z2), "S3n": (_G3, _Z3), "P2g": (_G2, _Z2 / _G1),
+            "P3n": (_G3, _Z3 / _G2), "A1": (_G1, 0.25), "A2": (_G2, 0.0), "A2a": (_G3, 0.0)},
+    "generic": {v: (0.37, -0.21) for v in VARIANTS if v != "T"},
+}
+
+
+def calls():
+    """Every (variant, coefficient set) of the matrix; T has no coefficients and runs once."""
+    return [(v, c) for v in VARIANTS for c in COEFFS if v in COEFFS[c]]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# inputs and the oracle's tendencies, once per (shape, formulation, forcing, precision)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def random_fields(Nx, Ny, form, dtype, seed):
+    """(q, aux): the state as test_model_gpu.random_state makes it (rough random fields, halos periodic-filled), each field from a
+    stream of its own, and four independent fields of the same make for Gm / W / Uprev whose halos hold the sentinel."""
+    shp = (Ny + 2 * H, Nx + 2 * H)
+    out = []
+    for base in (0, 4):
+        r = [np.random.default_rng([seed, base + k]) for k in range(4)]
+        u, v = 0.5 * r[0].standard_normal(shp), 0.5 * r[1].standard_normal(shp)
+        h = 1.0 + 0.3 * r[2].random(shp)
+        A = r[3].standard_normal(shp)
+        q1, q2 = (u, v) if form == 1 else (h * u, h * v)
+        out.append([np.ascontiguousarray(Hh.fill_halo_periodic(a, Nx, Ny, H, H).astype(dtype)) for a in (q1, q2, h, A)])
+    q, aux = out
+    for a in aux:
+        keep = Hh.interior(a, Nx, Ny, H, H).copy()
+        a[...] = SENTINEL
+        Hh.interior(a, Nx, Ny, H, H)[...] = keep
+    return q, aux
+
+
+class StageData:
+    """Inputs of one (shape, formulation, forcing, precision) and the oracle's float64 tendencies of them."""
+
+    def __init__(self, oracle, Nx, Ny, form, lor, dtype, seed=None):
+        self.Nx, self.Ny, self.form, self.lor, self.dtype = Nx, Ny, form, lor, np.dtype(dtype)
+        seed = 1000 * Nx + Ny if seed is None else seed
+        self.q, self.aux = random_fields(Nx, Ny, form, dtype, seed)
+        q64 = [a.astype(np.float64) for a in self.q]                      # exact widening
+        # spacings and constants as the call receives them (c_float rounds 0.11, 0.13 and 9.81)
+        self.dx, self.dy, self.grav, self.fcor = (float(self.dtype.type(x)) for x in (DX, DY, GRAV, FCOR))
+        G = oracle.tendencies(*q64, Nx, Ny, H, H, self.dx, self.dy, form, lor, self.grav, self.fcor, nthreads=NTHREADS)
+        self.G = [Hh.interior(g, Nx, Ny, H, H).copy() for g in G]
+        force = 0.0
+        if lor:
+            op = oracle.lorentz_jacobian if lor == 1 else oracle.lorentz_divergence
+            force = max(float(np.abs(Hh.interior(w, Nx, Ny, H, H)).max()) for w in op(q64[3], q64[2], Nx, Ny, H, H, self.dx, self.dy, nthreads=NTHREADS))
+        self.scales = [float(s) for s in Hh.term_scales(FORM[form], q64, self.dx, self.dy, force)]
+        self.Gmax = [float(np.abs(g).max()) for g in self.G]
+        self.Umax = [float(np.abs(Hh.interior(a, Nx, Ny, H, H)).max()) for a in q64]
+
+    def dt(self, gamma):
+        """dt with dt |gamma| max|G| = max|U| (maxima over the four fields): one stage has no stability limit, and an increment of the
+        size of the state makes qnew as sharp a witness of G as Gn is.  Rounded to the precision of the call."""
+        if gamma == 0.0:
+            return 0.0
+        return float(self.dtype.type(max(self.Umax) / (abs(gamma) * max(self.Gmax))))
+
+
+def reference_stage(oracle, q, operand, variant, coeffs, Nx, Ny, dx, dy, form, lor, dt, rows=None, G=None):
+    """Expected interior rows [j0, j1) of every output of one call: {"qnew": 4 arrays | None (the call has none), "Gn": 4 arrays | KEEP}.
+    q: halo-filled parents in the precision of the call; operand: the parents of Gm / W / Uprev (None: first-stage forms);
+    coeffs: (gamma, zeta) as passed; G: the oracle's float64 interior tendencies if the caller has them already."""
+    v = VARIANTS[variant]
+    j0, j1 = (0, Ny) if rows is None else rows
+    dtype = q[0].dtype
+    if G is None:
+        q64 = [a.astype(np.float64) for a in q]
+        G = [Hh.interior(g, Nx, Ny, H, H) for g in oracle.tendencies(*q64, Nx, Ny, H, H, dx, dy, form, lor, float(dtype.type(GRAV)),
+                                                                        float(dtype.type(FCOR)), nthreads=NTHREADS)]
+    G = [np.asarray(g[j0:j1], dtype=np.float64) for g in G]
+    if not v["fused"]:
+        return {"qnew": None, "Gn": G}
+    LD = np.longdouble
+    cut = lambda a: Hh.interior(a, Nx, Ny, H, H)[j0:j1].astype(LD)
+    gam, zet, dtl = (LD(dtype.type(x)) for x in (coeffs[0], coeffs[1], dt))     # the values the kernel receives
+    U, Gl = [cut(a) for a in q], [g.astype(LD) for g in G]
+    Op = [cut(a) for a in operand] if v["operand"] else None
+    if v["anchor"] and Op is None:
+        return {"qnew": [u + dtl * gam * g for u, g in zip(U, Gl)], "Gn": [u + dtl * zet * g for u, g in zip(U, Gl)]}
+    if v["anchor"]:
+        return {"qnew": [w + dtl * gam * g for w, g in zip(Op, Gl)], "Gn": KEEP}
+    if Op is None:
+        qnew = [u + dtl * gam * g for u, g in zip(U, Gl)]
+    elif v["operand"] == "Uprev":
+        qnew = [u + dtl * gam * g + zet * (u - p) for u, g, p in zip(U, Gl, Op)]
+    else:
+        qnew = [u + dtl * (gam * g + zet * m) for u, g, m in zip(U, Gl, Op)]
+    return {"qnew": qnew, "Gn": G if v["store_G"] else KEEP}
+
+
+def stage_bounds(data, q, operand, variant, coeffs, dt, ref, rows=None):
+    """Allowed max-norm error of each written output, per field: {"qnew": [4] | None, "Gn": [4] | None} (module docstring)."""
+    v = VARIANTS[variant]
+    j0, j1 = (0, data.Ny) if rows is None else rows
+    eps = float(np.finfo(data.dtype).eps)
+    gam, zet = (abs(float(data.dtype.type(x))) for x in coeffs)
+    tb = [TOL[data.dtype] * max(gm, s) for gm, s in zip(data.Gmax, data.scales)]
+    if not v["fused"]:
+        return {"qnew": None, "Gn": tb}
+    cut = lambda a: Hh.interior(a, data.Nx, data.Ny, H, H)[j0:j1].astype(np.float64)
+    amax = lambda a: float(np.abs(a).max())
+    out = {"qnew": [], "Gn": None}
+    for f in range(4):
+        U = cut(q[f])
+        terms = [amax(ref["qnew"][f]), dt * gam * data.Gmax[f]]
+        weight = gam
+        if v["operand"] == "W":
+            terms.append(amax(cut(operand[f])))
+        else:
+            terms.append(amax(U))
+        if v["operand"] == "Gm":
+            terms.append(dt * zet * amax(cut(operand[f])))
+            weight = gam + zet
+        if v["operand"] == "Uprev":
+            terms.append(zet * amax(U - cut(operand[f])))
+        out["qnew"].append(dt * weight * tb[f] + 4 * eps * max(terms))
+    if v["anchor"] and v["operand"] is None:      # W through the G pointers
+        out["Gn"] = [dt * zet * tb[f] + 4 * eps * max(amax(cut(q[f])), dt * zet * data.Gmax[f], amax(ref["Gn"][f])) for f in range(4)]
+    elif ref["Gn"] is not KEEP:
+        out["Gn"] = tb
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# layouts: what each width and row count of the matrix is there for, asserted against swmhd_tendency_launch_geometry
+# ---------------------------------------------------------------------------------------------------------------------------------
+TXO = {256: 250, 128: 122}          # output columns of a strip
+PACKED_TXO = 504
+# Nx: (lanes, strips, output columns of the last strip) of the default chooser for both formulations and precisions (unpacked)
+LAYOUTS = {
+    250: (256, 1, 250),     # one strip, exactly full
+    2501: (256, 11, 1),     # last strip of ONE column (the smallest such width that keeps 256 lanes: at 251 ... 2251 the chooser
+                            # takes 128-lane strips); folds in the fp64 vector-invariant kernel
+    372: (256, 2, 122),     # the widest last strip that folds
+    373: (256, 2, 123),     # does not fold
+    500: (256, 2, 250),     # two full strips
+    100: (128, 1, 100),     # one partial 128-lane strip
+    251: (128, 3, 7),       # 128-lane strips with a 7-column tail (what the chooser makes of 250 + 1)
+    366: (128, 3, 122),     # three exactly full strips
+    600: (128, 5, 112),     # five strips, 112-column tail
+    3: (128, 1, 3),         # Nx = Hx, the smallest width WRAP allows
+    7: (128, 1, 7),
+}
+PACKED_WIDTHS = {8: (1, 8), 504: (1, 504), 506: (2, 2), 1000: (2, 496)}     # strips, output columns of the last strip
+ROWS = {3: (1, 3), 25: (5, 1), 31: (6, 1), 33: (6, 3), 24: (4, 6)}           # launch rows: (segments of 6 rows, rows of the last one)
+PARTIAL = (5, 29)                   # j_begin = 5, j_end = Ny - 4 on Ny = 33
+
+
+def is_packed(Nx, form, dtype, flags):
+    return np.dtype(dtype) == np.float32 and form == 1 and bool(flags & WRAP_X) and Nx % 2 == 0 and Nx >= 8
+
+
+def family(Nx, form, dtype, flags):
+    return "packed" if is_packed(Nx, form, dtype, flags) else ("vi" if form == 1 else "cons")
+
+
+def fold_enabled():
+    """The environment lets the launcher fold (launch_plan.hpp tendency_fold_enabled: SWMHD_T_FOLD unset or non-zero)."""
+    e = os.environ.get("SWMHD_T_FOLD")
+    try:
+        return e is None or int(e.strip() or 0) != 0
+    except ValueError:
+        return False          # atoi of a non-number is 0
+
+
+def folds(Nx, form, dtype, geo):
+    """The launch folds its last strip.  INFERRED, not queried: swmhd_tendency_launch_geometry does not report the fold, so this
+    restates launch_plan.hpp (fp64 vector-invariant, 256 lanes, more than one strip, tail <= 122, SWMHD_T_FOLD not 0).  With
+    SWMHD_T_FOLD=0 in the environment nothing folds: fold_enabled() is what the GPU module asserts before it relies on this."""
+    if not fold_enabled():
+        return False
+    return (form == 1 and np.dtype(dtype) == np.float64 and geo["kind"] == 2 and geo["threads"] == 256 and geo["nstrips"] > 1
+            and Nx - (geo["nstrips"] - 1) * TXO[256] <= 122)
+
+
+def check_layout(L, Nx, nrows, form, dtype, flags, lanes=None, LY=6, layouts=LAYOUTS):
+    """Assert that the launch of Nx x nrows has the layout the matrix wants from this shape; returns a one-line description."""
+    elem = np.dtype(dtype).itemsize
+    geo = L.tendency_launch_geometry(Nx, nrows, form, elem, MARCH_KERNEL | (flags & (WRAP_X | WRAP_Y)))
+    if is_packed(Nx, form, dtype, flags):
+        strips = -(-Nx // PACKED_TXO)
+        assert (geo["kind"], geo["threads"], geo["nstrips"]) == (3, 256, strips), (Nx, geo)
+        if Nx in PACKED_WIDTHS:
+            assert PACKED_WIDTHS[Nx] == (strips, Nx - (strips - 1) * PACKED_TXO), (Nx, geo)
+        tail = Nx - (strips - 1) * PACKED_TXO
+    else:
+        want = layouts[Nx] if lanes is None else (lanes, -(-Nx // TXO[lanes]), Nx - (-(-Nx // TXO[lanes]) - 1) * TXO[lanes])
+        tail = Nx - (geo["nstrips"] - 1) * TXO[geo["threads"]]
+        assert (geo["kind"], geo["threads"], geo["nstrips"], tail) == (2,) + want, (Nx, geo, want)
+    nseg, last = -(-nrows // LY), nrows - (-(-nrows // LY) - 1) * LY
+    assert (geo["rows_per_segment"], geo["nseg"]) == (LY, nseg), (nrows, geo)
+    if LY == 6:
+        assert ROWS[nrows] == (nseg, last), (nrows, geo)
+    fold = folds(Nx, form, dtype, geo)
+    return (f"kind {geo['kind']}, {geo['threads']} lanes, {geo['nstrips']} strips, last strip {tail} columns"
+            f"{' (folded)' if fold else ''}, {nseg} segments of {LY} rows, last {last}")
+
+
+def shape_groups():
+    """(Nx, Ny, rows | None, [flags], packed-only) of the matrix: every width with Ny = 31; every Ny with the widths 2501, 372, 600
+    and (packed) 506; one partial row range; WRAP_X alone and WRAP_Y alone once per kernel family.  2501 stands where 251 was meant
+    as the 256-lane width with a one-column last strip (at 251 the chooser takes three 128-lane strips); 251 itself runs at Ny = 31
+    only, as a 128-lane class with a 7-column tail."""
+    XY = WRAP_X | WRAP_Y
+    out = [(Nx, 31, None, [0, XY, WRAP_X, WRAP_Y] if Nx == 372 else [0, XY], False) for Nx in LAYOUTS]
+    out += [(Nx, Ny, None, [0, XY], False) for Nx in (2501, 372, 600) for Ny in (3, 25, 33)]
+    out += [(372, 33, PARTIAL, [0, XY], False)]
+    out += [(Nx, 31, None, [XY, WRAP_X], True) for Nx in PACKED_WIDTHS]
+    out += [(506, Ny, None, [XY], True) for Ny in (3, 25, 33)]
+    out += [(506, 33, PARTIAL, [XY], True)]
+    return out
+
+
+def matrix():
+    """Every (Nx, Ny, rows, form, lor, dtype, flags) of the matrix, grouped so that consecutive entries share their StageData."""
+    for Nx, Ny, rows, flagsets, packed_only in shape_groups():
+        for form, lor in FORMS:
+            for dtype in DTYPES:
+                if packed_only and not (form == 1 and dtype == np.float32):
+                    continue
+                for flags in flagsets:
+                    yield Nx, Ny, rows, form, lor, dtype, flags
+
+
+def case_id(Nx, Ny, rows, form, lor, dtype, flags):
+    wrap = {0: "nowrap", WRAP_X: "wrapX", WRAP_Y: "wrapY", WRAP_X | WRAP_Y: "wrapXY"}[flags]
+    return (f"{Nx}x{Ny}{'' if rows is None else f'-rows{rows[0]}to{rows[1]}'}-{'vi' if form == 1 else 'cons'}-lor{lor}-"
+            f"{'f64' if dtype == np.float64 else 'f32'}-{wrap}")
+
+
+_DATA = {}
+
+
+def stage_data(oracle, Nx, Ny, form, lor, dtype):
+    """StageData of a shape, computed once (the oracle is not called per case); only the latest width is kept."""
+    key = (Nx, Ny, form, lor, np.dtype(dtype).name)
+    if key not in _DATA:
+        for k in [k for k in _DATA if k[:2] != (Nx, Ny)]:
+            del _DATA[k]
+        _DATA[key] = StageData(oracle, Nx, Ny, form, lor, dtype)
+    return _DATA[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# one call on the GPU, and its comparison
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _same_bits(a, b):
+    u = np.uint64 if a.dtype.itemsize == 8 else np.uint32
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(u), np.ascontiguousarray(b).view(u))
+
+
+def run_stage(S, data, variant, cset, flags=0, rows=None):
+    """One call through the C-ABI with SWMHD_MARCH_KERNEL | flags.  Inputs: data.q with NaN in the halos of every wrapped direction;
+    the operand data.aux (sentinel halos).  Every output buffer starts as the sentinel (qnew of P*: as Uprev).  Returns the parents
+    before and after: {"q": (before, after), "operand": ..., "qnew": ..., "Gn": ...} (None where the call has no such buffer)."""
+    import torch
+    L = S._lib
+    v = VARIANTS[variant]
+    Nx, Ny = data.Nx, data.Ny
+    j0, j1 = (0, Ny) if rows is None else rows
+    gam, zet = COEFFS[cset][variant]
+    dt = data.dt(gam)
+    sfx = "f64" if data.dtype == np.float64 else "f32"
+    q_in = [a.copy() for a in data.q]
+    for a in q_in:
+        Hh.poison_halo(a, Nx, Ny, H, H, x=bool(flags & WRAP_X), y=bool(flags & WRAP_Y))
+    sent = np.full_like(data.q[0], SENTINEL)
+    dev = lambda arrs: [torch.from_numpy(a).cuda() for a in arrs]
+    P = lambda ts: L.ptr_array([t.data_ptr() for t in ts])
+    tq = dev(q_in)
+    before = {"q": q_in, "operand": None, "qnew": None, "Gn": [sent] * 4}
+    top = tnew = None
+    if v["operand"]:
+        top, before["operand"] = dev(data.aux), data.aux
+    if v["fused"]:
+        if v["operand"] == "Uprev":
+            tnew, before["qnew"] = top, data.aux       # the new state goes into the buffers that hold the previous one
+        else:
+            tnew, before["qnew"] = dev([sent] * 4), [sent] * 4
+    if v["alias"]:
+        tGn, before["Gn"] = top, data.aux
+    else:
+        tGn = dev([sent] * 4)
+    fl = MARCH_KERNEL | flags | (GM_IS_PREV_STATE if v["operand"] == "Uprev" else 0) | (RK3_ANCHOR if v["anchor"] else 0)
+    sy = Nx + 2 * H
+    if not v["fused"]:
+        rc = getattr(L.lib(), f"swmhd_tendencies_{sfx}")(*[t.data_ptr() for t in tq], *[t.data_ptr() for t in tGn], Nx, Ny, H, H, sy,
+                                                           data.dx, data.dy, data.grav, data.fcor, data.form, data.lor, j0, j1, fl, None)
+    else:
+        rc = getattr(L.lib(), f"swmhd_tendencies_rk3_{sfx}")(P(tq), P(tnew), P(tGn), P(top) if top is not None else None, Nx, Ny, H, H, sy,
+                                                               data.dx, data.dy, data.grav, data.fcor, data.form, data.lor, dt, gam, zet, v["store_G"], j0, j1,
+                                                               fl, None)
+    L.check(rc, f"{variant}/{cset}")
+    torch.cuda.synchronize()
+    host = lambda ts: None if ts is None else [t.cpu().numpy() for t in ts]
+    after = {"q": host(tq), "operand": host(top), "qnew": host(tnew), "Gn": host(tGn)}
+    return {k: (before[k], after[k]) for k in before}
+
+
+def check_case(S, oracle, data, variant, cset, flags=0, rows=None):
+    """run_stage against reference_stage: (failures, ratios).  failures: one line per violated assertion (empty: the case passes);
+    ratios: {"qnew" | "Gn": largest error / bound over the four fields} of the outputs the call writes."""
+    v = VARIANTS[variant]
+    Nx, Ny = data.Nx, data.Ny
+    j0, j1 = (0, Ny) if rows is None else rows
+    coeffs = COEFFS[cset][variant]
+    dt = data.dt(coeffs[0])
+    operand = data.aux if v["operand"] else None
+    ref = reference_stage(oracle, data.q, operand, variant, coeffs, Nx, Ny, data.dx, data.dy, data.form, data.lor, dt, rows=rows, G=data.G)
+    bounds = stage_bounds(data, data.q, operand, variant, coeffs, dt, ref, rows=rows)
+    out = run_stage(S, data, variant, cset, flags, rows)
+    fails, ratios = [], {}
+    # 3. inputs bitwise unchanged (Uprev of P* is the qnew buffer; the aliased Gn of A2a is the operand W)
+    for f in range(4):
+        if not _same_bits(*[x[f] for x in out["q"]]):
+            fails.append(f"input field {f} was changed")
+        if v["operand"] and v["operand"] != "Uprev" and not _same_bits(*[x[f] for x in out["operand"]]):
+            fails.append(f"operand {v['operand']} field {f} was changed")
+    for name in ("qnew", "Gn"):
+        if out[name][1] is None or (name == "Gn" and v["alias"]):
+            continue
+        for f in range(4):
+            b, a = out[name][0][f], out[name][1][f]
+            if ref[name] is KEEP:
+                # 2. an output the call must not write: bitwise its sentinel everywhere
+                if not _same_bits(a, b):
+                    fails.append(f"{name}[{f}] must keep its sentinel: {int((a != b).sum())} cells written")
+                continue
+            # 2. halos and rows outside [j_begin, j_end): bitwise what they held
+            a_out, b_out = a.copy(), b.copy()
+            a_out[H + j0:H + j1, H:H + Nx] = 0
+            b_out[H + j0:H + j1, H:H + Nx] = 0
+            if not _same_bits(a_out, b_out):
+                fails.append(f"{name}[{f}]: {int((a_out != b_out).sum())} cells written outside rows [{j0}, {j1}) of the interior")
+            # 1. finite and within tolerance over the whole range, max-norm
+            got = a[H + j0:H + j1, H:H + Nx].astype(np.longdouble)
+            if not np.isfinite(got).all():
+                fails.append(f"{name}[{f}]: {int((~np.isfinite(got)).sum())} non-finite cells")
+                ratios[name] = float("inf")
+                continue
+            err, bound = float(np.abs(got - ref[name][f]).max()), bounds[name][f]
+            ratios[name] = max(ratios.get(name, 0.0), err / bound)
+            if not err <= bound:
+                fails.append(f"{name}[{f}]: max error {err:.3e} > bound {bound:.3e}")
+    return fails, ratios
+
+
+def run_cases(S, oracle, Nx, Ny, rows, form, lor, dtype, flags, worst=None, stop_at_first=False):
+    """All variants and coefficient sets of one matrix entry.  Returns the failures, each prefixed with its call; `worst` collects
+    the largest error / bound ratio per (family, precision, variant)."""
+    data = stage_data(oracle, Nx, Ny, form, lor, dtype)
+    fam, prec = family(Nx, form, dtype, flags), ("f64" if np.dtype(dtype) == np.float64 else "f32")
+    failures = []
+    for variant, cset in calls():
+        fails, ratios = check_case(S, oracle, data, variant, cset, flags, rows)
+        print(f"  {case_id(Nx, Ny, rows, form, lor, dtype, flags)} {variant}/{cset}: "
+              + ", ".join(f"{k} {r:.3g}" for k, r in ratios.items()) + (f"  FAILED: {fails}" if fails else ""))
+        if worst is not None and ratios:
+            key = f"{fam}/{prec}/{variant}"
+            worst[key] = max(worst.get(key, 0.0), max(ratios.values()))
+        failures += [f"{variant}/{cset}: {m}" for m in fails]
+        if failures and stop_at_first:
+            break
+    return failures
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# forced layouts: the chooser's read-once knobs, in a child process of their own (test_stage_matrix_gpu.test_forced_layouts)
+# ---------------------------------------------------------------------------------------------------------------------------------
+FORCED = {
+    # 128-lane strips with a one-column tail: 123 = 122 + 1, 489 = 4 x 122 + 1
+    "nt128": dict(env={"SWMHD_T_NT": "128"}, shapes=[(123, 31), (489, 31)], lanes=128, LY=6),
+    # segments longer than 6 rows on a small grid: 33 rows = 13 + 13 + 7 (an odd count: the folded workgroup's second half of the fp64
+    # vector-invariant kernel owns no rows at 2501), default strips
+    "ly13": dict(env={"SWMHD_T_LY": "13"}, shapes=[(2501, 33), (600, 33)], lanes=None, LY=13),
+}
+
+
+def forced_main(name, out_path):
+    """Child process: all variants for (1, 1) and (0, 2) in fp64 and fp32, without and with WRAP_X | WRAP_Y, under the knob `name`
+    (set by the parent in the environment).  Writes {"ok", "failed", "layouts", "worst"} and exits non-zero at the first failure."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import swmhd_amd as S
+    from oracle import oracle as O
+    cfg = FORCED[name]
+    for k, val in cfg["env"].items():
+        assert os.environ.get(k) == val, f"{k} must be {val} in the environment of this process"
+    worst, layouts, failures = {}, {}, []
+    for Nx, Ny in cfg["shapes"]:
+        for form, lor in ((1, 1), (0, 2)):
+            for dtype in DTYPES:
+                for flags in (0, WRAP_X | WRAP_Y):
+                    cid = case_id(Nx, Ny, None, form, lor, dtype, flags)
+                    layouts[cid] = check_layout(S._lib, Nx, Ny, form, dtype, flags, lanes=cfg["lanes"], LY=cfg["LY"])
+                    failures = run_cases(S, O, Nx, Ny, None, form, lor, dtype, flags, worst=worst, stop_at_first=True)
+                    if failures:
+                        break
+                if failures:
+                    break
+            if failures:
+                break
+        if failures:
+            break
+    with open(out_path, "w") as fh:
+        json.dump({"ok": not failures, "failed": [f"{cid} {m}" for m in failures], "layouts": layouts, "worst": worst}, fh, indent=1,
+                  sort_keys=True)
+    return 1 if failures else 0
+
+
+if __name__ == "__main__":
+    sys.exit(forced_main(sys.argv[1], sys.argv[2]))

@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import term_scales
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out", "fullsize_parity.json")
@@ -35,20 +37,6 @@ def record(key, value):
     d = json.load(open(OUT)) if os.path.exists(OUT) else {}
     d[key] = value
     json.dump(d, open(OUT, "w"), indent=1, sort_keys=True)
-
-
-def term_scales(form, q, dx, dy, force):
-    """Magnitude of the largest term summed into each of the four tendencies (see the module docstring)."""
-    q1, q2, h, A = (np.abs(a).max() for a in q)
-    hmin = q[2].min()
-    rd = 1.0 / dx + 1.0 / dy
-    if form == "VectorInvariant":
-        zeta = 2 * (q2 / dx + q1 / dy)
-        mom = max((q1 + q2) * zeta, 0.5 * (q1 ** 2 + q2 ** 2) * rd, G * h * rd, F * (q1 + q2), force)
-        return [mom, mom, (q1 / dx + q2 / dy) * h, (q1 / dx + q2 / dy) * A]
-    u, v = q1 / hmin, q2 / hmin
-    mom = max((q1 + q2) * (u + v) * rd, 0.5 * G * h * h * rd, F * (q1 + q2), force)
-    return [mom, mom, q1 / dx + q2 / dy, (u / dx + v / dy) * A]
 
 
 def compare(tag, names, got, want, scales, tol, I):

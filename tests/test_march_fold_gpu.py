@@ -72,8 +72,8 @@ def test_folded_tendencies_match_strict(swmhd, rem, odd):
 
 @pytest.mark.parametrize("rem", [6, 96, 122])
 def test_folded_fused_stage_matches_strict(swmhd, rem):
-    """One fused RK3 stage of the classic form (the first stage writes U1 and G0) on an odd segment count: fast vs strict within the
-    fast tolerance, and nothing outside the interior of U1 written."""
+    """One fused RK3 stage of the classic form (the first stage writes U1 and G0) on an odd segment count: U1 and G0 of the
+    fast kernel vs the strict one within the fast tolerance, and nothing outside the interior of either written."""
     S, L = swmhd, swmhd._lib
     Nx = WIDTHS[rem]
     rows, geo = _rows_for(L, Nx, True)
@@ -85,14 +85,22 @@ def test_folded_fused_stage_matches_strict(swmhd, rem):
     for name, fl in (("fast", 0), ("strict", L.STRICT)):
         U1 = [S.Field(g, dtype=torch.float64) for _ in range(4)]
         G0 = [S.Field(g, dtype=torch.float64) for _ in range(4)]
-        for x in U1:
+        for x in U1 + G0:
             x.data.fill_(-555.5)
         L.check(L.lib().swmhd_tendencies_rk3_f64(P(U), P(U1), P(G0), None, g.Nx, g.Ny, g.Hx, g.Hy, sy, g.dx, g.dy, 9.81, 1.0, 1, 1,
                                                  1e-3, 8.0 / 15.0, 0.0, 1, 0, g.Ny, fl, None), name)
         torch.cuda.synchronize()
         out[name] = [x.numpy() for x in U1]
+        out[name + " G0"] = [x.numpy() for x in G0]
     I = g.interior
     for f, s in zip(out["fast"], out["strict"]):
+        assert np.abs(f[I] - s[I]).max() <= 1e-12 * np.abs(s[I]).max()
+        mask = np.ones(f.shape, bool)
+        mask[I] = False
+        assert np.all(f[mask] == -555.5)
+    # the stored tendencies G0: the bar of test_folded_tendencies_match_strict, and nothing outside the interior written
+    for f, s in zip(out["fast G0"], out["strict G0"]):
+        assert np.isfinite(f[I]).all()
         assert np.abs(f[I] - s[I]).max() <= 1e-12 * np.abs(s[I]).max()
         mask = np.ones(f.shape, bool)
         mask[I] = False

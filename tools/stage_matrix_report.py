@@ -1,0 +1,41 @@
+"""Largest achieved error / allowed error of the stage matrix (tests/stage_cases.py: the calls of tests/test_stage_matrix_gpu.py) per
+kernel family (vi, cons, packed) x precision x call form, on the current GPU.  Prints the table and writes it as JSON:
+
+    python tools/stage_matrix_report.py [out.json]        (default: profiles/stage_matrix/achieved.json)
+
+A ratio of 1 would be a call at its bound (include/swmhd.h: 1e-12 / 1e-4 of max(max|G|, S) per tendency, carried into the new state)."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import stage_cases as SC      # noqa: E402
+
+
+def main(out_path):
+    import torch
+    import swmhd_amd as S
+    from oracle import oracle as O
+    worst, layouts, failures, ncases = {}, {}, [], 0
+    for case in SC.matrix():
+        Nx, Ny, rows, form, lor, dtype, flags = case
+        ncases += 1
+        nrows = Ny if rows is None else rows[1] - rows[0]
+        prec = "f64" if dtype == SC.DTYPES[0] else "f32"
+        layouts[f"{Nx} x {nrows} rows {SC.family(Nx, form, dtype, flags)}/{prec}"] = SC.check_layout(S._lib, Nx, nrows, form, dtype, flags)
+        failures += [f"{SC.case_id(*case)} {m}" for m in SC.run_cases(S, O, *case, worst=worst)]
+    rec = {"device": torch.cuda.get_device_name(0), "kernel_source_hash": S._lib.source_hash(), "cases": ncases,
+           "calls_per_case": len(SC.calls()), "failures": failures,
+           "max_error_over_bound": {k: float(f"{v:.3g}") for k, v in sorted(worst.items())}, "layouts": layouts}
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+    print(json.dumps(rec["max_error_over_bound"], indent=1))
+    print(f"{ncases} cases x {len(SC.calls())} calls, {len(failures)} failures -> {out_path}")
+    return 1 if failures else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "stage_matrix", "achieved.json")))
