@@ -22,6 +22,12 @@ runs the reference's commented channel experiment (SWMHD_example.jl:18-22, diver
 gradient g, one member of a swmhd_amd.BoundedShallowWaterEnsemble per value: topology (Periodic, Bounded, Flat), A = g y with
 GradientBoundaryCondition(g) on A north and south (an imposed uniform B_x = -g / h), h = 1 and the vortex above.  Output as for --amps.
 
+    python examples/run_swmhd.py --coriolis 0.5,1,2 [--gravity 9.81,4,1] [--dts 0.01,0.01,0.005] [--amps ... | --channel --gradients ...]
+sweeps the physical parameters: one ensemble member per entry with its own f (coriolis = FPlane(f = ...)), g
+(gravitational_acceleration) and time step.  The lists are zipped with each other and with --amps / --gradients: every list has one
+entry (used for all members) or the common length.  --energies gets the member's g, f and dt as columns after `member`; with --dts a
+member's time is iteration x its dt, and the run ends when the member with the largest dt reaches --stop-time.
+
     python examples/run_swmhd.py --plot-case jacobian_formulation/128x128_two_Gaussians_low_B
 re-runs one of the twelve runs behind the reference's committed energy plots (energy_plots/*/*.png; set-up from the scripts' commented
 alternatives, see tests/plot_cases.py) and prints, beside every energy row, the value read off the plot at that time
@@ -42,6 +48,9 @@ def main():
     ap.add_argument("--amps", default=None, help="comma-separated A amplitudes: one ensemble member per amplitude")
     ap.add_argument("--channel", action="store_true", help="(Periodic, Bounded) channel with gradient boundary conditions on A")
     ap.add_argument("--gradients", default=None, help="with --channel: comma-separated gradients of A, one ensemble member each")
+    ap.add_argument("--coriolis", default=None, help="comma-separated Coriolis parameters f: one ensemble member per entry")
+    ap.add_argument("--gravity", default=None, help="comma-separated gravitational accelerations g: one ensemble member per entry")
+    ap.add_argument("--dts", default=None, help="comma-separated time steps: one ensemble member per entry (overrides --dt)")
     ap.add_argument("--every", type=int, default=100, help="iterations between progress lines / energy rows")
     ap.add_argument("--energies", default=None, help="CSV file for (time, KE, ME, PE, total)")
     ap.add_argument("--dump-every", type=float, default=0.0, help="model time between field dumps (0 = none)")
@@ -52,8 +61,8 @@ def main():
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
     for k in range(len(argv) - 1):   # "--gradients -0.01,-0.05": argparse would read the negative list as an option
-        if argv[k] == "--gradients":
-            argv[k:k + 2] = ["--gradients=" + argv[k + 1]]
+        if argv[k] in ("--gradients", "--coriolis"):
+            argv[k] = argv[k] + "=" + argv.pop(k + 1)
             break
     a = ap.parse_args(argv)
     if a.plot_case:
@@ -62,7 +71,10 @@ def main():
         ap.error("--channel and --gradients go together")
     if a.channel and a.amps:
         ap.error("--channel sweeps --gradients, not --amps")
-    if a.amps or a.channel:
+    a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts))
+    if a.dts and a.frames > 0:
+        ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
+    if a.amps or a.channel or a.sweep:
         return run_ensemble(a)
 
     import torch
@@ -146,21 +158,35 @@ def save_frames(a, series):
 
 
 def run_ensemble(a):
-    """--amps: the same run for several A amplitudes, one ensemble member each.  --channel: one member per gradient of A."""
+    """--amps: the same run for several A amplitudes, one ensemble member each.  --channel: one member per gradient of A.
+    --coriolis, --gravity, --dts: one member per entry with its own f, g and time step, zipped with the former."""
     import torch
     import swmhd_amd as S
     from swmhd_amd import configs
-    amps = [float(x) for x in (a.gradients if a.channel else a.amps).split(",") if x.strip()]
-    N, L = a.size, 10.0
     form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
+    floats = lambda txt: [float(x) for x in txt.split(",") if x.strip()]
+    if a.channel or a.amps:
+        amps = floats(a.gradients if a.channel else a.amps)
+    else:
+        amps = [a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)]
+    lists = {"--coriolis": floats(a.coriolis or ""), "--gravity": floats(a.gravity or ""), "--dts": floats(a.dts or "")}
+    B = max([len(amps)] + [len(v) for v in lists.values()])
+    for name, v in [("--gradients" if a.channel else "--amps", amps)] + [(k, v) for k, v in lists.items() if v]:
+        if len(v) not in (1, B):
+            sys.exit(f"{name}: {len(v)} entries; every list has 1 entry or the common length {B}")
+    amps = amps * (B // len(amps))
+    per = lambda v, default: default if not v else (v * (B // len(v)))      # a list of B values, or the scalar default
+    gs, fs, dt = per(lists["--gravity"], configs.G), per(lists["--coriolis"], configs.F), per(lists["--dts"], a.dt)
+    a.dt = max(dt) if a.dts else a.dt                                           # the step that the stop time and --every are counted in
+    N, L = a.size, 10.0
     if a.channel:
         grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2), topology=("Periodic", "Bounded", "Flat"))
         bcs = [{"A": S.FieldBoundaryConditions(north=S.GradientBoundaryCondition(gr), south=S.GradientBoundaryCondition(gr))} for gr in amps]
-        ens = S.BoundedShallowWaterEnsemble(grid, len(amps), configs.G, configs.F, formulation=form, boundary_conditions=bcs)
+        ens = S.BoundedShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form, boundary_conditions=bcs)
         A0 = [lambda X, Y, gr=gr: gr * Y for gr in amps]
     else:
         grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
-        ens = S.ShallowWaterEnsemble(grid, len(amps), configs.G, configs.F, formulation=form)
+        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form)
         A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
     label = "gradient" if a.channel else "amp"
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
@@ -172,19 +198,22 @@ def run_ensemble(a):
 
     def report(wall):
         for m, d in enumerate(ens.diagnostics()):
-            print(f"member {m} ({label} {amps[m]:g}) Time: {ens.clock_time:9.3f}, iteration: {ens.iteration}, "
+            t = float(ens.clock_times[m])
+            print(f"member {m} ({label} {amps[m]:g}{sweep(m)}) Time: {t:9.3f}, iteration: {ens.iteration}, "
                   f"max(|u|): {max(d['max_abs_u'], d['max_abs_v']):.2e}, max(|A|): {d['max_abs_A']:.2e}, min(h): {d['min_h']:.2e}, "
                   f"wall time: {wall * 1e3:.1f} ms | KE {d['kinetic_energy']:.6f} ME {d['magnetic_energy']:.6f} "
                   f"PE {d['potential_energy']:.3e} total {d['total_energy']:.6f}", flush=True)
-            rows.append((m, ens.clock_time, d["kinetic_energy"], d["magnetic_energy"], d["potential_energy"], d["total_energy"]))
+            rows.append((m,) + (params(m) if a.sweep else ()) + (t, d["kinetic_energy"], d["magnetic_energy"], d["potential_energy"], d["total_energy"]))
 
+    params = lambda m: (float(ens.g_values[m]), float(ens.f_values[m]), dt[m] if a.dts else a.dt)
+    sweep = lambda m: ", g {:g}, f {:g}, dt {:g}".format(*params(m)) if a.sweep else ""
     report(0.0)
-    e0 = [r[5] for r in rows]
+    e0 = [r[-1] for r in rows]
     series, fevery = frame_writer(a, ens, nsteps)
-    ens.time_step(a.dt)
+    ens.time_step(dt)
     if fevery == 1:
         series.write()
-    ens.capture_graph(a.dt)
+    ens.capture_graph(dt)
     t_start = time.perf_counter()
     t0 = None
     while ens.iteration < nsteps:
@@ -192,7 +221,7 @@ def run_ensemble(a):
         n = min(a.every - ens.iteration % a.every, nsteps - ens.iteration)
         if fevery:
             n = min(n, fevery - ens.iteration % fevery)
-        ens.time_steps(n, a.dt)
+        ens.time_steps(n, dt)
         if fevery and ens.iteration % fevery == 0:
             series.write(time=ens.iteration * a.dt)           # all members in one launch, no synchronisation
         if ens.iteration % a.every != 0 and ens.iteration != nsteps:
@@ -201,13 +230,15 @@ def run_ensemble(a):
         report(time.perf_counter() - t0)
         t0 = None
     total = time.perf_counter() - t_start
-    drift = ", ".join(f"{abs(rows[-len(amps) + m][5] - e0[m]) * 100:.4f}" for m in range(len(amps)))
+    drift = ", ".join(f"{abs(rows[-len(amps) + m][-1] - e0[m]) * 100:.4f}" for m in range(len(amps)))
     print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations of {len(amps)} members, "
           f"{len(amps) * N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); energy drift abs(E - E0) * 100 per member = {drift}")
     save_frames(a, series)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
-            w = csv.writer(f); w.writerow(["member", "time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
+            w = csv.writer(f)
+            w.writerow(["member"] + (["g", "f", "dt"] if a.sweep else []) + ["time", "kinetic", "magnetic", "potential", "total"])
+            w.writerows(rows)
 
 
 def plot_case(a):

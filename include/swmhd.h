@@ -461,7 +461,8 @@ int swmhd_diagnostics_f32(const float *q1, const float *q2, const float *h, cons
 /* ------------------------------------------------------------------------------------------------
  * Ensembles: `members` independent runs of ONE periodic grid stepped together -- the reference's runs are sweeps of small grids
  * (64^2, 128^2; initial conditions that differ in the amplitude of A), where one grid fills a few percent of the chip.  Every
- * member has the same Nx, Ny, Hx, Hy, stride_y, dx, dy, g, f, formulation, forcing, precision and dt; members differ in their state.
+ * member has the same Nx, Ny, Hx, Hy, stride_y, dx, dy, g, f, formulation, forcing, precision and dt; members differ in their state
+ * (the *_params calls further down lift that for g, f and dt).
  * Layout: field f of member m is the halo-padded parent (conventions above) at  ptr[f] + m * stride_m  (elements), for every pointer
  * argument; stride_m >= (Ny + 2Hy) * stride_y.  A larger stride_m (pitched members) is allowed: nothing between two members is read
  * or written.  1 <= members <= SWMHD_ENSEMBLE_MAX_MEMBERS.  All members of a call run in one launch per kernel.
@@ -559,6 +560,57 @@ int swmhd_ensemble_step_rk3_bc_f32(float *const *q, float *const *q_alt, float *
                                    int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
                                    float dx, float dy, float g, float f, int formulation, int lorentz, float dt, int nsteps,
                                    const float *gradient, int flags, int *state_in_alt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-member parameters: ensembles whose members differ in g, f and dt as well as in their state -- a Rossby- or Froude-number sweep
+ * (coriolis = FPlane(f = ...), gravitational_acceleration) at fixed state, or an amplitude sweep in which every member steps at its
+ * own dt.  Each *_params call below is its counterpart above with the scalars g, f, dt (diagnostics: g) removed and, in their place,
+ *   params: a DEVICE table of members x SWMHD_ENSEMBLE_NPARAMS values in the call's element type; member m's (g, f, dt) at
+ *           params + 3 m.  The diagnostics call reads g only, from the same table, so one table serves a whole run.
+ * Formulation, forcing kind, grid and precision stay those of the ensemble (compile-time in the kernel); no workspace is needed (the
+ * stage kernel forms dt * gamma and dt * (gamma1 + zeta2) itself, one multiply in the element type each, as the host does for one grid).
+ * Enqueue-only: the host never reads the table.  The kernels read it when they RUN, so a captured graph steps with whatever the table
+ * holds at replay, and a table changed between two calls on one stream takes effect from the second.  Every argument check precedes
+ * the first HIP call; params == NULL returns SWMHD_EINVAL; accepted and refused flags, return codes, launch counts, buffer rotation
+ * and *state_in_alt are exactly those of the counterpart.  A non-finite parameter poisons that member only.
+ * Results: SWMHD_STRICT members are bit-identical to the oracle's time_step / tendencies called with that member's (g, f, dt), and so
+ * to the scalar call when all rows are equal.  Fast members are within the fast tolerances of a fast single model built with the
+ * member's parameters, not bitwise: as for Bounded members, the compiler groups uniform factors differently between instantiations.
+ * Out of scope: per-member formulation or forcing kind, and output schedules in time units across members whose clocks diverge.
+ * ---------------------------------------------------------------------------------------------- */
+#define SWMHD_ENSEMBLE_NPARAMS 3
+int swmhd_ensemble_tendencies_rk3_params_f64(const double *const *q, double *const *qnew, double *const *Gn, const double *const *Gm,
+                                             int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                             double dx, double dy, const double *params, int formulation, int lorentz,
+                                             double gamma, double zeta, int store_G, int flags, void *stream);
+int swmhd_ensemble_tendencies_rk3_params_f32(const float *const *q, float *const *qnew, float *const *Gn, const float *const *Gm,
+                                             int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                             float dx, float dy, const float *params, int formulation, int lorentz,
+                                             float gamma, float zeta, int store_G, int flags, void *stream);
+int swmhd_ensemble_step_rk3_params_f64(double *const *q, double *const *q_alt, double *const *Ga, double *const *Gb,
+                                       int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                       double dx, double dy, const double *params, int formulation, int lorentz, int nsteps,
+                                       int flags, int *state_in_alt, void *stream);
+int swmhd_ensemble_step_rk3_params_f32(float *const *q, float *const *q_alt, float *const *Ga, float *const *Gb,
+                                       int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                       float dx, float dy, const float *params, int formulation, int lorentz, int nsteps,
+                                       int flags, int *state_in_alt, void *stream);
+int swmhd_ensemble_step_rk3_bc_params_f64(double *const *q, double *const *q_alt, double *const *Ga, double *const *Gb,
+                                          int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                          double dx, double dy, const double *params, int formulation, int lorentz, int nsteps,
+                                          const double *gradient, int flags, int *state_in_alt, void *stream);
+int swmhd_ensemble_step_rk3_bc_params_f32(float *const *q, float *const *q_alt, float *const *Ga, float *const *Gb,
+                                          int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                          float dx, float dy, const float *params, int formulation, int lorentz, int nsteps,
+                                          const float *gradient, int flags, int *state_in_alt, void *stream);
+int swmhd_ensemble_diagnostics_params_f64(const double *q1, const double *q2, const double *h, const double *A,
+                                          int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                          double dx, double dy, const double *params, double h_ref, int formulation,
+                                          double *workspace, double *out, void *stream);
+int swmhd_ensemble_diagnostics_params_f32(const float *q1, const float *q2, const float *h, const float *A,
+                                          int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                          float dx, float dy, const float *params, float h_ref, int formulation,
+                                          double *workspace, double *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Output frames: the fields an output writer stores, made on the device in ONE pass over the four prognostic parents -- derived

@@ -24,6 +24,7 @@ DIAG_NOUT, DIAG_WORKSPACE = 7, 1024 * 7
 # SWMHD_OUT_*: the output fields of swmhd_output_fields_*, by the names of the reference's writer, in bit (= frame) order
 OUT_BITS = {"u": 1, "v": 2, "h": 4, "A": 8, "s": 16, "B_x": 32, "B_y": 64}
 ENSEMBLE_MAX_MEMBERS = 65535
+ENSEMBLE_NPARAMS = 3    # SWMHD_ENSEMBLE_NPARAMS: (g, f, dt) per member in the table of the swmhd_ensemble_*_params calls
 
 
 def ensemble_diag_workspace(members, Nx, Ny):
@@ -111,6 +112,19 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_step_rk3_bc_{sfx}")
         f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, i, p, i, C.POINTER(i), p]
         f.restype = i
+        # per-member (g, f, dt): the scalars replaced by a device table
+        f = getattr(lib, f"swmhd_ensemble_tendencies_rk3_params_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, p, i, i, ft, ft, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_step_rk3_params_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, p, i, i, i, i, C.POINTER(i), p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_step_rk3_bc_params_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [i, i64, i, i, i, i, i64, ft, ft, p, i, i, i, p, i, C.POINTER(i), p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_diagnostics_params_{sfx}")
+        f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, p, ft, i, p, p, p]
+        f.restype = i
         f = getattr(lib, f"swmhd_ring_exchange_y_{sfx}")
         f.argtypes = [p, C.POINTER(p), i, i, i, i, i, i64, p]
         f.restype = i
@@ -163,7 +177,8 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "fill_halo", "fill_halo_periodic", "fill_halo_periodic_multi", "tendencies", "tendencies_rk3", "rk3_substep", "step_rk3", "diagnostics",
         "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
         "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc", "fill_halo_walls", "ring_exchange_y_sides", "ring_step_rk3_bc",
-        "output_fields", "ensemble_output_fields")] + [
+        "output_fields", "ensemble_output_fields", "ensemble_tendencies_rk3_params", "ensemble_step_rk3_params",
+        "ensemble_step_rk3_bc_params", "ensemble_diagnostics_params")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

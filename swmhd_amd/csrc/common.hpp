@@ -110,7 +110,16 @@ struct EnsTendArgs : TendArgs<T> {
     int fold;             // 1: the member is folded into blockIdx.x (XCD-remapped over all tiles of all members, so a member's tiles
                           // share an XCD); 0: the member is blockIdx.y and the remap runs over the tiles of one member
 };
-template <typename T, bool ENS> using TileArgs = std::conditional_t<ENS, EnsTendArgs<T>, TendArgs<T>>;
+// Per-member parameters (swmhd_ensemble_*_params): member m takes (g, f, dt) from the DEVICE table params[3 m .. 3 m + 2] when the
+// kernel runs.  The tile kernel's PAR variant loads them after it has found its member and forms dtg and dtw from the member's dt as the
+// host does for one grid (one multiply in T each); grav, fcor, dt, dtg and dtw of the base struct are not read.
+template <typename T>
+struct EnsParTendArgs : EnsTendArgs<T> {
+    const T *params;
+};
+constexpr int ENS_NPARAMS = 3;   // = SWMHD_ENSEMBLE_NPARAMS
+template <typename T, bool ENS, bool PAR = false>
+using TileArgs = std::conditional_t<PAR, EnsParTendArgs<T>, std::conditional_t<ENS, EnsTendArgs<T>, TendArgs<T>>>;
 // ---- RK3 stage schedule of the step drivers (step_common in swmhd_api.hip, both schedules of ring_step in ring.hip) --------------
 // Oceananigans' RungeKutta3 (TimeSteppers): gamma = 8/15, 5/12, 3/4; zeta = -, -17/60, -5/12.  Since gamma1 + zeta2 = 1/4 and
 // zeta3 = -gamma2, the step is exactly
@@ -222,6 +231,9 @@ template <typename T> hipError_t launch_rk3_substep_fast(const Rk3Args<T> &a, hi
 // no Bounded frame: Bounded members run the wall kernel on every tile).  The launcher sets a.fold.
 template <typename T> hipError_t launch_tendency_ensemble_fast(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_tendency_ensemble_strict(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
+// the same stage with per-member (g, f, dt): the PAR instantiations of the same kernels, same plan, same member mapping
+template <typename T> hipError_t launch_ensemble_params_stage_fast(const EnsParTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
+template <typename T> hipError_t launch_ensemble_params_stage_strict(const EnsParTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 // internal twins of swmhd_tendencies_rk3_* and swmhd_fill_halo_periodic_multi_* for the slab driver (ring.hip), same argument checks
 // and return codes; the first serves rows [j0, j1) and [j0b, j1b) of one RK3 stage in ONE launch where the kernel chosen supports it
 // (an empty second range: exactly the exported call)
@@ -239,10 +251,12 @@ int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, lon
 template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, hipStream_t s);
 
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
-// rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE
+// rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
+// (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read
 template <typename T>
 hipError_t launch_diagnostics(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int j0, int j1, long sy, T dx, T dy,
-                              T grav, T href, int form, double *workspace, double *out, hipStream_t s, int members = 0, long stride_m = 0);
+                              T grav, T href, int form, double *workspace, double *out, hipStream_t s, int members = 0, long stride_m = 0,
+                              const T *params = nullptr);
 
 // Periodic "gather on read": with TendArgs::wrap the tendency kernels map a halo index to its periodic image in the interior when
 // they LOAD (one integer select per row / per lane, outside the arithmetic), so the state needs no halo-fill launch between RK3

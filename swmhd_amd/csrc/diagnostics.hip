@@ -39,7 +39,13 @@ struct DiagArgsEns : DiagArgs<T> {
     long stride_m;
     int nb;
 };
-template <typename T, bool ENS> using DiagArgsT = std::conditional_t<ENS, DiagArgsEns<T>, DiagArgs<T>>;
+// Per-member g (swmhd_ensemble_diagnostics_params): member m's g is params[3 m], read when the kernel runs; grav is not read.
+template <typename T>
+struct DiagArgsPar : DiagArgsEns<T> {
+    const T *params;
+};
+template <typename T, bool ENS, bool PAR = false>
+using DiagArgsT = std::conditional_t<PAR, DiagArgsPar<T>, std::conditional_t<ENS, DiagArgsEns<T>, DiagArgs<T>>>;
 
 __device__ __forceinline__ void fold(double *acc, const double *v) {
     acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2];
@@ -64,13 +70,15 @@ __device__ void block_reduce(double *acc, double (*sm)[NQ]) {
     }
 }
 
-template <typename T, bool ENS = false>
-__global__ __launch_bounds__(NT) void k_diag_partial(DiagArgsT<T, ENS> a) {
+template <typename T, bool ENS = false, bool PAR = false>
+__global__ __launch_bounds__(NT) void k_diag_partial(DiagArgsT<T, ENS, PAR> a) {
+    static_assert(ENS || !PAR, "per-member g needs an ensemble launch");
     __shared__ double sm[NT][NQ];
     if constexpr (ENS) {
         const long o = (long)blockIdx.y * a.stride_m;
         a.q1 += o; a.q2 += o; a.h += o; a.A += o;
         a.part += (long)blockIdx.y * a.nb * NQ;
+        if constexpr (PAR) a.grav = a.params[(long)ENS_NPARAMS * blockIdx.y];   // potential energy is the only use of g
     }
     double acc[NQ] = {0, 0, 0, 0, 0, 0, 1e300};
     const double rdx = 1.0 / (double)a.dx, rdy = 1.0 / (double)a.dy;
@@ -140,7 +148,8 @@ __global__ __launch_bounds__(NT) void k_diag_final(DiagArgsT<T, ENS> a) {
 
 template <typename T>
 hipError_t launch_diagnostics(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int j0, int j1, long sy, T dx, T dy,
-                              T grav, T href, int form, double *workspace, double *out, hipStream_t s, int members, long stride_m) {
+                              T grav, T href, int form, double *workspace, double *out, hipStream_t s, int members, long stride_m,
+                              const T *params) {
     DiagArgs<T> a{q1, q2, h, A, Nx, Ny, j0, j1, sy, dx, dy, grav, href, form, workspace, out};
     if (members > 0) {
         DiagArgsEns<T> e;
@@ -149,7 +158,13 @@ hipError_t launch_diagnostics(const T *q1, const T *q2, const T *h, const T *A, 
         const long ncell = (long)Nx * (j1 - j0);
         e.nb = ncell >= (long)NB * NT ? NB : (int)((ncell + NT - 1) / NT);
         if (e.nb < 1) e.nb = 1;
-        hipLaunchKernelGGL((k_diag_partial<T, true>), dim3(e.nb, members), dim3(NT), 0, s, e);
+        if (params) {
+            DiagArgsPar<T> p;
+            static_cast<DiagArgsEns<T> &>(p) = e;
+            p.params = params;
+            hipLaunchKernelGGL((k_diag_partial<T, true, true>), dim3(e.nb, members), dim3(NT), 0, s, p);
+        } else
+            hipLaunchKernelGGL((k_diag_partial<T, true>), dim3(e.nb, members), dim3(NT), 0, s, e);
         hipLaunchKernelGGL((k_diag_final<T, true>), dim3(members), dim3(NT), 0, s, e);
         return hipGetLastError();
     }
@@ -158,9 +173,9 @@ hipError_t launch_diagnostics(const T *q1, const T *q2, const T *h, const T *A, 
     return hipGetLastError();
 }
 template hipError_t launch_diagnostics<double>(const double *, const double *, const double *, const double *, int, int, int, int, long,
-                                               double, double, double, double, int, double *, double *, hipStream_t, int, long);
+                                               double, double, double, double, int, double *, double *, hipStream_t, int, long, const double *);
 template hipError_t launch_diagnostics<float>(const float *, const float *, const float *, const float *, int, int, int, int, long, float,
-                                              float, float, float, int, double *, double *, hipStream_t, int, long);
+                                              float, float, float, int, double *, double *, hipStream_t, int, long, const float *);
 
 }  // namespace swmhd
 

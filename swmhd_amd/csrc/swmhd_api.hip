@@ -19,6 +19,9 @@ struct Ens {
     int members;
     int64_t stride_m;
     bool bc = false;
+    // the *_params calls: `params` is the DEVICE table of members x (g, f, dt) in the call's element type; the scalars are not used
+    bool par = false;
+    const void *params = nullptr;
 };
 constexpr int ENS_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_RK3_ANCHOR;
 constexpr int ENS_NOTSUP = SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_LEAVE_ROOM;
@@ -27,6 +30,7 @@ constexpr int ENS_BC_NOTSUP = SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMH
 // the checks of the ensemble itself (the caller's single-grid checks follow): member count, member stride, flags
 inline int ens_check(const Ens &e, int Ny, int Hy, int64_t sy, int flags) {
     const int ok = e.bc ? ENS_BC_FLAGS : ENS_FLAGS, notsup = e.bc ? ENS_BC_NOTSUP : ENS_NOTSUP;
+    if (e.par && !e.params) return SWMHD_EINVAL;
     if (e.members < 1 || e.members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
     if (Ny <= 0 || Hy < 0 || sy <= 0 || e.stride_m < ((int64_t)Ny + 2 * Hy) * sy) return SWMHD_EINVAL;
     if (flags & ~(ok | notsup)) return SWMHD_EINVAL;
@@ -219,6 +223,13 @@ int tend_common(const T *q1, const T *q2, const T *h, const T *A, T *G1, T *G2, 
         EnsTendArgs<T> e;
         static_cast<TendArgs<T> &>(e) = a;
         e.stride_m = (long)ens->stride_m; e.members = ens->members; e.fold = 1;
+        if (ens->par) {   // (g, f, dt and the products of dt come from the table, in the kernel)
+            EnsParTendArgs<T> ep;
+            static_cast<EnsTendArgs<T> &>(ep) = e;
+            ep.params = static_cast<const T *>(ens->params);
+            return hiprc((flags & SWMHD_STRICT) ? launch_ensemble_params_stage_strict<T>(ep, formulation, lorentz, s)
+                                                : launch_ensemble_params_stage_fast<T>(ep, formulation, lorentz, s));
+        }
         return hiprc((flags & SWMHD_STRICT) ? launch_tendency_ensemble_strict<T>(e, formulation, lorentz, s)
                                             : launch_tendency_ensemble_fast<T>(e, formulation, lorentz, s));
     }
@@ -318,7 +329,8 @@ int diag_common(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny
     if (Hx < 1 || Hy < 1) return SWMHD_EHALO;
     const long off = (long)Hy * sy + Hx;
     return hiprc(launch_diagnostics<T>(q1 + off, q2 + off, h + off, A + off, Nx, Ny, j0, j1, (long)sy, dx, dy, grav, href, form, ws,
-                                       out, (hipStream_t)stream, ens ? ens->members : 0, ens ? (long)ens->stride_m : 0));
+                                       out, (hipStream_t)stream, ens ? ens->members : 0, ens ? (long)ens->stride_m : 0,
+                                       ens && ens->par ? static_cast<const T *>(ens->params) : nullptr));
 }
 
 }  // namespace
@@ -342,6 +354,7 @@ int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, lon
 }
 static_assert(GM_IS_PREV_STATE == SWMHD_GM_IS_PREV_STATE, "common.hpp mirrors swmhd.h");
 static_assert(RK3_ANCHOR == SWMHD_RK3_ANCHOR, "common.hpp mirrors swmhd.h");
+static_assert(ENS_NPARAMS == SWMHD_ENSEMBLE_NPARAMS, "common.hpp mirrors swmhd.h");
 #define SW_INST(T)                                                                                                                   \
     template int tendencies_rk3_two_ranges<T>(const T *const *, T *const *, T *const *, const T *const *, int, int, int, int, long, T, \
                                               T, T, T, int, int, T, T, T, int, int, int, int, int, int, void *);                      \
@@ -496,6 +509,37 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
         const Ens e{members, stride_m, true};                                                                          \
         return step_common<T>(q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, nsteps, flags, \
                               state_in_alt, stream, &e, true, gradient);                                               \
+    }                                                                                                                  \
+    int swmhd_ensemble_tendencies_rk3_params_##sfx(const T *const *q, T *const *qnew, T *const *Gn, const T *const *Gm, \
+                                                   int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy,       \
+                                                   int64_t sy, T dx, T dy, const T *params, int formulation, int lorentz, \
+                                                   T gamma, T zeta, int store_G, int flags, void *stream) {              \
+        const Ens e{members, stride_m, false, true, params};                                                           \
+        return tend_rk3_common<T>(q, qnew, Gn, Gm, Nx, Ny, Hx, Hy, sy, dx, dy, T(0), T(0), formulation, lorentz, T(0),  \
+                                  gamma, zeta, store_G, 0, Ny, flags, stream, 0, 0, &e);                                \
+    }                                                                                                                  \
+    int swmhd_ensemble_step_rk3_params_##sfx(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int members,    \
+                                             int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy,  \
+                                             const T *params, int formulation, int lorentz, int nsteps, int flags,      \
+                                             int *state_in_alt, void *stream) {                                         \
+        const Ens e{members, stride_m, false, true, params};                                                           \
+        return step_common<T>(q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, T(0), T(0), formulation, lorentz, T(0),     \
+                              nsteps, flags, state_in_alt, stream, &e);                                                 \
+    }                                                                                                                  \
+    int swmhd_ensemble_step_rk3_bc_params_##sfx(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int members, \
+                                                int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx,     \
+                                                T dy, const T *params, int formulation, int lorentz, int nsteps,        \
+                                                const T *gradient, int flags, int *state_in_alt, void *stream) {        \
+        const Ens e{members, stride_m, true, true, params};                                                            \
+        return step_common<T>(q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, T(0), T(0), formulation, lorentz, T(0),     \
+                              nsteps, flags, state_in_alt, stream, &e, true, gradient);                                 \
+    }                                                                                                                  \
+    int swmhd_ensemble_diagnostics_params_##sfx(const T *q1, const T *q2, const T *h, const T *A, int members,         \
+                                                int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx,     \
+                                                T dy, const T *params, T href, int form, double *ws, double *out,       \
+                                                void *stream) {                                                         \
+        const Ens e{members, stride_m, false, true, params};                                                           \
+        return diag_common<T>(q1, q2, h, A, Nx, Ny, Hx, Hy, sy, dx, dy, T(0), href, form, 0, Ny, ws, out, stream, &e);  \
     }
 
 SWMHD_DEF_LORENTZ(f64, double)

@@ -61,16 +61,16 @@ static hipError_t launch_march(const TendLaunch &l, TendArgs<T> &a, int formulat
 }
 
 // LDS-tiled kernel, 64 x 4 threads, RY output rows per thread; ENS: every tile of a.members members (grid folded or 2-D, see EnsTendArgs)
-template <typename T, int RY, bool BND = false, bool ENS = false>
-static hipError_t launch_tile(const TileArgs<T, ENS> &a, int formulation, int lorentz, int ntx, int nty, hipStream_t s) {
+template <typename T, int RY, bool BND = false, bool ENS = false, bool PAR = false>
+static hipError_t launch_tile(const TileArgs<T, ENS, PAR> &a, int formulation, int lorentz, int ntx, int nty, hipStream_t s) {
     constexpr int TX = TILE_X, TYB = 4;
     dim3 grid(ntx * nty);
     const dim3 block(TX, TYB);
     if constexpr (ENS) grid = a.fold ? dim3(ntx * nty * a.members) : dim3(ntx * nty, a.members);
-    if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY, BND, ENS>), grid, block, 0, s, a, ntx, nty);
+    if (formulation == 1 && lorentz == 1) hipLaunchKernelGGL((k_tendency_tile<T, 1, 1, TX, TYB, RY, BND, ENS, PAR>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 1 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 1, 0, TX, TYB, RY, BND, ENS, PAR>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0 && lorentz == 2) hipLaunchKernelGGL((k_tendency_tile<T, 0, 2, TX, TYB, RY, BND, ENS, PAR>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0 && lorentz == 0) hipLaunchKernelGGL((k_tendency_tile<T, 0, 0, TX, TYB, RY, BND, ENS, PAR>), grid, block, 0, s, a, ntx, nty);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -104,8 +104,8 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
 // the fused substep differently in this instantiation (an ulp in a few cells per stage), within the fast tolerances.
 // Members are folded into blockIdx.x by default.  Tile height and mapping were measured (tools/time_ensemble.py, profiles/ensemble/).
 // Knob (read once; measurement only): SWMHD_ENS_MAP = 1 folds the member into blockIdx.x, 2 makes it blockIdx.y.
-template <typename T>
-hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s) {
+template <typename T, bool PAR>
+static hipError_t launch_ensemble_stage(const TileArgs<T, true, PAR> &a, int formulation, int lorentz, hipStream_t s) {
     static int map_cache = 0;
     if (a.j1 <= a.j0 || a.members <= 0) return hipSuccess;
     TendPlanIn in = plan_input<T>(a, formulation, a.members);
@@ -116,11 +116,22 @@ hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)(const EnsTendArgs<
     const int map = env_knob("SWMHD_ENS_MAP", map_cache);
     const long blocks = (long)l.ntx * l.nty * a.members;
     if (blocks >= (1L << 31) || (map == 2 && a.members > 65535)) return hipErrorInvalidConfiguration;
-    EnsTendArgs<T> e = a;
+    TileArgs<T, true, PAR> e = a;
     e.fold = map == 2 ? 0 : 1;
-    if (l.kernel == TendKernel::TILE_BOUNDED) return launch_tile<T, 2, true, true>(e, formulation, lorentz, l.ntx, l.nty, s);
-    return l.kernel == TendKernel::TILE_RY1 ? launch_tile<T, 1, false, true>(e, formulation, lorentz, l.ntx, l.nty, s)
-                                            : launch_tile<T, 2, false, true>(e, formulation, lorentz, l.ntx, l.nty, s);
+    if (l.kernel == TendKernel::TILE_BOUNDED) return launch_tile<T, 2, true, true, PAR>(e, formulation, lorentz, l.ntx, l.nty, s);
+    return l.kernel == TendKernel::TILE_RY1 ? launch_tile<T, 1, false, true, PAR>(e, formulation, lorentz, l.ntx, l.nty, s)
+                                            : launch_tile<T, 2, false, true, PAR>(e, formulation, lorentz, l.ntx, l.nty, s);
+}
+template <typename T>
+hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)(const EnsTendArgs<T> &a, int formulation, int lorentz, hipStream_t s) {
+    return launch_ensemble_stage<T, false>(a, formulation, lorentz, s);
+}
+// The same stage with per-member (g, f, dt) from a device table: the PAR instantiation of whichever kernel the plan names (the plan
+// does not depend on the parameters), same member mapping.
+template <typename T>
+hipError_t LAUNCH_NAME(launch_ensemble_params_stage_, LAUNCH_SFX)(const EnsParTendArgs<T> &a, int formulation, int lorentz, hipStream_t s) {
+    if (!a.params) return hipErrorInvalidValue;
+    return launch_ensemble_stage<T, true>(a, formulation, lorentz, s);
 }
 
 template <typename T>
@@ -134,6 +145,8 @@ template hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)<double>(const Tend
 template hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)<float>(const TendArgs<float> &, int, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)<double>(const EnsTendArgs<double> &, int, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_tendency_ensemble_, LAUNCH_SFX)<float>(const EnsTendArgs<float> &, int, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_ensemble_params_stage_, LAUNCH_SFX)<double>(const EnsParTendArgs<double> &, int, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_ensemble_params_stage_, LAUNCH_SFX)<float>(const EnsParTendArgs<float> &, int, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_rk3_substep_, LAUNCH_SFX)<double>(const Rk3Args<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_rk3_substep_, LAUNCH_SFX)<float>(const Rk3Args<float> &, hipStream_t);
 

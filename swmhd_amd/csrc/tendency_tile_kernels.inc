@@ -27,8 +27,8 @@ constexpr bool STRICT = (SWMHD_STRICT != 0);
 
 // Ensemble workgroup (ENS variant): pick the member, point every field of `a` at it, return the tile index within the member.
 template <typename T>
-__device__ __forceinline__ unsigned ens_member(EnsTendArgs<T> &a, unsigned ntiles) {
-    unsigned m, t;
+__device__ __forceinline__ unsigned ens_member(EnsTendArgs<T> &a, unsigned ntiles, unsigned &m) {
+    unsigned t;
     if (a.fold) {
         const unsigned L = xcd_remap(blockIdx.x, ntiles * (unsigned)a.members);
         m = L / ntiles; t = L - m * ntiles;
@@ -46,13 +46,27 @@ __device__ __forceinline__ unsigned ens_member(EnsTendArgs<T> &a, unsigned ntile
     return t;
 }
 
+// Per-member parameters (PAR variant): (g, f, dt) of member m from the device table, and the products of dt the host forms for one
+// grid (tend_common: dtg = dt * gamma, dtw = dt * zeta in the first anchored stage), each one multiply in T of the same operands.  m
+// comes from blockIdx alone, so the address is workgroup-uniform and the three values arrive by scalar loads: no VGPR holds them.
+// (cu and cg, the coefficient form of the marching kernels, are not read by this kernel.)
+template <typename T>
+__device__ __forceinline__ void ens_member_params(EnsParTendArgs<T> &a, unsigned m) {
+    const T *p = a.params + (long)ENS_NPARAMS * m;
+    a.grav = p[0]; a.fcor = p[1]; a.dt = p[2];
+    a.dtg = a.dt * a.gamma;
+    a.dtw = a.dt * a.zeta;
+}
+
 // FORM: 0 conservative, 1 vector invariant.  LOR: 0 none, 1 Jacobian (FORM 1 only), 2 divergence (FORM 0 only).
 // BND: at least one direction is Bounded -- reconstructions near walls drop to the boundary schemes (sw_device.inc) and the divergence-
 // form Lorentz fluxes take the reference's wall branches (sw_mhd_divergence_functions.jl:42-53,66-77,90-101,114-125).  With
 // BND = false every order is the compile-time constant 5 and the code is the periodic kernel.
 // ENS: ensemble launch (EnsTendArgs) -- the workgroup's member offsets every field pointer; otherwise the body is the same.
-template <typename T, int FORM, int LOR, int TX, int TYB, int RY, bool BND = false, bool ENS = false>
-__global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS> a, int ntx, int nty) {
+// PAR (with ENS): the member also brings its own g, f and dt (EnsParTendArgs, ens_member_params); the body is the same again.
+template <typename T, int FORM, int LOR, int TX, int TYB, int RY, bool BND = false, bool ENS = false, bool PAR = false>
+__global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS, PAR> a, int ntx, int nty) {
+    static_assert(ENS || !PAR, "per-member parameters need an ensemble launch");
     constexpr int TY = TYB * RY, NT = TX * TYB;
     constexpr int W = TX + 6, HH = TY + 6;
     __shared__ T s1[HH][W];   // u | uh   (Face, Center)
@@ -68,8 +82,11 @@ __global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS> a, i
     __shared__ T sL3[LOR == 2 ? LH : 1][LOR == 2 ? LW : 1];
 
     unsigned bid;
-    if constexpr (ENS) bid = ens_member<T>(a, (unsigned)(ntx * nty));
-    else bid = xcd_remap(blockIdx.x, (unsigned)(ntx * nty));
+    if constexpr (ENS) {
+        unsigned m;
+        bid = ens_member<T>(a, (unsigned)(ntx * nty), m);
+        if constexpr (PAR) ens_member_params<T>(a, m);
+    } else bid = xcd_remap(blockIdx.x, (unsigned)(ntx * nty));
     // tile rows of the optional second row range follow those of the first
     const int tyi = (int)(bid / ntx), ntya = (a.j1 - a.j0 + TY - 1) / TY;
     const bool second = tyi >= ntya;

@@ -2,8 +2,8 @@
 
 The reference's runs are sweeps of small grids -- 64^2 and 128^2, two formulations, initial conditions that differ in the amplitude of A
 (SWMHD_example.jl:11,35-37; divergence_sw_mhd.jl:11,32-34; its twelve energy_plots/*).  A 64^2 grid gives the chip 16 workgroups per
-stage; an ensemble of B members gives it 16 B, in the same three launches per RK3 step.  Every member has the grid, physics, precision
-and dt of the ensemble; members differ only in their state.  Member m of field f is row m of a (members, Ny+2Hy, Nx+2Hx) tensor: the
+stage; an ensemble of B members gives it 16 B, in the same three launches per RK3 step.  Every member has the grid, formulation, forcing
+and precision of the ensemble; members differ in their state and, where sequences are given, in g, f and dt.  Member m of field f is row m of a (members, Ny+2Hy, Nx+2Hx) tensor: the
 halo-padded parent a ShallowWaterModel would hold.  `member(m)` hands one member to the single-grid tools (checkpoints, inspection).
 
 BoundedShallowWaterEnsemble does the same for a grid with Bounded directions, each member with its own boundary conditions: the
@@ -23,10 +23,31 @@ from .model import ShallowWaterModel, VectorInvariantFormulation
 LOCS = ((Face, Center), (Center, Face), (Center, Center), (Center, Center))
 
 
+def is_per_member(v):
+    """True for a sequence (one value per member), False for a scalar."""
+    return isinstance(v, (list, tuple)) or np.ndim(v) > 0
+
+
+def per_member_values(v, members, name):
+    """(values, per_member): float64 array of `members` values from a scalar or a sequence of exactly `members` numbers."""
+    if not is_per_member(v):
+        return np.full(members, float(v)), False
+    arr = np.asarray(v, dtype=np.float64)
+    if arr.ndim != 1 or arr.shape[0] != members:
+        raise _lib.SwmhdError(f"{name}: {arr.size if arr.ndim == 1 else arr.shape} values for {members} members (a scalar or one per member)")
+    return arr.copy(), True
+
+
 class ShallowWaterEnsemble:
     """`members` ShallowWaterModels of one periodic grid in one set of tensors.  Arguments as ShallowWaterModel's; `member_stride`
     (elements, >= (Ny+2Hy)(Nx+2Hx)) pitches the members apart inside one allocation (the gaps are never read or written).
-    fuse_halo=False fills every member's halos after each stage instead of reading the periodic images (ShallowWaterModel's option)."""
+    fuse_halo=False fills every member's halos after each stage instead of reading the periodic images (ShallowWaterModel's option).
+
+    Parameter sweeps: gravitational_acceleration and coriolis_f take a scalar or a sequence of `members` values, and so does the dt of
+    time_step, time_steps and capture_graph.  As soon as anything is per member the ensemble holds `parameters`, the (members, 3)
+    device table of (g, f, dt) in its dtype, and steps through the swmhd_ensemble_*_params entry points; with scalars everywhere it
+    calls exactly what it always called.  `clock_times` has every member's model time; `clock_time` is their common value and raises
+    once per-member time steps have made them differ."""
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
@@ -41,7 +62,12 @@ class ShallowWaterEnsemble:
         self.members = int(members)
         if not 1 <= self.members <= _lib.ENSEMBLE_MAX_MEMBERS:
             raise _lib.SwmhdError(f"members = {members}: 1 .. {_lib.ENSEMBLE_MAX_MEMBERS}")
-        self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
+        # checked before anything touches a device
+        self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
+        self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
+        self.grid = grid
+        self.g = self.g_values if g_seq else float(gravitational_acceleration)
+        self.f = self.f_values if f_seq else float(coriolis_f)
         self.formulation, self.strict, self.dtype = formulation, strict, dtype
         self.lorentz_forcing = lorentz_forcing
         self.form_code = _lib.VECTOR_INVARIANT if formulation == VectorInvariantFormulation else _lib.CONSERVATIVE
@@ -67,8 +93,68 @@ class ShallowWaterEnsemble:
             return flat.as_strided((self.members, Py, Px), (self.stride_m, Px, 1))
         self._state, self._alt = [mk() for _ in LOCS], [mk() for _ in LOCS]
         self.Gn, self.Gm = [mk() for _ in LOCS], [mk() for _ in LOCS]
+        self.clock_times = np.zeros(self.members)
         self.clock_time, self.iteration = 0.0, 0
         self._L = _lib.lib()
+        self.parameters, self._table_dt = None, None
+        if g_seq or f_seq:
+            self._make_parameters()
+
+    # --- per-member parameters and clocks ------------------------------------------------------------------------
+    def _make_parameters(self):
+        """The device table (members, 3) of (g, f, dt); the dt column is written by _set_table_dt before the first step."""
+        host = np.stack([self.g_values, self.f_values, np.zeros(self.members)], axis=1)
+        self.parameters = torch.from_numpy(host).to(device=self._state[0].device, dtype=self.dtype)
+        self._table_dt = None
+        self._graph = None      # (a graph captured with scalar arguments does not read the table)
+
+    def _dt_values(self, dt):
+        """None for a scalar dt on an ensemble without per-member parameters (the scalar entry points), else the dt of every member."""
+        if not is_per_member(dt) and self.parameters is None:
+            return None
+        return per_member_values(dt, self.members, "dt")[0]
+
+    def _set_table_dt(self, dts):
+        """Write the dt column of the table (stream-ordered) unless it holds these values already."""
+        if self.parameters is None:
+            self._make_parameters()
+        if self._table_dt is None or not np.array_equal(self._table_dt, dts):
+            self.parameters[:, 2].copy_(torch.from_numpy(dts).to(self.dtype))
+            self._table_dt = dts.copy()
+
+    @staticmethod
+    def _dt_key(dt):
+        return tuple(float(x) for x in dt) if is_per_member(dt) else dt
+
+    @property
+    def clock_time(self):
+        """The model time all members share; SwmhdError once per-member time steps have made their times differ (see clock_times)."""
+        if self._clocks_differ:
+            raise _lib.SwmhdError("clock_time: the members' times differ after per-member time steps; read clock_times")
+        return self._clock_time
+
+    @clock_time.setter
+    def clock_time(self, t):
+        self._clock_time, self._clocks_differ = t, False
+        self.clock_times[:] = t
+
+    def _advance_clock(self, n, dt, dts):
+        if dts is None or np.all(dts == dts[0]):
+            step = dt if dts is None else (dt if not is_per_member(dt) else float(dts[0]))
+            if not self._clocks_differ:
+                self._clock_time += n * step
+                self.clock_times[:] = self._clock_time
+                return
+            dts = np.full(self.members, float(step))
+        self.clock_times += n * dts
+        self._clocks_differ = True
+
+    def _clock_state(self):
+        return self._clock_time, self._clocks_differ, self.clock_times.copy()
+
+    def _restore_clock(self, state):
+        self._clock_time, self._clocks_differ = state[0], state[1]
+        self.clock_times[:] = state[2]
 
     def _check_topology(self, grid):
         if grid.topo_codes() != (_lib.PERIODIC, _lib.PERIODIC):
@@ -131,30 +217,43 @@ class ShallowWaterEnsemble:
                      _lib.HALO_X | _lib.HALO_Y, _stream_ptr()), "swmhd_ensemble_fill_halo_periodic")
 
     # --- time stepping (the native ensemble step driver: 3 launches per RK3 step for all members) ---------------------
-    def _native_steps(self, dt, n):
+    def _enqueue_steps(self, dt, n, swapped):
+        """n steps through swmhd_ensemble_step_rk3 (dt: the scalar) or, with dt None, swmhd_ensemble_step_rk3_params (the table)."""
         g = self.grid
+        head = (self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(self.Gm), self.members, self.stride_m,
+                g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy)
+        tail = (n, self._flags | self._rwrap, ctypes.byref(swapped), _stream_ptr())
+        if dt is not None:
+            f = getattr(self._L, f"swmhd_ensemble_step_rk3_{self.sfx}")
+            _lib.check(f(*head, self.g, self.f, self.form_code, self.lorentz_code, dt, *tail), "swmhd_ensemble_step_rk3")
+        else:
+            f = getattr(self._L, f"swmhd_ensemble_step_rk3_params_{self.sfx}")
+            _lib.check(f(*head, self.parameters.data_ptr(), self.form_code, self.lorentz_code, *tail), "swmhd_ensemble_step_rk3_params")
+
+    def _native_steps(self, dt, n):
+        dts = self._dt_values(dt)
+        if dts is not None:
+            self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        f = getattr(self._L, f"swmhd_ensemble_step_rk3_{self.sfx}")
-        rc = f(self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(self.Gm), self.members, self.stride_m,
-               g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
-               self._flags | self._rwrap, ctypes.byref(swapped), _stream_ptr())
-        _lib.check(rc, "swmhd_ensemble_step_rk3")
+        self._enqueue_steps(dt if dts is None else None, n, swapped)
         if swapped.value:
             self._state, self._alt = self._alt, self._state
             self.Gn, self.Gm = self.Gm, self.Gn
         if n > 0 and self._rwrap:
             self._halo_stale = True
-        self.clock_time += n * dt
+        self._advance_clock(n, dt, dts)
         self.iteration += n
 
     def time_step(self, dt):
         self._native_steps(dt, 1)
 
     def capture_graph(self, dt):
-        """Capture TWO RK3 steps of every member into one HIP graph (ShallowWaterModel.capture_graph: same role tracking)."""
+        """Capture TWO RK3 steps of every member into one HIP graph (ShallowWaterModel.capture_graph: same role tracking).  dt: a scalar
+        or one value per member; with per-member parameters the graph reads the table at replay, and time_steps keeps its dt column
+        at the captured values."""
         self._ensure_halos()
         keep = [t.clone() for t in self._state] + [t.clone() for t in self.Gm]
-        t0, i0 = self.clock_time, self.iteration
+        t0, i0 = self._clock_state(), self.iteration
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -163,12 +262,13 @@ class ShallowWaterEnsemble:
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self.time_step(dt); self.time_step(dt)
-        self._graph_dt = dt
+        self._graph_dt = self._dt_key(dt)
         self._graph_roles = self._roles()
         for t, k in zip(self._state + self.Gm, keep):
             t.copy_(k)
         self._halo_stale = False
-        self.clock_time, self.iteration = t0, i0
+        self._restore_clock(t0)
+        self.iteration = i0
         return self
 
     def _roles(self):
@@ -177,14 +277,18 @@ class ShallowWaterEnsemble:
     def time_steps(self, n, dt):
         """n RK3 steps of every member: graph replays (2 steps each) when a graph was captured for this dt, else the step driver."""
         gr = getattr(self, "_graph", None)
-        if gr is not None and self._graph_dt == dt and n >= 2 and self._roles() != self._graph_roles:
+        same_dt = gr is not None and self._graph_dt == self._dt_key(dt)     # the captured dt VALUES, scalar or per member
+        if same_dt and n >= 2 and self._roles() != self._graph_roles:
             self._native_steps(dt, 1)           # an odd number of steps since capture: one eager step restores the captured roles
             n -= 1
-        if gr is not None and self._graph_dt == dt and self._roles() == self._graph_roles:
+        if same_dt and n >= 2 and self._roles() == self._graph_roles:
+            dts = self._dt_values(dt)
+            if dts is not None:
+                self._set_table_dt(dts)         # the graph reads the table when it runs
             for _ in range(n // 2):
                 gr.replay()
                 self._halo_stale = self._halo_stale or bool(self._rwrap)
-                self.clock_time += 2 * dt
+                self._advance_clock(2, dt, dts)
                 self.iteration += 2
             n = n % 2
         if n > 0:
@@ -201,10 +305,12 @@ class ShallowWaterEnsemble:
         if not hasattr(self, "_diag_ws"):
             self._diag_ws = torch.empty(_lib.ensemble_diag_workspace(self.members, g.Nx, g.Ny), dtype=torch.float64, device=out.device)
         q = self._state
-        f = getattr(self._L, f"swmhd_ensemble_diagnostics_{self.sfx}")
+        par = self.parameters is not None       # potential energy with each member's g, from the table
+        f = getattr(self._L, f"swmhd_ensemble_diagnostics_{'params_' if par else ''}{self.sfx}")
         rc = f(q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), q[3].data_ptr(), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy,
-               q[0].stride(1), g.dx, g.dy, self.g, h_ref, self.form_code, self._diag_ws.data_ptr(), out.data_ptr(), _stream_ptr())
-        _lib.check(rc, "swmhd_ensemble_diagnostics")
+               q[0].stride(1), g.dx, g.dy, self.parameters.data_ptr() if par else self.g, h_ref, self.form_code,
+               self._diag_ws.data_ptr(), out.data_ptr(), _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_diagnostics_params" if par else "swmhd_ensemble_diagnostics")
         return out
 
     def diagnostics(self, h_ref=1.0):
@@ -225,7 +331,7 @@ class ShallowWaterEnsemble:
 
     # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
     def member(self, m):
-        """A ShallowWaterModel holding a copy of member m (state with halos, G-, clock and iteration)."""
+        """A ShallowWaterModel holding a copy of member m (state with halos, G-, the member's g, f, clock and iteration)."""
         if not 0 <= m < self.members:
             raise IndexError(f"member {m} of {self.members}")
         self._ensure_halos()
@@ -234,12 +340,12 @@ class ShallowWaterEnsemble:
             fld.data.copy_(t[m])
         for fld, t in zip(model.Gm, self.Gm):
             fld.data.copy_(t[m])
-        model.clock_time, model.iteration = self.clock_time, self.iteration
+        model.clock_time, model.iteration = float(self.clock_times[m]), self.iteration
         return model
 
     def _member_model(self, m):
-        return ShallowWaterModel(self.grid, self.g, self.f, formulation=self.formulation, lorentz_forcing=self.lorentz_forcing,
-                                 dtype=self.dtype, device=self._state[0].device, strict=self.strict)
+        return ShallowWaterModel(self.grid, float(self.g_values[m]), float(self.f_values[m]), formulation=self.formulation,
+                                 lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
@@ -307,21 +413,19 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
         _lib.check(f(self._ptrs(self._state), 4, self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), tx, ty,
                      0b0001, 0b0010, self.gradients.data_ptr(), g.dx, g.dy, _stream_ptr()), "swmhd_ensemble_fill_halo")
 
-    def _native_steps(self, dt, n):
+    def _enqueue_steps(self, dt, n, swapped):
         g = self.grid
-        swapped = ctypes.c_int(0)
-        f = getattr(self._L, f"swmhd_ensemble_step_rk3_bc_{self.sfx}")
-        rc = f(self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(self.Gm), self.members, self.stride_m,
-               g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy, self.g, self.f, self.form_code, self.lorentz_code, dt, n,
-               self.gradients.data_ptr(), self._flags | self._kwrap, ctypes.byref(swapped), _stream_ptr())
-        _lib.check(rc, "swmhd_ensemble_step_rk3_bc")
-        if swapped.value:
-            self._state, self._alt = self._alt, self._state
-            self.Gn, self.Gm = self.Gm, self.Gn
-        self.clock_time += n * dt
-        self.iteration += n
+        head = (self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(self.Gm), self.members, self.stride_m,
+                g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy)
+        tail = (n, self.gradients.data_ptr(), self._flags | self._kwrap, ctypes.byref(swapped), _stream_ptr())
+        if dt is not None:
+            f = getattr(self._L, f"swmhd_ensemble_step_rk3_bc_{self.sfx}")
+            _lib.check(f(*head, self.g, self.f, self.form_code, self.lorentz_code, dt, *tail), "swmhd_ensemble_step_rk3_bc")
+        else:
+            f = getattr(self._L, f"swmhd_ensemble_step_rk3_bc_params_{self.sfx}")
+            _lib.check(f(*head, self.parameters.data_ptr(), self.form_code, self.lorentz_code, *tail), "swmhd_ensemble_step_rk3_bc_params")
 
     def _member_model(self, m):
-        return ShallowWaterModel(self.grid, self.g, self.f, formulation=self.formulation, lorentz_forcing=self.lorentz_forcing,
-                                 dtype=self.dtype, device=self._state[0].device, strict=self.strict,
+        return ShallowWaterModel(self.grid, float(self.g_values[m]), float(self.f_values[m]), formulation=self.formulation,
+                                 lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
                                  boundary_conditions=self._member_bcs[m])

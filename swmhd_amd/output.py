@@ -180,7 +180,11 @@ def run(model, dt, stop_time=None, stop_iteration=None, writers=()):
     """run!(simulation): step `model` (a ShallowWaterModel or an ensemble) to stop_time or stop_iteration with the writers attached.
     Every writer gets a frame of the state the run starts from (as Oceananigans' writers do at iteration 0) and then one whenever its
     schedule is due: model.time_steps(n, dt) -- graph replays when a graph was captured for dt -- followed by one output_fields launch.
-    Nothing here synchronises with the device.  Refuses up front (SwmhdError, before any step) when a writer's capacity is too small."""
+    Nothing here synchronises with the device.  Refuses up front (SwmhdError, before any step) when a writer's capacity is too small.
+    An ensemble with per-member g and f runs here under a scalar dt; a per-member dt is refused."""
+    if isinstance(dt, (list, tuple)) or getattr(dt, "ndim", 0) > 0:
+        raise _lib.SwmhdError("run: a per-member dt is not supported (schedules in time units across members whose clocks diverge); "
+                              "step the ensemble with time_steps(n, dts) and write frames by iteration")
     if (stop_time is None) == (stop_iteration is None):
         raise _lib.SwmhdError("run: give stop_time or stop_iteration")
     it0, t0 = model.iteration, model.clock_time
