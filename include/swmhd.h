@@ -446,6 +446,10 @@ int swmhd_ring_launch_times(swmhd_ring *ring, float *ms, int *rows, int capacity
  *   energies already multiplied by dx*dy (sum over ranks = the reference's mean(...)*Lx*Ly); always double.
  * `out` (7 doubles) and `workspace` (SWMHD_DIAG_WORKSPACE doubles) are DEVICE buffers; deterministic summation order.
  * Needs halo >= 1, filled.  For formulation SWMHD_CONSERVATIVE velocities are uh/ℑxᶠh, vh/ℑyᶠh.
+ * Non-finite data: the four extrema PROPAGATE NaN, like the maximum(abs, u), maximum(abs, A), minimum(h) of the reference's callback
+ * (Julia reductions): a NaN in a cell of the row range (for the conservative velocities: in uh, vh or the h they are divided by) makes
+ * that extremum NaN, as it makes the energies it enters NaN; outputs it does not enter keep the bits of the clean data's.  An empty
+ * row range (j_begin == j_end) returns the identity of the reduction: energies 0, maxima 0, min h = 1e300.
  * ---------------------------------------------------------------------------------------------- */
 #define SWMHD_DIAG_NOUT 7
 #define SWMHD_DIAG_WORKSPACE (1024 * 7)

@@ -12,6 +12,8 @@
 //   both               ME = Σ ½ h · ℑyᶜ[Bx² + ℑxyᶜᶠ(By²)] Δx Δy,  Bx = −∂yA/ℑyᶠh @cfc, By = ∂xA/ℑxᶠh @fcc   (:69-70,:72 / :67-68,:75)
 //                      PE = Σ ½ g (h − hᵢ)² Δx Δy                                                                             (:73 / :76)
 //   max|u|, max|v| (divergence driver: u = uh/ℑxᶠh, v = vh/ℑyᶠh), max|A|, min h over the interior                                                            SWMHD_example.jl:47-65
+// Non-finite data: the callback's maximum(abs, u), maximum(abs, A), minimum(h) (SWMHD_example.jl:47-65) are Julia reductions, which
+// PROPAGATE NaN; so do the four extrema here (fold()): one NaN cell in the rows of a call makes that extremum NaN, as the sums become.
 // Two deterministic stages: per-workgroup partials (fixed grid), then one workgroup folds them in index order.
 #include "common.hpp"
 
@@ -47,9 +49,14 @@ struct DiagArgsPar : DiagArgsEns<T> {
 template <typename T, bool ENS, bool PAR = false>
 using DiagArgsT = std::conditional_t<PAR, DiagArgsPar<T>, std::conditional_t<ENS, DiagArgsEns<T>, DiagArgs<T>>>;
 
+// Extrema as Julia's maximum / minimum take them: a NaN in either operand gives NaN (fmax / fmin alone return the other operand, and
+// a run that has blown up would report finite extrema beside NaN energies).  Finite operands: fmax / fmin, unchanged.
+__device__ __forceinline__ double max_nan(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+__device__ __forceinline__ double min_nan(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
+
 __device__ __forceinline__ void fold(double *acc, const double *v) {
     acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2];
-    acc[3] = fmax(acc[3], v[3]); acc[4] = fmax(acc[4], v[4]); acc[5] = fmax(acc[5], v[5]); acc[6] = fmin(acc[6], v[6]);
+    acc[3] = max_nan(acc[3], v[3]); acc[4] = max_nan(acc[4], v[4]); acc[5] = max_nan(acc[5], v[5]); acc[6] = min_nan(acc[6], v[6]);
 }
 
 __device__ void block_reduce(double *acc, double (*sm)[NQ]) {
