@@ -29,6 +29,13 @@ template <typename T> __device__ __forceinline__ T fast_recip(T x) {
     }
 }
 
+// 1/x from v_rcp_f64 and ONE Newton step (2.2e-15 relative, tools/rcp_probe.hip): two FMAs less than fast_recip.  Used only by the fp64
+// vector-invariant marching kernel, whose Lorentz term is held to 1e-13 of its scale; the stand-alone operator kernels keep fast_recip.
+__device__ __forceinline__ double recip_newton1(double x) {
+    const double r = __builtin_amdgcn_rcp(x);
+    return __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
+}
+
 // reference :3   upwind_biased_product(ũ, ψᴸ, ψᴿ) = ((ũ + |ũ|) ψᴸ + (ũ − |ũ|) ψᴿ) / 2
 template <typename T>
 __device__ __forceinline__ T upwind_biased_product(T u, T pL, T pR) {
@@ -63,7 +70,8 @@ __device__ __forceinline__ void jac_centre_B(const AF &A_, const HF &H_, int ii,
     }
 }
 // lorentz_force_func_x/y (:20-26) = jacobian_x/y (:10-18) / face-averaged h, given centre B accessors
-template <typename T, typename AF, typename HF, typename BXF, typename BYF>
+// RCP1 (fast builds, T = double): the two face reciprocals by recip_newton1
+template <typename T, bool RCP1 = false, typename AF, typename HF, typename BXF, typename BYF>
 __device__ __forceinline__ void jac_force(const AF &A_, const HF &H_, const BXF &BX_, const BYF &BY_, int i, int j,
                                           const Geo<T> &g, T &fx, T &fy) {
     if constexpr (STRICT) {
@@ -98,8 +106,13 @@ __device__ __forceinline__ void jac_force(const AF &A_, const HF &H_, const BXF 
         T T3 = qx * ((A_(i + 1, j - 1) - A_(i - 1, j - 1)) + (A_(i + 1, j) - A_(i - 1, j)));
         T dyBy = (BY_(i, j) - BY_(i, j - 1)) * g.rdy;
         T T4 = qx * ((BY_(i + 1, j - 1) - BY_(i - 1, j - 1)) + (BY_(i + 1, j) - BY_(i - 1, j)));
-        fx = (dxA * T1 - T2 * dxBx) * (T(2) * fast_recip<T>(H_(i - 1, j) + H_(i, j)));
-        fy = (T3 * dyBy - dyA * T4) * (T(2) * fast_recip<T>(H_(i, j - 1) + H_(i, j)));
+        if constexpr (RCP1) {
+            fx = (dxA * T1 - T2 * dxBx) * (T(2) * recip_newton1(H_(i - 1, j) + H_(i, j)));
+            fy = (T3 * dyBy - dyA * T4) * (T(2) * recip_newton1(H_(i, j - 1) + H_(i, j)));
+        } else {
+            fx = (dxA * T1 - T2 * dxBx) * (T(2) * fast_recip<T>(H_(i - 1, j) + H_(i, j)));
+            fy = (T3 * dyBy - dyA * T4) * (T(2) * fast_recip<T>(H_(i, j - 1) + H_(i, j)));
+        }
     }
 }
 

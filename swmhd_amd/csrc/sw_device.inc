@@ -153,10 +153,31 @@ template <typename T, typename M> __device__ __forceinline__ void weno_betas4(co
     b1 = fma_<T>(T(13.0 / 3.0) * w.e2, w.e2, fma_<T>(g1, g1, eps4));
     b2 = fma_<T>(T(13.0 / 3.0) * w.e1, w.e1, fma_<T>(g2, g2, eps4));
 }
+// ---- MARCH64: the arithmetic of the fp64 vector-invariant marching kernel ----------------------------------------------
+// The helpers below take a compile-time switch `MARCH64` (default off).  Only k_tendency_vi_march<double, ...> turns it on; every
+// other kernel instantiates the forms above and below exactly as before (their register budgets are pinned by tests, and editing a
+// shared helper in place re-rolls the allocation of all of them).  The MARCH64 forms are algebraically the same expressions with
+// fewer instructions; results differ by rounding only.
+//
+// weno_betas4 ACCUMULATING into b0..b2: the velocity-stencil indicator is the sum of the u- and the v-stencil's, so the second
+// stencil's innermost fma starts from the first one's b_k (which carries eps) -- no separate bu_k + bv_k adds.
+template <typename T, typename M> __device__ __forceinline__ void weno_betas4_acc(const WenoDiffs<T> &w, M pos, T &b0, T &b1, T &b2) {
+    const T kA = pos ? T(3) : T(1), kB = pos ? T(1) : T(3);
+    const T g0 = fma_<T>(kB, w.d4, -(kA * w.d3)), g1 = w.d2 + w.d3, g2 = fma_<T>(kA, w.d2, -(kB * w.d1));
+    b0 = fma_<T>(T(13.0 / 3.0) * w.e3, w.e3, fma_<T>(g0, g0, b0));
+    b1 = fma_<T>(T(13.0 / 3.0) * w.e2, w.e2, fma_<T>(g1, g1, b1));
+    b2 = fma_<T>(T(13.0 / 3.0) * w.e1, w.e1, fma_<T>(g2, g2, b2));
+}
+// 1/h for the centre B of the Lorentz force: one Newton step under MARCH64 (lorentz_device.inc: recip_newton1), else recip
+template <typename T, bool MARCH64> __device__ __forceinline__ T recip_lorentz(T x) {
+    if constexpr (MARCH64) return recip_newton1(x);
+    else return recip<T>(x);
+}
 // value at the face given the differences of the reconstructed quantity (wz, centre value c) and b_k ~ beta_k + eps (any
 // common factor).  With s_k = b_k^2, q_k = prod_{j != k} s_j, P = s0 s1 s2 the multiplied-through weights are
 // m_k = P + tau^2 q_k (times c_k = 3/10, 6/10, 1/10); everything is divided by c_0.
-template <typename T> __device__ __forceinline__ T weno_combine_diff(const WenoDiffs<T> &wz, T c, T b0, T b1, T b2) {
+// MARCH64: value = c + (1/6) [(d2 + 2 d3) - num r] in three fmas (p1 and the last fma above take five).
+template <typename T, bool MARCH64 = false> __device__ __forceinline__ T weno_combine_diff(const WenoDiffs<T> &wz, T c, T b0, T b1, T b2) {
     const T p1 = c + fma_<T>(T(1.0 / 3.0), wz.d3, T(1.0 / 6.0) * wz.d2);
     const T f1 = wz.e2 - wz.e1, f2 = wz.e3 - wz.e2;
     const T tau = b2 - b0, t2 = tau * tau;
@@ -168,21 +189,28 @@ template <typename T> __device__ __forceinline__ T weno_combine_diff(const WenoD
         const T num = fma_<T>(m0, f2, T(2.0 / 3.0) * (m2 * f1));               // (0.3 m0 f2 + 0.2 m2 f1) / 0.3
         double r = __builtin_amdgcn_rcp(S);
         r = __builtin_fma(r, __builtin_fma(-S, r, 1.0), r);
-        return fma_<T>(T(-1.0 / 6.0) * num, r, p1);
+        if constexpr (MARCH64) return fma_<T>(T(1.0 / 6.0), fma_<T>(-num, r, fma_<T>(T(2), wz.d3, wz.d2)), c);
+        else return fma_<T>(T(-1.0 / 6.0) * num, r, p1);
     } else {   // fp32: the multiplied-through weights would leave the exponent range; per-term reciprocals instead
         const T r0 = recip<T>(b0), r1 = recip<T>(b1), r2 = recip<T>(b2);
         const T a0 = T(0.3) * (T(1) + t2 * r0 * r0), a1 = T(0.6) * (T(1) + t2 * r1 * r1), a2 = T(0.1) * (T(1) + t2 * r2 * r2);
         return p1 - (T(1.0 / 6.0) * (a0 * f2 + T(2) * a2 * f1)) * recip<T>(a0 + a1 + a2);
     }
 }
-template <typename T, typename M> __device__ __forceinline__ T weno5_upwind_ordered(const T *q, M pos) {
+template <typename T, bool MARCH64 = false, typename M> __device__ __forceinline__ T weno5_upwind_ordered(const T *q, M pos) {
     const WenoDiffs<T> w = weno_diffs<T>(q);
     T b0, b1, b2;
     weno_betas4<T>(w, T(4) * SW_EPS, pos, b0, b1, b2);
-    return weno_combine_diff<T>(w, q[2], b0, b1, b2);
+    return weno_combine_diff<T, MARCH64>(w, q[2], b0, b1, b2);
 }
 // Same with VelocityStencil smoothness: reconstructs z using the mean of the u- and v-stencil indicators (here: 8x the mean).
-template <typename T, typename M> __device__ __forceinline__ T weno5_vel_upwind_ordered(const T *z, const T *u, const T *v, M pos) {
+template <typename T, bool MARCH64 = false, typename M> __device__ __forceinline__ T weno5_vel_upwind_ordered(const T *z, const T *u, const T *v, M pos) {
+    if constexpr (MARCH64) {
+        T b0, b1, b2;
+        weno_betas4<T>(weno_diffs<T>(u), T(8) * SW_EPS, pos, b0, b1, b2);
+        weno_betas4_acc<T>(weno_diffs<T>(v), pos, b0, b1, b2);
+        return weno_combine_diff<T, true>(weno_diffs<T>(z), z[2], b0, b1, b2);
+    }
     T bu0, bu1, bu2, bv0, bv1, bv2;
     weno_betas4<T>(weno_diffs<T>(u), T(0), pos, bu0, bu1, bu2);
     weno_betas4<T>(weno_diffs<T>(v), T(8) * SW_EPS, pos, bv0, bv1, bv2);
@@ -191,7 +219,7 @@ template <typename T, typename M> __device__ __forceinline__ T weno5_vel_upwind_
 
 // upwind_biased_product(u, weno_left(q), weno_right(q)).
 // fast: reconstruct only the upwind side, from the values in upwind order.
-template <typename T> __device__ __forceinline__ T upwind_weno(T u, const T *q) {
+template <typename T, bool MARCH64 = false> __device__ __forceinline__ T upwind_weno(T u, const T *q) {
     if constexpr (STRICT) {
         return upw<T>(u, weno_left<T>(q), weno_right<T>(q));
     } else {
@@ -199,7 +227,7 @@ template <typename T> __device__ __forceinline__ T upwind_weno(T u, const T *q) 
         T w[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) w[k] = pos ? q[k] : q[5 - k];
-        return u * weno5_upwind_ordered<T>(w, pos);
+        return u * weno5_upwind_ordered<T, MARCH64>(w, pos);
     }
 }
 template <typename T> __device__ __forceinline__ T upwind_weno_vel(T u, const T *z, const T *us, const T *vs) {
@@ -219,7 +247,7 @@ template <typename T> __device__ __forceinline__ T upwind_weno_vel(T u, const T 
 // need only DIFFERENCES of uf = (u(j-1) + u(j))/2 and vf = sv/2, and they are quadratic in them: with D = 2 d they come out
 // 4x larger, the sign of the (mirrored) stencil drops out, and -- all b_k carrying the same factor -- the weights are unchanged.
 // Saves forming uf, vf (24 ops) and one select per field.
-template <typename T> __device__ __forceinline__ T upwind_weno_vel_raw(T u, const T *z, const T *uw, const T *sv) {
+template <typename T, bool MARCH64 = false> __device__ __forceinline__ T upwind_weno_vel_raw(T u, const T *z, const T *uw, const T *sv) {
     const auto pos = u >= T(0);
     T Du[5], Dv[5];
 #pragma unroll
@@ -229,10 +257,18 @@ template <typename T> __device__ __forceinline__ T upwind_weno_vel_raw(T u, cons
     wv.d1 = pos ? Dv[0] : Dv[4]; wv.d2 = pos ? Dv[1] : Dv[3]; wv.d3 = Dv[2]; wv.d4 = pos ? Dv[3] : Dv[1];
     wu.e1 = wu.d2 - wu.d1; wu.e2 = wu.d3 - wu.d2; wu.e3 = wu.d4 - wu.d3;
     wv.e1 = wv.d2 - wv.d1; wv.e2 = wv.d3 - wv.d2; wv.e3 = wv.d4 - wv.d3;
+    T wz[5];
+    if constexpr (MARCH64) {
+        T b0, b1, b2;
+        weno_betas4<T>(wu, T(32) * SW_EPS, pos, b0, b1, b2);
+        weno_betas4_acc<T>(wv, pos, b0, b1, b2);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) wz[k] = pos ? z[k] : z[5 - k];
+        return u * weno_combine_diff<T, true>(weno_diffs<T>(wz), wz[2], b0, b1, b2);
+    }
     T bu0, bu1, bu2, bv0, bv1, bv2;
     weno_betas4<T>(wu, T(0), pos, bu0, bu1, bu2);
     weno_betas4<T>(wv, T(32) * SW_EPS, pos, bv0, bv1, bv2);            // 16 beta_u + 16 beta_v + 32 eps = 32 (mean + eps)
-    T wz[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) wz[k] = pos ? z[k] : z[5 - k];
     return u * weno_combine_diff<T>(weno_diffs<T>(wz), wz[2], bu0 + bv0, bu1 + bv1, bu2 + bv2);

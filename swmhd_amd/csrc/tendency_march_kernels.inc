@@ -52,6 +52,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     constexpr bool FUSE = (MODE & 1) != 0, HAS_GM = (MODE & 2) != 0, STORE_G = (MODE & 4) != 0, ANCHOR = (MODE & 8) != 0;
     constexpr bool STORE_W = ANCHOR && FUSE && !HAS_GM;   // first anchored stage: W goes out through the G descriptors
     constexpr bool FOLDS = NT == 256 && sizeof(T) == 8;  // built with the folded layout (the launcher folds nothing else)
+    constexpr bool M64 = is_f64<T>::value;               // the MARCH64 arithmetic of sw_device.inc: every fp64 variant of this kernel, nothing else
     constexpr int XH = 3, NH = NT / 2, TXO = NT - 2 * XH;
     constexpr int RW = FOLDS ? 2 * (NH + 2 * XH) : NT + 2 * XH;   // LDS columns: a full strip, or two sub-strips side by side
     __shared__ T Ru[3][RW];    // u rows jo-1, jo (+1: written while the previous row's readers may still run)
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
     __shared__ T RBy[3][RW];   // centre By rows jo-1 .. jo+1
     __shared__ T RFh[1][RW];   // x-face flux of h at face c, row jo
     __shared__ T RFA[1][RW];   // x-face flux of A
-    __shared__ T RK[1][RW];    // Kh(c, jo): computed once per cell in P2, read by the right neighbour in P3
+    __shared__ T RK[1][RW];    // Kh(c, jo) (fp64: Kh + g h): computed once per cell in P2, read by the right neighbour in P3
     __shared__ T RZUV[RW][3];  // per column: zeta(c, jo) and the velocities uf, vf at the vorticity point, for the x-direction stencil
                                // (interleaved: one LDS address per stencil point serves all three; 24-B stride is conflict-free)
 
@@ -156,16 +157,17 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         }
         uw[7] = T(0); vw[6] = T(0); zw[5] = T(0); zw[6] = T(0); svw[5] = T(0); svw[6] = T(0); hw[6] = T(1); aw[6] = T(0);
         // carried in: y-face fluxes at face J0 (advecting velocity v(c, J0), stencil rows J0-3 .. J0+2) and Kh(c, J0-1)
-        fhy = upwind_weno<T>(vw[2], ph);
-        fay = upwind_weno<T>(vw[2], pa);
+        fhy = upwind_weno<T, M64>(vw[2], ph);
+        fay = upwind_weno<T, M64>(vw[2], pa);
         km = T(0.25) * ((sq(uw[2]) + sq(ue_m)) + (sq(vw[1]) + sq(vw[2])));
+        if constexpr (M64) km = fma_<T>(a.grav, hw[1], km);   // (M64 carries the Bernoulli sum Kh + g h: see RK below)
         // LDS rows the first iteration reads but does not write: u(J0-1); A(J0-1), A(J0); centre B of rows J0-1, J0
         const int q3o = ((J0 % 3) + 3) % 3, q3m = (q3o + 2) % 3;
         Ru[q3m][lc] = uw[2];
         RHA[(J0 - 1) & 3][lc][0] = aw[1];
         RHA[J0 & 3][lc][0] = aw[2];
         if constexpr (LOR == 1) {
-            const T rhm = recip<T>(hw[1]), rho = recip<T>(hw[2]);
+            const T rhm = recip_lorentz<T, M64>(hw[1]), rho = recip_lorentz<T, M64>(hw[2]);
             RBy[q3m][lc] = (T(0.5) * rdx) * (a_em - a_wm) * rhm;
             RBx[q3m][lc] = -(T(0.5) * rdy) * (aw[2] - aw[0]) * rhm;
             RBy[q3o][lc] = (T(0.5) * rdx) * (a_eo - a_wo) * rho;
@@ -211,13 +213,15 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
         if constexpr (LOR == 1) {
             const T cxA = RHA[s4p][lc + 1][0] - RHA[s4p][lc - 1][0];
             const T cyA = Aa[4] - Aa[2];
-            const T rh = recip<T>(Hh[3]);
+            const T rh = recip_lorentz<T, M64>(Hh[3]);
             RBy[s3p][lc] = (T(0.5) * rdx) * cxA * rh;
             RBx[s3p][lc] = -(T(0.5) * rdy) * cyA * rh;
         }
         {   // Kh(c, jo): once per cell (read back below, together with the left neighbour's: nothing is held across the barrier)
             const T ue2 = Ru[s3o][lc + 1];
-            RK[0][lc] = T(0.25) * ((sq(U[3]) + sq(ue2)) + (sq(V[2]) + sq(V[3])));
+            const T kh = T(0.25) * ((sq(U[3]) + sq(ue2)) + (sq(V[2]) + sq(V[3])));
+            if constexpr (M64) RK[0][lc] = fma_<T>(a.grav, Hh[2], kh);   // Kh + g h: G1 and G2 then need one difference each
+            else RK[0][lc] = kh;
         }
         // vorticity and the velocities at the vorticity point (f,f) for row jo: consumed by the x-direction stencil
         RZUV[lc][0] = Z[2];
@@ -230,8 +234,8 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             T qh[5], qa[5];
 #pragma unroll
             for (int k = 0; k < 5; ++k) { const T *r = RHA[s4o][base + st * k]; qa[k] = r[0]; qh[k] = r[1]; }
-            RFh[0][lc] = uadv * weno5_upwind_ordered<T>(qh, pos);
-            RFA[0][lc] = uadv * weno5_upwind_ordered<T>(qa, pos);
+            RFh[0][lc] = uadv * weno5_upwind_ordered<T, M64>(qh, pos);
+            RFA[0][lc] = uadv * weno5_upwind_ordered<T, M64>(qa, pos);
         }
         __syncthreads();
         if constexpr (FUSE && HAS_GM) {   // G- of the output row: needed at the very end, ~2/3 of an iteration away
@@ -240,11 +244,11 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
 
         // ---- P3: everything else for row jo ----
         // y-face fluxes at face jo+1 (advecting velocity v(c, jo+1)); the face-jo values are carried
-        const T fhy_n = upwind_weno<T>(V[3], Hh);
-        const T fay_n = upwind_weno<T>(V[3], Aa);
+        const T fhy_n = upwind_weno<T, M64>(V[3], Hh);
+        const T fay_n = upwind_weno<T, M64>(V[3], Aa);
         // vertical_vorticity_U: zeta reconstructed along y to (f,c), VelocityStencil smoothness
         const T vhat = T(0.25) * (SV[2] + SV[3]);
-        const T vortU = -upwind_weno_vel_raw<T>(vhat, Z, U, SV);
+        const T vortU = -upwind_weno_vel_raw<T, M64>(vhat, Z, U, SV);
         // vertical_vorticity_V: zeta reconstructed along x to (c,f); upwind-ordered reads (lane-local LDS addressing)
         const T *su0 = Ru[s3m], *su1 = Ru[s3o];
         const T ue = su1[lc + 1];
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             T zx[5], ufx[5], vfx[5];
 #pragma unroll
             for (int k = 0; k < 5; ++k) { const T *r = RZUV[base + st * k]; zx[k] = r[0]; ufx[k] = r[1]; vfx[k] = r[2]; }
-            vortV = uhat * weno5_vel_upwind_ordered<T>(zx, ufx, vfx, pos);
+            vortV = uhat * weno5_vel_upwind_ordered<T, M64>(zx, ufx, vfx, pos);
         }
         const T kc = RK[0][lc], kl = RK[0][lc - 1];   // Kh(c, jo) and the left neighbour's
         const T hl = RHA[s4o][lc - 1][1];
@@ -266,10 +270,16 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             auto H_ = [&](int di, int dj) -> T { return di == 0 ? Hh[2 + dj] : hl; };   // only (-1,0) is off-column
             auto BX_ = [&](int di, int dj) -> T { return RBx[dj < 0 ? s3m : (dj > 0 ? s3p : s3o)][lc + di]; };
             auto BY_ = [&](int di, int dj) -> T { return RBy[dj < 0 ? s3m : (dj > 0 ? s3p : s3o)][lc + di]; };
-            jac_force<T>(A_, H_, BX_, BY_, 0, 0, g, Fx, Fy);
+            jac_force<T, M64>(A_, H_, BX_, BY_, 0, 0, g, Fx, Fy);
         }
-        const T G1 = -vortU - (kc - kl) * rdx - a.grav * (Hh[2] - hl) * rdx + a.fcor * vhat + Fx;
-        const T G2 = -vortV - (kc - km) * rdy - a.grav * (Hh[2] - Hh[1]) * rdy - a.fcor * uhat + Fy;
+        T G1, G2;
+        if constexpr (M64) {   // kc, kl, km are Bernoulli sums
+            G1 = -vortU - (kc - kl) * rdx + a.fcor * vhat + Fx;
+            G2 = -vortV - (kc - km) * rdy - a.fcor * uhat + Fy;
+        } else {
+            G1 = -vortU - (kc - kl) * rdx - a.grav * (Hh[2] - hl) * rdx + a.fcor * vhat + Fx;
+            G2 = -vortV - (kc - km) * rdy - a.grav * (Hh[2] - Hh[1]) * rdy - a.fcor * uhat + Fy;
+        }
         const T Gh = -((RFh[0][lc + 1] - RFh[0][lc]) * rdx + (fhy_n - fhy) * rdy);
         const T GA = -((RFA[0][lc + 1] - RFA[0][lc]) * rdx + (fay_n - fay) * rdy)
                      + Aa[2] * ((ue - U[3]) * rdx + (V[3] - V[2]) * rdy);

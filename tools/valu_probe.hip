@@ -1,5 +1,9 @@
 // What does the fp64 VALU of one gfx950 SIMD sustain?  CH independent fma chains per wave, W waves per SIMD.
 // Reports cycles per wave-instruction seen by one SIMD (4.0 = the 16-lane SIMD saturated by wave64 fp64 ops).
+// Also times, the same way (independent chains, 1-4 waves per SIMD), the other instructions the fp64 marching kernel's loop issues
+// besides fma / mul / add: v_rcp_f64, v_mov_b64 and v_cndmask_b32 -- does a reciprocal cost one issue slot or several, and do the
+// window moves and selects cost what an fma costs?  (bench.py's issue floor counts them all alike.)
+// Build: hipcc --offload-arch=gfx950 -O3 -o valu_probe valu_probe.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 template <int CH, int OP>
@@ -7,6 +11,8 @@ __global__ __launch_bounds__(256) void k(double *out, double a, double b, int it
     double x[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) x[c] = threadIdx.x * 1e-3 + c;
+    const unsigned long long sel = __ballot(threadIdx.x & 1);
+    (void)sel;
     for (int i = 0; i < iters; ++i) {
 #pragma unroll
         for (int r = 0; r < 8; ++r)
@@ -15,7 +21,14 @@ __global__ __launch_bounds__(256) void k(double *out, double a, double b, int it
                 if (OP == 0) x[c] = __builtin_fma(x[c], a, b);
                 else if (OP == 1) x[c] = x[c] * a;
                 else if (OP == 2) x[c] = x[c] + b;
-                else { float y = (float)x[c]; y = __builtin_fmaf(y, (float)a, (float)b); x[c] = y; }
+                else if (OP == 3) { float y = (float)x[c]; y = __builtin_fmaf(y, (float)a, (float)b); x[c] = y; }
+                else if (OP == 4) x[c] = __builtin_amdgcn_rcp(x[c]);                                   // v_rcp_f64 (x <-> 1/x)
+                else if (OP == 5) asm volatile("v_mov_b64 %0, %1" : "=v"(x[c]) : "v"(x[c]));            // (kept by the asm: the compiler would fold it)
+                else {   // v_cndmask_b32 on the low word, lanes alternating
+                    unsigned lo = (unsigned)__double_as_longlong(x[c]), hi = (unsigned)(__double_as_longlong(x[c]) >> 32);
+                    asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(lo) : "v"(lo), "v"(hi), "s"(sel));
+                    x[c] = __longlong_as_double(((long long)hi << 32) | lo);
+                }
             }
     }
     double s = 0;
@@ -42,5 +55,8 @@ int main() {
     run<1, 0>("fma64", out); run<2, 0>("fma64", out); run<4, 0>("fma64", out); run<8, 0>("fma64", out);
     run<1, 1>("mul64", out); run<4, 1>("mul64", out);
     run<1, 2>("add64", out); run<4, 2>("add64", out);
+    run<1, 4>("rcp64", out); run<4, 4>("rcp64", out); run<8, 4>("rcp64", out);
+    run<4, 5>("mov64", out); run<8, 5>("mov64", out);
+    run<4, 6>("cndmask", out); run<8, 6>("cndmask", out);
     return 0;
 }
