@@ -51,6 +51,12 @@
  *     reference's 128^2 low_B_low_U run: energy error 3.9 instead of 0.53 by t = 15 in Float32; the divergence form, first differences
  *     only, is unaffected).  Use fp32 where 1e-7 of the fluxes is enough; the fp32-vs-fp64 state after 100 steps of that
  *     configuration agrees to 9e-5 of the velocity scale (tests/test_fullsize_gpu.py).
+ *     fp64 DOMAIN of the fast vector-invariant row-marching kernel: it takes the WENO weights of the h and the A reconstruction at a
+ *     face from ONE reciprocal of the product of their two denominators S ~ (10/3) b^6, b = 4 (smoothness indicator + 1e-6).  The
+ *     product cannot underflow (b >= 4e-6: S1 S2 >= 1.8e-64); it is finite and its reciprocal a normal number for b <= 1e25 and
+ *     overflows from b = 4.0e25 on (no run-time guard).  b <= 33.4 D^2 where neighbouring values differ by at most D, so the
+ *     tolerances above hold while neighbouring values of h and of A differ by no more than 5.4e11; beyond, h and A tendencies turn
+ *     non-finite.  (A single denominator, as every other fast fp64 kernel forms it, overflows from b = 1.9e51 on, D ~ 7e24.)
  *   Which scheme: the oracle's base right-hand side restates the Oceananigans version the reference ran and is pinned to the reference's
  *     twelve committed energy plots at plot-reading accuracy (tests/test_reference_plots.py); last bits of a Julia
  *     run are not pinned.

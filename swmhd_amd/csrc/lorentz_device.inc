@@ -70,7 +70,7 @@ __device__ __forceinline__ void jac_centre_B(const AF &A_, const HF &H_, int ii,
     }
 }
 // lorentz_force_func_x/y (:20-26) = jacobian_x/y (:10-18) / face-averaged h, given centre B accessors
-// RCP1 (fast builds, T = double): the two face reciprocals by recip_newton1
+// RCP1 (fast builds, T = double): the two face reciprocals from one recip_newton1 of the product of the two h sums
 template <typename T, bool RCP1 = false, typename AF, typename HF, typename BXF, typename BYF>
 __device__ __forceinline__ void jac_force(const AF &A_, const HF &H_, const BXF &BX_, const BYF &BY_, int i, int j,
                                           const Geo<T> &g, T &fx, T &fy) {
@@ -106,9 +106,11 @@ __device__ __forceinline__ void jac_force(const AF &A_, const HF &H_, const BXF 
         T T3 = qx * ((A_(i + 1, j - 1) - A_(i - 1, j - 1)) + (A_(i + 1, j) - A_(i - 1, j)));
         T dyBy = (BY_(i, j) - BY_(i, j - 1)) * g.rdy;
         T T4 = qx * ((BY_(i + 1, j - 1) - BY_(i - 1, j - 1)) + (BY_(i + 1, j) - BY_(i - 1, j)));
-        if constexpr (RCP1) {
-            fx = (dxA * T1 - T2 * dxBx) * (T(2) * recip_newton1(H_(i - 1, j) + H_(i, j)));
-            fy = (T3 * dyBy - dyA * T4) * (T(2) * recip_newton1(H_(i, j - 1) + H_(i, j)));
+        if constexpr (RCP1) {   // both from ONE reciprocal, of the product of the two h sums: 1/hx = hy r, 1/hy = hx r (h^2 is far inside the range)
+            const T hx = H_(i - 1, j) + H_(i, j), hy = H_(i, j - 1) + H_(i, j);
+            const T r2 = T(2) * recip_newton1(hx * hy);
+            fx = (dxA * T1 - T2 * dxBx) * (hy * r2);
+            fy = (T3 * dyBy - dyA * T4) * (hx * r2);
         } else {
             fx = (dxA * T1 - T2 * dxBx) * (T(2) * fast_recip<T>(H_(i - 1, j) + H_(i, j)));
             fy = (T3 * dyBy - dyA * T4) * (T(2) * fast_recip<T>(H_(i, j - 1) + H_(i, j)));

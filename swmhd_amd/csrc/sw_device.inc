@@ -159,19 +159,59 @@ template <typename T, typename M> __device__ __forceinline__ void weno_betas4(co
 // shared helper in place re-rolls the allocation of all of them).  The MARCH64 forms are algebraically the same expressions with
 // fewer instructions; results differ by rounding only.
 //
-// weno_betas4 ACCUMULATING into b0..b2: the velocity-stencil indicator is the sum of the u- and the v-stencil's, so the second
-// stencil's innermost fma starts from the first one's b_k (which carries eps) -- no separate bu_k + bv_k adds.
-template <typename T, typename M> __device__ __forceinline__ void weno_betas4_acc(const WenoDiffs<T> &w, M pos, T &b0, T &b1, T &b2) {
+// The velocity-stencil indicator is the sum of the u- and the v-stencil's.  Formed in one chain per b_k, eps riding in on the innermost
+// fma (no separate bu_k + bv_k adds), and with the 13/3 factor paid once: five instructions
+//     b_k = 13/3 (e_u^2 + e_v^2) + (g_u^2 + g_v^2 + eps)
+// where accumulating weno_betas4 over the two stencils took six (a 13/3 e multiply and two fmas, twice).
+template <typename T, typename M> __device__ __forceinline__ void weno_betas4_vel(const WenoDiffs<T> &wu, const WenoDiffs<T> &wv, T eps4, M pos, T &b0, T &b1, T &b2) {
     const T kA = pos ? T(3) : T(1), kB = pos ? T(1) : T(3);
-    const T g0 = fma_<T>(kB, w.d4, -(kA * w.d3)), g1 = w.d2 + w.d3, g2 = fma_<T>(kA, w.d2, -(kB * w.d1));
-    b0 = fma_<T>(T(13.0 / 3.0) * w.e3, w.e3, fma_<T>(g0, g0, b0));
-    b1 = fma_<T>(T(13.0 / 3.0) * w.e2, w.e2, fma_<T>(g1, g1, b1));
-    b2 = fma_<T>(T(13.0 / 3.0) * w.e1, w.e1, fma_<T>(g2, g2, b2));
+    const T gu0 = fma_<T>(kB, wu.d4, -(kA * wu.d3)), gu1 = wu.d2 + wu.d3, gu2 = fma_<T>(kA, wu.d2, -(kB * wu.d1));
+    const T gv0 = fma_<T>(kB, wv.d4, -(kA * wv.d3)), gv1 = wv.d2 + wv.d3, gv2 = fma_<T>(kA, wv.d2, -(kB * wv.d1));
+    b0 = fma_<T>(T(13.0 / 3.0), fma_<T>(wu.e3, wu.e3, wv.e3 * wv.e3), fma_<T>(gu0, gu0, fma_<T>(gv0, gv0, eps4)));
+    b1 = fma_<T>(T(13.0 / 3.0), fma_<T>(wu.e2, wu.e2, wv.e2 * wv.e2), fma_<T>(gu1, gu1, fma_<T>(gv1, gv1, eps4)));
+    b2 = fma_<T>(T(13.0 / 3.0), fma_<T>(wu.e1, wu.e1, wv.e1 * wv.e1), fma_<T>(gu2, gu2, fma_<T>(gv2, gv2, eps4)));
 }
 // 1/h for the centre B of the Lorentz force: one Newton step under MARCH64 (lorentz_device.inc: recip_newton1), else recip
 template <typename T, bool MARCH64> __device__ __forceinline__ T recip_lorentz(T x) {
     if constexpr (MARCH64) return recip_newton1(x);
     else return recip<T>(x);
+}
+// MARCH64: weno_combine_diff (below) in two parts, so that two reconstructions can share ONE v_rcp_f64.  The first part is everything
+// up to the reciprocal: S, num (as below), dd = d2 + 2 d3 and the centre value c; the finish takes r ~ 1/S:
+//     value = c + (1/6) [dd - num r].
+template <typename T> struct WenoParts { T S, num, dd, c; };
+template <typename T> __device__ __forceinline__ WenoParts<T> weno_combine_parts(const WenoDiffs<T> &wz, T c, T b0, T b1, T b2) {
+    const T f1 = wz.e2 - wz.e1, f2 = wz.e3 - wz.e2;
+    const T tau = b2 - b0, t2 = tau * tau;
+    const T s0 = b0 * b0, s1 = b1 * b1, s2 = b2 * b2;
+    const T q0 = s1 * s2, q1 = s0 * s2, q2 = s0 * s1, P = s0 * q0;
+    const T m0 = fma_<T>(t2, q0, P), m1 = fma_<T>(t2, q1, P), m2 = fma_<T>(t2, q2, P);
+    WenoParts<T> p;
+    p.S = fma_<T>(T(1.0 / 3.0), m2, fma_<T>(T(2), m1, m0));
+    p.num = fma_<T>(m0, f2, T(2.0 / 3.0) * (m2 * f1));
+    p.dd = fma_<T>(T(2), wz.d3, wz.d2);
+    p.c = c;
+    return p;
+}
+template <typename T> __device__ __forceinline__ T weno_combine_finish(const WenoParts<T> &p, T r) {
+    return fma_<T>(T(1.0 / 6.0), fma_<T>(-p.num, r, p.dd), p.c);
+}
+// Two reconstructions, one reciprocal: r12 = 1/(S1 S2) by v_rcp_f64 + one Newton step, then 1/S1 = S2 r12 and 1/S2 = S1 r12 -- one
+// multiply, one v_rcp_f64, two fmas and two multiplies (~8 issue slots at the ~3 slots of a v_rcp_f64, tools/valu_probe.hip) where two
+// separate reciprocals with their Newton steps take ~10.  Each 1/S carries two roundings more than the single form (the product's and the last
+// multiply's: 2.4e-15 instead of 2.2e-15 relative) and multiplies only the nonlinear correction.
+// DOMAIN (no run-time guard: a select per reconstruction would cost what the pairing saves).  S = m0 + 2 m1 + m2/3 with
+// m_k = P + tau^2 q_k <= 2 b^6 for indicators b_k <= b, so 10/3 b_min^6 <= S <= 20/3 b^6; equal indicators give S = 10/3 b^6.
+//   lower end: b_k >= 4 eps = 4e-6 gives S >= 1.3e-32 and S1 S2 >= 1.8e-64: no underflow;
+//   upper end: S1 S2 <= 44.5 b^12 is finite for every b <= 3.5e25 and, at 11.1 b^12 for equal indicators, overflows (1.8e308) from
+//   b = 4.0e25 on.  The documented domain is b <= 1e25: there S1 S2 <= 4.5e301 and r12 is a normal number.  (The
+//   single form, S alone, overflows from b = 1.9e51 on.)  The kernel pairs the reconstructions of h and A only (x-face fluxes, y-face fluxes):
+//   with neighbouring values differing by at most D their b <= 33.4 D^2, so b <= 1e25 holds while neighbouring h and neighbouring A
+//   differ by no more than 5.4e11.  The velocity-stencil reconstructions keep the single form and its range.
+template <typename T> __device__ __forceinline__ void weno_combine_finish_pair(const WenoParts<T> &pa, const WenoParts<T> &pb, T &va, T &vb) {
+    const T r = recip_newton1(pa.S * pb.S);
+    va = weno_combine_finish<T>(pa, pb.S * r);
+    vb = weno_combine_finish<T>(pb, pa.S * r);
 }
 // value at the face given the differences of the reconstructed quantity (wz, centre value c) and b_k ~ beta_k + eps (any
 // common factor).  With s_k = b_k^2, q_k = prod_{j != k} s_j, P = s0 s1 s2 the multiplied-through weights are
@@ -189,13 +229,28 @@ template <typename T, bool MARCH64 = false> __device__ __forceinline__ T weno_co
         const T num = fma_<T>(m0, f2, T(2.0 / 3.0) * (m2 * f1));               // (0.3 m0 f2 + 0.2 m2 f1) / 0.3
         double r = __builtin_amdgcn_rcp(S);
         r = __builtin_fma(r, __builtin_fma(-S, r, 1.0), r);
-        if constexpr (MARCH64) return fma_<T>(T(1.0 / 6.0), fma_<T>(-num, r, fma_<T>(T(2), wz.d3, wz.d2)), c);
+        if constexpr (MARCH64) return weno_combine_finish<T>(WenoParts<T>{S, num, fma_<T>(T(2), wz.d3, wz.d2), c}, r);   // (the single form: velocity stencils, segment prologues)
         else return fma_<T>(T(-1.0 / 6.0) * num, r, p1);
     } else {   // fp32: the multiplied-through weights would leave the exponent range; per-term reciprocals instead
         const T r0 = recip<T>(b0), r1 = recip<T>(b1), r2 = recip<T>(b2);
         const T a0 = T(0.3) * (T(1) + t2 * r0 * r0), a1 = T(0.6) * (T(1) + t2 * r1 * r1), a2 = T(0.1) * (T(1) + t2 * r2 * r2);
         return p1 - (T(1.0 / 6.0) * (a0 * f2 + T(2) * a2 * f1)) * recip<T>(a0 + a1 + a2);
     }
+}
+// MARCH64: weno5_upwind_ordered / upwind_weno (below) up to the reciprocal: the marching kernel pairs two of them in
+// weno_combine_finish_pair and multiplies by the advecting velocity itself.
+template <typename T, typename M> __device__ __forceinline__ WenoParts<T> weno5_upwind_ordered_parts(const T *q, M pos) {
+    const WenoDiffs<T> w = weno_diffs<T>(q);
+    T b0, b1, b2;
+    weno_betas4<T>(w, T(4) * SW_EPS, pos, b0, b1, b2);
+    return weno_combine_parts<T>(w, q[2], b0, b1, b2);
+}
+template <typename T> __device__ __forceinline__ WenoParts<T> upwind_weno_parts(T u, const T *q) {
+    const auto pos = u >= T(0);
+    T w[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) w[k] = pos ? q[k] : q[5 - k];
+    return weno5_upwind_ordered_parts<T>(w, pos);
 }
 template <typename T, bool MARCH64 = false, typename M> __device__ __forceinline__ T weno5_upwind_ordered(const T *q, M pos) {
     const WenoDiffs<T> w = weno_diffs<T>(q);
@@ -207,8 +262,7 @@ template <typename T, bool MARCH64 = false, typename M> __device__ __forceinline
 template <typename T, bool MARCH64 = false, typename M> __device__ __forceinline__ T weno5_vel_upwind_ordered(const T *z, const T *u, const T *v, M pos) {
     if constexpr (MARCH64) {
         T b0, b1, b2;
-        weno_betas4<T>(weno_diffs<T>(u), T(8) * SW_EPS, pos, b0, b1, b2);
-        weno_betas4_acc<T>(weno_diffs<T>(v), pos, b0, b1, b2);
+        weno_betas4_vel<T>(weno_diffs<T>(u), weno_diffs<T>(v), T(8) * SW_EPS, pos, b0, b1, b2);
         return weno_combine_diff<T, true>(weno_diffs<T>(z), z[2], b0, b1, b2);
     }
     T bu0, bu1, bu2, bv0, bv1, bv2;
@@ -260,8 +314,7 @@ template <typename T, bool MARCH64 = false> __device__ __forceinline__ T upwind_
     T wz[5];
     if constexpr (MARCH64) {
         T b0, b1, b2;
-        weno_betas4<T>(wu, T(32) * SW_EPS, pos, b0, b1, b2);
-        weno_betas4_acc<T>(wv, pos, b0, b1, b2);
+        weno_betas4_vel<T>(wu, wv, T(32) * SW_EPS, pos, b0, b1, b2);
 #pragma unroll
         for (int k = 0; k < 5; ++k) wz[k] = pos ? z[k] : z[5 - k];
         return u * weno_combine_diff<T, true>(weno_diffs<T>(wz), wz[2], b0, b1, b2);

@@ -234,8 +234,15 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
             T qh[5], qa[5];
 #pragma unroll
             for (int k = 0; k < 5; ++k) { const T *r = RHA[s4o][base + st * k]; qa[k] = r[0]; qh[k] = r[1]; }
-            RFh[0][lc] = uadv * weno5_upwind_ordered<T, M64>(qh, pos);
-            RFA[0][lc] = uadv * weno5_upwind_ordered<T, M64>(qa, pos);
+            if constexpr (M64) {   // the two reconstructions share one reciprocal (sw_device.inc: weno_combine_finish_pair)
+                T rh_, ra_;
+                weno_combine_finish_pair<T>(weno5_upwind_ordered_parts<T>(qh, pos), weno5_upwind_ordered_parts<T>(qa, pos), rh_, ra_);
+                RFh[0][lc] = uadv * rh_;
+                RFA[0][lc] = uadv * ra_;
+            } else {
+                RFh[0][lc] = uadv * weno5_upwind_ordered<T, M64>(qh, pos);
+                RFA[0][lc] = uadv * weno5_upwind_ordered<T, M64>(qa, pos);
+            }
         }
         __syncthreads();
         if constexpr (FUSE && HAS_GM) {   // G- of the output row: needed at the very end, ~2/3 of an iteration away
@@ -244,8 +251,15 @@ __global__ __launch_bounds__(NT, 3) void k_tendency_vi_march(TendArgs<T> a, int 
 
         // ---- P3: everything else for row jo ----
         // y-face fluxes at face jo+1 (advecting velocity v(c, jo+1)); the face-jo values are carried
-        const T fhy_n = upwind_weno<T, M64>(V[3], Hh);
-        const T fay_n = upwind_weno<T, M64>(V[3], Aa);
+        // (M64: the two reconstructions share one reciprocal, as RFh / RFA above)
+        T fhy_n, fay_n;
+        if constexpr (M64) {
+            weno_combine_finish_pair<T>(upwind_weno_parts<T>(V[3], Hh), upwind_weno_parts<T>(V[3], Aa), fhy_n, fay_n);
+            fhy_n *= V[3]; fay_n *= V[3];
+        } else {
+            fhy_n = upwind_weno<T, M64>(V[3], Hh);
+            fay_n = upwind_weno<T, M64>(V[3], Aa);
+        }
         // vertical_vorticity_U: zeta reconstructed along y to (f,c), VelocityStencil smoothness
         const T vhat = T(0.25) * (SV[2] + SV[3]);
         const T vortU = -upwind_weno_vel_raw<T, M64>(vhat, Z, U, SV);
