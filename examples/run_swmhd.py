@@ -12,6 +12,8 @@ sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the field
 --frames T collects the reference's output frames on the device (swmhd_amd.FieldTimeSeries: the fields (u, v, A, s) every T time units,
 :80-84, or those of --frame-fields out of u v h A s B_x B_y, as --frame-dtype f32|f64) and writes them to <out>/frames.npz at the end.
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
+--dye adds one passive tracer c = tanh(y) to the run (ShallowWaterModel(tracers=("c",)): the reference's `tracers = (:A)` with a second
+name): its min / max join the progress line and the field goes into the --dump-every dumps (single runs only).
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
@@ -57,6 +59,7 @@ def main():
     ap.add_argument("--frames", type=float, default=0.0, help="model time between output frames (0 = none); written to <out>/frames.npz")
     ap.add_argument("--frame-fields", default="u,v,A,s", help="comma-separated fields of a frame: u v h A s B_x B_y")
     ap.add_argument("--frame-dtype", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--dye", action="store_true", help="advect one passive tracer c = tanh(y) with the flow")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -74,6 +77,8 @@ def main():
     a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts))
     if a.dts and a.frames > 0:
         ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
+    if a.dye and (a.amps or a.channel or a.sweep):
+        ap.error("--dye: single runs only (the ensembles carry no tracers)")
     if a.amps or a.channel or a.sweep:
         return run_ensemble(a)
 
@@ -83,20 +88,26 @@ def main():
     N, L = a.size, 10.0
     grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
     form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
-    model = S.ShallowWaterModel(grid, configs.G, configs.F, formulation=form)
+    model = S.ShallowWaterModel(grid, configs.G, configs.F, formulation=form, tracers=("c",) if a.dye else ())
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)
     A0 = (lambda X, Y: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp)
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
     v0 = lambda X, Y: -5 * X * np.exp(-(X ** 2 + Y ** 2))
     n1, n2 = model.names[:2]
     model.set(**{n1: u0, n2: v0, "h": lambda X, Y: np.ones_like(X), "A": A0})      # h = 1: (uh, vh) = (u, v)
+    if a.dye:
+        model.set(c=lambda X, Y: np.tanh(Y))
     nsteps = int(round(a.stop_time / a.dt))
     rows = []
 
     def report(wall):
         d = model.diagnostics()
+        dye = ""
+        if a.dye:
+            c = model.tracers["c"].interior()
+            dye = f"min(c): {c.min().item():.4f}, max(c): {c.max().item():.4f}, "
         print(f"Time: {model.clock_time:9.3f}, iteration: {model.iteration}, max(|u|): {max(d['max_abs_u'], d['max_abs_v']):.2e}, "
-              f"max(|A|): {d['max_abs_A']:.2e}, min(h): {d['min_h']:.2e}, wall time: {wall * 1e3:.1f} ms "
+              f"max(|A|): {d['max_abs_A']:.2e}, min(h): {d['min_h']:.2e}, {dye}wall time: {wall * 1e3:.1f} ms "
               f"| KE {d['kinetic_energy']:.6f} ME {d['magnetic_energy']:.6f} PE {d['potential_energy']:.3e} total {d['total_energy']:.6f}", flush=True)
         rows.append((model.clock_time, d["kinetic_energy"], d["magnetic_energy"], d["potential_energy"], d["total_energy"]))
 

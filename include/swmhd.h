@@ -304,6 +304,42 @@ int swmhd_tendencies_rk3_f32(const float *const *q, float *const *qnew, float *c
                              int j_begin, int j_end, int flags, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Passive tracers: the reference's `tracers = (:A)` (SWMHD_example.jl:29) is a tuple of names; every further name is a centre field
+ * that Oceananigans advects with tracer_advection = WENO5() exactly as it advects A, with no way back into the flow.  One call
+ * advances ALL `ntracers` such fields through one RK3 stage in ONE launch:
+ *     Gn[k]   = -(1/Az)(dx flux_x(U, c[k]) + dy flux_y(V, c[k])) + c[k] div(U)     (written iff store_G != 0)
+ *     cnew[k] = c[k] + dt * (gamma * Gn[k] + zeta * Gm[k])                          (Gm == NULL: first-stage form)
+ * i.e. G_A of swmhd_tendencies with c[k] in the place of A, for both formulations and for Bounded directions.
+ *   q1, q2, h   the state this stage STARTS from: the q given to swmhd_tendencies_rk3 of the same stage, not its qnew; halos filled
+ *               (or SWMHD_WRAP_X / _Y)
+ *   c, cnew, Gn, Gm   HOST arrays of `ntracers` (1 .. SWMHD_MAX_TRACERS) device parents.  cnew == NULL: tendencies only (store_G
+ *               must be set).  cnew[k] must not alias any c[k'] (nor q1, q2, h, nor another cnew).
+ * Written: the interior of rows [j_begin, j_end), 0 <= j_begin <= j_end <= Ny; halos are never written.
+ * flags: SWMHD_STRICT (bitwise the oracle's G_A and the update as written above), SWMHD_WRAP_X / _Y, SWMHD_BOUNDED_X / _Y,
+ *   SWMHD_TILE_KERNEL (the only kernel: a no-op), and SWMHD_RK3_ANCHOR for fast periodic launches as for swmhd_tendencies_rk3: the
+ *   first stage (Gm == NULL) writes W = c + dt zeta G through Gn, later stages read W through Gm, cnew = W + dt gamma G, no G store.
+ *   SWMHD_ENOTSUP  SWMHD_MARCH_KERNEL, SWMHD_GM_IS_PREV_STATE, SWMHD_OPEN_SOUTH / _NORTH, SWMHD_LEAVE_ROOM; SWMHD_RK3_ANCHOR with
+ *                  SWMHD_STRICT or a Bounded direction
+ *   SWMHD_EINVAL   null pointers, ntracers outside 1 .. SWMHD_MAX_TRACERS, bad extents / pitch / spacing / rows / formulation,
+ *                  aliasing, unknown flags, a direction both Bounded and wrapped, wrap with N < H, cnew == NULL without store_G
+ *                  or with SWMHD_RK3_ANCHOR
+ *   SWMHD_EHALO    Hx < 3 or Hy < 3
+ *   Every check precedes the first HIP call.
+ * Tolerance of the fast path: that of A above (S = (|u|/dx + |v|/dy) max|c|).
+ * ---------------------------------------------------------------------------------------------- */
+#define SWMHD_MAX_TRACERS 8
+int swmhd_tracers_rk3_f64(const double *q1, const double *q2, const double *h,
+                          const double *const *c, double *const *cnew, double *const *Gn, const double *const *Gm,
+                          int ntracers, int Nx, int Ny, int Hx, int Hy, int64_t stride_y, double dx, double dy,
+                          int formulation, double dt, double gamma, double zeta, int store_G,
+                          int j_begin, int j_end, int flags, void *stream);
+int swmhd_tracers_rk3_f32(const float *q1, const float *q2, const float *h,
+                          const float *const *c, float *const *cnew, float *const *Gn, const float *const *Gm,
+                          int ntracers, int Nx, int Ny, int Hx, int Hy, int64_t stride_y, float dx, float dy,
+                          int formulation, float dt, float gamma, float zeta, int store_G,
+                          int j_begin, int j_end, int flags, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Native step driver: `nsteps` complete RK3 time steps of the periodic single-GPU model, i.e. Oceananigans'
  * time_step!(model, dt) (timestepper = :RungeKutta3, SWMHD_example.jl:23,42 / divergence_sw_mhd.jl:20,39) repeated:
  *     3 x { swmhd_tendencies_rk3 (gamma, zeta of the stage) ; swap state sets ; swap G sets ; periodic halo fill }

@@ -25,6 +25,7 @@ DIAG_NOUT, DIAG_WORKSPACE = 7, 1024 * 7
 OUT_BITS = {"u": 1, "v": 2, "h": 4, "A": 8, "s": 16, "B_x": 32, "B_y": 64}
 ENSEMBLE_MAX_MEMBERS = 65535
 ENSEMBLE_NPARAMS = 3    # SWMHD_ENSEMBLE_NPARAMS: (g, f, dt) per member in the table of the swmhd_ensemble_*_params calls
+MAX_TRACERS = 8         # SWMHD_MAX_TRACERS: passive tracers per swmhd_tracers_rk3_* launch
 
 
 def ensemble_diag_workspace(members, Nx, Ny):
@@ -87,6 +88,9 @@ def _declare(lib):
         f.restype = i
         f = getattr(lib, f"swmhd_step_rk3_{sfx}")
         f.argtypes = [C.POINTER(p)] * 4 + [i, i, i, i, i64, ft, ft, ft, ft, i, i, ft, i, i, C.POINTER(i), p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_tracers_rk3_{sfx}")
+        f.argtypes = [p, p, p] + [C.POINTER(p)] * 4 + [i, i, i, i, i, i64, ft, ft, i, ft, ft, ft, i, i, i, i, p]
         f.restype = i
         f = getattr(lib, f"swmhd_diagnostics_{sfx}")
         f.argtypes = [p, p, p, p, i, i, i, i, i64, ft, ft, ft, ft, i, i, i, p, p, p]
@@ -178,7 +182,7 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
         "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc", "fill_halo_walls", "ring_exchange_y_sides", "ring_step_rk3_bc",
         "output_fields", "ensemble_output_fields", "ensemble_tendencies_rk3_params", "ensemble_step_rk3_params",
-        "ensemble_step_rk3_bc_params", "ensemble_diagnostics_params")] + [
+        "ensemble_step_rk3_bc_params", "ensemble_diagnostics_params", "tracers_rk3")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

@@ -250,6 +250,27 @@ int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, lon
                         const T *gtab, T dx, T dy, void *stream);
 template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, hipStream_t s);
 
+// Passive tracers (swmhd_tracers_rk3_*, tracer_kernels.inc): K extra centre fields advected by the state (q1, q2, h) a stage starts
+// from, all of them through that RK3 stage in ONE launch of an LDS-tiled kernel.  Pointers address interior cell (1,1) like TendArgs;
+// fuse / first / store_G / anchor / wrap / topo / dtg / dtw mean what they mean there.
+constexpr int MAX_TRACERS = 8;            // = SWMHD_MAX_TRACERS
+constexpr int TRACER_TILE_X = 64, TRACER_TILE_Y = 16;   // cells of a workgroup's tile (profiles/tracers/README.md)
+template <typename T>
+struct TracerArgs {
+    const T *q1, *q2, *h;
+    const T *c[MAX_TRACERS];
+    T *cnew[MAX_TRACERS], *Gn[MAX_TRACERS];
+    const T *Gm[MAX_TRACERS];
+    int K, Nx, Ny, Hx, Hy;
+    long sy;
+    T dx, dy, rdx, rdy;
+    int j0, j1;
+    int fuse, first, store_G, anchor, wrap, topo_x, topo_y;
+    T dt, gamma, zeta, dtg, dtw;
+};
+template <typename T> hipError_t launch_tracers_fast(const TracerArgs<T> &a, int formulation, hipStream_t s);
+template <typename T> hipError_t launch_tracers_strict(const TracerArgs<T> &a, int formulation, hipStream_t s);
+
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
 // (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read

@@ -272,6 +272,58 @@ int rk3_common(T *const *U, const T *const *Gn, const T *const *Gm, int Nx, int 
     return hiprc((flags & SWMHD_STRICT) ? launch_rk3_substep_strict<T>(a, s) : launch_rk3_substep_fast<T>(a, s));
 }
 
+// swmhd_tracers_rk3: K passive tracers through one RK3 stage in one launch (tracer_kernels.inc).  Every check precedes the first HIP call.
+template <typename T>
+int tracers_common(const T *q1, const T *q2, const T *h, const T *const *c, T *const *cnew, T *const *Gn, const T *const *Gm, int K,
+                   int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, int formulation, T dt, T gamma, T zeta, int store_G, int j0,
+                   int j1, int flags, void *stream) {
+    constexpr int OK = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_RK3_ANCHOR;
+    constexpr int NOTSUP = SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_OPEN_SOUTH | SWMHD_OPEN_NORTH | SWMHD_LEAVE_ROOM;
+    if (!q1 || !q2 || !h || !c || !Gn) return SWMHD_EINVAL;
+    if (K < 1 || K > SWMHD_MAX_TRACERS) return SWMHD_EINVAL;
+    if (Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
+    if (!(dx > T(0)) || !(dy > T(0))) return SWMHD_EINVAL;
+    if (j0 < 0 || j1 > Ny || j0 > j1) return SWMHD_EINVAL;
+    if (formulation != SWMHD_CONSERVATIVE && formulation != SWMHD_VECTOR_INVARIANT) return SWMHD_EINVAL;
+    if (flags & ~(OK | NOTSUP)) return SWMHD_EINVAL;
+    if (!cnew && !store_G) return SWMHD_EINVAL;                 // tendencies only: they must be stored
+    if (!cnew && (flags & SWMHD_RK3_ANCHOR)) return SWMHD_EINVAL;   // the anchor form is a form of the update
+    for (int k = 0; k < K; ++k) {
+        if (!c[k] || !Gn[k] || (cnew && !cnew[k]) || (Gm && !Gm[k])) return SWMHD_EINVAL;
+        if (!cnew) continue;
+        if (cnew[k] == q1 || cnew[k] == q2 || cnew[k] == h) return SWMHD_EINVAL;
+        for (int m = 0; m < K; ++m)
+            if (cnew[k] == c[m] || (m != k && cnew[k] == cnew[m])) return SWMHD_EINVAL;   // neighbouring workgroups still read c through their halos
+    }
+    if (((flags & SWMHD_BOUNDED_X) && (flags & SWMHD_WRAP_X)) || ((flags & SWMHD_BOUNDED_Y) && (flags & SWMHD_WRAP_Y))) return SWMHD_EINVAL;
+    if (((flags & SWMHD_WRAP_X) && Nx < Hx) || ((flags & SWMHD_WRAP_Y) && Ny < Hy)) return SWMHD_EINVAL;   // one period must cover the halo
+    if (flags & NOTSUP) return SWMHD_ENOTSUP;
+    if ((flags & SWMHD_RK3_ANCHOR) && (flags & (SWMHD_STRICT | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y))) return SWMHD_ENOTSUP;
+    if (Hx < 3 || Hy < 3) return SWMHD_EHALO;
+    if (j0 == j1) return SWMHD_OK;
+    TracerArgs<T> a;
+    const long off = (long)Hy * sy + Hx;
+    a.q1 = q1 + off; a.q2 = q2 + off; a.h = h + off;
+    for (int k = 0; k < MAX_TRACERS; ++k) {
+        const bool on = k < K;
+        a.c[k] = on ? c[k] + off : nullptr; a.Gn[k] = on ? Gn[k] + off : nullptr;
+        a.cnew[k] = on && cnew ? cnew[k] + off : nullptr; a.Gm[k] = on && Gm ? Gm[k] + off : nullptr;
+    }
+    a.K = K; a.Nx = Nx; a.Ny = Ny; a.Hx = Hx; a.Hy = Hy; a.sy = (long)sy;
+    a.dx = dx; a.dy = dy; a.rdx = T(1) / dx; a.rdy = T(1) / dy; a.j0 = j0; a.j1 = j1;
+    a.fuse = cnew ? 1 : 0; a.first = Gm ? 0 : 1; a.store_G = store_G ? 1 : 0;
+    a.anchor = (flags & SWMHD_RK3_ANCHOR) ? 1 : 0;
+    a.wrap = ((flags & SWMHD_WRAP_X) ? 1 : 0) | ((flags & SWMHD_WRAP_Y) ? 2 : 0);
+    a.topo_x = (flags & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC; a.topo_y = (flags & SWMHD_BOUNDED_Y) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
+    a.dt = dt; a.gamma = gamma; a.zeta = zeta; a.dtg = dt * gamma; a.dtw = T(0);
+    if (a.anchor) {   // no G store: the first stage writes W through Gn, later stages only read W (tend_common)
+        a.store_G = 0;
+        a.dtw = Gm ? T(0) : dt * zeta;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    return hiprc((flags & SWMHD_STRICT) ? launch_tracers_strict<T>(a, formulation, s) : launch_tracers_fast<T>(a, formulation, s));
+}
+
 // The RK3 step driver.  Periodic: stages in anchor form (fast) and a periodic fill of whatever the kernel does not wrap.  With `bc`
 // (Bounded ensembles, swmhd_ensemble_step_rk3_bc): ShallowWaterModel.time_step's Bounded schedule -- every stage in G- form, then the
 // boundary-condition fill of the four fields (u|uh at Face in x, v|vh at Face in y), gradient values from the DEVICE table bc_gradient.
@@ -355,6 +407,7 @@ int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, lon
 static_assert(GM_IS_PREV_STATE == SWMHD_GM_IS_PREV_STATE, "common.hpp mirrors swmhd.h");
 static_assert(RK3_ANCHOR == SWMHD_RK3_ANCHOR, "common.hpp mirrors swmhd.h");
 static_assert(ENS_NPARAMS == SWMHD_ENSEMBLE_NPARAMS, "common.hpp mirrors swmhd.h");
+static_assert(MAX_TRACERS == SWMHD_MAX_TRACERS, "common.hpp mirrors swmhd.h");
 #define SW_INST(T)                                                                                                                   \
     template int tendencies_rk3_two_ranges<T>(const T *const *, T *const *, T *const *, const T *const *, int, int, int, int, long, T, \
                                               T, T, T, int, int, T, T, T, int, int, int, int, int, int, void *);                      \
@@ -452,6 +505,13 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
                                    T gamma, T zeta, int store_G, int j0, int j1, int flags, void *stream) {              \
         return tend_rk3_common<T>(q, qnew, Gn, Gm, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, gamma,   \
                                   zeta, store_G, j0, j1, flags, stream);                                                \
+    }                                                                                                                  \
+    int swmhd_tracers_rk3_##sfx(const T *q1, const T *q2, const T *h, const T *const *c, T *const *cnew, T *const *Gn,  \
+                                const T *const *Gm, int ntracers, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, \
+                                int formulation, T dt, T gamma, T zeta, int store_G, int j0, int j1, int flags,          \
+                                void *stream) {                                                                        \
+        return tracers_common<T>(q1, q2, h, c, cnew, Gn, Gm, ntracers, Nx, Ny, Hx, Hy, sy, dx, dy, formulation, dt,     \
+                                 gamma, zeta, store_G, j0, j1, flags, stream);                                         \
     }                                                                                                                  \
     int swmhd_diagnostics_##sfx(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int Hx, int Hy,      \
                                 int64_t sy, T dx, T dy, T g, T href, int form, int j0, int j1, double *ws, double *out, \

@@ -21,6 +21,26 @@ RK3_ZETA = (0.0, -17.0 / 60.0, -5.0 / 12.0)
 
 
 RK3_ANCHOR_WEIGHT = 0.25    # gamma1 + zeta2 = 8/15 - 17/60
+# names a passive tracer may not take: the prognostic fields of either formulation and the derived output fields
+RESERVED_NAMES = ("u", "v", "uh", "vh", "h", "A", "s", "B_x", "B_y")
+
+
+def tracer_names(tracers):
+    """`tracers=` of ShallowWaterModel as a tuple of checked names (the reference's `tracers = (:A)` is a tuple of names: every
+    further one is a centre field advected like A).  Raises SwmhdError; touches no device."""
+    if tracers is None:
+        return ()
+    names = (tracers,) if isinstance(tracers, str) else tuple(tracers)
+    for n in names:
+        if not isinstance(n, str) or not n:
+            raise _lib.SwmhdError(f"tracers: {n!r} is not a name (a non-empty string)")
+        if n in RESERVED_NAMES:
+            raise _lib.SwmhdError(f"tracers: {n!r} names a field of the model or of its output frames ({' '.join(RESERVED_NAMES)})")
+    if len(set(names)) != len(names):
+        raise _lib.SwmhdError(f"tracers: duplicate names in {names!r}")
+    if len(names) > _lib.MAX_TRACERS:
+        raise _lib.SwmhdError(f"tracers: {len(names)} names, at most {_lib.MAX_TRACERS} (SWMHD_MAX_TRACERS)")
+    return names
 
 
 def rk3_stage(stage, anchor):
@@ -46,7 +66,17 @@ def loopback_rings(nranks, timeout_s=60.0):
 class ShallowWaterModel:
     def __init__(self, grid, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, device="cuda", strict=False, decomp=None, group=None,
-                 overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None):
+                 overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None,
+                 tracers=()):
+        # passive tracers (swmhd_tracers_rk3_*): names and what they cannot be combined with are checked before anything is allocated
+        self.tracer_names = tracer_names(tracers)
+        if self.tracer_names:
+            if decomp is not None and decomp.world_size > 1:
+                raise _lib.SwmhdError("tracers on a y-slab decomposition are not supported (SWMHD_ENOTSUP): one rank only")
+            if ring is not None:
+                raise _lib.SwmhdError("tracers with ring= are not supported (SWMHD_ENOTSUP): the slab driver steps the four fields only")
+            if not fused:
+                raise _lib.SwmhdError("tracers need the fused stage kernel (SWMHD_ENOTSUP): fused=False has no tracer substep")
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code = _lib.VECTOR_INVARIANT if formulation == VectorInvariantFormulation else _lib.CONSERVATIVE
@@ -96,6 +126,12 @@ class ShallowWaterModel:
         self._alt = {n: mk(l) for n, l in zip(self.names, locs)} if fused else None
         self.Gn = [mk(l) for l in locs]     # Gⁿ
         self.Gm = [mk(l) for l in locs]     # G⁻
+        # tracers: centre fields with an alternate set and two G sets like the state, swapped together with the state's (time_step)
+        cc = (Center, Center)
+        self._tr = {n: mk(cc) for n in self.tracer_names}
+        self._tr_alt = {n: mk(cc) for n in self.tracer_names}
+        self._tGn = [mk(cc) for _ in self.tracer_names]
+        self._tGm = [mk(cc) for _ in self.tracer_names]
         self.sfx = _SFX[dtype]
         self.clock_time, self.iteration = 0.0, 0
         self._comm_stream = torch.cuda.Stream() if (self.decomp.ring and torch.cuda.is_available()) else None
@@ -199,15 +235,21 @@ class ShallowWaterModel:
     def set(self, **kw):
         self._join()
         for k, v in kw.items():
-            self._state[k].set(v)
+            (self._tr[k] if k in self._tr else self._state[k]).set(v)
         self.update_state()
         return self
 
     @property
     def solution(self):
-        """The prognostic fields by name (u|uh, v|vh, h, A), halos current."""
+        """The prognostic fields by name (u|uh, v|vh, h, A, then the tracers), halos current."""
         self._ensure_halos()
-        return self._state
+        return {**self._state, **self._tr} if self._tr else self._state
+
+    @property
+    def tracers(self):
+        """The passive tracers by name, halos current."""
+        self._ensure_halos()
+        return dict(self._tr)
 
     @property
     def fields(self):
@@ -250,7 +292,34 @@ class ShallowWaterModel:
                (ct * 16)(*grads), g.dx, g.dy, _stream_ptr(stream))
         _lib.check(rc, "swmhd_fill_halo")
 
+    def _fill_tracers(self, stream=None):
+        """The halo fill of the tracers, in groups of at most four fields (the limit of the fills): the periodic copy, or on a grid with
+        a Bounded direction swmhd_fill_halo for centre fields with each tracer's own gradient values (default: no flux)."""
+        import ctypes
+        g = self.grid
+        tx, ty = g.topo_codes()
+        ct = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
+        names = self.tracer_names
+        for k in range(0, len(names), 4):
+            grp = names[k:k + 4]
+            ptrs = _lib.ptr_array([self._tr[n].ptr for n in grp])
+            sy = self._tr[grp[0]].stride_y
+            if any(self._bounded):
+                grads = []
+                for n in grp:
+                    bc = self.boundary_conditions.get(n)
+                    grads += bc.gradients() if bc is not None else [float("nan")] * 4
+                f = getattr(self._L, f"swmhd_fill_halo_{self.sfx}")
+                rc = f(ptrs, len(grp), g.Nx, g.Ny, g.Hx, g.Hy, sy, tx, ty, 0, 0, (ct * len(grads))(*grads), g.dx, g.dy, _stream_ptr(stream))
+                _lib.check(rc, "swmhd_fill_halo (tracers)")
+            else:
+                f = getattr(self._L, f"swmhd_fill_halo_periodic_multi_{self.sfx}")
+                rc = f(ptrs, len(grp), g.Nx, g.Ny, g.Hx, g.Hy, sy, _lib.HALO_X | _lib.HALO_Y, _stream_ptr(stream))
+                _lib.check(rc, "fill_halo_multi (tracers)")
+
     def _fill_x(self, stream=None):
+        if self._tr:
+            self._fill_tracers(stream)
         if any(self._bounded):
             return self._fill_bc(stream)
         g = self.grid
@@ -337,6 +406,26 @@ class ShallowWaterModel:
             self.tendency_events.append((e0, e1, j1 - j0))
         _lib.check(rc, "swmhd_tendencies_rk3")
 
+    def _tracer_stage(self, dt, stage):
+        """All tracers through RK3 stage `stage` in one launch (swmhd_tracers_rk3_*), advected by the state the stage started from: call
+        it after _stage_fused and BEFORE the state sets are swapped.  Same (gamma, zeta, store_G, anchor) as the state's stage."""
+        g = self.grid
+        q = self._raw_fields
+        names = self.tracer_names
+        P = _lib.ptr_array
+        gamma, zeta, store, anchor = rk3_stage(stage, not self.strict and not any(self._bounded))
+        flags = (self._flags & ~(_lib.TILE_KERNEL | _lib.MARCH_KERNEL)) | self._rwrap
+        if anchor:   # stage 0 writes W into Gn; the swaps hand it to stage 1 as G- and to stage 2 as Gn (_stage_fused)
+            flags |= _lib.RK3_ANCHOR
+            Gm = None if stage == 0 else P([f.ptr for f in (self._tGm if stage == 1 else self._tGn)])
+        else:
+            Gm = P([f.ptr for f in self._tGm]) if stage > 0 else None
+        f = getattr(self._L, f"swmhd_tracers_rk3_{self.sfx}")
+        rc = f(q[0].ptr, q[1].ptr, q[2].ptr, P([self._tr[n].ptr for n in names]), P([self._tr_alt[n].ptr for n in names]),
+               P([x.ptr for x in self._tGn]), Gm, len(names), g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride_y, g.dx, g.dy, self.form_code,
+               dt, gamma, zeta, store, 0, g.Ny, flags, _stream_ptr())
+        _lib.check(rc, "swmhd_tracers_rk3")
+
     # --- time_step!(model, dt): RungeKutta3 ------------------------------------------------------------------
     def _native_steps(self, dt, n):
         """n RK3 steps in ONE C call that enqueues every launch: the native ring driver (swmhd_ring_step_rk3_*) on a slab, the step
@@ -395,6 +484,10 @@ class ShallowWaterModel:
                 torch.cuda.current_stream().wait_stream(self._comm_stream)
             else:
                 run()
+            if self._tr:       # the tracers follow the state this stage started from: still self._state here
+                self._tracer_stage(dt, stage)
+                self._tr, self._tr_alt = self._tr_alt, self._tr
+                self._tGn, self._tGm = self._tGm, self._tGn
             if self.fused:
                 self._state, self._alt = self._alt, self._state      # the new state becomes current
             else:
@@ -423,7 +516,8 @@ class ShallowWaterModel:
         if self.decomp.ring or not self.fused:
             raise _lib.SwmhdError("capture_graph: single-GPU fused path only (halo exchange is not capturable)")
         self._ensure_halos()
-        keep = [f.data.clone() for f in self._raw_fields] + [f.data.clone() for f in self.Gm]
+        saved = self._raw_fields + self.Gm + [self._tr[n] for n in self.tracer_names] + self._tGm
+        keep = [f.data.clone() for f in saved]
         t0, i0 = self.clock_time, self.iteration
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -437,7 +531,7 @@ class ShallowWaterModel:
         # the graph has the device pointers of THIS role assignment baked in (state in `solution`, scratch in `_alt`, Gn/Gm as
         # they are now): it may only be replayed while the roles are the same, i.e. after an even number of eager steps
         self._graph_roles = self._roles()
-        for f, k in zip(self._raw_fields + self.Gm, keep):   # capture does not execute; undo the two warm-up steps
+        for f, k in zip(saved, keep):   # capture does not execute; undo the two warm-up steps (which left every role where it was)
             f.data.copy_(k)
         self._halo_stale = False
         self.clock_time, self.iteration = t0, i0
@@ -467,7 +561,8 @@ class ShallowWaterModel:
             self._driver_steps(dt, n)
 
     def _driver_steps(self, dt, n):
-        if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)):
+        if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)
+                                      and not self._tr):     # (the native step driver steps the four fields only)
             return self._native_steps(dt, n)
         for _ in range(n):
             self.time_step(dt)
@@ -515,7 +610,9 @@ class ShallowWaterModel:
         self.synchronize()
         np.savez(path, time=self.clock_time, iteration=self.iteration,
                  **{n: f.numpy() for n, f in zip(self.names, self.fields)},
-                 **{"Gm_" + n: f.numpy() for n, f in zip(self.names, self.Gm)})
+                 **{"Gm_" + n: f.numpy() for n, f in zip(self.names, self.Gm)},
+                 **{"tracer_" + n: self._tr[n].numpy() for n in self.tracer_names},
+                 **{"tracer_Gm_" + n: f.numpy() for n, f in zip(self.tracer_names, self._tGm)})
 
     def load_checkpoint(self, path):
         import numpy as np
@@ -526,6 +623,9 @@ class ShallowWaterModel:
             f.data.copy_(torch.from_numpy(z[n]).to(f.data.dtype))
         for n, f in zip(self.names, self.Gm):
             f.data.copy_(torch.from_numpy(z["Gm_" + n]).to(f.data.dtype))
+        for n, f in zip(self.tracer_names, self._tGm):
+            self._tr[n].data.copy_(torch.from_numpy(z["tracer_" + n]).to(f.data.dtype))
+            f.data.copy_(torch.from_numpy(z["tracer_Gm_" + n]).to(f.data.dtype))
         self.clock_time, self.iteration = float(z["time"]), int(z["iteration"])
         return self
 

@@ -22,11 +22,13 @@ DEFAULT_NAMES = ("u", "v", "A", "s")    # the reference's writer
 _ELEM = {torch.float32: 4, torch.float64: 8}
 
 
-def _runs(names):
+def _runs(names, tracers=()):
     """The frame's fields as launches: the kernel writes the fields of a mask in bit order (u v h A s B_x B_y), so `names` is cut into
     runs that ascend in that order -- one launch for the default frame, and any order or repetition of names is honoured."""
     runs = []
     for n in names:
+        if n in tracers:
+            raise _lib.SwmhdError(f"output field {n!r} is a tracer: frames hold {' '.join(_lib.OUT_BITS)} only; read model.tracers[{n!r}]")
         if n not in _lib.OUT_BITS:
             raise _lib.SwmhdError(f"output field {n!r}: one of {' '.join(_lib.OUT_BITS)} (velocities u, v also for the conservative model)")
         bit = _lib.OUT_BITS[n]
@@ -47,7 +49,7 @@ def frame_shape(model, names):
 def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32):
     """ShallowWaterModel.output_fields / ShallowWaterEnsemble.output_fields: see there."""
     names = tuple(names)
-    runs = _runs(names)
+    runs = _runs(names, getattr(model, "tracer_names", ()))
     ens = getattr(model, "members", None) is not None
     g = model.grid
     if ens:
@@ -133,7 +135,7 @@ class FieldTimeSeries:
 
     def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None, array_type=torch.float32):
         self.model, self.names, self.schedule = model, tuple(names), schedule
-        _runs(self.names)
+        _runs(self.names, getattr(model, "tracer_names", ()))
         if array_type not in _ELEM:
             raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
         if capacity is None or int(capacity) < 1:
