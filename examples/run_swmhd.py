@@ -13,7 +13,9 @@ sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the field
 :80-84, or those of --frame-fields out of u v h A s B_x B_y, as --frame-dtype f32|f64) and writes them to <out>/frames.npz at the end.
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
 --dye adds one passive tracer c = tanh(y) to the run (ShallowWaterModel(tracers=("c",)): the reference's `tracers = (:A)` with a second
-name): its min / max join the progress line and the field goes into the --dump-every dumps (single runs only).
+name): its min / max join the progress line and the field goes into the --dump-every dumps.  With --amps, --coriolis, --gravity or
+--dts every member of the ensemble carries the dye (ShallowWaterEnsemble(tracers=("c",)): one more launch per RK3 stage for all of
+them); the interiors of all members go to <out>/tracers.npz at the end.  Not with --channel (Bounded ensembles carry no tracers).
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
@@ -77,8 +79,8 @@ def main():
     a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts))
     if a.dts and a.frames > 0:
         ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
-    if a.dye and (a.amps or a.channel or a.sweep):
-        ap.error("--dye: single runs only (the ensembles carry no tracers)")
+    if a.dye and a.channel:
+        ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
     if a.amps or a.channel or a.sweep:
         return run_ensemble(a)
 
@@ -197,22 +199,26 @@ def run_ensemble(a):
         A0 = [lambda X, Y, gr=gr: gr * Y for gr in amps]
     else:
         grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
-        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form)
+        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form, tracers=("c",) if a.dye else ())
         A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
     label = "gradient" if a.channel else "amp"
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
     v0 = lambda X, Y: -5 * X * np.exp(-(X ** 2 + Y ** 2))
     n1, n2 = ens.names[:2]
     ens.set(**{n1: u0, n2: v0, "h": lambda X, Y: np.ones_like(X), "A": A0})
+    if a.dye:
+        ens.set(c=lambda X, Y: np.tanh(Y))
     nsteps = int(round(a.stop_time / a.dt))
     rows = []
 
     def report(wall):
+        c = ens.tracers["c"][(slice(None),) + grid.interior] if a.dye else None
         for m, d in enumerate(ens.diagnostics()):
             t = float(ens.clock_times[m])
+            dye = f"min(c): {c[m].min().item():.4f}, max(c): {c[m].max().item():.4f}, " if a.dye else ""
             print(f"member {m} ({label} {amps[m]:g}{sweep(m)}) Time: {t:9.3f}, iteration: {ens.iteration}, "
                   f"max(|u|): {max(d['max_abs_u'], d['max_abs_v']):.2e}, max(|A|): {d['max_abs_A']:.2e}, min(h): {d['min_h']:.2e}, "
-                  f"wall time: {wall * 1e3:.1f} ms | KE {d['kinetic_energy']:.6f} ME {d['magnetic_energy']:.6f} "
+                  f"{dye}wall time: {wall * 1e3:.1f} ms | KE {d['kinetic_energy']:.6f} ME {d['magnetic_energy']:.6f} "
                   f"PE {d['potential_energy']:.3e} total {d['total_energy']:.6f}", flush=True)
             rows.append((m,) + (params(m) if a.sweep else ()) + (t, d["kinetic_energy"], d["magnetic_energy"], d["potential_energy"], d["total_energy"]))
 
@@ -245,6 +251,10 @@ def run_ensemble(a):
     print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations of {len(amps)} members, "
           f"{len(amps) * N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); energy drift abs(E - E0) * 100 per member = {drift}")
     save_frames(a, series)
+    if a.dye:
+        os.makedirs(a.out, exist_ok=True)
+        np.savez(os.path.join(a.out, "tracers.npz"), c=ens.tracers["c"][(slice(None),) + grid.interior].cpu().numpy(),
+                 time=ens.clock_times, iteration=ens.iteration)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f)

@@ -659,6 +659,49 @@ int swmhd_ensemble_diagnostics_params_f32(const float *q1, const float *q2, cons
                                           double *workspace, double *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Passive tracers of a periodic ensemble: swmhd_tracers_rk3 over all rows of every member -- ALL `ntracers` tracers of ALL `members`
+ * members through one RK3 stage in ONE launch (the 64 x 16 tile of the single-grid kernel, the member folded into the block index).
+ * Arguments as swmhd_tracers_rk3 without j_begin / j_end, plus the ensemble's members and stride_m (layout and limits above):
+ *   q1, q2, h         member 0's parents of the state this stage STARTS from (the q of swmhd_ensemble_tendencies_rk3 of the same stage)
+ *   c, cnew, Gn, Gm   HOST arrays of `ntracers` device pointers to member 0's parents; member m of each at ptr + m * stride_m
+ *   params (the _params form, in place of dt): the DEVICE table of the *_params calls above; member m steps with params[3 m + 2].
+ *                     g and f are not read (they do not enter a tracer's tendency).  With SWMHD_STRICT the update is evaluated as
+ *                     written at swmhd_tracers_rk3 with the member's dt; in the anchor form the kernel forms dt * gamma and
+ *                     dt * (gamma1 + zeta2) itself, one multiply in the element type each, as the host does for one grid.
+ * Accepted flags: SWMHD_STRICT, SWMHD_TILE_KERNEL (a no-op), SWMHD_WRAP_X, SWMHD_WRAP_Y, SWMHD_RK3_ANCHOR, each as in swmhd_tracers_rk3.
+ *   SWMHD_EINVAL   everything swmhd_tracers_rk3 returns it for; members outside 1 .. SWMHD_ENSEMBLE_MAX_MEMBERS;
+ *                  stride_m < (Ny + 2Hy) * stride_y; params == NULL
+ *   SWMHD_ENOTSUP  SWMHD_BOUNDED_X / _Y (periodic members only), SWMHD_MARCH_KERNEL, SWMHD_GM_IS_PREV_STATE, SWMHD_OPEN_SOUTH / _NORTH,
+ *                  SWMHD_LEAVE_ROOM; SWMHD_RK3_ANCHOR with SWMHD_STRICT
+ *   SWMHD_EHALO    Hx < 3 or Hy < 3
+ *   Every check precedes the first HIP call.
+ * Results: each member gets the arithmetic of swmhd_tracers_rk3 on that member alone (the same kernel body).  SWMHD_STRICT members are
+ * bit-identical to it and to the oracle, and the strict _params call to the scalar call made per member with that member's dt.  Fast
+ * members are within the fast tolerance of A.  Nothing between two members of a pitched ensemble is read or written, and a
+ * non-finite member does not affect the others.
+ * ---------------------------------------------------------------------------------------------- */
+int swmhd_ensemble_tracers_rk3_f64(const double *q1, const double *q2, const double *h,
+                                   const double *const *c, double *const *cnew, double *const *Gn, const double *const *Gm,
+                                   int ntracers, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                   double dx, double dy, int formulation, double dt, double gamma, double zeta, int store_G,
+                                   int flags, void *stream);
+int swmhd_ensemble_tracers_rk3_f32(const float *q1, const float *q2, const float *h,
+                                   const float *const *c, float *const *cnew, float *const *Gn, const float *const *Gm,
+                                   int ntracers, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t stride_y,
+                                   float dx, float dy, int formulation, float dt, float gamma, float zeta, int store_G,
+                                   int flags, void *stream);
+int swmhd_ensemble_tracers_rk3_params_f64(const double *q1, const double *q2, const double *h,
+                                          const double *const *c, double *const *cnew, double *const *Gn, const double *const *Gm,
+                                          int ntracers, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy,
+                                          int64_t stride_y, double dx, double dy, int formulation, const double *params,
+                                          double gamma, double zeta, int store_G, int flags, void *stream);
+int swmhd_ensemble_tracers_rk3_params_f32(const float *q1, const float *q2, const float *h,
+                                          const float *const *c, float *const *cnew, float *const *Gn, const float *const *Gm,
+                                          int ntracers, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy,
+                                          int64_t stride_y, float dx, float dy, int formulation, const float *params,
+                                          float gamma, float zeta, int store_G, int flags, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Output frames: the fields an output writer stores, made on the device in ONE pass over the four prognostic parents -- derived
  * fields included, halo-stripped, in the writer's element type.  The reference writes (u, v, A, s), s = sqrt(u^2 + v^2), every 0.1
  * time units (JLD2OutputWriter, SWMHD_example.jl:67-68,80-84; divergence_sw_mhd.jl:64-66,75-82 with u = uh / h, v = vh / h) and looks

@@ -129,6 +129,13 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_diagnostics_params_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, p, ft, i, p, p, p]
         f.restype = i
+        # the tracers of a periodic ensemble: swmhd_tracers_rk3 without the row range, with members and stride_m (dt: scalar | table)
+        f = getattr(lib, f"swmhd_ensemble_tracers_rk3_{sfx}")
+        f.argtypes = [p, p, p] + [C.POINTER(p)] * 4 + [i, i, i64, i, i, i, i, i64, ft, ft, i, ft, ft, ft, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_tracers_rk3_params_{sfx}")
+        f.argtypes = [p, p, p] + [C.POINTER(p)] * 4 + [i, i, i64, i, i, i, i, i64, ft, ft, i, p, ft, ft, i, i, p]
+        f.restype = i
         f = getattr(lib, f"swmhd_ring_exchange_y_{sfx}")
         f.argtypes = [p, C.POINTER(p), i, i, i, i, i, i64, p]
         f.restype = i
@@ -182,7 +189,8 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "ring_exchange_y", "ring_step_rk3", "ensemble_tendencies_rk3", "ensemble_step_rk3", "ensemble_fill_halo_periodic",
         "ensemble_diagnostics", "ensemble_fill_halo", "ensemble_step_rk3_bc", "fill_halo_walls", "ring_exchange_y_sides", "ring_step_rk3_bc",
         "output_fields", "ensemble_output_fields", "ensemble_tendencies_rk3_params", "ensemble_step_rk3_params",
-        "ensemble_step_rk3_bc_params", "ensemble_diagnostics_params", "tracers_rk3")] + [
+        "ensemble_step_rk3_bc_params", "ensemble_diagnostics_params", "tracers_rk3", "ensemble_tracers_rk3",
+        "ensemble_tracers_rk3_params")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
 RING_ID_BYTES = 128

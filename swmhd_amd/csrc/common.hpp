@@ -270,6 +270,27 @@ struct TracerArgs {
 };
 template <typename T> hipError_t launch_tracers_fast(const TracerArgs<T> &a, int formulation, hipStream_t s);
 template <typename T> hipError_t launch_tracers_strict(const TracerArgs<T> &a, int formulation, hipStream_t s);
+// Tracers of an ensemble (swmhd_ensemble_tracers_rk3_*): all K tracers of all `members` periodic members through one stage in ONE
+// launch, member m of every parent (q1, q2, h, c[k], cnew[k], Gn[k], Gm[k]) at ptr + m * stride_m.  The kernel's ENS variant folds the
+// member into blockIdx.x (EnsTendArgs::fold = 1) and adds the offset where it forms an address; the pointer arrays are not rewritten
+// (they are indexed by the tracer loop: a modified copy would live in scratch).  All rows of every member; j0 / j1 = 0 / Ny.
+template <typename T>
+struct EnsTracerArgs : TracerArgs<T> {
+    long stride_m;
+    int members;
+};
+// Per-member dt from the DEVICE table params[3 m + 2] (EnsParTendArgs; g and f do not enter a tracer's tendency): the PAR variant forms
+// dtg and dtw from it as the host does for one grid; dt, dtg and dtw of the base struct are not read.
+template <typename T>
+struct EnsParTracerArgs : EnsTracerArgs<T> {
+    const T *params;
+};
+template <typename T, bool ENS, bool PAR = false>
+using TracerTileArgs = std::conditional_t<PAR, EnsParTracerArgs<T>, std::conditional_t<ENS, EnsTracerArgs<T>, TracerArgs<T>>>;
+template <typename T> hipError_t launch_tracers_ensemble_fast(const EnsTracerArgs<T> &a, int formulation, hipStream_t s);
+template <typename T> hipError_t launch_tracers_ensemble_strict(const EnsTracerArgs<T> &a, int formulation, hipStream_t s);
+template <typename T> hipError_t launch_tracers_ensemble_params_fast(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s);
+template <typename T> hipError_t launch_tracers_ensemble_params_strict(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s);
 
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr

@@ -273,12 +273,19 @@ int rk3_common(T *const *U, const T *const *Gn, const T *const *Gm, int Nx, int 
 }
 
 // swmhd_tracers_rk3: K passive tracers through one RK3 stage in one launch (tracer_kernels.inc).  Every check precedes the first HIP call.
+// With `ens` (swmhd_ensemble_tracers_rk3[_params]): the tracers of every member of a periodic ensemble; the ensemble's own argument
+// errors come first, then the single-grid checks in their order, with the Bounded flags among the unsupported ones.
 template <typename T>
 int tracers_common(const T *q1, const T *q2, const T *h, const T *const *c, T *const *cnew, T *const *Gn, const T *const *Gm, int K,
                    int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, int formulation, T dt, T gamma, T zeta, int store_G, int j0,
-                   int j1, int flags, void *stream) {
+                   int j1, int flags, void *stream, const Ens *ens = nullptr) {
     constexpr int OK = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y | SWMHD_RK3_ANCHOR;
-    constexpr int NOTSUP = SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_OPEN_SOUTH | SWMHD_OPEN_NORTH | SWMHD_LEAVE_ROOM;
+    const int NOTSUP = SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_OPEN_SOUTH | SWMHD_OPEN_NORTH | SWMHD_LEAVE_ROOM |
+                       (ens ? SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y : 0);
+    if (ens) {   // members, stride_m, the table (the flags are checked below, with this call's own sets)
+        const int rc = ens_check(*ens, Ny, Hy, sy, 0);
+        if (rc) return rc;
+    }
     if (!q1 || !q2 || !h || !c || !Gn) return SWMHD_EINVAL;
     if (K < 1 || K > SWMHD_MAX_TRACERS) return SWMHD_EINVAL;
     if (Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
@@ -321,6 +328,20 @@ int tracers_common(const T *q1, const T *q2, const T *h, const T *const *c, T *c
         a.dtw = Gm ? T(0) : dt * zeta;
     }
     hipStream_t s = (hipStream_t)stream;
+    if (ens) {
+        EnsTracerArgs<T> e;
+        static_cast<TracerArgs<T> &>(e) = a;
+        e.stride_m = (long)ens->stride_m; e.members = ens->members;
+        if (ens->par) {   // (dt and its products come from the table, in the kernel)
+            EnsParTracerArgs<T> ep;
+            static_cast<EnsTracerArgs<T> &>(ep) = e;
+            ep.params = static_cast<const T *>(ens->params);
+            return hiprc((flags & SWMHD_STRICT) ? launch_tracers_ensemble_params_strict<T>(ep, formulation, s)
+                                                : launch_tracers_ensemble_params_fast<T>(ep, formulation, s));
+        }
+        return hiprc((flags & SWMHD_STRICT) ? launch_tracers_ensemble_strict<T>(e, formulation, s)
+                                            : launch_tracers_ensemble_fast<T>(e, formulation, s));
+    }
     return hiprc((flags & SWMHD_STRICT) ? launch_tracers_strict<T>(a, formulation, s) : launch_tracers_fast<T>(a, formulation, s));
 }
 
@@ -512,6 +533,23 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
                                 void *stream) {                                                                        \
         return tracers_common<T>(q1, q2, h, c, cnew, Gn, Gm, ntracers, Nx, Ny, Hx, Hy, sy, dx, dy, formulation, dt,     \
                                  gamma, zeta, store_G, j0, j1, flags, stream);                                         \
+    }                                                                                                                  \
+    int swmhd_ensemble_tracers_rk3_##sfx(const T *q1, const T *q2, const T *h, const T *const *c, T *const *cnew,      \
+                                         T *const *Gn, const T *const *Gm, int ntracers, int members, int64_t stride_m, \
+                                         int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, int formulation, T dt, \
+                                         T gamma, T zeta, int store_G, int flags, void *stream) {                       \
+        const Ens e{members, stride_m};                                                                                \
+        return tracers_common<T>(q1, q2, h, c, cnew, Gn, Gm, ntracers, Nx, Ny, Hx, Hy, sy, dx, dy, formulation, dt,     \
+                                 gamma, zeta, store_G, 0, Ny, flags, stream, &e);                                       \
+    }                                                                                                                  \
+    int swmhd_ensemble_tracers_rk3_params_##sfx(const T *q1, const T *q2, const T *h, const T *const *c, T *const *cnew, \
+                                                T *const *Gn, const T *const *Gm, int ntracers, int members,            \
+                                                int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx,     \
+                                                T dy, int formulation, const T *params, T gamma, T zeta, int store_G,   \
+                                                int flags, void *stream) {                                              \
+        const Ens e{members, stride_m, false, true, params};                                                           \
+        return tracers_common<T>(q1, q2, h, c, cnew, Gn, Gm, ntracers, Nx, Ny, Hx, Hy, sy, dx, dy, formulation, T(0),   \
+                                 gamma, zeta, store_G, 0, Ny, flags, stream, &e);                                       \
     }                                                                                                                  \
     int swmhd_diagnostics_##sfx(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int Hx, int Hy,      \
                                 int64_t sy, T dx, T dy, T g, T href, int form, int j0, int j1, double *ws, double *out, \

@@ -8,7 +8,9 @@
 // flux difference, c div U and the RK3 update per cell.  Three barriers per tracer: after the tile is loaded, after the fluxes are
 // written, and after the last read of the tile (the cell's own c in the update) before the next tracer's tile overwrites it.
 //
-// Kernels and launcher; included by tracer_fast.hip / tracer_strict.hip with SWMHD_STRICT and LAUNCH_SFX defined.
+// The same body serves periodic ensembles (swmhd_ensemble_tracers_rk3[_params]): the ENS / PAR instantiations walk the members.
+//
+// Kernels and launchers; included by tracer_fast.hip / tracer_strict.hip with SWMHD_STRICT and LAUNCH_SFX defined.
 
 #ifndef SWMHD_STRICT
 #error "include with SWMHD_STRICT defined"
@@ -25,8 +27,13 @@ constexpr bool STRICT = (SWMHD_STRICT != 0);
 
 // FORM: 0 conservative, 1 vector invariant.  BND: at least one direction is Bounded (wall orders of the reconstructions).
 // 64 x TYB threads; a thread owns column threadIdx.x of rows threadIdx.y * RY .. + RY - 1 of a TX x (TYB RY) tile.
-template <typename T, int FORM, bool BND, int TX, int TYB, int RY>
-__global__ __launch_bounds__(TX *TYB) void k_tracers_tile(TracerArgs<T> a, int ntx, int nty) {
+// ENS: ensemble launch (EnsTracerArgs) -- blockIdx.x runs over the tiles of all members (XCD-remapped over all of them, so a member's
+// tiles share an XCD, as in k_tendency_tile's folded mapping) and the workgroup's member offset `mo` enters every address; otherwise
+// the body is the same.  PAR (with ENS): the member also brings its own dt (EnsParTracerArgs); the body is the same again.
+template <typename T, int FORM, bool BND, int TX, int TYB, int RY, bool ENS = false, bool PAR = false>
+__global__ __launch_bounds__(TX *TYB) void k_tracers_tile(TracerTileArgs<T, ENS, PAR> a, int ntx, int nty) {
+    static_assert(ENS || !PAR, "per-member parameters need an ensemble launch");
+    static_assert(!ENS || !BND, "ensemble members are periodic");
     constexpr int TY = TYB * RY, NT = TX * TYB;
     constexpr int W = TX + 6, HH = TY + 6;
     constexpr bool CONS = FORM == 0;
@@ -39,18 +46,31 @@ __global__ __launch_bounds__(TX *TYB) void k_tracers_tile(TracerArgs<T> a, int n
     __shared__ T sFy[TY + 1][TX];       //                  through the y-faces
     static_assert(!CONS || (TY + 2) * (TX + 2) <= HH * W, "h on tile + 1 is staged in the tracer tile");
 
-    const unsigned bid = xcd_remap(blockIdx.x, (unsigned)(ntx * nty));
+    unsigned bid;
+    long mo = 0;                        // element offset of this workgroup's member in every parent
+    T dt = a.dt, dtg = a.dtg, dtw = a.dtw;
+    if constexpr (ENS) {
+        const unsigned ntiles = (unsigned)(ntx * nty);
+        const unsigned L = xcd_remap(blockIdx.x, ntiles * (unsigned)a.members), m = L / ntiles;
+        bid = L - m * ntiles;
+        mo = (long)m * a.stride_m;
+        if constexpr (PAR) {            // m comes from blockIdx alone: a scalar load; the products as the host forms them for one grid
+            dt = a.params[(long)ENS_NPARAMS * m + 2];
+            dtg = dt * a.gamma;
+            dtw = dt * a.zeta;
+        }
+    } else bid = xcd_remap(blockIdx.x, (unsigned)(ntx * nty));
     const int tyi = (int)(bid / ntx), txi = (int)(bid % ntx);
     const int x0 = txi * TX, y0 = a.j0 + tyi * TY;
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TX + tx;
     const int xlo = -a.Hx, xhi = a.Nx + a.Hx - 1, ylo = -a.Hy, yhi = a.Ny + a.Hy - 1;
     const Geo<T> g{a.dx, a.dy, a.rdx, a.rdy};
 
-    load_tile<T, TX + 1, TY, NT>(sU, a.q1, a.sy, x0, y0, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
-    load_tile<T, TX, TY + 1, NT>(sV, a.q2, a.sy, x0, y0, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
+    load_tile<T, TX + 1, TY, NT>(sU, a.q1 + mo, a.sy, x0, y0, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
+    load_tile<T, TX, TY + 1, NT>(sV, a.q2 + mo, a.sy, x0, y0, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
     if constexpr (CONS) {
         auto &sH = *reinterpret_cast<T(*)[TY + 2][TX + 2]>(&sC[0][0]);
-        load_tile<T, TX + 2, TY + 2, NT>(sH, a.h, a.sy, x0 - 1, y0 - 1, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
+        load_tile<T, TX + 2, TY + 2, NT>(sH, a.h + mo, a.sy, x0 - 1, y0 - 1, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
         __syncthreads();
         auto H_ = [&](int ii, int jj) -> T { return sH[jj + 1][ii + 1]; };
         // he = hw of the next cell, hn = hs of the next row: one value per face
@@ -112,7 +132,7 @@ __global__ __launch_bounds__(TX *TYB) void k_tracers_tile(TracerArgs<T> a, int n
 
 #pragma unroll 1
     for (int k = 0; k < a.K; ++k) {
-        load_tile<T, W, HH, NT>(sC, a.c[k], a.sy, x0 - 3, y0 - 3, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
+        load_tile<T, W, HH, NT>(sC, a.c[k] + mo, a.sy, x0 - 3, y0 - 3, xlo, xhi, ylo, yhi, tid, a.Nx, a.Ny, a.wrap);
         __syncthreads();
         // every face of the tile once: the thread's own west and south faces, then column TX (wave 0) and row TY (the last wave)
 #pragma unroll 1
@@ -137,22 +157,22 @@ __global__ __launch_bounds__(TX *TYB) void k_tracers_tile(TracerArgs<T> a, int n
                 G = -rAz * ((fxe - fxw) + (fyn - fys)) + c * divU[r];
             }
             if (gxi < a.Nx && gyj < a.j1) {
-                const long o = (long)gyj * a.sy + gxi;
+                const long o = mo + (long)gyj * a.sy + gxi;
                 if (a.store_G) a.Gn[k][o] = G;
                 if (a.fuse) {
                     T un;
                     if (!STRICT && !BND && a.anchor) {   // anchor form (common.hpp: Rk3Buffers): W out through Gn, or W in through Gm
                         if (a.first) {
-                            un = c + a.dtg * G;
-                            a.Gn[k][o] = c + a.dtw * G;
+                            un = c + dtg * G;
+                            a.Gn[k][o] = c + dtw * G;
                         } else {
-                            un = a.Gm[k][o] + a.dtg * G;
+                            un = a.Gm[k][o] + dtg * G;
                         }
                     } else if (a.first) {
-                        if constexpr (STRICT) un = c + a.dt * a.gamma * G;
-                        else un = c + (a.dt * a.gamma) * G;
+                        if constexpr (STRICT) un = c + dt * a.gamma * G;
+                        else un = c + (dt * a.gamma) * G;
                     } else {
-                        un = c + a.dt * (a.gamma * G + a.zeta * a.Gm[k][o]);
+                        un = c + dt * (a.gamma * G + a.zeta * a.Gm[k][o]);
                     }
                     a.cnew[k][o] = un;
                 }
@@ -185,5 +205,34 @@ hipError_t LAUNCH_NAME(launch_tracers_, LAUNCH_SFX)(const TracerArgs<T> &a, int 
 }
 template hipError_t LAUNCH_NAME(launch_tracers_, LAUNCH_SFX)<double>(const TracerArgs<double> &, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_tracers_, LAUNCH_SFX)<float>(const TracerArgs<float> &, int, hipStream_t);
+
+// Ensemble stage: the same 64 x 16 tile over every tile of every member, all rows, one launch (periodic members only).
+template <typename T, bool PAR>
+static hipError_t launch_tracers_ensemble_stage(const TracerTileArgs<T, true, PAR> &a, int formulation, hipStream_t s) {
+    constexpr int TX = TRACER_TILE_X, TYB = 4, RY = TRACER_TILE_Y / TYB;
+    if (a.j1 <= a.j0 || a.K <= 0 || a.members <= 0) return hipSuccess;
+    if (is_bounded(a.topo_x, a.topo_y)) return hipErrorInvalidValue;
+    const int ntx = (a.Nx + TX - 1) / TX, nty = (a.j1 - a.j0 + TRACER_TILE_Y - 1) / TRACER_TILE_Y;
+    const long blocks = (long)ntx * nty * a.members;
+    if (blocks >= (1L << 31)) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)blocks), block(TX, TYB);
+    if (formulation == 1) hipLaunchKernelGGL((k_tracers_tile<T, 1, false, TX, TYB, RY, true, PAR>), grid, block, 0, s, a, ntx, nty);
+    else if (formulation == 0) hipLaunchKernelGGL((k_tracers_tile<T, 0, false, TX, TYB, RY, true, PAR>), grid, block, 0, s, a, ntx, nty);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t LAUNCH_NAME(launch_tracers_ensemble_, LAUNCH_SFX)(const EnsTracerArgs<T> &a, int formulation, hipStream_t s) {
+    return launch_tracers_ensemble_stage<T, false>(a, formulation, s);
+}
+template <typename T>
+hipError_t LAUNCH_NAME(launch_tracers_ensemble_params_, LAUNCH_SFX)(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s) {
+    if (!a.params) return hipErrorInvalidValue;
+    return launch_tracers_ensemble_stage<T, true>(a, formulation, s);
+}
+template hipError_t LAUNCH_NAME(launch_tracers_ensemble_, LAUNCH_SFX)<double>(const EnsTracerArgs<double> &, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_tracers_ensemble_, LAUNCH_SFX)<float>(const EnsTracerArgs<float> &, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_tracers_ensemble_params_, LAUNCH_SFX)<double>(const EnsParTracerArgs<double> &, int, hipStream_t);
+template hipError_t LAUNCH_NAME(launch_tracers_ensemble_params_, LAUNCH_SFX)<float>(const EnsParTracerArgs<float> &, int, hipStream_t);
 
 }  // namespace swmhd

@@ -18,8 +18,9 @@ import torch
 from . import _lib
 from .fields import _SFX, _stream_ptr
 from .grid import Center, Face
-from .model import ShallowWaterModel
-from .shared import VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, formulation_codes, gradient_values
+from .model import ShallowWaterModel, rk3_operands, tracer_names
+from .shared import (VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups, finish_stage,
+                     formulation_codes, gradient_values)
 
 LOCS = ((Face, Center), (Center, Face), (Center, Center), (Center, Center))
 
@@ -48,11 +49,17 @@ class ShallowWaterEnsemble:
     time_step, time_steps and capture_graph.  As soon as anything is per member the ensemble holds `parameters`, the (members, 3)
     device table of (g, f, dt) in its dtype, and steps through the swmhd_ensemble_*_params entry points; with scalars everywhere it
     calls exactly what it always called.  `clock_times` has every member's model time; `clock_time` is their common value and raises
-    once per-member time steps have made them differ."""
+    once per-member time steps have made them differ.
+
+    Passive tracers: `tracers=("c", "d")` gives every member those centre fields (ShallowWaterModel's argument, same names and limit),
+    laid out like the state.  Such an ensemble steps stage by stage: swmhd_ensemble_tendencies_rk3[_params], then
+    swmhd_ensemble_tracers_rk3[_params] on the state the stage started from -- six launches per step for all tracers of all members
+    with fused halos -- and its four state fields come out bitwise what the native driver gives the ensemble without tracers."""
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True):
+                 fuse_halo=True, tracers=()):
+        self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
         if decomp is not None or grid.Ny_global != grid.Ny or grid.j_offset != 0:
             raise _lib.SwmhdError("ShallowWaterEnsemble runs on one GPU: no slab decomposition")
         self._check_topology(grid)
@@ -89,6 +96,10 @@ class ShallowWaterEnsemble:
             return flat.as_strided((self.members, Py, Px), (self.stride_m, Px, 1))
         self._state, self._alt = [mk() for _ in LOCS], [mk() for _ in LOCS]
         self.Gn, self.Gm = [mk() for _ in LOCS], [mk() for _ in LOCS]
+        # tracers: a current and an alternate set and two G sets like the state's, swapped with them stage by stage (finish_stage)
+        self._tr, self._tr_alt = {n: mk() for n in self.tracer_names}, {n: mk() for n in self.tracer_names}
+        self._tGn, self._tGm = [mk() for _ in self.tracer_names], [mk() for _ in self.tracer_names]
+        self._anchor = not strict                      # the stage form of the native driver (common.hpp: Rk3Buffers)
         self.clock_times = np.zeros(self.members)
         self.clock_time, self.iteration = 0.0, 0
         self._L = _lib.lib()
@@ -160,12 +171,12 @@ class ShallowWaterEnsemble:
     # --- state ---------------------------------------------------------------------------------------------------
     def set(self, **kw):
         """set!(model, ...) for every member.  Each value: a callable (X, Y) used for every member, a list of `members` callables,
-        or an array of shape (members, Ny, Nx) (interiors) or (members, Ny+2Hy, Nx+2Hx) (parents)."""
+        or an array of shape (members, Ny, Nx) (interiors) or (members, Ny+2Hy, Nx+2Hx) (parents).  Tracers by their names, as A."""
         g = self.grid
         B = self.members
         for k, v in kw.items():
-            idx = self.names.index(k)
-            X, Y = g.nodes(LOCS[idx])
+            target, loc = (self._tr[k], (Center, Center)) if k in self._tr else (self._state[self.names.index(k)], LOCS[self.names.index(k)])
+            X, Y = g.nodes(loc)
             evaluate = lambda fn: np.asarray(fn(X, Y), dtype=np.float64) + np.zeros(g.parent_shape)
             if callable(v):
                 full = np.repeat(evaluate(v)[None], B, axis=0)
@@ -182,7 +193,7 @@ class ShallowWaterEnsemble:
                     full = arr
                 else:
                     raise ValueError(f"{k}: shape {arr.shape}, expected ({B}, {g.Ny}, {g.Nx}) or ({B}, {g.parent_shape[0]}, {g.parent_shape[1]})")
-            self._state[idx].copy_(torch.from_numpy(np.ascontiguousarray(full)).to(self.dtype))
+            target.copy_(torch.from_numpy(np.ascontiguousarray(full)).to(self.dtype))
         self.update_state()
         return self
 
@@ -194,8 +205,15 @@ class ShallowWaterEnsemble:
 
     @property
     def solution(self):
+        """The prognostic tensors by name (u|uh, v|vh, h, A, then the tracers), halos current."""
         self._ensure_halos()
-        return dict(zip(self.names, self._state))
+        return {**dict(zip(self.names, self._state)), **self._tr}
+
+    @property
+    def tracers(self):
+        """The passive tracers by name, (members, Ny+2Hy, Nx+2Hx) each, halos current."""
+        self._ensure_halos()
+        return dict(self._tr)
 
     def _ptrs(self, ts):
         return _lib.ptr_array([t.data_ptr() for t in ts])
@@ -205,12 +223,53 @@ class ShallowWaterEnsemble:
             self.update_state()
 
     def update_state(self):
-        """fill_halo_regions! of every member (one launch for all four fields of all members)."""
+        """fill_halo_regions! of every member: one launch for all four fields of all members, and one for every four tracers."""
         g = self.grid
         self._halo_stale = False
         f = getattr(self._L, f"swmhd_ensemble_fill_halo_periodic_{self.sfx}")
-        _lib.check(f(self._ptrs(self._state), 4, self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1),
-                     _lib.HALO_X | _lib.HALO_Y, _stream_ptr()), "swmhd_ensemble_fill_halo_periodic")
+        for ts in [self._state] + [[self._tr[n] for n in grp] for grp in fill_groups(self.tracer_names)]:
+            _lib.check(f(self._ptrs(ts), len(ts), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1),
+                         _lib.HALO_X | _lib.HALO_Y, _stream_ptr()), "swmhd_ensemble_fill_halo_periodic")
+
+    # --- time stepping with tracers: stage by stage, as ShallowWaterModel.time_step (two launches per stage for all members) ----
+    def _stage_fused(self, dt, stage):
+        """RK3 stage `stage` of the state of every member in one launch (swmhd_ensemble_tendencies_rk3, or _params with dt None): reads
+        the current state, writes the alternate set, with the operands the native driver picks (rk3_operands)."""
+        g = self.grid
+        gamma, zeta, store, anchor_flag, third = rk3_operands(stage, self._anchor, self.Gn, self.Gm)
+        head = (self._ptrs(self._state), self._ptrs(self._alt), self._ptrs(self.Gn), self._ptrs(third) if third is not None else None,
+                self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy)
+        tail = (gamma, zeta, store, self._flags | self._rwrap | anchor_flag, _stream_ptr())
+        if dt is not None:
+            f = getattr(self._L, f"swmhd_ensemble_tendencies_rk3_{self.sfx}")
+            _lib.check(f(*head, self.g, self.f, self.form_code, self.lorentz_code, dt, *tail), "swmhd_ensemble_tendencies_rk3")
+        else:
+            f = getattr(self._L, f"swmhd_ensemble_tendencies_rk3_params_{self.sfx}")
+            _lib.check(f(*head, self.parameters.data_ptr(), self.form_code, self.lorentz_code, *tail), "swmhd_ensemble_tendencies_rk3_params")
+
+    def _tracer_stage(self, dt, stage):
+        """All tracers of all members through RK3 stage `stage` in one launch (swmhd_ensemble_tracers_rk3, or _params with dt None),
+        advected by the state the stage started from: after _stage_fused and BEFORE the state sets are swapped (finish_stage)."""
+        g = self.grid
+        q, names = self._state, self.tracer_names
+        gamma, zeta, store, anchor_flag, third = rk3_operands(stage, self._anchor, self._tGn, self._tGm)
+        head = (q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), self._ptrs([self._tr[n] for n in names]),
+                self._ptrs([self._tr_alt[n] for n in names]), self._ptrs(self._tGn), self._ptrs(third) if third is not None else None,
+                len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride(1), g.dx, g.dy, self.form_code)
+        tail = (gamma, zeta, store, self._flags | self._rwrap | anchor_flag, _stream_ptr())
+        par = dt is None
+        f = getattr(self._L, f"swmhd_ensemble_tracers_rk3_{'params_' if par else ''}{self.sfx}")
+        _lib.check(f(*head, self.parameters.data_ptr() if par else dt, *tail), "swmhd_ensemble_tracers_rk3" + ("_params" if par else ""))
+
+    def _stage_steps(self, dt, n):
+        """n steps stage by stage (dt: the scalar, or None for the table).  Without fused halos every stage ends with the periodic fill
+        of the state and of the tracers, as the native driver fills the state."""
+        for _ in range(n):
+            for stage in range(3):
+                self._stage_fused(dt, stage)
+                finish_stage(self, dt, stage)
+                if not self._rwrap:
+                    self.update_state()
 
     # --- time stepping (the native ensemble step driver: 3 launches per RK3 step for all members) ---------------------
     def _enqueue_steps(self, dt, n, swapped):
@@ -231,7 +290,10 @@ class ShallowWaterEnsemble:
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        self._enqueue_steps(dt if dts is None else None, n, swapped)
+        if self._tr:        # (the native step driver steps the four fields only)
+            self._stage_steps(dt if dts is None else None, n)
+        else:
+            self._enqueue_steps(dt if dts is None else None, n, swapped)
         if swapped.value:
             self._state, self._alt = self._alt, self._state
             self.Gn, self.Gm = self.Gm, self.Gn
@@ -248,7 +310,8 @@ class ShallowWaterEnsemble:
         or one value per member; with per-member parameters the graph reads the table at replay, and time_steps keeps its dt column
         at the captured values."""
         self._ensure_halos()
-        keep = [t.clone() for t in self._state] + [t.clone() for t in self.Gm]
+        saved = self._state + self.Gm + [self._tr[n] for n in self.tracer_names] + self._tGm
+        keep = [t.clone() for t in saved]
         t0, i0 = self._clock_state(), self.iteration
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -260,7 +323,7 @@ class ShallowWaterEnsemble:
             self.time_step(dt); self.time_step(dt)
         self._graph_dt = self._dt_key(dt)
         self._graph_roles = self._roles()
-        for t, k in zip(self._state + self.Gm, keep):
+        for t, k in zip(saved, keep):   # (the two warm-up steps left every role where it was)
             t.copy_(k)
         self._halo_stale = False
         self._restore_clock(t0)
@@ -323,7 +386,8 @@ class ShallowWaterEnsemble:
 
     # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
     def member(self, m):
-        """A ShallowWaterModel holding a copy of member m (state with halos, G-, the member's g, f, clock and iteration)."""
+        """A ShallowWaterModel holding a copy of member m (state and tracers with halos, their G-, the member's g, f, clock and
+        iteration)."""
         if not 0 <= m < self.members:
             raise IndexError(f"member {m} of {self.members}")
         self._ensure_halos()
@@ -332,12 +396,16 @@ class ShallowWaterEnsemble:
             fld.data.copy_(t[m])
         for fld, t in zip(model.Gm, self.Gm):
             fld.data.copy_(t[m])
+        for k, n in enumerate(self.tracer_names):
+            model._tr[n].data.copy_(self._tr[n][m])
+            model._tGm[k].data.copy_(self._tGm[k][m])
         model.clock_time, model.iteration = float(self.clock_times[m]), self.iteration
         return model
 
     def _member_model(self, m):
         return ShallowWaterModel(self.grid, float(self.g_values[m]), float(self.f_values[m]), formulation=self.formulation,
-                                 lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict)
+                                 lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
+                                 tracers=self.tracer_names)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
@@ -356,7 +424,10 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, boundary_conditions=None):
+                 fuse_halo=True, boundary_conditions=None, tracers=()):
+        if tracer_names(tracers):     # before anything is allocated
+            raise _lib.SwmhdError("tracers on a Bounded ensemble are not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc steps the "
+                                  "four fields only and that schedule has no per-stage entry point")
         tx, ty = grid.topo_codes()
         self._bounded = (tx == _lib.BOUNDED, ty == _lib.BOUNDED)
         if not any(self._bounded):

@@ -14,8 +14,8 @@ from . import _lib
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
 from .grid import Center, Face
-from .shared import (ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict,
-                     formulation_codes, gradient_values)
+from .shared import (ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups,
+                     finish_stage, formulation_codes, gradient_values)
 
 RK3_GAMMA = (8.0 / 15.0, 5.0 / 12.0, 3.0 / 4.0)
 RK3_ZETA = (0.0, -17.0 / 60.0, -5.0 / 12.0)
@@ -291,8 +291,7 @@ class ShallowWaterModel:
 
     def _fill_x(self, stream=None):
         """The halo fill after a stage: the tracers first, in groups of four centre fields, then the state."""
-        for k in range(0, len(self.tracer_names), 4):
-            grp = self.tracer_names[k:k + 4]
+        for grp in fill_groups(self.tracer_names):
             self._fill([self._tr[n] for n in grp], grp, 0, 0, _lib.HALO_X | _lib.HALO_Y, stream, " (tracers)")
         self._fill(self._raw_fields, self.names, 0b0001, 0b0010, _lib.HALO_X | (0 if self.decomp.ring else _lib.HALO_Y), stream)
 
@@ -444,15 +443,9 @@ class ShallowWaterModel:
                 torch.cuda.current_stream().wait_stream(self._comm_stream)
             else:
                 run()
-            if self._tr:       # the tracers follow the state this stage started from: still self._state here
-                self._tracer_stage(dt, stage)
-                self._tr, self._tr_alt = self._tr_alt, self._tr
-                self._tGn, self._tGm = self._tGm, self._tGn
-            if self.fused:
-                self._state, self._alt = self._alt, self._state      # the new state becomes current
-            else:
+            if not self.fused:
                 self._substep(dt, stage)
-            self.Gn, self.Gm = self.Gm, self.Gn          # store_tendencies!: G⁻ <- Gⁿ (pointer swap, 0 bytes)
+            finish_stage(self, dt, stage, self.fused)    # the tracers' launch, then the swaps of state, tracers and G sets
             if any(self._bounded) or not (self._rwrap & _lib.WRAP_X):
                 self._fill_x()                           # (otherwise the next stage reads the periodic images itself)
             else:

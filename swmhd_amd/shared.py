@@ -1,5 +1,5 @@
-"""Set-up helpers ShallowWaterModel and the ensembles share on the host: formulation codes, boundary-condition checks, gradient rows
-and the diagnostics dict.  Nothing here touches a device."""
+"""Helpers ShallowWaterModel and the ensembles share on the host: formulation codes, boundary-condition checks, gradient rows, the
+diagnostics dict, and the tail of a fused RK3 stage (tracers and buffer swaps).  Nothing here touches a device itself."""
 from . import _lib
 from .grid import FieldBoundaryConditions
 
@@ -37,3 +37,22 @@ def diagnostics_dict(v):
     """The 7 values of swmhd_diagnostics_* (KE, ME, PE, max|u|, max|v|, max|A|, min h) by name, with their total energy."""
     return dict(kinetic_energy=v[0], magnetic_energy=v[1], potential_energy=v[2], total_energy=v[0] + v[1] + v[2],
                 max_abs_u=v[3], max_abs_v=v[4], max_abs_A=v[5], min_h=v[6])
+
+
+def finish_stage(o, dt, stage, fused=True):
+    """What follows the state's launch of RK3 stage `stage` of `o` (a ShallowWaterModel or a ShallowWaterEnsemble), before its halo
+    fill: the tracers through the same stage in one launch (o._tracer_stage), advected by the state the stage STARTED from -- still
+    o._state here -- then the pointer swaps: the new tracers and the new state become current, and G- <- Gn for both
+    (store_tendencies!, 0 bytes).  fused=False: the state was advanced in place by a substep, only its G sets swap."""
+    if o._tr:
+        o._tracer_stage(dt, stage)
+        o._tr, o._tr_alt = o._tr_alt, o._tr
+        o._tGn, o._tGm = o._tGm, o._tGn
+    if fused:
+        o._state, o._alt = o._alt, o._state
+    o.Gn, o.Gm = o.Gm, o.Gn
+
+
+def fill_groups(names):
+    """The tracer names in groups of at most four: the limit of one halo-fill call."""
+    return [names[k:k + 4] for k in range(0, len(names), 4)]
