@@ -1,9 +1,19 @@
 """Reference of ONE call of the fused tendency entry points (swmhd_tendencies_*, swmhd_tendencies_rk3_* in include/swmhd.h) and the
-matrix of calls that tests/test_stage_matrix_gpu.py, its forced-layout child processes and tools/stage_matrix_report.py run through the
-row-marching kernels (k_tendency_vi_march, k_tendency_cons_march, k_tendency_vi_march_pk).
+matrices of calls made through every kernel path of those entry points (PATHS):
+    march        the row-marching kernels (k_tendency_vi_march, k_tendency_cons_march, k_tendency_vi_march_pk): matrix(), run by
+                 tests/test_stage_matrix_gpu.py, its forced-layout child processes and tools/stage_matrix_report.py
+    tile4, tile8, strict, wall, wall-strict
+                 the LDS-tiled kernel k_tendency_tile in its fast 64 x 4 and 64 x 8 bodies, the strict 64 x 8 body and the fast and
+                 strict wall bodies (Bounded directions): tile_matrix(), run by tests/test_tile_stage_matrix_gpu.py and
+                 tools/stage_matrix_report.py --tile
 
-The tendencies G come from the CPU oracle in float64 (fp32 inputs widened exactly); the substep is evaluated in np.longdouble from the
-formulas of the header.  The reference part (reference_stage, stage_bounds, StageData) is numpy only; run_stage / check_case need a GPU.
+Fast paths: the tendencies G come from the CPU oracle in float64 (fp32 inputs widened exactly); the substep is evaluated in
+np.longdouble from the formulas of the header.  Strict paths: G is the oracle's in the precision of the call and the substep is
+tracer_cases.substep (the oracle's expression order in that precision); both are compared bitwise.  Bounded paths: the oracle with
+topo=..., on inputs whose halos hold the boundary conditions (tracer_cases.fill_state, a gradient condition on A where y is Bounded).
+The strict and wall paths implement T, S1g, S1n, S2g, S3n only; for the other forms the header promises SWMHD_ENOTSUP, which is
+asserted together with "nothing was written".  The reference part (reference_stage, reference_stage_strict, stage_bounds, StageData)
+is numpy only; run_stage / check_case need a GPU.
 
 Variants, at the level of the call (which compiled stage MODE a call lands on is launch_plan.hpp's business, pinned by
 tests/launch_plan_check.cpp):
@@ -31,6 +41,7 @@ import sys
 import numpy as np
 
 import helpers as Hh
+import tracer_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = 3                               # halo width in x and y
@@ -43,6 +54,8 @@ FORMS = [(1, 1), (1, 0), (0, 2), (0, 0)]      # (formulation, lorentz)
 DTYPES = [np.float64, np.float32]
 TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.float32): 1e-4}
 MARCH_KERNEL, WRAP_X, WRAP_Y, GM_IS_PREV_STATE, RK3_ANCHOR = 4, 16, 32, 1024, 2048      # include/swmhd.h
+STRICT, TILE_KERNEL, BOUNDED_X, BOUNDED_Y, ENOTSUP = 1, 2, 256, 512, 3                  # include/swmhd.h
+P, B = TC.P, TC.B                   # topology codes
 NTHREADS = max(1, min(len(os.sched_getaffinity(0)), 8))
 
 # variant: fused substep, operand (None | "Gm" | "Uprev" | "W"), store_G, anchor form, Gn aliases the operand
@@ -74,6 +87,24 @@ def calls():
     return [(v, c) for v in VARIANTS for c in COEFFS if v in COEFFS[c]]
 
 
+# Kernel paths.  flags: what selects the path (a wall path adds SWMHD_BOUNDED_* from the topology of its StageData); strict: compared
+# bitwise; wall: a Bounded direction; ty: rows of a tile (None: not a tile kernel); refused: the call forms the path answers with
+# SWMHD_ENOTSUP (SWMHD_GM_IS_PREV_STATE and SWMHD_RK3_ANCHOR are fast and periodic only).
+FAST_ONLY = ("P2g", "P3n", "A1", "A2", "A2a")
+PATHS = {
+    "march": dict(flags=MARCH_KERNEL, strict=False, wall=False, ty=None, refused=()),
+    "tile4": dict(flags=TILE_KERNEL, strict=False, wall=False, ty=4, refused=()),
+    "tile8": dict(flags=TILE_KERNEL, strict=False, wall=False, ty=8, refused=()),
+    "strict": dict(flags=STRICT, strict=True, wall=False, ty=8, refused=FAST_ONLY),
+    "wall": dict(flags=TILE_KERNEL, strict=False, wall=True, ty=8, refused=FAST_ONLY),
+    "wall-strict": dict(flags=STRICT, strict=True, wall=True, ty=8, refused=FAST_ONLY),
+}
+
+
+def topo_flags(topo):
+    return (BOUNDED_X if topo[0] == B else 0) | (BOUNDED_Y if topo[1] == B else 0)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # inputs and the oracle's tendencies, once per (shape, formulation, forcing, precision)
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -98,24 +129,45 @@ def random_fields(Nx, Ny, form, dtype, seed):
 
 
 class StageData:
-    """Inputs of one (shape, formulation, forcing, precision) and the oracle's float64 tendencies of them."""
+    """Inputs of one (shape, formulation, forcing, precision, topology) and the oracle's float64 tendencies of them.  With a Bounded
+    direction the halos of q hold the boundary conditions (tracer_cases.fill_state in the precision of the call: impenetrable walls,
+    no-flux mirrors, the gradient condition tracer_cases.grad_A on A where y is Bounded) and the oracle runs with that topology;
+    wall_failures then says whether its result differs from the periodic one inside the wall buffers and nowhere else."""
 
-    def __init__(self, oracle, Nx, Ny, form, lor, dtype, seed=None):
-        self.Nx, self.Ny, self.form, self.lor, self.dtype = Nx, Ny, form, lor, np.dtype(dtype)
+    # defaults of a subclass that builds its own (periodic) inputs without this constructor (tests/test_weno_arith_gpu.py)
+    topo, wall_failures, _G_strict = (P, P), (), None
+
+    def __init__(self, oracle, Nx, Ny, form, lor, dtype, seed=None, topo=(P, P)):
+        self.Nx, self.Ny, self.form, self.lor, self.dtype, self.topo = Nx, Ny, form, lor, np.dtype(dtype), tuple(topo)
         seed = 1000 * Nx + Ny if seed is None else seed
         self.q, self.aux = random_fields(Nx, Ny, form, dtype, seed)
-        q64 = [a.astype(np.float64) for a in self.q]                      # exact widening
         # spacings and constants as the call receives them (c_float rounds 0.11, 0.13 and 9.81)
         self.dx, self.dy, self.grav, self.fcor = (float(self.dtype.type(x)) for x in (DX, DY, GRAV, FCOR))
-        G = oracle.tendencies(*q64, Nx, Ny, H, H, self.dx, self.dy, form, lor, self.grav, self.fcor, nthreads=NTHREADS)
+        kw = {}
+        if self.topo != (P, P):
+            TC.fill_state(oracle, self.q, Nx, Ny, self.topo, TC.grad_A(self.topo), self.dx, self.dy)
+            kw = dict(topo=self.topo)
+        q64 = [a.astype(np.float64) for a in self.q]                      # exact widening
+        G = oracle.tendencies(*q64, Nx, Ny, H, H, self.dx, self.dy, form, lor, self.grav, self.fcor, nthreads=NTHREADS, **kw)
         self.G = [Hh.interior(g, Nx, Ny, H, H).copy() for g in G]
         force = 0.0
         if lor:
-            op = oracle.lorentz_jacobian if lor == 1 else oracle.lorentz_divergence
-            force = max(float(np.abs(Hh.interior(w, Nx, Ny, H, H)).max()) for w in op(q64[3], q64[2], Nx, Ny, H, H, self.dx, self.dy, nthreads=NTHREADS))
+            w = (oracle.lorentz_jacobian(q64[3], q64[2], Nx, Ny, H, H, self.dx, self.dy, nthreads=NTHREADS) if lor == 1 else
+                 oracle.lorentz_divergence(q64[3], q64[2], Nx, Ny, H, H, self.dx, self.dy, nthreads=NTHREADS, **kw))
+            force = max(float(np.abs(Hh.interior(x, Nx, Ny, H, H)).max()) for x in w)
         self.scales = [float(s) for s in Hh.term_scales(FORM[form], q64, self.dx, self.dy, force)]
         self.Gmax = [float(np.abs(g).max()) for g in self.G]
         self.Umax = [float(np.abs(Hh.interior(a, Nx, Ny, H, H)).max()) for a in q64]
+        self._oracle, self._G_strict = oracle, None
+        self.wall_failures = wall_buffer_failures(oracle, self, q64) if self.topo != (P, P) else []
+
+    def G_strict(self):
+        """The oracle's tendencies in the precision of the call (parents): what a strict call must give bit for bit."""
+        if self._G_strict is None:
+            kw = dict(topo=self.topo) if self.topo != (P, P) else {}
+            self._G_strict = self._oracle.tendencies(*self.q, self.Nx, self.Ny, H, H, self.dx, self.dy, self.form, self.lor, self.grav,
+                                                     self.fcor, nthreads=NTHREADS, **kw)
+        return self._G_strict
 
     def dt(self, gamma):
         """dt with dt |gamma| max|G| = max|U| (maxima over the four fields): one stage has no stability limit, and an increment of the
@@ -155,6 +207,62 @@ def reference_stage(oracle, q, operand, variant, coeffs, Nx, Ny, dx, dy, form, l
     else:
         qnew = [u + dtl * (gam * g + zet * m) for u, g, m in zip(U, Gl, Op)]
     return {"qnew": qnew, "Gn": G if v["store_G"] else KEEP}
+
+
+def reference_stage_strict(data, variant, coeffs, dt, rows=None):
+    """reference_stage for a strict call, to be compared bitwise: Gn is the oracle's tendency in the precision of the call, qnew is
+    tracer_cases.substep (U + dt gamma G | U + dt (gamma G + zeta Gm), each operation rounded to that precision in the oracle's
+    order) of the parents.  The call forms of the strict paths only (no previous-state operand, no anchor)."""
+    v = VARIANTS[variant]
+    assert not v["anchor"] and v["operand"] in (None, "Gm"), variant
+    Nx, Ny = data.Nx, data.Ny
+    j0, j1 = (0, Ny) if rows is None else rows
+    cut = lambda a: Hh.interior(a, Nx, Ny, H, H)[j0:j1]
+    G = data.G_strict()
+    if not v["fused"]:
+        return {"qnew": None, "Gn": [cut(g) for g in G]}
+    Gm = data.aux if v["operand"] else [None] * 4
+    qnew = [cut(TC.substep(U, g, m, Nx, Ny, dt, coeffs[0], coeffs[1], m is None)) for U, g, m in zip(data.q, G, Gm)]
+    return {"qnew": qnew, "Gn": [cut(g) for g in G] if v["store_G"] else KEEP}
+
+
+WALL_DEPTH = 7      # cells from a wall beyond which the Bounded tendencies are the periodic ones (test_bounded_oracle: the boundary
+                    # buffers are 2 interpolation points deep, the widest stencil reaches 3 cells, +1 for the flux differences, +3
+                    # for the divergence forcing's face quantities)
+
+
+def wall_buffers(Nx, Ny, topo):
+    """{"west" | "east" | "south" | "north": boolean mask of the interior cells within WALL_DEPTH of that wall}, Bounded sides only."""
+    y, x = np.meshgrid(np.arange(Ny), np.arange(Nx), indexing="ij")
+    out = {}
+    if topo[0] == B:
+        out["west"], out["east"] = x < WALL_DEPTH, x >= Nx - WALL_DEPTH
+    if topo[1] == B:
+        out["south"], out["north"] = y < WALL_DEPTH, y >= Ny - WALL_DEPTH
+    return out
+
+
+def wall_buffer_failures(oracle, data, q64):
+    """The Bounded reference of `data` against the periodic one of the same interior (halos periodic-filled instead): it must differ
+    inside the buffer of every wall and equal it bit for bit outside all of them.  A matrix whose reference never took a wall branch
+    fails here.  Returns one line per violation."""
+    Nx, Ny = data.Nx, data.Ny
+    qp = [oracle.fill_halo_periodic(a.copy(), Nx, Ny, H, H) for a in q64]
+    Gp = [Hh.interior(g, Nx, Ny, H, H) for g in oracle.tendencies(*qp, Nx, Ny, H, H, data.dx, data.dy, data.form, data.lor, data.grav,
+                                                                    data.fcor, nthreads=NTHREADS)]
+    differs = np.zeros((Ny, Nx), dtype=bool)
+    for gb, gp in zip(data.G, Gp):
+        differs |= gb != gp
+    buffers = wall_buffers(Nx, Ny, data.topo)
+    near = np.zeros((Ny, Nx), dtype=bool)
+    fails = []
+    for side, mask in buffers.items():
+        near |= mask
+        if not (differs & mask).any():
+            fails.append(f"the Bounded reference equals the periodic one in the whole {side} wall buffer")
+    if (differs & ~near).any():
+        fails.append(f"the Bounded reference differs from the periodic one in {int((differs & ~near).sum())} cells outside the wall buffers")
+    return fails
 
 
 def stage_bounds(data, q, operand, variant, coeffs, dt, ref, rows=None):
@@ -219,7 +327,10 @@ def is_packed(Nx, form, dtype, flags):
     return np.dtype(dtype) == np.float32 and form == 1 and bool(flags & WRAP_X) and Nx % 2 == 0 and Nx >= 8
 
 
-def family(Nx, form, dtype, flags):
+def family(Nx, form, dtype, flags, path="march"):
+    """Key of the achieved-ratio tables: the marching kernel family, or the tile path."""
+    if path != "march":
+        return path
     return "packed" if is_packed(Nx, form, dtype, flags) else ("vi" if form == 1 else "cons")
 
 
@@ -242,8 +353,51 @@ def folds(Nx, form, dtype, geo):
             and Nx - (geo["nstrips"] - 1) * TXO[256] <= 122)
 
 
-def check_layout(L, Nx, nrows, form, dtype, flags, lanes=None, LY=6, layouts=LAYOUTS):
+TILE_X = 64                         # columns of a tile (common.hpp TILE_X)
+TILE_MIN_CELLS_RY2 = 330000         # launch_plan.hpp SW_MARCH_MIN_CELLS: forced onto the tile kernel, launches of that many cells keep 64 x 8 tiles
+
+
+def tiles(n, t):
+    """(tiles, cells of the last one) of n cells cut into tiles of t."""
+    nt = -(-n // t)
+    return nt, n - (nt - 1) * t
+
+
+def wall_tiles(Nx, nrows):
+    """(tile columns, tile rows, rows of a tile) of a Bounded launch.  INFERRED, not queried: swmhd_tendency_launch_geometry does not
+    model the topology, so this restates launch_plan.hpp plan_tendency (pinned by tests/launch_plan_check.cpp): a Bounded grid runs on
+    the wall kernel, 64 x 8 tiles over every row of the range, unless it is a fast launch of SW_MARCH_MIN_CELLS cells or more, at least
+    256 columns and 48 rows that does NOT force the tile kernel -- then the marching kernel runs first and the wall kernel only
+    overwrites a frame.  The wall paths force the tile kernel (SWMHD_TILE_KERNEL, or SWMHD_STRICT, which has no other), and their shapes
+    also lie below every one of those thresholds, which is what this asserts."""
+    assert Nx * nrows < TILE_MIN_CELLS_RY2 and (Nx < 4 * TILE_X or nrows < 48), (Nx, nrows)
+    return tiles(Nx, TILE_X)[0], tiles(nrows, 8)[0], 8
+
+
+def check_tile_layout(L, path, Nx, nrows, form, dtype, flags):
+    """check_layout of the tile paths: kind 1, ceil(Nx / 64) tile columns, and the tile height the path is there for (4 rows for
+    tile4, 8 for tile8 and strict) from the planner's own answer for SWMHD_TILE_KERNEL (| SWMHD_STRICT) and the rows of the launch;
+    the wall paths take the height from wall_tiles."""
+    p = PATHS[path]
+    q = TILE_KERNEL | (STRICT if p["strict"] else 0) | (flags & (WRAP_X | WRAP_Y))
+    geo = L.tendency_launch_geometry(Nx, nrows, form, np.dtype(dtype).itemsize, q)
+    ntx, lastx = tiles(Nx, TILE_X)
+    assert (geo["kind"], geo["nstrips"]) == (1, ntx), (path, Nx, nrows, geo)
+    if p["wall"]:
+        wx, nty, ty = wall_tiles(Nx, nrows)
+        assert wx == ntx
+        note = " (wall kernel: inferred)"
+    else:
+        ty, nty, note = p["ty"], tiles(nrows, p["ty"])[0], ""
+        assert (geo["rows_per_segment"], geo["nseg"]) == (ty, nty), (path, Nx, nrows, geo)
+    lasty = tiles(nrows, ty)[1]
+    return f"kind 1, {ntx} tile columns, last {lastx} wide, {nty} tile rows of {ty}, last {lasty}{note}"
+
+
+def check_layout(L, Nx, nrows, form, dtype, flags, lanes=None, LY=6, layouts=LAYOUTS, path="march"):
     """Assert that the launch of Nx x nrows has the layout the matrix wants from this shape; returns a one-line description."""
+    if path != "march":
+        return check_tile_layout(L, path, Nx, nrows, form, dtype, flags)
     elem = np.dtype(dtype).itemsize
     geo = L.tendency_launch_geometry(Nx, nrows, form, elem, MARCH_KERNEL | (flags & (WRAP_X | WRAP_Y)))
     if is_packed(Nx, form, dtype, flags):
@@ -297,16 +451,76 @@ def case_id(Nx, Ny, rows, form, lor, dtype, flags):
             f"{'f64' if dtype == np.float64 else 'f32'}-{wrap}")
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the tile matrix: the smallest shapes at which a 64-wide tile of 4 or 8 rows can go wrong
+# ---------------------------------------------------------------------------------------------------------------------------------
+TILE_WIDTHS = (3, 7, 63, 64, 65, 129)     # Nx = Hx (every tile cell beyond x = 2 is a wrapped or clamped load); 7; below, at and above
+                                          # one tile; three tile columns, the last of one column
+TILE_ROWS = (3, 4, 5, 8, 9, 31)           # below, at and above one 4-row tile; at and above one 8-row tile; 8 | 4 tile rows, last of 3 | 7
+TILE8_SHAPE = (2579, 129)                 # 332 691 cells: 41 tile columns, the last 19 wide; 17 tile rows of 8, the last of one row
+WALL_SHAPES = [(65, 9), (67, 11), (64, 8), (7, 8), (129, 31)]     # a tile edge 1 and 3 cells from the east / north wall (inside its
+                                          # boundary buffer, at its start), on the wall, the buffers of opposite walls meet, several tiles a side
+WALL_TOPOS = [(P, B), (B, P), (B, B)]
+WALL_FORMS = [(1, 1), (0, 2), (0, 0)]     # the divergence forcing has wall branches of its own
+
+
+def tile_shape_groups():
+    """(Nx, Ny, rows | None, [flags]) of the periodic tile paths tile4 and strict: every width at Ny = 9 (65 also with WRAP_X alone and
+    WRAP_Y alone); every row count at the widths 65 and 129; the partial row range at 129 x 33."""
+    XY = WRAP_X | WRAP_Y
+    out = [(Nx, 9, None, [0, XY, WRAP_X, WRAP_Y] if Nx == 65 else [0, XY]) for Nx in TILE_WIDTHS]
+    out += [(Nx, Ny, None, [0, XY]) for Nx in (65, 129) for Ny in TILE_ROWS if Ny != 9]
+    out += [(129, 33, PARTIAL, [0, XY])]
+    return out
+
+
+def wall_shape_groups():
+    """(Nx, Ny, rows | None, topology, [flags]) of the wall paths: WRAP in the periodic direction of (P, B) and of (B, P) once, at 65 x 9."""
+    out = []
+    for Nx, Ny, rows in [(Nx, Ny, None) for Nx, Ny in WALL_SHAPES] + [(129, 33, PARTIAL)]:
+        for topo in WALL_TOPOS:
+            wrap = {(P, B): [WRAP_X], (B, P): [WRAP_Y]}.get(topo, []) if (Nx, Ny) == (65, 9) else []
+            out.append((Nx, Ny, rows, topo, [0] + wrap))
+    return out
+
+
+def tile_matrix():
+    """Every (path, Nx, Ny, rows, form, lor, dtype, flags, topology) of the tile matrix, grouped so that consecutive entries share
+    their StageData.  tile8 runs whole row ranges only: the planner counts the rows of the launch, a partial range of TILE8_SHAPE
+    would fall back to 64 x 4 tiles."""
+    for Nx, Ny, rows, flagsets in tile_shape_groups():
+        for form, lor in FORMS:
+            for dtype in DTYPES:
+                for path in ("tile4", "strict"):
+                    for flags in flagsets:
+                        yield path, Nx, Ny, rows, form, lor, dtype, flags, (P, P)
+    for form, lor in FORMS:
+        for dtype in DTYPES:
+            for flags in (0, WRAP_X | WRAP_Y):
+                yield ("tile8",) + TILE8_SHAPE + (None, form, lor, dtype, flags, (P, P))
+    for Nx, Ny, rows, topo, flagsets in wall_shape_groups():
+        for form, lor in WALL_FORMS:
+            for dtype in DTYPES:
+                for path in ("wall", "wall-strict"):
+                    for flags in flagsets:
+                        yield path, Nx, Ny, rows, form, lor, dtype, flags, topo
+
+
+def tile_case_id(path, Nx, Ny, rows, form, lor, dtype, flags, topo=(P, P)):
+    t = "" if tuple(topo) == (P, P) else "-" + "".join("PB"[d] for d in topo)
+    return f"{path}{t}-{case_id(Nx, Ny, rows, form, lor, dtype, flags)}"
+
+
 _DATA = {}
 
 
-def stage_data(oracle, Nx, Ny, form, lor, dtype):
+def stage_data(oracle, Nx, Ny, form, lor, dtype, topo=(P, P)):
     """StageData of a shape, computed once (the oracle is not called per case); only the latest width is kept."""
-    key = (Nx, Ny, form, lor, np.dtype(dtype).name)
+    key = (Nx, Ny, form, lor, np.dtype(dtype).name, tuple(topo))
     if key not in _DATA:
         for k in [k for k in _DATA if k[:2] != (Nx, Ny)]:
             del _DATA[k]
-        _DATA[key] = StageData(oracle, Nx, Ny, form, lor, dtype)
+        _DATA[key] = StageData(oracle, Nx, Ny, form, lor, dtype, topo=topo)
     return _DATA[key]
 
 
@@ -318,10 +532,11 @@ def _same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(u), np.ascontiguousarray(b).view(u))
 
 
-def run_stage(S, data, variant, cset, flags=0, rows=None):
-    """One call through the C-ABI with SWMHD_MARCH_KERNEL | flags.  Inputs: data.q with NaN in the halos of every wrapped direction;
-    the operand data.aux (sentinel halos).  Every output buffer starts as the sentinel (qnew of P*: as Uprev).  Returns the parents
-    before and after: {"q": (before, after), "operand": ..., "qnew": ..., "Gn": ...} (None where the call has no such buffer)."""
+def run_stage(S, data, variant, cset, flags=0, rows=None, path="march", expect_rc=0):
+    """One call through the C-ABI with the flags of `path` (SWMHD_MARCH_KERNEL by default; the Bounded flags of data.topo) | flags.
+    Inputs: data.q with NaN in the halos of every wrapped direction; the operand data.aux (sentinel halos).  Every output buffer starts
+    as the sentinel (qnew of P*: as Uprev).  The return code must be expect_rc.  Returns the parents before and after:
+    {"q": (before, after), "operand": ..., "qnew": ..., "Gn": ...} (None where the call has no such buffer)."""
     import torch
     L = S._lib
     v = VARIANTS[variant]
@@ -335,7 +550,7 @@ def run_stage(S, data, variant, cset, flags=0, rows=None):
         Hh.poison_halo(a, Nx, Ny, H, H, x=bool(flags & WRAP_X), y=bool(flags & WRAP_Y))
     sent = np.full_like(data.q[0], SENTINEL)
     dev = lambda arrs: [torch.from_numpy(a).cuda() for a in arrs]
-    P = lambda ts: L.ptr_array([t.data_ptr() for t in ts])
+    PA = lambda ts: L.ptr_array([t.data_ptr() for t in ts])
     tq = dev(q_in)
     before = {"q": q_in, "operand": None, "qnew": None, "Gn": [sent] * 4}
     top = tnew = None
@@ -350,34 +565,58 @@ def run_stage(S, data, variant, cset, flags=0, rows=None):
         tGn, before["Gn"] = top, data.aux
     else:
         tGn = dev([sent] * 4)
-    fl = MARCH_KERNEL | flags | (GM_IS_PREV_STATE if v["operand"] == "Uprev" else 0) | (RK3_ANCHOR if v["anchor"] else 0)
+    assert PATHS[path]["wall"] == (data.topo != (P, P)), (path, data.topo)
+    fl = PATHS[path]["flags"] | topo_flags(data.topo) | flags | (GM_IS_PREV_STATE if v["operand"] == "Uprev" else 0) | (RK3_ANCHOR if v["anchor"] else 0)
     sy = Nx + 2 * H
     if not v["fused"]:
         rc = getattr(L.lib(), f"swmhd_tendencies_{sfx}")(*[t.data_ptr() for t in tq], *[t.data_ptr() for t in tGn], Nx, Ny, H, H, sy,
                                                            data.dx, data.dy, data.grav, data.fcor, data.form, data.lor, j0, j1, fl, None)
     else:
-        rc = getattr(L.lib(), f"swmhd_tendencies_rk3_{sfx}")(P(tq), P(tnew), P(tGn), P(top) if top is not None else None, Nx, Ny, H, H, sy,
+        rc = getattr(L.lib(), f"swmhd_tendencies_rk3_{sfx}")(PA(tq), PA(tnew), PA(tGn), PA(top) if top is not None else None, Nx, Ny, H, H, sy,
                                                                data.dx, data.dy, data.grav, data.fcor, data.form, data.lor, dt, gam, zet, v["store_G"], j0, j1,
                                                                fl, None)
-    L.check(rc, f"{variant}/{cset}")
+    if expect_rc == 0:
+        L.check(rc, f"{variant}/{cset}")
+    assert rc == expect_rc, f"{variant}/{cset}: rc={rc}, expected {expect_rc}"
     torch.cuda.synchronize()
     host = lambda ts: None if ts is None else [t.cpu().numpy() for t in ts]
     after = {"q": host(tq), "operand": host(top), "qnew": host(tnew), "Gn": host(tGn)}
     return {k: (before[k], after[k]) for k in before}
 
 
-def check_case(S, oracle, data, variant, cset, flags=0, rows=None):
+def check_refusal(S, data, variant, cset, flags=0, rows=None, path="strict"):
+    """A call form the path does not implement: the call must return SWMHD_ENOTSUP and leave every buffer it was given bitwise as it
+    was (the refusal precedes the first launch).  Returns the failures."""
+    try:
+        out = run_stage(S, data, variant, cset, flags, rows, path=path, expect_rc=ENOTSUP)
+    except AssertionError as e:
+        return [str(e)]
+    fails = []
+    for name, (before, after) in out.items():
+        for f in range(4 if after is not None else 0):
+            if not _same_bits(before[f], after[f]):
+                fails.append(f"refused call changed {name}[{f}] in {int((before[f] != after[f]).sum())} cells")
+    return fails
+
+
+def check_case(S, oracle, data, variant, cset, flags=0, rows=None, path="march"):
     """run_stage against reference_stage: (failures, ratios).  failures: one line per violated assertion (empty: the case passes);
-    ratios: {"qnew" | "Gn": largest error / bound over the four fields} of the outputs the call writes."""
+    ratios: {"qnew" | "Gn": largest error / bound over the four fields} of the outputs the call writes.  Strict paths are compared
+    bitwise with reference_stage_strict (ratio 0: every written cell equal; inf otherwise); a form the path refuses: check_refusal."""
     v = VARIANTS[variant]
+    if variant in PATHS[path]["refused"]:
+        return check_refusal(S, data, variant, cset, flags, rows, path), {}
     Nx, Ny = data.Nx, data.Ny
     j0, j1 = (0, Ny) if rows is None else rows
     coeffs = COEFFS[cset][variant]
     dt = data.dt(coeffs[0])
     operand = data.aux if v["operand"] else None
-    ref = reference_stage(oracle, data.q, operand, variant, coeffs, Nx, Ny, data.dx, data.dy, data.form, data.lor, dt, rows=rows, G=data.G)
-    bounds = stage_bounds(data, data.q, operand, variant, coeffs, dt, ref, rows=rows)
-    out = run_stage(S, data, variant, cset, flags, rows)
+    if PATHS[path]["strict"]:
+        ref, bounds = reference_stage_strict(data, variant, coeffs, dt, rows=rows), None
+    else:
+        ref = reference_stage(oracle, data.q, operand, variant, coeffs, Nx, Ny, data.dx, data.dy, data.form, data.lor, dt, rows=rows, G=data.G)
+        bounds = stage_bounds(data, data.q, operand, variant, coeffs, dt, ref, rows=rows)
+    out = run_stage(S, data, variant, cset, flags, rows, path=path)
     fails, ratios = [], {}
     # 3. inputs bitwise unchanged (Uprev of P* is the qnew buffer; the aliased Gn of A2a is the operand W)
     for f in range(4):
@@ -407,6 +646,13 @@ def check_case(S, oracle, data, variant, cset, flags=0, rows=None):
                 fails.append(f"{name}[{f}]: {int((~np.isfinite(got)).sum())} non-finite cells")
                 ratios[name] = float("inf")
                 continue
+            if bounds is None:      # strict: every written cell equal to the reference in the precision of the call
+                same = a[H + j0:H + j1, H:H + Nx] == ref[name][f]
+                ratios[name] = max(ratios.get(name, 0.0), 0.0 if same.all() else float("inf"))
+                if not same.all():
+                    fails.append(f"{name}[{f}]: {int((~same).sum())} cells differ from the oracle's, max |difference| "
+                                 f"{float(np.abs(got - ref[name][f]).max()):.3e}")
+                continue
             err, bound = float(np.abs(got - ref[name][f]).max()), bounds[name][f]
             ratios[name] = max(ratios.get(name, 0.0), err / bound)
             if not err <= bound:
@@ -414,15 +660,18 @@ def check_case(S, oracle, data, variant, cset, flags=0, rows=None):
     return fails, ratios
 
 
-def run_cases(S, oracle, Nx, Ny, rows, form, lor, dtype, flags, worst=None, stop_at_first=False):
+def run_cases(S, oracle, Nx, Ny, rows, form, lor, dtype, flags, worst=None, stop_at_first=False, path="march", topo=(P, P)):
     """All variants and coefficient sets of one matrix entry.  Returns the failures, each prefixed with its call; `worst` collects
-    the largest error / bound ratio per (family, precision, variant)."""
-    data = stage_data(oracle, Nx, Ny, form, lor, dtype)
-    fam, prec = family(Nx, form, dtype, flags), ("f64" if np.dtype(dtype) == np.float64 else "f32")
-    failures = []
+    the largest error / bound ratio per (family | path, precision, variant).  A Bounded entry also fails if its reference never took
+    a wall branch (StageData.wall_failures)."""
+    data = stage_data(oracle, Nx, Ny, form, lor, dtype, topo)
+    fam, prec = family(Nx, form, dtype, flags, path), ("f64" if np.dtype(dtype) == np.float64 else "f32")
+    cid = case_id(Nx, Ny, rows, form, lor, dtype, flags) if path == "march" else tile_case_id(path, Nx, Ny, rows, form, lor, dtype, flags, topo)
+    failures = [f"reference: {m}" for m in data.wall_failures]
     for variant, cset in calls():
-        fails, ratios = check_case(S, oracle, data, variant, cset, flags, rows)
-        print(f"  {case_id(Nx, Ny, rows, form, lor, dtype, flags)} {variant}/{cset}: "
+        fails, ratios = check_case(S, oracle, data, variant, cset, flags, rows, path)
+        refused = "refused (SWMHD_ENOTSUP), nothing written" if variant in PATHS[path]["refused"] and not fails else ""
+        print(f"  {cid} {variant}/{cset}: {refused}"
               + ", ".join(f"{k} {r:.3g}" for k, r in ratios.items()) + (f"  FAILED: {fails}" if fails else ""))
         if worst is not None and ratios:
             key = f"{fam}/{prec}/{variant}"

@@ -1,14 +1,18 @@
-"""Pins of tests/stage_cases.py, the reference of the stage matrix (tests/test_stage_matrix_gpu.py), on the CPU: its substep formulas
-composed into a whole RK3 step reproduce the oracle's time_step in all three operand forms, it marks the outputs a call must not write,
-its time step keeps the new state a sharp witness of the tendencies, and every width and row count of the matrix has the layout it is
-there for (the launch planner is host code: swmhd_tendency_launch_geometry answers without a GPU, with the 256 compute units of an
-MI355X).  No test here needs a GPU; the layout test needs the BUILT libswmhd.so (the `swmhd` fixture: build() first), the others only
+"""Pins of tests/stage_cases.py, the reference of the stage matrices (tests/test_stage_matrix_gpu.py,
+tests/test_tile_stage_matrix_gpu.py), on the CPU: its substep formulas composed into a whole RK3 step reproduce the oracle's time_step
+in all three operand forms, it marks the outputs a call must not write, its time step keeps the new state a sharp witness of the
+tendencies, and every width and row count of the matrix has the layout it is there for (the launch planner is host code:
+swmhd_tendency_launch_geometry answers without a GPU, with the 256 compute units of an MI355X).  Of the tile matrix: its shapes have
+the ragged last tiles they were chosen for and the tile height of their path by the planner's answer, the strict reference composed
+into a step is the oracle's time_step bit for bit, and the Bounded reference differs from the periodic one exactly inside the wall
+buffers.  No test here needs a GPU; the layout tests need the BUILT libswmhd.so (the `swmhd` fixture: build() first), the others only
 the CPU oracle."""
 import numpy as np
 import pytest
 
 import helpers as Hh
 import stage_cases as SC
+import tracer_cases as TC
 
 Nx, Ny, H = 40, 33, SC.H
 G1, G2, G3, Z2, Z3 = SC._G1, SC._G2, SC._G3, SC._Z2, SC._Z3
@@ -132,3 +136,137 @@ def test_every_shape_of_the_matrix_has_its_layout(swmhd):
         assert (3, 256, Nx, 31) in seen
     for nrows in (3, 25, 31, 33, 24):
         assert any(s[3] == nrows for s in seen)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the tile matrix
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _last(n, t):
+    return n - (-(-n // t) - 1) * t
+
+
+def test_the_tile_matrix_has_its_ragged_classes():
+    """Last tile column and last tile row of every shape, computed here for both tile heights: one-column and one-row last tiles
+    (4- and 8-row tiles), exactly full and nearly full ones, a one-tile-wide domain of Nx = Hx, a row range that starts off a tile
+    multiple, the single-direction WRAP flags and the wall shapes whose three-cell boundary buffers straddle, end on and miss a tile
+    edge; every path, form and precision the matrix promises."""
+    cases = list(SC.tile_matrix())
+    assert len({SC.tile_case_id(*c) for c in cases}) == len(cases)
+    by_path = {p: [c for c in cases if c[0] == p] for p in SC.PATHS if p != "march"}
+    assert all(by_path.values())
+    XY = SC.WRAP_X | SC.WRAP_Y
+    for path in ("tile4", "strict"):
+        cs = by_path[path]
+        shapes = {(Nx, Ny if rows is None else rows[1] - rows[0]) for _, Nx, Ny, rows, *_ in cs}
+        assert {Nx for Nx, n in shapes if n == 9} == {3, 7, 63, 64, 65, 129}
+        for W in (65, 129):
+            assert {n for Nx, n in shapes if Nx == W} >= {3, 4, 5, 8, 9, 31}
+        assert {_last(Nx, 64) for Nx, _ in shapes} == {3, 7, 63, 64, 1}                 # last tile column
+        assert sum(1 for Nx, _ in shapes if -(-Nx // 64) == 3 and _last(Nx, 64) == 1)   # three tile columns, the last of one
+        assert {_last(n, 4) for _, n in shapes} == {1, 3, 4} and {5, 9} <= {n for _, n in shapes if _last(n, 4) == 1}
+        assert {_last(n, 8) for _, n in shapes} == {1, 3, 4, 5, 7, 8} and 9 in {n for _, n in shapes if _last(n, 8) == 1}
+        assert any(rows == SC.PARTIAL and Ny == 33 and Nx == 129 and rows[0] % 8 and rows[0] % 4 for _, Nx, Ny, rows, *_ in cs)
+        for c in cs:
+            assert c[8] == (SC.P, SC.P)
+        groups = {}
+        for _, Nx, Ny, rows, form, lor, dtype, flags, _t in cs:
+            groups.setdefault((Nx, Ny, rows), set()).add((form, lor, np.dtype(dtype).name, flags))
+        for shape, g in groups.items():
+            want = {0, XY} | ({SC.WRAP_X, SC.WRAP_Y} if shape == (65, 9, None) else set())
+            assert g == {(f, l, d, w) for f, l in SC.FORMS for d in ("float64", "float32") for w in want}, shape
+    t8 = by_path["tile8"]
+    assert {(c[1], c[2], c[3]) for c in t8} == {(2579, 129, None)} and 2579 * 129 >= 330000 > 2579 * 127
+    assert (-(-2579 // 64), _last(2579, 64), -(-129 // 8), _last(129, 8)) == (41, 19, 17, 1)
+    assert {(c[4], c[5], np.dtype(c[6]).name, c[7]) for c in t8} == {(f, l, d, w) for f, l in SC.FORMS for d in ("float64", "float32") for w in (0, XY)}
+    for path in ("wall", "wall-strict"):
+        cs = by_path[path]
+        for topo in SC.WALL_TOPOS:
+            mine = [c for c in cs if c[8] == topo]
+            assert {(c[1], c[2], c[3]) for c in mine} == {(65, 9, None), (67, 11, None), (64, 8, None), (7, 8, None), (129, 31, None),
+                                                          (129, 33, SC.PARTIAL)}
+            assert {(c[4], c[5]) for c in mine} == {(1, 1), (0, 2), (0, 0)} and {np.dtype(c[6]).name for c in mine} == {"float64", "float32"}
+            wrapped = {(c[1], c[2], c[7]) for c in mine if c[7]}
+            assert wrapped == {(SC.P, SC.B): {(65, 9, SC.WRAP_X)}, (SC.B, SC.P): {(65, 9, SC.WRAP_Y)}, (SC.B, SC.B): set()}[topo]
+        # last tile column | row of 1 and 3 cells (a tile edge 1 and 3 cells from the east | north wall: inside its boundary buffer and at
+        # its start), a full last tile (the buffer ends on the edge), one partial tile shared by both walls, several tiles a side
+        assert [_last(Nx, 64) for Nx, _ in SC.WALL_SHAPES] == [1, 3, 64, 7, 1] and [-(-Nx // 64) for Nx, _ in SC.WALL_SHAPES] == [2, 2, 1, 1, 3]
+        assert [_last(Ny, 8) for _, Ny in SC.WALL_SHAPES] == [1, 3, 8, 8, 7] and [-(-Ny // 8) for _, Ny in SC.WALL_SHAPES] == [2, 2, 1, 1, 4]
+    # every path makes all 19 calls; the strict and wall paths are refused the five fast-only forms
+    assert all(SC.PATHS[p]["refused"] == (() if p in ("march", "tile4", "tile8") else ("P2g", "P3n", "A1", "A2", "A2a")) for p in SC.PATHS)
+
+
+def test_every_shape_of_the_tile_matrix_has_its_layout(swmhd):
+    """The planner's own answer (swmhd_tendency_launch_geometry with SWMHD_TILE_KERNEL and the rows of the launch) puts every tile4
+    shape on 64 x 4 tiles and the tile8 shape, just above the threshold, on 64 x 8; strict launches have 64 x 8 tiles at every size;
+    the wall shapes lie below the hybrid thresholds (stage_cases.wall_tiles, inferred).  A partial row range of the tile8 shape would
+    fall back to 64 x 4 tiles, which is why that path runs whole ranges only.  (The GPU test asserts the same on the device.)"""
+    L = swmhd._lib
+    heights = {}
+    for path, Nx, Ny, rows, form, lor, dtype, flags, topo in SC.tile_matrix():
+        nrows = Ny if rows is None else rows[1] - rows[0]
+        line = SC.check_layout(L, Nx, nrows, form, dtype, flags, path=path)
+        geo = L.tendency_launch_geometry(Nx, nrows, form, np.dtype(dtype).itemsize, SC.TILE_KERNEL | (SC.STRICT if SC.PATHS[path]["strict"] else 0) | flags)
+        heights.setdefault(path, set()).add(geo["rows_per_segment"])
+        assert f"{-(-Nx // 64)} tile columns, last {_last(Nx, 64)} wide" in line
+        if path in ("tile4", "wall", "wall-strict"):
+            assert Nx * nrows < 330000
+    assert heights["tile4"] == {4} and heights["tile8"] == {8} and heights["strict"] == {8} and heights["wall-strict"] == {8}
+    assert heights["wall"] == {4}        # what the query, which knows no topology, says of these sizes: the wall kernel's 8 rows are inferred
+    Nx, Ny = SC.TILE8_SHAPE
+    for form in (0, 1):
+        for elem in (4, 8):
+            assert L.tendency_launch_geometry(Nx, Ny - 2, form, elem, SC.TILE_KERNEL)["rows_per_segment"] == 4
+            assert L.tendency_launch_geometry(Nx, SC.PARTIAL[1] - SC.PARTIAL[0], form, elem, SC.TILE_KERNEL)["rows_per_segment"] == 4
+            assert L.tendency_launch_geometry(Nx, Ny, form, elem, SC.TILE_KERNEL)["rows_per_segment"] == 8
+
+
+@pytest.mark.parametrize("topo", [(SC.P, SC.P), (SC.P, SC.B), (SC.B, SC.B)])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("form,lor", [(1, 1), (0, 2)])
+def test_composed_strict_stages_are_the_oracle_time_step(oracle, form, lor, dtype, topo):
+    """S1g, S2g and S3n of reference_stage_strict with the oracle's halo fills between them against oracle.time_step on a 40 x 33 grid,
+    bit for bit in the precision of the call: the strict reference restates neither the tendencies nor the substep differently from
+    the oracle, for periodic and Bounded grids (with the gradient condition on A)."""
+    data = SC.StageData(oracle, Nx, Ny, form, lor, dtype, seed=13, topo=topo)
+    dt = float(np.dtype(dtype).type(1e-4))
+    want = [a.copy() for a in data.q]
+    oracle.time_step(*want, Nx, Ny, H, H, data.dx, data.dy, dt, form, lor, data.grav, data.fcor, topo=topo, gradA=TC.grad_A(topo))
+
+    def embed(interior):
+        a = np.full_like(data.q[0], SC.SENTINEL)
+        Hh.interior(a, Nx, Ny, H, H)[...] = interior
+        return a
+    for variant, coeffs in (("S1g", (G1, 0.0)), ("S2g", (G2, Z2)), ("S3n", (G3, Z3))):
+        ref = SC.reference_stage_strict(data, variant, coeffs, dt)
+        assert all(a.dtype == np.dtype(dtype) for a in ref["qnew"])
+        if ref["Gn"] is not SC.KEEP:
+            data.aux = [embed(g) for g in ref["Gn"]]
+        data.q = TC.fill_state(oracle, [embed(x) for x in ref["qnew"]], Nx, Ny, topo, TC.grad_A(topo), data.dx, data.dy)
+        data._G_strict = None
+    assert ref["Gn"] is SC.KEEP
+    for got, w in zip(data.q, want):
+        assert np.array_equal(Hh.interior(got, Nx, Ny, H, H), Hh.interior(w, Nx, Ny, H, H))
+    # a row range cuts every output, and T has no new state
+    part = SC.reference_stage_strict(data, "T", (0.0, 0.0), 0.0, rows=SC.PARTIAL)
+    assert part["qnew"] is None and all(g.shape == (SC.PARTIAL[1] - SC.PARTIAL[0], Nx) for g in part["Gn"])
+
+
+@pytest.mark.parametrize("form,lor", SC.WALL_FORMS)
+def test_the_bounded_reference_differs_exactly_inside_the_wall_buffers(oracle, form, lor):
+    """Every Bounded shape and topology of the tile matrix: the oracle's Bounded tendencies of the boundary-condition-filled inputs
+    differ from the periodic ones of the same interior inside the buffer of every wall (7 cells: test_bounded_oracle) and are equal bit
+    for bit outside.  Control: a reference that took no wall branch -- the periodic oracle -- is caught."""
+    for Nx_, Ny_, rows, topo, _flags in SC.wall_shape_groups():
+        for dtype in SC.DTYPES:
+            data = SC.StageData(oracle, Nx_, Ny_, form, lor, dtype, topo=topo)
+            assert data.wall_failures == [], (Nx_, Ny_, topo, dtype, data.wall_failures)
+            assert all(np.isfinite(g).all() for g in data.G)
+            buffers = SC.wall_buffers(Nx_, Ny_, topo)
+            assert set(buffers) == ({"west", "east"} if topo[0] == SC.B else set()) | ({"south", "north"} if topo[1] == SC.B else set())
+            q64 = [a.astype(np.float64) for a in data.q]
+            qp = [oracle.fill_halo_periodic(a.copy(), Nx_, Ny_, H, H) for a in q64]
+            data.G = [Hh.interior(g, Nx_, Ny_, H, H).copy() for g in oracle.tendencies(*qp, Nx_, Ny_, H, H, data.dx, data.dy, form, lor, data.grav, data.fcor)]
+            assert len(SC.wall_buffer_failures(oracle, data, q64)) == len(buffers)
+    far = SC.wall_buffers(129, 31, (SC.B, SC.B))
+    assert far["west"].sum() == far["east"].sum() == 7 * 31 and far["south"].sum() == far["north"].sum() == 7 * 129
+    assert not (far["west"] | far["east"] | far["south"] | far["north"])[7:24, 7:122].any()

@@ -3,10 +3,18 @@ kernel family (vi, cons, packed) x precision x call form, on the current GPU.  P
 
     python tools/stage_matrix_report.py [out.json]        (default: profiles/stage_matrix/achieved.json)
 
-A ratio of 1 would be a call at its bound (include/swmhd.h: 1e-12 / 1e-4 of max(max|G|, S) per tendency, carried into the new state)."""
+A ratio of 1 would be a call at its bound (include/swmhd.h: 1e-12 / 1e-4 of max(max|G|, S) per tendency, carried into the new state).
+
+The same for the tile matrix (the calls of tests/test_tile_stage_matrix_gpu.py) per tile path (tile4, tile8, strict, wall,
+wall-strict) x precision x call form, with the number of cases per path and the wall time of the whole matrix in this process:
+
+    python tools/stage_matrix_report.py --tile [out.json] (default: profiles/stage_matrix/achieved_tile.json)
+
+The strict paths are compared bitwise: their ratio is 0 (every written cell equal to the oracle's) or inf."""
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
@@ -37,5 +45,34 @@ def main(out_path):
     return 1 if failures else 0
 
 
+def main_tile(out_path):
+    import torch
+    import swmhd_amd as S
+    from oracle import oracle as O
+    worst, layouts, failures, ncases, refusals = {}, {}, [], {}, 0
+    t0 = time.perf_counter()
+    for case in SC.tile_matrix():
+        path, Nx, Ny, rows, form, lor, dtype, flags, topo = case
+        ncases[path] = ncases.get(path, 0) + 1
+        refusals += sum(1 for v, _ in SC.calls() if v in SC.PATHS[path]["refused"])
+        nrows = Ny if rows is None else rows[1] - rows[0]
+        layouts[f"{Nx} x {nrows} rows {path}"] = SC.check_layout(S._lib, Nx, nrows, form, dtype, flags, path=path)
+        failures += [f"{SC.tile_case_id(*case)} {m}" for m in SC.run_cases(S, O, Nx, Ny, rows, form, lor, dtype, flags, worst=worst,
+                                                                          path=path, topo=topo)]
+    seconds = time.perf_counter() - t0
+    rec = {"device": torch.cuda.get_device_name(0), "kernel_source_hash": S._lib.source_hash(), "cases": sum(ncases.values()),
+           "cases_per_path": ncases, "calls_per_case": len(SC.calls()), "refused_calls": refusals, "seconds": float(f"{seconds:.1f}"),
+           "failures": failures, "max_error_over_bound": {k: float(f"{v:.3g}") for k, v in sorted(worst.items())}, "layouts": layouts}
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+    print(json.dumps(rec["max_error_over_bound"], indent=1))
+    print(f"{rec['cases']} cases x {len(SC.calls())} calls ({refusals} of them refusals) in {seconds:.1f} s, {len(failures)} failures -> {out_path}")
+    return 1 if failures else 0
+
+
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "stage_matrix", "achieved.json")))
+    args = sys.argv[1:]
+    if args and args[0] == "--tile":
+        sys.exit(main_tile(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "stage_matrix", "achieved_tile.json")))
+    sys.exit(main(args[0] if args else os.path.join(ROOT, "profiles", "stage_matrix", "achieved.json")))
