@@ -234,20 +234,7 @@ template <typename T> hipError_t launch_tendency_ensemble_strict(const EnsTendAr
 // the same stage with per-member (g, f, dt): the PAR instantiations of the same kernels, same plan, same member mapping
 template <typename T> hipError_t launch_ensemble_params_stage_fast(const EnsParTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
 template <typename T> hipError_t launch_ensemble_params_stage_strict(const EnsParTendArgs<T> &a, int formulation, int lorentz, hipStream_t s);
-// internal twins of swmhd_tendencies_rk3_* and swmhd_fill_halo_periodic_multi_* for the slab driver (ring.hip), same argument checks
-// and return codes; the first serves rows [j0, j1) and [j0b, j1b) of one RK3 stage in ONE launch where the kernel chosen supports it
-// (an empty second range: exactly the exported call)
-template <typename T>
-int tendencies_rk3_two_ranges(const T *const *q, T *const *qnew, T *const *Gn, const T *const *Gm, int Nx, int Ny, int Hx, int Hy, long sy,
-                              T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, T gamma, T zeta, int store_G, int j0, int j1,
-                              int j0b, int j1b, int flags, void *stream);
-template <typename T>
-int fill_halo_periodic_multi(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int which, void *stream);
-// boundary-condition fill of one slab (swmhd_fill_halo_walls with a DEVICE gradient table of 4 nf values, NULL = defaults): x in the
-// grid's x topology, y walls only on the sides of walls_y (bit 0 south, bit 1 north); same checks and return codes
-template <typename T>
-int fill_halo_walls_dev(T *const *f, int nf, int Nx, int Ny, int Hx, int Hy, long sy, int topo_x, int walls_y, int face_x, int face_y,
-                        const T *gtab, T dx, T dy, void *stream);
+// (internal twins of exported calls for the slab driver: api_args.hpp, host only)
 template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, hipStream_t s);
 
 // Passive tracers (swmhd_tracers_rk3_*, tracer_kernels.inc): K extra centre fields advected by the state (q1, q2, h) a stage starts

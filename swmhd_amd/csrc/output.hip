@@ -19,7 +19,7 @@
 // 16-byte store of a float32 frame), a chunk that crosses the end of a row falls back to single elements.  Parents and frames are
 // only element-aligned (the interior starts Hx elements into a row; a frame row is Nx elements), hence the under-aligned vector types.
 // Reach: one cell (x−1, y−1, y+1).  With SWMHD_WRAP_X / _Y those neighbours are taken at (x mod Nx, y mod Ny) instead of the halo.
-#include "../../include/swmhd.h"
+#include "api_args.hpp"
 #include "common.hpp"
 
 namespace swmhd {
@@ -168,50 +168,47 @@ __global__ __launch_bounds__(OUT_NT) void k_output_fields(OutArgs<T> a) {
     }
 }
 
-inline int hiprc(hipError_t e) { return e == hipSuccess ? SWMHD_OK : -(int)e; }
-
-struct OutEns {
-    int members;
-    int64_t stride_m, out_stride_m;
+// the frame: `which` fields of `elem`-byte elements at out; row, field and (ensembles) member stride in elements
+struct OutFrame {
+    int which;
+    void *out;
+    int elem;
+    int64_t osy, osf, osm = 0;
 };
 
 template <typename T>
-int output_common(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy,
-                  int form, int j0, int j1, int which, void *out, int elem, int64_t osy, int64_t osf, int flags, void *stream,
-                  const OutEns *ens = nullptr) {
-    if (!q1 || !q2 || !h || !A || !out) return SWMHD_EINVAL;
-    if (Nx <= 0 || Ny <= 0 || Hx < 0 || Hy < 0 || sy < (int64_t)Nx + 2 * Hx || !(dx > T(0)) || !(dy > T(0))) return SWMHD_EINVAL;
-    if (form != SWMHD_CONSERVATIVE && form != SWMHD_VECTOR_INVARIANT) return SWMHD_EINVAL;
-    if (j0 < 0 || j1 > Ny || j0 > j1) return SWMHD_EINVAL;
-    if (which <= 0 || (which & ~SWMHD_OUT_ALL)) return SWMHD_EINVAL;
-    if (elem != 4 && elem != 8) return SWMHD_EINVAL;
-    if (flags & ~(SWMHD_WRAP_X | SWMHD_WRAP_Y)) return SWMHD_EINVAL;
-    const int nf = __builtin_popcount((unsigned)which);
-    if (osy < Nx || osf < (int64_t)(j1 - j0) * osy) return SWMHD_EINVAL;
+int output_common(const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, const Rows &r, const OutFrame &o, int flags,
+                  void *stream, const Ens *ens = nullptr) {
+    if (!q1 || !q2 || !h || !A || !o.out) return SWMHD_EINVAL;
+    if (!g.extents_ok() || !g.spacing_ok() || !formulation_ok(form) || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
+    if (o.which <= 0 || (o.which & ~SWMHD_OUT_ALL)) return SWMHD_EINVAL;
+    if (o.elem != 4 && o.elem != 8) return SWMHD_EINVAL;
+    if (flags & ~OUTPUT_FLAGS) return SWMHD_EINVAL;
+    const int nf = __builtin_popcount((unsigned)o.which);
+    if (o.osy < g.Nx || o.osf < (int64_t)(r.j1 - r.j0) * o.osy) return SWMHD_EINVAL;
     if (ens) {
         if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (ens->stride_m < ((int64_t)Ny + 2 * Hy) * sy || ens->out_stride_m < (int64_t)nf * osf) return SWMHD_EINVAL;
+        if (ens->stride_m < g.min_member_stride() || o.osm < (int64_t)nf * o.osf) return SWMHD_EINVAL;
     }
-    if (Hx < 1 || Hy < 1) return SWMHD_EHALO;
-    if (j0 == j1) return SWMHD_OK;
-    const long off = (long)Hy * sy + Hx;
+    if (!g.halo_at_least(1)) return SWMHD_EHALO;
+    if (r.j0 == r.j1) return SWMHD_OK;
     OutArgs<T> a;
-    a.q1 = q1 + off; a.q2 = q2 + off; a.h = h + off; a.A = A + off;
-    a.out = out;
-    a.Nx = Nx; a.Ny = Ny; a.j0 = j0; a.j1 = j1; a.nchunk = (Nx + OUT_VEC - 1) / OUT_VEC;
-    a.sy = (long)sy; a.osy = (long)osy; a.osf = (long)osf;
-    a.dx = (double)dx; a.dy = (double)dy;
-    a.form = form; a.which = which;
-    a.wrap = ((flags & SWMHD_WRAP_X) ? 1 : 0) | ((flags & SWMHD_WRAP_Y) ? 2 : 0);
-    a.stride_m = ens ? (long)ens->stride_m : 0; a.ostride_m = ens ? (long)ens->out_stride_m : 0;
-    const long threads = (long)(j1 - j0) * a.nchunk;
+    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = g.interior(h); a.A = g.interior(A);
+    a.out = o.out;
+    a.Nx = g.Nx; a.Ny = g.Ny; a.j0 = r.j0; a.j1 = r.j1; a.nchunk = (g.Nx + OUT_VEC - 1) / OUT_VEC;
+    a.sy = (long)g.sy; a.osy = (long)o.osy; a.osf = (long)o.osf;
+    a.dx = g.dx; a.dy = g.dy;
+    a.form = form; a.which = o.which;
+    a.wrap = decode_flags(flags).wrap;
+    a.stride_m = ens ? (long)ens->stride_m : 0; a.ostride_m = ens ? (long)o.osm : 0;
+    const long threads = (long)(r.j1 - r.j0) * a.nchunk;
     const dim3 grid((unsigned)((threads + OUT_NT - 1) / OUT_NT), ens ? ens->members : 1);
     hipStream_t s = (hipStream_t)stream;
     if (ens) {
-        if (elem == 4) hipLaunchKernelGGL((k_output_fields<T, float, true>), grid, dim3(OUT_NT), 0, s, a);
+        if (o.elem == 4) hipLaunchKernelGGL((k_output_fields<T, float, true>), grid, dim3(OUT_NT), 0, s, a);
         else hipLaunchKernelGGL((k_output_fields<T, double, true>), grid, dim3(OUT_NT), 0, s, a);
     } else {
-        if (elem == 4) hipLaunchKernelGGL((k_output_fields<T, float, false>), grid, dim3(OUT_NT), 0, s, a);
+        if (o.elem == 4) hipLaunchKernelGGL((k_output_fields<T, float, false>), grid, dim3(OUT_NT), 0, s, a);
         else hipLaunchKernelGGL((k_output_fields<T, double, false>), grid, dim3(OUT_NT), 0, s, a);
     }
     return hiprc(hipGetLastError());
@@ -226,16 +223,16 @@ extern "C" {
     int swmhd_output_fields_##sfx(const T *q1, const T *q2, const T *h, const T *A, int Nx, int Ny, int Hx, int Hy, int64_t sy,     \
                                   T dx, T dy, int formulation, int j0, int j1, int which, void *out, int out_elem_size,             \
                                   int64_t out_stride_y, int64_t out_stride_f, int flags, void *stream) {                           \
-        return swmhd::output_common<T>(q1, q2, h, A, Nx, Ny, Hx, Hy, sy, dx, dy, formulation, j0, j1, which, out, out_elem_size,    \
-                                       out_stride_y, out_stride_f, flags, stream);                                                  \
+        return swmhd::output_common<T>(q1, q2, h, A, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, formulation, swmhd::Rows{j0, j1},     \
+                                       swmhd::OutFrame{which, out, out_elem_size, out_stride_y, out_stride_f}, flags, stream);      \
     }                                                                                                                                \
     int swmhd_ensemble_output_fields_##sfx(const T *q1, const T *q2, const T *h, const T *A, int members, int64_t stride_m, int Nx, \
                                            int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, int formulation, int j0, int j1,         \
                                            int which, void *out, int out_elem_size, int64_t out_stride_y, int64_t out_stride_f,     \
                                            int64_t out_stride_m, int flags, void *stream) {                                         \
-        const swmhd::OutEns e{members, stride_m, out_stride_m};                                                                      \
-        return swmhd::output_common<T>(q1, q2, h, A, Nx, Ny, Hx, Hy, sy, dx, dy, formulation, j0, j1, which, out, out_elem_size,    \
-                                       out_stride_y, out_stride_f, flags, stream, &e);                                              \
+        const swmhd::Ens e{members, stride_m};                                                                                       \
+        return swmhd::output_common<T>(q1, q2, h, A, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, formulation, swmhd::Rows{j0, j1},     \
+                                       swmhd::OutFrame{which, out, out_elem_size, out_stride_y, out_stride_f, out_stride_m}, flags, stream, &e);  \
     }
 
 SWMHD_DEF_OUTPUT(f64, double)

@@ -9,8 +9,8 @@
 //
 // RCCL is bound at run time (dlopen of the path the host passes -- the copy PyTorch already loaded when the host is the
 // Python harness) so that libswmhd.so itself carries no link-time dependency on it; single-GPU users never touch it.
+#include "api_args.hpp"
 #include "common.hpp"
-#include "../../include/swmhd.h"
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -207,15 +207,15 @@ int loopback_exchange(swmhd_ring *r, const Rows &rows, int nf, size_t bytes, int
 // field) is what makes the 1- and 2-rank rings, where both neighbours are the same peer, pair up correctly: RCCL matches sends and
 // receives of a peer in issue order.
 template <typename T>
-int exchange(swmhd_ring *r, T *const *fields, int nf, int Nx, int Ny, int Hx, int Hy, int64_t sy, hipStream_t s, int sides = 3) {
+int exchange(swmhd_ring *r, T *const *fields, int nf, const swmhd::Grid &g, hipStream_t s, int sides = 3) {
     if (!r || !fields || nf <= 0 || (sides & ~3)) return SWMHD_EINVAL;
-    if (Nx <= 0 || Ny < Hy || Hy <= 0 || sy < (int64_t)Nx + 2 * Hx) return SWMHD_EINVAL;
+    if (g.Nx <= 0 || g.Ny < g.Hy || g.Hy <= 0 || !g.stride_ok()) return SWMHD_EINVAL;   // (rows to send: a halo, and a slab that covers it)
     for (int f = 0; f < nf; ++f)
         if (!fields[f]) return SWMHD_EINVAL;
     if (!sides) return SWMHD_OK;
     if (r->hub && nf > LoopHub::MAXF) return SWMHD_EINVAL;
-    const size_t count = (size_t)Hy * (size_t)sy;   // Hy full rows (the pitch padding of the last row travels too: harmless)
-    auto rows = [&](int f) { return edge_rows(fields[f], Ny, Hy, sy); };
+    const size_t count = (size_t)g.Hy * (size_t)g.sy;   // Hy full rows (the pitch padding of the last row travels too: harmless)
+    auto rows = [&](int f) { return edge_rows(fields[f], g.Ny, g.Hy, g.sy); };
     if (r->hub) return loopback_exchange(r, rows, nf, count * sizeof(T), sides, s);
     ncclResult_t rc = r->api.GroupStart();
     if (rc != ncclSuccess) return fail(r, "ncclGroupStart", rc);
@@ -266,21 +266,23 @@ struct Slab {
     swmhd_ring *r;
     hipStream_t s, c;   // the caller's stream (main) and, from begin() on, the ring's comm stream
     swmhd::Rk3Buffers<T> b;
-    int Nx, Ny, Hx, Hy; int64_t sy; T dx, dy, grav, fcor; int formulation, lorentz; T dt;   // the grid and physics of every stage
+    swmhd::Grid g;
+    swmhd::Physics<T> ph;   // the model and dt; run() adds the stage's scalars
     bool anchor;   // fast periodic slabs: the anchor form, 96 B/cell in every stage (common.hpp: Rk3Buffers); else the G- form
     int *state_in_alt;
 
     // rows [j0, j1) and [j0b, j1b) of stage g on stream `on`
-    int run(const swmhd::Rk3Stage<T> &g, int j0, int j1, int j0b, int j1b, int fl, hipStream_t on) {
-        return swmhd::tendencies_rk3_two_ranges<T>(b.cur, b.alt, b.gn, g.Gm, Nx, Ny, Hx, Hy, (long)sy, dx, dy, grav, fcor, formulation,
-                                                   lorentz, dt, g.gamma, g.zeta, g.store_G, j0, j1, j0b, j1b, fl | g.flags, (void *)on);
+    int run(const swmhd::Rk3Stage<T> &sg, int j0, int j1, int j0b, int j1b, int fl, hipStream_t on) {
+        swmhd::Physics<T> st = ph;
+        st.gamma = sg.gamma; st.zeta = sg.zeta; st.store_G = sg.store_G;
+        return swmhd::tendencies_rk3<T>(b.cur, b.alt, b.gn, sg.Gm, g, st, swmhd::Rows{j0, j1, j0b, j1b}, fl | sg.flags, (void *)on);
     }
     // checks of both drivers, before any HIP call or read of the ring: the first stage's over an empty row range, and the fill's own
     int check(T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int flags) {
-        if (Ny < 2 * Hy + 1) return SWMHD_EINVAL;   // a slab needs interior rows between its two strips
+        if (g.Ny < 2 * g.Hy + 1) return SWMHD_EINVAL;   // a slab needs interior rows between its two strips
         if (!b.set(q, q_alt, Ga, Gb)) return SWMHD_EINVAL;
         if (int rc = run(b.stage(0, anchor), 0, 0, 0, 0, flags, s)) return rc;
-        return Hx > Nx ? SWMHD_EHALO : SWMHD_OK;
+        return g.Hx > g.Nx ? SWMHD_EHALO : SWMHD_OK;
     }
     // drain an exchange in flight for another state; what the caller enqueued so far precedes all this call puts on the comm stream
     int begin() {
@@ -299,21 +301,21 @@ struct Slab {
     int comm_waits() { const hipError_t e = follow(c, s, r->ev_main); return e == hipSuccess ? SWMHD_OK : hipfail(r, "comm waits for main", e); }
     int main_waits() { const hipError_t e = follow(s, c, r->ev_comm); return e == hipSuccess ? SWMHD_OK : hipfail(r, "main waits for comm", e); }
     int exchange_cur(int cuts) {
-        const int rc = exchange<T>(r, b.cur, 4, Nx, Ny, Hx, Hy, sy, c, cuts);
+        const int rc = exchange<T>(r, b.cur, 4, g, c, cuts);
         if (!rc) r->pending = b.cur[0];
         return rc;
     }
     // the interior launch of a stage on the main stream, between two timing events while swmhd_ring_time_launches asks for them
     // (timing-only events: without the system-scope fence a default event performs when it is recorded -- with the comm stream's
     //  kernels running beside the interior launch that fence cost 16 % of the step, 1.53 vs 1.32 ms)
-    int run_interior(const swmhd::Rk3Stage<T> &g, int j0, int j1, int fl) {
-        if (r->t0.size() >= r->tcap) return run(g, j0, j1, 0, 0, fl, s);
+    int run_interior(const swmhd::Rk3Stage<T> &sg, int j0, int j1, int fl) {
+        if (r->t0.size() >= r->tcap) return run(sg, j0, j1, 0, 0, fl, s);
         hipEvent_t t0 = nullptr, t1 = nullptr;
         hipError_t e;
         if ((e = hipEventCreateWithFlags(&t0, hipEventDisableSystemFence)) != hipSuccess) return hipfail(r, "hipEventCreate", e);
         if ((e = hipEventCreateWithFlags(&t1, hipEventDisableSystemFence)) != hipSuccess) { (void)hipEventDestroy(t0); return hipfail(r, "hipEventCreate", e); }
         (void)hipEventRecord(t0, s);
-        const int rc = run(g, j0, j1, 0, 0, fl, s);
+        const int rc = run(sg, j0, j1, 0, 0, fl, s);
         if (rc) { (void)hipEventDestroy(t0); (void)hipEventDestroy(t1); return rc; }
         (void)hipEventRecord(t1, s);
         r->t0.push_back(t0); r->t1.push_back(t1); r->trows.push_back(j1 - j0);
@@ -324,18 +326,17 @@ struct Slab {
     //      condition fill (gradient: device table of 16 values, or NULL), x halos in memory the periodic x fill, x wrapped on read none
     int per_stage(int nsteps, int fl, int cuts, const T *gradient) {
         const bool walls = fl & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y), fill = walls || !(fl & SWMHD_WRAP_X);
-        const int topo_x = (fl & SWMHD_BOUNDED_X) ? SWMHD_BOUNDED : SWMHD_PERIODIC;
-        constexpr int FACE_X = 0b0001, FACE_Y = 0b0010;
-        const int lo = (cuts & 1) ? Hy : 0, hi = (cuts & 2) ? Ny - Hy : Ny;   // rows [lo, hi) need no remote data
+        const swmhd::BcSides sides{swmhd::decode_flags(fl).topo_x, SWMHD_BOUNDED, swmhd::FACE_X, swmhd::FACE_Y};
+        const int Ny = g.Ny, lo = (cuts & 1) ? g.Hy : 0, hi = (cuts & 2) ? Ny - g.Hy : Ny;   // rows [lo, hi) need no remote data
         for (int n = 0; n < nsteps; ++n)
             for (int st = 0; st < 3; ++st) {
-                const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
+                const swmhd::Rk3Stage<T> sg = b.stage(st, anchor);
                 const bool split = r->pending != nullptr;
                 int rc;
                 // (interior rows: leave a few workgroup slots free, or the exchange and the strips could not start before it ends)
-                if ((rc = split ? run_interior(g, lo, hi, fl | SWMHD_LEAVE_ROOM) : run_interior(g, 0, Ny, fl))) return rc;
+                if ((rc = split ? run_interior(sg, lo, hi, fl | SWMHD_LEAVE_ROOM) : run_interior(sg, 0, Ny, fl))) return rc;
                 // the cut strips in one launch: they sit on the exchange -> strips -> exchange chain that bounds a thin slab
-                if (split && ((rc = lo > 0 ? run(g, 0, lo, hi, Ny, fl, c) : run(g, hi, Ny, 0, 0, fl, c)) || (rc = main_waits()))) return rc;
+                if (split && ((rc = lo > 0 ? run(sg, 0, lo, hi, Ny, fl, c) : run(sg, hi, Ny, 0, 0, fl, c)) || (rc = main_waits()))) return rc;
                 b.rotate();
                 r->pending = nullptr;   // the exchange of the OLD state has been consumed; none of the new state is in flight yet
                 if (split && !fill) {
@@ -345,11 +346,8 @@ struct Slab {
                     if ((rc = exchange_cur(cuts)) || (rc = comm_waits())) return rc;
                     continue;
                 }
-                if (walls && (rc = swmhd::fill_halo_walls_dev<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, topo_x, 3 & ~cuts, FACE_X, FACE_Y, gradient,
-                                                                 dx, dy, (void *)s)))
-                    return rc;
-                if (!walls && fill && (rc = swmhd::fill_halo_periodic_multi<T>(b.cur, 4, Nx, Ny, Hx, Hy, (long)sy, SWMHD_HALO_X, (void *)s)))
-                    return rc;
+                if (walls && (rc = swmhd::fill_halo_walls<T>(b.cur, 4, g, sides, 3 & ~cuts, nullptr, gradient, (void *)s))) return rc;
+                if (!walls && fill && (rc = swmhd::fill_halo_periodic_multi<T>(b.cur, 4, g, SWMHD_HALO_X, (void *)s))) return rc;
                 if (!cuts) continue;   // a chain of one: both walls local, nothing to exchange
                 if ((rc = comm_waits()) || (rc = exchange_cur(cuts))) return rc;
             }
@@ -371,14 +369,15 @@ struct Slab {
         const int ilo[3] = {3, 9, 12}, blo[3] = {-6, -3, 0};
         // boundary zones of a wide slab take the row-marching kernel too (both zones in one launch, a few dozen workgroups beside the
         // interior launch); the LDS-tiled kernel re-loads a 10-row halo per 4-row tile and costs ten times as much per row
-        const int bflags = flags | ((!(flags & (SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL)) && Nx >= 1024) ? SWMHD_MARCH_KERNEL : 0);
+        const int bflags = flags | ((!(flags & (SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL)) && g.Nx >= 1024) ? SWMHD_MARCH_KERNEL : 0);
+        const int Ny = g.Ny;
         int rc;
         for (int n = 0; n < nsteps; ++n) {
             for (int st = 0; st < 3; ++st) {
-                const swmhd::Rk3Stage<T> g = b.stage(st, anchor);
-                if ((rc = run_interior(g, ilo[st], Ny - ilo[st], flags | SWMHD_LEAVE_ROOM))) return rc;
+                const swmhd::Rk3Stage<T> sg = b.stage(st, anchor);
+                if ((rc = run_interior(sg, ilo[st], Ny - ilo[st], flags | SWMHD_LEAVE_ROOM))) return rc;
                 // boundary rows of this stage, both sides in one launch, behind the exchange (stage 1) / the previous boundary launch
-                if ((rc = run(g, blo[st], ilo[st], Ny - ilo[st], Ny - blo[st], bflags, c))) return rc;
+                if ((rc = run(sg, blo[st], ilo[st], Ny - ilo[st], Ny - blo[st], bflags, c))) return rc;
                 if (st < 2 && (rc = comm_waits())) return rc;   // the next boundary launch reads rows of this interior launch
                 b.rotate();
             }
@@ -393,18 +392,16 @@ struct Slab {
 
 // swmhd_ring_step_rk3: a periodic ring -- both sides cut, stages in anchor form (fast) or G- form (strict)
 template <typename T>
-int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy,
-              T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, int flags, int *state_in_alt,
-              void *stream) {
+int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, const swmhd::Grid &g, const swmhd::Physics<T> &ph,
+              int nsteps, int flags, int *state_in_alt, void *stream) {
     if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
     if (flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y)) return SWMHD_ENOTSUP;   // walls: swmhd_ring_step_rk3_bc (its fill is the BC fill)
     if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;   // y images belong to the neighbours (x may be wrapped on read: no x-halo kernel then)
-    Slab<T> x{r, (hipStream_t)stream, nullptr, {}, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt,
-              !(flags & SWMHD_STRICT), state_in_alt};
+    Slab<T> x{r, (hipStream_t)stream, nullptr, {}, g, ph, !(flags & SWMHD_STRICT), state_in_alt};
     if (int rc = x.check(q, q_alt, Ga, Gb, flags)) return rc;
     if (nsteps == 0) return x.end(SWMHD_OK);
     if (int rc = x.begin()) return rc;
-    const bool deep = (flags & SWMHD_WRAP_X) && Hy >= 9 && Ny >= 32;
+    const bool deep = (flags & SWMHD_WRAP_X) && g.Hy >= 9 && g.Ny >= 32;
     return x.end(deep ? x.deep_halo(nsteps, flags) : x.per_stage(nsteps, flags, 3, nullptr));
 }
 
@@ -412,18 +409,14 @@ int ring_step(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *cons
 // condition fill.  With SWMHD_BOUNDED_Y the ranks form a CHAIN -- rank 0 holds the south wall, the last rank the north wall, every
 // other side is a cut to a neighbour; with SWMHD_BOUNDED_X alone a periodic-y ring whose x walls are local to every slab.
 template <typename T>
-int ring_step_bc(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny, int Hx, int Hy, int64_t sy,
-                 T dx, T dy, T grav, T fcor, int formulation, int lorentz, T dt, int nsteps, const T *gradient, int flags,
-                 int *state_in_alt, void *stream) {
-    constexpr int KNOWN = SWMHD_STRICT | SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL | SWMHD_WRAP_X | SWMHD_WRAP_Y | SWMHD_BOUNDED_X |
-                          SWMHD_BOUNDED_Y | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR | SWMHD_LEAVE_ROOM;
-    if (flags & ~KNOWN) return SWMHD_EINVAL;                                   // (SWMHD_OPEN_*: the chain decides its walls)
-    if (!(flags & (SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y))) return SWMHD_EINVAL;   // periodic slabs: swmhd_ring_step_rk3
-    if (flags & (SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | SWMHD_RK3_ANCHOR)) return SWMHD_ENOTSUP;
-    if (flags & SWMHD_WRAP_Y) return SWMHD_EINVAL;
-    if ((flags & SWMHD_BOUNDED_X) && (flags & SWMHD_WRAP_X)) return SWMHD_EINVAL;
+int ring_step_bc(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, const swmhd::Grid &g, const swmhd::Physics<T> &ph,
+                 int nsteps, const T *gradient, int flags, int *state_in_alt, void *stream) {
+    if (flags & ~(swmhd::RING_BC_FLAGS | swmhd::RING_BC_NOTSUP)) return SWMHD_EINVAL;
+    if (!(flags & swmhd::BOUNDED_FLAGS)) return SWMHD_EINVAL;   // periodic slabs: swmhd_ring_step_rk3
+    if (flags & swmhd::RING_BC_NOTSUP) return SWMHD_ENOTSUP;
+    if ((flags & SWMHD_WRAP_Y) || swmhd::bounded_wrap_conflict(flags)) return SWMHD_EINVAL;   // y images belong to the neighbours
     if (!r || !q || !q_alt || !Ga || !Gb || nsteps < 0) return SWMHD_EINVAL;
-    Slab<T> x{r, (hipStream_t)stream, nullptr, {}, Nx, Ny, Hx, Hy, sy, dx, dy, grav, fcor, formulation, lorentz, dt, false, state_in_alt};
+    Slab<T> x{r, (hipStream_t)stream, nullptr, {}, g, ph, false, state_in_alt};
     if (int rc = x.check(q, q_alt, Ga, Gb, flags)) return rc;   // (the SWMHD_OPEN_* bits set below change none of its checks)
     if (nsteps == 0) return x.end(SWMHD_OK);
     const bool chain = flags & SWMHD_BOUNDED_Y;
@@ -475,7 +468,7 @@ int swmhd_ring_create(swmhd_ring **out, const char *rccl_path, int nranks, int r
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     if (r->api.CommInitRank(&r->comm, nranks, id, rank) != ncclSuccess) { delete r; return SWMHD_ECOMM; }
-    if (hipError_t e = init_ring(r, nranks, rank)) { swmhd_ring_destroy(r); return -(int)e; }
+    if (hipError_t e = init_ring(r, nranks, rank)) { swmhd_ring_destroy(r); return swmhd::hiprc(e); }
     *out = r;
     return SWMHD_OK;
 }
@@ -542,30 +535,29 @@ int swmhd_ring_launch_times(swmhd_ring *r, float *ms, int *rows, int capacity) {
 #define SWMHD_DEF_RING(sfx, T)                                                                                                   \
     int swmhd_ring_exchange_y_##sfx(swmhd_ring *r, T *const *fields, int nfields, int Nx, int Ny, int Hx, int Hy, int64_t sy,    \
                                     void *stream) {                                                                              \
-        return exchange<T>(r, fields, nfields, Nx, Ny, Hx, Hy, sy, (hipStream_t)stream);                                         \
+        return exchange<T>(r, fields, nfields, swmhd::Grid{Nx, Ny, Hx, Hy, sy}, (hipStream_t)stream);                            \
+    }                                                                                                                            \
+    int swmhd_ring_exchange_y_sides_##sfx(swmhd_ring *r, T *const *fields, int nfields, int Nx, int Ny, int Hx, int Hy,          \
+                                          int64_t sy, int sides, void *stream) {                                                 \
+        return exchange<T>(r, fields, nfields, swmhd::Grid{Nx, Ny, Hx, Hy, sy}, (hipStream_t)stream, sides);                     \
     }                                                                                                                            \
     int swmhd_ring_step_rk3_##sfx(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny,       \
                                   int Hx, int Hy, int64_t sy, T dx, T dy, T g, T f, int formulation, int lorentz, T dt,          \
                                   int nsteps, int flags, int *state_in_alt, void *stream) {                                      \
-        return ring_step<T>(r, q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, nsteps, flags,      \
-                            state_in_alt, stream);                                                                               \
-    }
-
-#define SWMHD_DEF_RING_BC(sfx, T)                                                                                                \
-    int swmhd_ring_exchange_y_sides_##sfx(swmhd_ring *r, T *const *fields, int nfields, int Nx, int Ny, int Hx, int Hy,          \
-                                          int64_t sy, int sides, void *stream) {                                                 \
-        return exchange<T>(r, fields, nfields, Nx, Ny, Hx, Hy, sy, (hipStream_t)stream, sides);                                  \
+        swmhd::Physics<T> ph{g, f, formulation, lorentz};                                                                        \
+        ph.dt = dt;                                                                                                              \
+        return ring_step<T>(r, q, q_alt, Ga, Gb, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, ph, nsteps, flags, state_in_alt, stream); \
     }                                                                                                                            \
     int swmhd_ring_step_rk3_bc_##sfx(swmhd_ring *r, T *const *q, T *const *q_alt, T *const *Ga, T *const *Gb, int Nx, int Ny,    \
                                      int Hx, int Hy, int64_t sy, T dx, T dy, T g, T f, int formulation, int lorentz, T dt,       \
                                      int nsteps, const T *gradient, int flags, int *state_in_alt, void *stream) {               \
-        return ring_step_bc<T>(r, q, q_alt, Ga, Gb, Nx, Ny, Hx, Hy, sy, dx, dy, g, f, formulation, lorentz, dt, nsteps, gradient, \
-                               flags, state_in_alt, stream);                                                                     \
+        swmhd::Physics<T> ph{g, f, formulation, lorentz};                                                                        \
+        ph.dt = dt;                                                                                                              \
+        return ring_step_bc<T>(r, q, q_alt, Ga, Gb, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, ph, nsteps, gradient, flags,        \
+                               state_in_alt, stream);                                                                            \
     }
 
 SWMHD_DEF_RING(f64, double)
 SWMHD_DEF_RING(f32, float)
-SWMHD_DEF_RING_BC(f64, double)
-SWMHD_DEF_RING_BC(f32, float)
 
 }  // extern "C"

@@ -1,0 +1,68 @@
+"""Are the device code objects of two source trees the same?  For a change that must not touch a kernel.
+
+    python tools/code_object_diff.py OTHER_TREE/swmhd_amd/csrc [swmhd_amd/csrc] [--json out.json]
+
+For every translation unit of the Makefile's OBJS the device side alone is compiled in both directories with the command line `make -n`
+prints for that unit (plus --offload-device-only --no-gpu-bundle-output), then `llvm-objdump -d --no-show-raw-insn` and `llvm-readelf --notes` of the two code
+objects are compared.  Lines that carry the object's path or the __hip_cuid_* symbol (a hash of the path) are left out.  Needs no GPU.
+Exit status 0: all equal."""
+import concurrent.futures
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROCM_LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def units(csrc):
+    out = subprocess.run(["make", "-C", csrc, "-n", "-B", "../libswmhd.so"], capture_output=True, text=True, check=True).stdout
+    cmds = {}
+    for line in out.splitlines():
+        m = re.search(r"-c (\S+)\.hip -o (\S+)\.o$", line)
+        if m:
+            cmds[m.group(1)] = line.split()
+    return cmds
+
+
+def device_listing(csrc, unit, cmd, tmp):
+    co = os.path.join(tmp, unit + ".co")
+    cmd = [c for c in cmd[:-1]] + [co]
+    cmd[1:1] = ["--offload-device-only", "--no-gpu-bundle-output"]
+    subprocess.run(cmd, cwd=csrc, check=True, capture_output=True)
+    text = []
+    for tool in (["llvm-objdump", "-d", "--no-show-raw-insn"], ["llvm-readelf", "--notes"]):
+        r = subprocess.run([os.path.join(ROCM_LLVM, tool[0])] + tool[1:] + [co], capture_output=True, text=True, check=True)
+        text.append([l for l in r.stdout.splitlines() if co not in l and "file format" not in l and "__hip_cuid_" not in l])
+    return text
+
+
+def main(argv):
+    js = None
+    if "--json" in argv:
+        k = argv.index("--json")
+        js = argv[k + 1]
+        del argv[k:k + 2]
+    other = os.path.abspath(argv[0])
+    mine = os.path.abspath(argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "swmhd_amd", "csrc"))
+    cmds = {d: units(d) for d in (other, mine)}
+    assert sorted(cmds[other]) == sorted(cmds[mine]), "the two Makefiles build different units"
+    report = {}
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb, concurrent.futures.ThreadPoolExecutor(8) as pool:
+        jobs = {(d, u): pool.submit(device_listing, d, u, cmds[d][u], t) for d, t in ((other, ta), (mine, tb)) for u in cmds[d]}
+        for u in sorted(cmds[mine]):
+            a, b = jobs[(other, u)].result(), jobs[(mine, u)].result()
+            report[u] = {"disassembly_lines": len(b[0]), "notes_lines": len(b[1]), "disassembly_equal": a[0] == b[0], "notes_equal": a[1] == b[1]}
+            print(u, report[u], flush=True)
+    if js:
+        with open(js, "w") as fh:
+            json.dump(report, fh, indent=1)
+            fh.write("\n")
+    return 0 if all(r["disassembly_equal"] and r["notes_equal"] for r in report.values()) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
