@@ -240,8 +240,7 @@ template <typename T> hipError_t launch_rk3_substep_strict(const Rk3Args<T> &a, 
 // Passive tracers (swmhd_tracers_rk3_*, tracer_kernels.inc): K extra centre fields advected by the state (q1, q2, h) a stage starts
 // from, all of them through that RK3 stage in ONE launch of an LDS-tiled kernel.  Pointers address interior cell (1,1) like TendArgs;
 // fuse / first / store_G / anchor / wrap / topo / dtg / dtw mean what they mean there.
-constexpr int MAX_TRACERS = 8;            // = SWMHD_MAX_TRACERS
-constexpr int TRACER_TILE_X = 64, TRACER_TILE_Y = 16;   // cells of a workgroup's tile (profiles/tracers/README.md)
+constexpr int MAX_TRACERS = 8;            // = SWMHD_MAX_TRACERS (the workgroup's tile: TRACER_TILE_X / _Y, launch_plan.hpp)
 template <typename T>
 struct TracerArgs {
     const T *q1, *q2, *h;

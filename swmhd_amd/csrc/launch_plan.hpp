@@ -1,4 +1,5 @@
-// Host-only launch planning of the fused tendency kernels: what a call will enqueue, decided as data before anything is launched.
+// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels and the tracer stage kernel: what a call will
+// enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
 #pragma once
@@ -81,9 +82,10 @@ inline int leave_room_64ths(int rows) {
 // 256 lanes = 1280, but 9 x 128 = 1152).  Rows per segment: the smallest whole number of rounds of resident workgroups
 // (wg_per_cu x CUs slots; ~5 % fewer with leave_room, so that another stream's kernels find room) whose segments are at most
 // 128 rows, but never shorter than ly_min rows.  fold_nt: the workgroup size whose kernel can fold its last strip (0: none); the strip
-// width is chosen first, and folding then only changes how many workgroups a segment row costs.
+// width is chosen first, and folding then only changes how many workgroups a segment row costs.  max_rounds: how many rounds are tried
+// before the segments fall back to 32 rows.
 inline MarchGeometry march_geometry(int Nx, int rows, int xh, const int *nts, const int *wgs, int ncand, int ly_min, bool leave_room,
-                                    int force_nt, int force_ly, int fold_nt = 0) {
+                                    int force_nt, int force_ly, int fold_nt = 0, int max_rounds = 64) {
     MarchGeometry g{};
     long best = -1;
     for (int k = 0; k < ncand; ++k) {
@@ -98,7 +100,7 @@ inline MarchGeometry march_geometry(int Nx, int rows, int xh, const int *nts, co
     int slots = device_cu_count() * g.wg_per_cu;
     if (leave_room) slots -= (slots * leave_room_64ths(rows)) / 64;
     int LY = 32;
-    for (int k = 1; k <= 64; ++k) {
+    for (int k = 1; k <= max_rounds; ++k) {
         const int ns = (2 * slots * k) / halves;
         if (ns < 1) continue;
         const int ly = (rows + ns - 1) / ns;
@@ -304,6 +306,104 @@ inline int tendency_launch_geometry(int Nx, int rows, int formulation, int elem_
     }
     out[7] = device_cu_count();
     return 0;
+}
+
+// ---- the plan of one Lorentz operator call ------------------------------------------------------------------------------------------
+// Marching operator kernels (lorentz_march_kernels.inc): 256 lanes, 2 (Jacobian form) / 3 (divergence form) halo lanes a side, 6 / 5
+// workgroups per CU.  Their geometry is march_geometry's with other parameters than the tendency kernels', because these kernels do
+// less: one workgroup size and no folded last strip (their kernels have neither variant), never a comm stream beside them (no
+// leave_room), and segments of at least 8 rows, not 6 (4-6 warm-up rows per segment; divergence form at 1024^2: 17 us at 8 rows, 23 us
+// at 16).  At most 16 rounds are tried, not 64: a grid taller than that takes 32-row segments.  SWMHD_OP_LY overrides the rows per
+// segment (tuning; read once).
+constexpr int OP_MARCH_NT = 256, OP_MARCH_MAX_ROUNDS = 16, OP_MARCH_LY_MIN = 8;
+constexpr int OP_JAC_TILE_Y = 16, OP_DIV_TILE_Y = 8;   // tile kernels: TILE_X columns x this many rows
+inline MarchGeometry lorentz_march_geometry(int Nx, int rows, bool divergence) {
+    static int ly_cache = 0;
+    const int nts[1] = {OP_MARCH_NT}, wgs[1] = {divergence ? 5 : 6};
+    return march_geometry(Nx, rows, divergence ? 3 : 2, nts, wgs, 1, OP_MARCH_LY_MIN, false, 0, env_knob("SWMHD_OP_LY", ly_cache), 0,
+                          OP_MARCH_MAX_ROUNDS);
+}
+// Cross-over of the tile and the marching kernels, fast builds: Jacobian form at ~2 Mcell; divergence form near 1000^2 (1024^2 17 vs
+// 20 us, 1448^2 27 vs 41 us).
+constexpr long OP_JAC_MARCH_MIN_CELLS = 2000000L, OP_DIV_MARCH_MIN_CELLS = 900000L;
+
+// What the decision depends on: the fields of OpArgs of the same names, plus the form and the build.
+struct OpPlanIn {
+    int Nx, Ny, j0, j1;
+    bool divergence, strict;
+    int kernel_variant, topo_x, topo_y, edge_cols;
+};
+enum class OpKernel { TILE, MARCH };
+struct OpLaunch {
+    OpKernel kernel;
+    int ntx, nty;         // tile kernel: tile columns, tile rows
+    MarchGeometry mg;     // marching kernel
+    int j0, j1;           // rows of this launch
+    int topo_x, topo_y;   // topology the kernel sees (0, 0 for the periodic body of a hybrid launch)
+    int edge_cols;
+};
+struct OpPlan {
+    int n = 0;
+    OpLaunch e[4];
+};
+
+// The launches of one operator call, in order (none: nothing to compute).  kernel_variant 1 / 2 force tile / marching; strict builds
+// have the tile kernels only.  The Jacobian form has no wall branches: its kernels read neither the topology nor edge_cols.
+inline OpPlan plan_lorentz(const OpPlanIn &a) {
+    OpPlan p;
+    const int rows = a.j1 - a.j0;
+    if (a.Nx <= 0 || rows <= 0) return p;
+    const bool bnd = a.divergence && is_bounded(a.topo_x, a.topo_y);
+    const bool big = (long)a.Nx * rows >= (a.divergence ? OP_DIV_MARCH_MIN_CELLS : OP_JAC_MARCH_MIN_CELLS);
+    auto launch = [&](OpKernel k, int j0, int j1, int topo_x, int topo_y, int edge_cols) {
+        OpLaunch l{};
+        l.kernel = k; l.j0 = j0; l.j1 = j1; l.topo_x = topo_x; l.topo_y = topo_y; l.edge_cols = edge_cols;
+        if (k == OpKernel::MARCH) l.mg = lorentz_march_geometry(a.Nx, j1 - j0, a.divergence);
+        else {
+            const int ty = a.divergence ? OP_DIV_TILE_Y : OP_JAC_TILE_Y;
+            l.ntx = a.divergence && edge_cols ? frame_tile_columns(a.Nx) : (a.Nx + TILE_X - 1) / TILE_X;
+            l.nty = (j1 - j0 + ty - 1) / ty;
+        }
+        p.e[p.n++] = l;
+    };
+    // (the marching divergence kernel implements the periodic branch only)
+    if (!a.strict && !bnd && (a.kernel_variant == 2 || (a.kernel_variant == 0 && big))) {
+        launch(OpKernel::MARCH, a.j0, a.j1, a.topo_x, a.topo_y, a.edge_cols);
+        return p;
+    }
+    // Large Bounded grids, divergence form: the marching kernel (periodic branch) over every row, then the tile kernel with the
+    // reference's wall branches over the frame of cells near the walls (bounded_frame, as in plan_tendency).  The two y strips are two
+    // launches: k_lorentz_divergence has one row range.
+    if (!a.strict && bnd && !a.edge_cols && a.kernel_variant == 0 && big && a.Nx >= 4 * TILE_X && a.Ny >= 48) {
+        const BoundedFrame f = bounded_frame(a.Ny, a.j0, a.j1, a.topo_x, a.topo_y);
+        launch(OpKernel::MARCH, a.j0, a.j1, 0, 0, 0);
+        if (f.s1 > f.s0) launch(OpKernel::TILE, f.s0, f.s1, a.topo_x, a.topo_y, 0);
+        if (f.n1 > f.n0) launch(OpKernel::TILE, f.n0, f.n1, a.topo_x, a.topo_y, 0);
+        if (f.x_walls) launch(OpKernel::TILE, a.j0, a.j1, a.topo_x, a.topo_y, 1);
+        return p;
+    }
+    launch(OpKernel::TILE, a.j0, a.j1, a.topo_x, a.topo_y, a.edge_cols);
+    return p;
+}
+
+// ---- the tiles of one tracer stage --------------------------------------------------------------------------------------------------
+constexpr int TRACER_TILE_X = 64, TRACER_TILE_Y = 16;   // cells of a workgroup's tile (profiles/tracers/README.md)
+struct TracerTiles {
+    int ntx, nty;
+    long blocks;      // ntx * nty * members: every tile of every member in one launch
+    bool none;        // nothing to compute: no rows, no tracers or no members
+    bool too_many;    // 2^31 blocks or more: beyond the grid of one launch
+};
+// members: 1 for a single grid
+inline TracerTiles tracer_tiles(int Nx, int rows, int K, int members) {
+    TracerTiles t{};
+    t.none = rows <= 0 || K <= 0 || members <= 0;
+    if (t.none) return t;
+    t.ntx = (Nx + TRACER_TILE_X - 1) / TRACER_TILE_X;
+    t.nty = (rows + TRACER_TILE_Y - 1) / TRACER_TILE_Y;
+    t.blocks = (long)t.ntx * t.nty * members;
+    t.too_many = t.blocks >= (1L << 31);
+    return t;
 }
 
 }  // namespace swmhd

@@ -4,3 +4,4 @@
 #define SWMHD_STRICT 0
 #define LAUNCH_SFX fast
 #include "lorentz_tile_kernels.inc"
+#include "lorentz_launch.inc"

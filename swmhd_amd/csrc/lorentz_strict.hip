@@ -5,3 +5,4 @@
 #define SWMHD_STRICT 1
 #define LAUNCH_SFX strict
 #include "lorentz_tile_kernels.inc"
+#include "lorentz_launch.inc"

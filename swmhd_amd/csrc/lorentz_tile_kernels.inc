@@ -1,5 +1,5 @@
 // Lorentz-force operator kernels, LDS-tiled form.  Included by lorentz_fast.hip and lorentz_strict.hip with
-// SWMHD_STRICT = 0 / 1 and LAUNCH_SFX = fast / strict.
+// SWMHD_STRICT = 0 / 1; kernels only (what is launched: plan_lorentz, launch_plan.hpp; the launchers: lorentz_launch.inc).
 //
 //   k_lorentz_jacobian    lorentz_force_func_x/y   jacobian_formulation/sw_mhd_jacobian_functions.jl:1-26
 //   k_lorentz_divergence  div_lorentz_x/y          divergence_formulation/sw_mhd_divergence_functions.jl:1-170
@@ -137,98 +137,7 @@ __global__ __launch_bounds__(TX *TYB) void k_lorentz_divergence(OpArgs<T> a, int
 
 #if !SWMHD_STRICT
 #include "lorentz_march_kernels.inc"
-
-// Rows per segment for the marching operator kernels: whole "waves" of resident workgroups (bpc per CU x 256 CUs), segments
-// of at most 128 rows (so that small grids still spread over the chip) and at least 8 (on mid-size grids filling the chip
-// matters more than the 4-6 warm-up rows per segment: divergence form at 1024^2 17 us at 8 rows, 23 us at 16).
-// SWMHD_OP_LY overrides (tuning).
-inline int march_rows_per_segment(int rows, int nstrips, int bpc) {
-    static int ly_cache = 0;
-    if (const int v = env_knob("SWMHD_OP_LY", ly_cache)) return v;
-    int LY = 32;
-    for (int k = 1; k <= 16; ++k) {
-        const int ns = (device_cu_count() * bpc * k) / nstrips;
-        if (ns < 1) continue;
-        const int ly = (rows + ns - 1) / ns;
-        if (ly <= 128) { LY = ly < 8 ? 8 : ly; break; }
-    }
-    return LY;
-}
 #endif
 
 }  // namespace
-
-#define LAUNCH_NAME_(base, sfx) base##sfx
-#define LAUNCH_NAME(base, sfx) LAUNCH_NAME_(base, sfx)
-
-template <typename T>
-hipError_t LAUNCH_NAME(launch_lorentz_jacobian_, LAUNCH_SFX)(const OpArgs<T> &a, hipStream_t s) {
-    constexpr int TX = 64, TYB = 4, RY = 4;
-    int ntx = (a.Nx + TX - 1) / TX, nty = (a.j1 - a.j0 + TYB * RY - 1) / (TYB * RY);
-    if (ntx <= 0 || nty <= 0) return hipSuccess;
-#if !SWMHD_STRICT
-    if (a.kernel_variant == 2 || (a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 2000000L)) {
-        // (a wavefront-shuffle variant -- one wave per workgroup, x neighbours by DPP lane shifts, no LDS -- measured 10-24 % slower and
-        // was removed, DESIGN.md 4.1)
-        // (fp32: a packed two-columns-per-lane variant was measured and dropped -- 117.7 vs 116.0 us at 16384 x 2048; with the hardware
-        // reciprocal the unpacked kernel is HBM-bound at the fp64 kernel's rate, 4.6 TB/s.  DESIGN.md 4.1)
-        constexpr int NT = 256, PF = 2, TXO = NT - 4;   // swept NT in {64,128,256,512} x PF in {1..4} on MI355X: all within 8 %
-        const int rows = a.j1 - a.j0, nstrips = (a.Nx + TXO - 1) / TXO;
-        const int LY = march_rows_per_segment(rows, nstrips, 6), nseg = (rows + LY - 1) / LY;
-        hipLaunchKernelGGL((k_lorentz_jacobian_march<T, NT, PF>), dim3(nstrips * nseg), dim3(NT), 0, s, a, nstrips, nseg, LY);
-        return hipGetLastError();
-    }
-#endif
-    hipLaunchKernelGGL((k_lorentz_jacobian<T, TX, TYB, RY>), dim3(ntx * nty), dim3(TX, TYB), 0, s, a, ntx, nty);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)(const OpArgs<T> &a, hipStream_t s) {
-    constexpr int TX = 64, TYB = 4, RY = 2;
-    int ntx = (a.Nx + TX - 1) / TX, nty = (a.j1 - a.j0 + TYB * RY - 1) / (TYB * RY);
-    if (ntx <= 0 || nty <= 0) return hipSuccess;
-#if !SWMHD_STRICT
-    // (cross-over with the tile kernel near 1000^2: 1024^2 17 vs 20 us, 1448^2 27 vs 41 us; the Jacobian form's is at ~2 Mcell)
-    if ((a.kernel_variant == 2 || (a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 900000L)) &&
-        !is_bounded(a.topo_x, a.topo_y)) {   // the marching kernel implements the periodic branch only
-        constexpr int NT = 256, PF = 2, TXO = NT - 6;
-        const int rows = a.j1 - a.j0, nstrips = (a.Nx + TXO - 1) / TXO;
-        const int LY = march_rows_per_segment(rows, nstrips, 5), nseg = (rows + LY - 1) / LY;
-        hipLaunchKernelGGL((k_lorentz_divergence_march<T, NT, PF>), dim3(nstrips * nseg), dim3(NT), 0, s, a, nstrips, nseg, LY);
-        return hipGetLastError();
-    }
-    // Large Bounded grids: the marching kernel (periodic branch) over every row, then the LDS-tiled kernel with the reference's wall
-    // branches over the frame of cells near the walls (bounded_frame, launch_plan.hpp: the frame of the fused tendency kernels' hybrid
-    // launch); the two y strips are two launches here
-    if (is_bounded(a.topo_x, a.topo_y) && !a.edge_cols && a.kernel_variant == 0 && (long)a.Nx * (a.j1 - a.j0) >= 900000L && a.Nx >= 4 * TX &&
-        a.Ny >= 48) {
-        const BoundedFrame fr = bounded_frame(a.Ny, a.j0, a.j1, a.topo_x, a.topo_y);
-        OpArgs<T> p = a;
-        p.topo_x = p.topo_y = 0;
-        hipError_t e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(p, s);
-        if (e != hipSuccess) return e;
-        OpArgs<T> f = a;
-        f.kernel_variant = 1;
-        f.j0 = fr.s0; f.j1 = fr.s1;
-        if (f.j1 > f.j0 && (e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
-        f.j0 = fr.n0; f.j1 = fr.n1;
-        if (f.j1 > f.j0 && (e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
-        if (fr.x_walls) {
-            f.j0 = a.j0; f.j1 = a.j1; f.edge_cols = 1;
-            if ((e = LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<T>(f, s)) != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-#endif
-    if (a.edge_cols) ntx = frame_tile_columns(a.Nx);
-    hipLaunchKernelGGL((k_lorentz_divergence<T, TX, TYB, RY>), dim3(ntx * nty), dim3(TX, TYB), 0, s, a, ntx, nty);
-    return hipGetLastError();
-}
-
-template hipError_t LAUNCH_NAME(launch_lorentz_jacobian_, LAUNCH_SFX)<double>(const OpArgs<double> &, hipStream_t);
-template hipError_t LAUNCH_NAME(launch_lorentz_jacobian_, LAUNCH_SFX)<float>(const OpArgs<float> &, hipStream_t);
-template hipError_t LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<double>(const OpArgs<double> &, hipStream_t);
-template hipError_t LAUNCH_NAME(launch_lorentz_divergence_, LAUNCH_SFX)<float>(const OpArgs<float> &, hipStream_t);
-
 }  // namespace swmhd

@@ -187,48 +187,46 @@ __global__ __launch_bounds__(TX *TYB) void k_tracers_tile(TracerTileArgs<T, ENS,
 #define LAUNCH_NAME_(base, sfx) base##sfx
 #define LAUNCH_NAME(base, sfx) LAUNCH_NAME_(base, sfx)
 
+
+// The stage kernel over the tiles of tracer_tiles (launch_plan.hpp): one grid, or (ENS) every tile of every member in one launch, the
+// member folded into blockIdx.x.  Ensemble members are periodic.
+template <typename T, bool ENS = false, bool PAR = false>
+static hipError_t launch_tracer_tiles(const TracerTileArgs<T, ENS, PAR> &a, int formulation, hipStream_t s) {
+    constexpr int TX = TRACER_TILE_X, TYB = 4, RY = TRACER_TILE_Y / TYB;
+    int members = 1;
+    if constexpr (ENS) members = a.members;
+    const TracerTiles t = tracer_tiles(a.Nx, a.j1 - a.j0, a.K, members);
+    if (t.none) return hipSuccess;
+    const bool bnd = is_bounded(a.topo_x, a.topo_y);
+    if (ENS && bnd) return hipErrorInvalidValue;
+    if (t.too_many) return hipErrorInvalidConfiguration;
+    void (*k)(TracerTileArgs<T, ENS, PAR>, int, int) = nullptr;
+    if (formulation == 1) {
+        if constexpr (!ENS) { if (bnd) k = k_tracers_tile<T, 1, true, TX, TYB, RY>; }
+        if (!k) k = k_tracers_tile<T, 1, false, TX, TYB, RY, ENS, PAR>;
+    } else if (formulation == 0) {
+        if constexpr (!ENS) { if (bnd) k = k_tracers_tile<T, 0, true, TX, TYB, RY>; }
+        if (!k) k = k_tracers_tile<T, 0, false, TX, TYB, RY, ENS, PAR>;
+    } else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3((unsigned)t.blocks), dim3(TX, TYB), 0, s, a, t.ntx, t.nty);
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t LAUNCH_NAME(launch_tracers_, LAUNCH_SFX)(const TracerArgs<T> &a, int formulation, hipStream_t s) {
-    constexpr int TX = TRACER_TILE_X, TYB = 4, RY = TRACER_TILE_Y / TYB;
-    if (a.j1 <= a.j0 || a.K <= 0) return hipSuccess;
-    const int ntx = (a.Nx + TX - 1) / TX, nty = (a.j1 - a.j0 + TRACER_TILE_Y - 1) / TRACER_TILE_Y;
-    const dim3 grid(ntx * nty), block(TX, TYB);
-    const bool bnd = is_bounded(a.topo_x, a.topo_y);
-    if (formulation == 1) {
-        if (bnd) hipLaunchKernelGGL((k_tracers_tile<T, 1, true, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-        else hipLaunchKernelGGL((k_tracers_tile<T, 1, false, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-    } else if (formulation == 0) {
-        if (bnd) hipLaunchKernelGGL((k_tracers_tile<T, 0, true, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-        else hipLaunchKernelGGL((k_tracers_tile<T, 0, false, TX, TYB, RY>), grid, block, 0, s, a, ntx, nty);
-    } else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return launch_tracer_tiles<T>(a, formulation, s);
 }
 template hipError_t LAUNCH_NAME(launch_tracers_, LAUNCH_SFX)<double>(const TracerArgs<double> &, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_tracers_, LAUNCH_SFX)<float>(const TracerArgs<float> &, int, hipStream_t);
 
-// Ensemble stage: the same 64 x 16 tile over every tile of every member, all rows, one launch (periodic members only).
-template <typename T, bool PAR>
-static hipError_t launch_tracers_ensemble_stage(const TracerTileArgs<T, true, PAR> &a, int formulation, hipStream_t s) {
-    constexpr int TX = TRACER_TILE_X, TYB = 4, RY = TRACER_TILE_Y / TYB;
-    if (a.j1 <= a.j0 || a.K <= 0 || a.members <= 0) return hipSuccess;
-    if (is_bounded(a.topo_x, a.topo_y)) return hipErrorInvalidValue;
-    const int ntx = (a.Nx + TX - 1) / TX, nty = (a.j1 - a.j0 + TRACER_TILE_Y - 1) / TRACER_TILE_Y;
-    const long blocks = (long)ntx * nty * a.members;
-    if (blocks >= (1L << 31)) return hipErrorInvalidConfiguration;
-    const dim3 grid((unsigned)blocks), block(TX, TYB);
-    if (formulation == 1) hipLaunchKernelGGL((k_tracers_tile<T, 1, false, TX, TYB, RY, true, PAR>), grid, block, 0, s, a, ntx, nty);
-    else if (formulation == 0) hipLaunchKernelGGL((k_tracers_tile<T, 0, false, TX, TYB, RY, true, PAR>), grid, block, 0, s, a, ntx, nty);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
 template <typename T>
 hipError_t LAUNCH_NAME(launch_tracers_ensemble_, LAUNCH_SFX)(const EnsTracerArgs<T> &a, int formulation, hipStream_t s) {
-    return launch_tracers_ensemble_stage<T, false>(a, formulation, s);
+    return launch_tracer_tiles<T, true>(a, formulation, s);
 }
 template <typename T>
 hipError_t LAUNCH_NAME(launch_tracers_ensemble_params_, LAUNCH_SFX)(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s) {
     if (!a.params) return hipErrorInvalidValue;
-    return launch_tracers_ensemble_stage<T, true>(a, formulation, s);
+    return launch_tracer_tiles<T, true, true>(a, formulation, s);
 }
 template hipError_t LAUNCH_NAME(launch_tracers_ensemble_, LAUNCH_SFX)<double>(const EnsTracerArgs<double> &, int, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_tracers_ensemble_, LAUNCH_SFX)<float>(const EnsTracerArgs<float> &, int, hipStream_t);

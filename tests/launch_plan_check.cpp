@@ -1,9 +1,11 @@
-// Host program: builds tendency launch plans (swmhd_amd/csrc/launch_plan.hpp) and checks the dispatch sequence of each case against
-// what the launcher enqueued before the plan existed (read off that launcher; the same cases were traced on an MI355X,
-// profiles/launch_plan/).  Launches nothing and allocates no device memory; without a device the CU count is taken as 256, which is the
-// MI355X's, so the numbers hold either way.  Compiled and run by tests/test_launch_plan_cpu.py with the SWMHD_* knobs unset.
+// Host program: builds the launch plans of the tendency, Lorentz operator and tracer kernels (swmhd_amd/csrc/launch_plan.hpp) and
+// checks the dispatch sequence of each case against what the launchers enqueued before the plans existed (read off those launchers; the
+// same cases were traced on an MI355X, profiles/launch_plan/ and profiles/op_launch_plan/).  Launches nothing and allocates no device
+// memory; without a device the CU count is taken as 256, which is the MI355X's, so the numbers hold either way.  Compiled and run by
+// tests/test_launch_plan_cpu.py with the SWMHD_* knobs unset, and once more as `launch_plan_check op_ly 5` with SWMHD_OP_LY=5.
 #include "launch_plan.hpp"
 #include <stdio.h>
+#include <string.h>
 
 using namespace swmhd;
 using K = TendKernel;
@@ -230,14 +232,196 @@ static void query() {
     CHECK(tendency_launch_geometry(4096, 4096, 1, 4, false, 0, 0, 1, o) == 0 && o[0] == 3 && o[2] == 9 && o[6] == 2);
 }
 
-int main() {
+// ---- Lorentz operators (plan_lorentz) ------------------------------------------------------------------------------------------------
+// an operator call on an Nx x Ny grid, rows [0, Ny), fast build, kernel by size, periodic
+static OpPlanIn op(int Nx, int Ny, bool divergence, int topo_x = 0, int topo_y = 0) {
+    OpPlanIn a{};
+    a.Nx = Nx; a.Ny = Ny; a.j1 = Ny; a.divergence = divergence; a.topo_x = topo_x; a.topo_y = topo_y;
+    return a;
+}
+// a marching launch: 256 lanes, no fold, 6 (Jacobian) / 5 (divergence) workgroups per CU
+static bool op_march_is(const OpLaunch &l, int nstrips, int nseg, int LY, int wg) {
+    return l.kernel == OpKernel::MARCH && l.mg.nt == 256 && l.mg.nstrips == nstrips && l.mg.nseg == nseg && l.mg.LY == LY &&
+           l.mg.wg_per_cu == wg && l.mg.fold == 0 && l.mg.blocks() == nstrips * nseg;
+}
+static bool op_tile_is(const OpLaunch &l, int ntx, int nty) { return l.kernel == OpKernel::TILE && l.ntx == ntx && l.nty == nty; }
+static bool op_args_are(const OpLaunch &l, int j0, int j1, int tx, int ty, int edge) {
+    return l.j0 == j0 && l.j1 == j1 && l.topo_x == tx && l.topo_y == ty && l.edge_cols == edge;
+}
+// the wall tile kernel alone, over the caller's rows with the caller's topology
+static bool wall_tile_alone(const OpPlanIn &a, int ntx) {
+    const OpPlan p = plan_lorentz(a);
+    return p.n == 1 && op_tile_is(p.e[0], ntx, (a.j1 - a.j0 + 7) / 8) && op_args_are(p.e[0], a.j0, a.j1, a.topo_x, a.topo_y, a.edge_cols);
+}
+
+static void operators_periodic() {
+    OpPlan p = plan_lorentz(op(4096, 4096, false));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 17, 90, 46, 6) && op_args_are(p.e[0], 0, 4096, 0, 0, 0));
+    p = plan_lorentz(op(4096, 4096, true));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 17, 75, 55, 5) && op_args_are(p.e[0], 0, 4096, 0, 0, 0));
+    p = plan_lorentz(op(16384, 2048, false));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 66, 23, 90, 6));
+    p = plan_lorentz(op(16384, 2048, true));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 66, 19, 108, 5));
+    // the Jacobian form's cross-over, 2 000 000 cells: 64 x 16 tiles below it
+    p = plan_lorentz(op(1415, 1414, false));   // 2 000 810
+    CHECK(p.n == 1 && op_march_is(p.e[0], 6, 177, 8, 6));
+    p = plan_lorentz(op(1414, 1414, false));   // 1 999 396
+    CHECK(p.n == 1 && op_tile_is(p.e[0], 23, 89) && op_args_are(p.e[0], 0, 1414, 0, 0, 0));
+    // the divergence form's, 900 000 cells: 64 x 8 tiles below it
+    p = plan_lorentz(op(1000, 900, true));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 4, 113, 8, 5));
+    p = plan_lorentz(op(999, 900, true));
+    CHECK(p.n == 1 && op_tile_is(p.e[0], 16, 113));
+    // the cells counted are those of the row range
+    OpPlanIn r = op(4096, 4096, false);
+    r.j0 = 100; r.j1 = 588;   // 488 rows: 1 998 848 cells
+    p = plan_lorentz(r);
+    CHECK(p.n == 1 && op_tile_is(p.e[0], 64, 31) && op_args_are(p.e[0], 100, 588, 0, 0, 0));
+    r.j1 = 589;               // 2 002 944: one round of 90 segments, 6 rows each, raised to the minimum of 8
+    p = plan_lorentz(r);
+    CHECK(p.n == 1 && op_march_is(p.e[0], 17, 62, 8, 6) && op_args_are(p.e[0], 100, 589, 0, 0, 0));
+    // forced either way; strict builds have the tile kernels only
+    for (int div = 0; div <= 1; ++div) {
+        OpPlanIn f = op(4096, 4096, div != 0);
+        f.kernel_variant = 1;
+        p = plan_lorentz(f);
+        CHECK(p.n == 1 && op_tile_is(p.e[0], 64, div ? 512 : 256));
+        f.kernel_variant = 0;
+        f.strict = true;
+        p = plan_lorentz(f);
+        CHECK(p.n == 1 && op_tile_is(p.e[0], 64, div ? 512 : 256));
+        f.kernel_variant = 2;
+        CHECK(plan_lorentz(f).n == 1 && plan_lorentz(f).e[0].kernel == OpKernel::TILE);
+        OpPlanIn s = op(128, 128, div != 0);
+        s.kernel_variant = 2;   // 1 strip, 1536 | 1280 slots: 128 segments of 1 row, raised to 8
+        p = plan_lorentz(s);
+        CHECK(p.n == 1 && op_march_is(p.e[0], 1, 16, 8, div ? 5 : 6));
+        s.kernel_variant = 0;
+        p = plan_lorentz(s);
+        CHECK(p.n == 1 && op_tile_is(p.e[0], 2, div ? 16 : 8));
+    }
+    // the Jacobian form has no walls: topology and edge_cols pass through and change nothing
+    OpPlanIn j = op(4096, 4096, false, 1, 1);
+    j.edge_cols = 1;
+    p = plan_lorentz(j);
+    CHECK(p.n == 1 && op_march_is(p.e[0], 17, 90, 46, 6) && op_args_are(p.e[0], 0, 4096, 1, 1, 1));
+    j.kernel_variant = 1;
+    p = plan_lorentz(j);
+    CHECK(p.n == 1 && op_tile_is(p.e[0], 64, 256) && op_args_are(p.e[0], 0, 4096, 1, 1, 1));
+    // at most 16 rounds of resident workgroups are tried: 2 strips, 1536 slots -> 768 k segments in round k.  1 600 000 rows need
+    // 131 rows per segment in round 16 and 123 in round 17, so the fall-back of 32 rows holds; 1 572 864 = 16 x 768 x 128 still fits
+    p = plan_lorentz(op(256, 1600000, false));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 2, 50000, 32, 6));
+    p = plan_lorentz(op(256, 1572864, false));
+    CHECK(p.n == 1 && op_march_is(p.e[0], 2, 12288, 128, 6));
+    // nothing to do
+    OpPlanIn e = op(4096, 4096, true);
+    e.j0 = e.j1 = 7;
+    CHECK(plan_lorentz(e).n == 0);
+    e.j0 = 9;
+    CHECK(plan_lorentz(e).n == 0);
+    CHECK(plan_lorentz(op(0, 4096, true)).n == 0 && plan_lorentz(op(0, 4096, false)).n == 0 && plan_lorentz(op(64, 0, false)).n == 0);
+}
+
+static void operators_bounded() {
+    const int B = 1;
+    // the hybrid: periodic body, south strip, north strip, x frame (1300 = 20 x 64 + 20: two frame tile columns)
+    OpPlan p = plan_lorentz(op(1300, 800, true, B, B));
+    CHECK(p.n == 4);
+    CHECK(op_march_is(p.e[0], 6, 100, 8, 5) && op_args_are(p.e[0], 0, 800, 0, 0, 0));
+    CHECK(op_tile_is(p.e[1], 21, 1) && op_args_are(p.e[1], 0, 8, B, B, 0));
+    CHECK(op_tile_is(p.e[2], 21, 1) && op_args_are(p.e[2], 792, 800, B, B, 0));
+    CHECK(op_tile_is(p.e[3], 2, 100) && op_args_are(p.e[3], 0, 800, B, B, 1));
+    p = plan_lorentz(op(1300, 800, true, 0, B));
+    CHECK(p.n == 3 && op_march_is(p.e[0], 6, 100, 8, 5) && op_args_are(p.e[0], 0, 800, 0, 0, 0));
+    CHECK(op_tile_is(p.e[1], 21, 1) && op_args_are(p.e[1], 0, 8, 0, B, 0) && op_tile_is(p.e[2], 21, 1) && op_args_are(p.e[2], 792, 800, 0, B, 0));
+    p = plan_lorentz(op(1300, 800, true, B, 0));
+    CHECK(p.n == 2 && op_march_is(p.e[0], 6, 100, 8, 5) && op_args_are(p.e[0], 0, 800, 0, 0, 0));
+    CHECK(op_tile_is(p.e[1], 2, 100) && op_args_are(p.e[1], 0, 800, B, 0, 1));
+    // a row range that ends below the north strip, on a grid whose last tile column is 4 wide: no north launch, three frame columns
+    OpPlanIn a = op(1284, 800, true, B, B);
+    a.j0 = 5; a.j1 = 790;
+    p = plan_lorentz(a);
+    CHECK(p.n == 3 && op_march_is(p.e[0], 6, 99, 8, 5) && op_args_are(p.e[0], 5, 790, 0, 0, 0));
+    CHECK(op_tile_is(p.e[1], 21, 1) && op_args_are(p.e[1], 5, 8, B, B, 0));
+    CHECK(op_tile_is(p.e[2], 3, 99) && op_args_are(p.e[2], 5, 790, B, B, 1));
+    // at the edge of all three thresholds at once (>= 900 000 cells, Nx >= 256, Ny >= 48): 18752 x 48 = 900 096 cells
+    p = plan_lorentz(op(18752, 48, true, B, B));
+    CHECK(p.n == 4 && op_march_is(p.e[0], 76, 6, 8, 5) && op_tile_is(p.e[1], 293, 1) && op_args_are(p.e[1], 0, 8, B, B, 0) &&
+          op_tile_is(p.e[2], 293, 1) && op_args_are(p.e[2], 40, 48, B, B, 0) && op_tile_is(p.e[3], 2, 6) && op_args_are(p.e[3], 0, 48, B, B, 1));
+    p = plan_lorentz(op(18750, 48, true, B, B));              // 900 000 cells exactly
+    CHECK(p.n == 4 && op_march_is(p.e[0], 75, 6, 8, 5) && op_tile_is(p.e[1], 293, 1) && op_tile_is(p.e[3], 2, 6));
+    CHECK(plan_lorentz(op(18751, 48, true, B, B)).n == 4);    // 900 048
+    CHECK(wall_tile_alone(op(18749, 48, true, B, B), 293));   // 899 952 cells
+    CHECK(wall_tile_alone(op(18752, 47, true, B, B), 293));   // Ny < 48 (881 344 cells; 19149 x 47 = 900 003 below)
+    CHECK(wall_tile_alone(op(19149, 47, true, B, B), 300));
+    CHECK(wall_tile_alone(op(255, 4096, true, B, B), 4));     // Nx < 256 (1 044 480 cells)
+    CHECK(wall_tile_alone(op(255, 4096, true, 0, B), 4) && wall_tile_alone(op(255, 4096, true, B, 0), 4));
+    // forced, strict or with a caller's own frame: the wall tile kernel alone
+    a = op(1300, 800, true, B, B);
+    a.kernel_variant = 1;
+    CHECK(wall_tile_alone(a, 21));
+    a.kernel_variant = 2;   // (the marching kernel has no walls)
+    CHECK(wall_tile_alone(a, 21));
+    a.kernel_variant = 0;
+    a.strict = true;
+    CHECK(wall_tile_alone(a, 21));
+    a.strict = false;
+    a.edge_cols = 1;
+    CHECK(wall_tile_alone(a, 2));
+    a.Nx = 1284;
+    CHECK(wall_tile_alone(a, 3));
+    // a y-slab's open sides count as Bounded and have no frame rows
+    p = plan_lorentz(op(1300, 800, true, 0, B | TOPO_OPEN_SOUTH));
+    CHECK(p.n == 2 && p.e[0].kernel == OpKernel::MARCH && op_tile_is(p.e[1], 21, 1) && op_args_are(p.e[1], 792, 800, 0, B | TOPO_OPEN_SOUTH, 0));
+}
+
+// SWMHD_OP_LY = ly (a process of its own: the knob is read once): that many rows per segment, even below the minimum of 8
+static void operators_forced_ly(int ly) {
+    for (int div = 0; div <= 1; ++div) {
+        const OpPlan p = plan_lorentz(op(4096, 4096, div != 0));
+        CHECK(p.n == 1 && op_march_is(p.e[0], 17, (4096 + ly - 1) / ly, ly, div ? 5 : 6));
+    }
+}
+
+// ---- tracers (tracer_tiles) ------------------------------------------------------------------------------------------------------------
+static bool tiles_are(const TracerTiles &t, int ntx, int nty, long blocks) {
+    return !t.none && !t.too_many && t.ntx == ntx && t.nty == nty && t.blocks == blocks;
+}
+static void tracers() {
+    CHECK(TRACER_TILE_X == 64 && TRACER_TILE_Y == 16);
+    // one grid: both directions round up
+    CHECK(tiles_are(tracer_tiles(65, 17, 3, 1), 2, 2, 4));
+    CHECK(tiles_are(tracer_tiles(64, 16, 1, 1), 1, 1, 1));
+    CHECK(tiles_are(tracer_tiles(63, 15, 1, 1), 1, 1, 1));
+    CHECK(tiles_are(tracer_tiles(4096, 4095, 8, 1), 64, 256, 16384) && tiles_are(tracer_tiles(4096, 4097, 8, 1), 64, 257, 16448));
+    // an ensemble: the tiles of every member
+    CHECK(tiles_are(tracer_tiles(65, 17, 3, 3), 2, 2, 12));
+    CHECK(tiles_are(tracer_tiles(4096, 8192, 1, 65535), 64, 512, 2147450880L));
+    const TracerTiles big = tracer_tiles(4096, 8193, 1, 65535);   // 64 x 513 x 65535 = 2 151 645 120 >= 2^31
+    CHECK(!big.none && big.too_many && big.blocks == 2151645120L);
+    CHECK(tracer_tiles(64, 64, 1, 1 << 29).too_many && !tracer_tiles(64, 64, 1, (1 << 29) - 1).too_many);   // 4 tiles: 2^31 | 2^31 - 4
+    // nothing to do: no tracers, no rows, no members
+    CHECK(tracer_tiles(64, 64, 0, 4).none && tracer_tiles(64, 0, 2, 4).none && tracer_tiles(64, -3, 2, 1).none && tracer_tiles(64, 64, 2, 0).none);
+}
+
+int main(int argc, char **argv) {
     CHECK(device_cu_count() == 256);
+    if (argc == 3 && !strcmp(argv[1], "op_ly")) {
+        operators_forced_ly(atoi(argv[2]));
+        printf(failures ? "%d plan checks FAILED\n" : "launch plans OK\n", failures);
+        return failures ? 1 : 0;
+    }
     CHECK(is_bounded(1, 0) && is_bounded(0, 1) && is_bounded(0, 1 | TOPO_OPEN_SOUTH | TOPO_OPEN_NORTH) && !is_bounded(0, 0));
     periodic_4096();
     bounded_4096();
     ranges_and_sizes();
     ensembles();
     query();
+    operators_periodic();
+    operators_bounded();
+    tracers();
     printf(failures ? "%d plan checks FAILED\n" : "launch plans OK\n", failures);
     return failures ? 1 : 0;
 }

@@ -21,7 +21,7 @@ def _golden():
 
 
 def _clean_env(extra):
-    env = {k: v for k, v in os.environ.items() if not k.startswith("SWMHD_T_") and k not in ("SWMHD_RING_ROOM", "SWMHD_ENS_RY", "SWMHD_ENS_MAP")}
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SWMHD_T_") and k not in ("SWMHD_RING_ROOM", "SWMHD_ENS_RY", "SWMHD_ENS_MAP", "SWMHD_OP_LY")}
     env.update(extra)
     return env
 
@@ -54,7 +54,9 @@ def test_geometry_query_reproduces_recorded_table(swmhd, table):
 
 def test_plan_dispatch_sequences(tmp_path):
     """launch_plan_check.cpp as a host program: the plans of periodic stages in every RK3 stage form, Bounded hybrids with and without
-    open sides, two-range and empty-range launches, parents beyond 4 GiB, Bounded grids below the hybrid thresholds, ensembles."""
+    open sides, two-range and empty-range launches, parents beyond 4 GiB, Bounded grids below the hybrid thresholds, ensembles; the
+    plans of the Lorentz operators (cross-overs, the Bounded hybrid and its thresholds, the round cap) and the tiles of a tracer stage.
+    Then once more in a fresh process with SWMHD_OP_LY=5 (read once): 5 rows per segment, below the minimum of 8."""
     exe = str(tmp_path / "launch_plan_check")
     rocm = os.path.dirname(os.path.dirname(os.path.realpath(HIPCC)))
     cc = subprocess.run([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
@@ -63,16 +65,24 @@ def test_plan_dispatch_sequences(tmp_path):
     assert cc.returncode == 0, cc.stderr[-3000:]
     r = subprocess.run([exe], env=_clean_env({}), capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "launch plans OK" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
+    r = subprocess.run([exe, "op_ly", "5"], env=_clean_env({"SWMHD_OP_LY": "5"}), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "launch plans OK" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
 
 
 def test_launchers_do_not_reenter():
-    """The tendency launchers enqueue their plan: neither calls a tendency launcher, and "Bounded" has one definition."""
+    """The tendency and Lorentz launchers enqueue their plans: none calls a launcher of its family, the operators have no geometry
+    function of their own, and "Bounded" has one definition."""
     csrc = os.path.join(ROOT, "swmhd_amd", "csrc")
     launch = open(os.path.join(csrc, "tendency_launch.inc")).read()
     uses = [l for l in launch.splitlines() if "LAUNCH_NAME(launch_tendency_" in l]
     # two definitions (single grid, ensemble) and their four explicit instantiations: no call
     assert len(uses) == 6 and all(l.startswith(("hipError_t ", "template hipError_t ")) for l in uses), uses
+    lorentz = open(os.path.join(csrc, "lorentz_launch.inc")).read()
+    uses = [l for l in lorentz.splitlines() if "launch_lorentz_" in l]
+    # two definitions (Jacobian form, divergence form) and their four explicit instantiations: no call
+    assert len(uses) == 6 and all(l.startswith(("hipError_t LAUNCH_NAME(", "template hipError_t LAUNCH_NAME(")) for l in uses), uses
     text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".inc", ".hpp")))
+    assert "march_rows_per_segment" not in text
     for spelled in ("topo_x == 1 || a.topo_y", "topo_x == 1 || topo_y == 1"):
         assert spelled not in text
     assert text.count("topo_x == 1 || topo_y != 0") == 1

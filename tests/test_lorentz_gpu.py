@@ -233,6 +233,41 @@ def test_bounded_wall_branches_large_grid_hybrid_launch(swmhd, oracle, topo, dty
         assert np.array_equal(a[I][frame], t[I][frame])
 
 
+@pytest.mark.parametrize("topo", [("Bounded", "Bounded"), ("Bounded", "Periodic"), ("Periodic", "Bounded")])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_hybrid_launch_row_range_and_narrow_last_tile_column(swmhd, oracle, topo, dtype):
+    """The hybrid launch of a Bounded grid where three things happen at once: it runs (785 x 1284 cells), the last tile column is 4 cells
+    wide, so the x frame takes the last TWO tile columns (columns from 1216), and the row range (5, 790) cuts the south strip to rows
+    5-7 and removes the north strip (rows from 792).  Within the fast tolerance of the oracle on the rows asked for, nothing written
+    outside them, and bitwise the all-tile launch inside the frame."""
+    Nx, Ny, H, j0, j1 = 1284, 800, 3, 5, 790
+    A, h = Hh.random_case(Nx, Ny, H, H, 1284, dtype, periodic=False)
+    g = swmhd.RectilinearGrid(size=(Nx, Ny), x=(0, 0.37 * Nx), y=(0, 0.41 * Ny), halo=(H, H), topology=(topo[0], topo[1], "Flat"))
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    f = {"A": swmhd.Field(g, dtype=tdt, data=torch.from_numpy(A).cuda()), "h": swmhd.Field(g, dtype=tdt, data=torch.from_numpy(h).cuda())}
+    code = {"Periodic": oracle.PERIODIC, "Bounded": oracle.BOUNDED}
+    want = oracle.lorentz_divergence(A, h, Nx, Ny, H, H, g.dx, g.dy, topo=(code[topo[0]], code[topo[1]]), nthreads=8)
+    sentinel = -777.25
+    runs = {}
+    for kernel in ("auto", "tile"):
+        out = (swmhd.Field(g, dtype=tdt), swmhd.Field(g, dtype=tdt))
+        for o in out:
+            o.data.fill_(sentinel)
+        runs[kernel] = _run(swmhd, "divergence", g, f, out=out, strict=False, kernel=kernel, rows=(j0, j1))
+    rows = (slice(H + j0, H + j1), slice(H, H + Nx))
+    frame = np.zeros((j1 - j0, Nx), dtype=bool)
+    if topo[1] == "Bounded":
+        frame[:8 - j0] = True
+    if topo[0] == "Bounded":
+        frame[:, :64] = True; frame[:, 1216:] = True
+    for w, a, t in zip(want, runs["auto"], runs["tile"]):
+        assert np.abs(w[rows] - a[rows]).max() <= TOL[dtype] * np.abs(w[rows]).max()
+        outside = np.ones_like(a, dtype=bool)
+        outside[rows] = False
+        assert np.all(a[outside] == sentinel), "a launch of the hybrid wrote outside the requested rows / into halos"
+        assert np.array_equal(a[rows][frame], t[rows][frame])
+
+
 def test_error_codes_on_device_pointers(swmhd):
     g = swmhd.RectilinearGrid(size=(16, 16), x=(0, 1), y=(0, 1), halo=(2, 2))
     A, h = swmhd.Field(g), swmhd.Field(g)

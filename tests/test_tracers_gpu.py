@@ -1,7 +1,7 @@
 """GPU tests of the passive tracers: the stage kernel through the ABI (swmhd_tracers_rk3_*, k_tracers_tile) and
 ShallowWaterModel(tracers=...).
 
-The kernel's tile is TX x TY = 64 x 16 cells (common.hpp TRACER_TILE_X / _Y, mirrored in tracer_cases.TX / TY); the stage matrix runs
+The kernel's tile is TX x TY = 64 x 16 cells (launch_plan.hpp TRACER_TILE_X / _Y, mirrored in tracer_cases.TX / TY); the stage matrix runs
 Nx in {3, 7, TX - 1, TX, TX + 1, 2 TX + 1} against Ny in {3, 9, TY - 1, TY, TY + 1} on a diagonal plus corners.
 
 References: tracer_cases (the oracle's tendency of a centre field in the A slot, numpy's update; pinned on the CPU by

@@ -21,7 +21,7 @@ PERIODIC_GRIDS = [(20, 12, (P, P)), (7, 9, (P, P))]
 BOUNDED_GRIDS = [(13, 10, (P, B)), (13, 10, (B, P)), (13, 10, (B, B))]
 DX, DY = 0.11, 0.13
 SENTINEL = -555.5                   # exact in fp32
-# the tracer kernel's tile (common.hpp TRACER_TILE_X / _Y): the stage matrix straddles it
+# the tracer kernel's tile (launch_plan.hpp TRACER_TILE_X / _Y): the stage matrix straddles it
 TX, TY = 64, 16
 STAGE_SHAPES = [(3, 3), (7, 9), (TX - 1, TY - 1), (TX, TY), (TX + 1, TY + 1), (2 * TX + 1, 9), (3, TY + 1), (2 * TX + 1, TY),
                 (TX, 3), (7, TY - 1)]      # diagonal of Nx x Ny plus corners
