@@ -11,6 +11,9 @@ reference's (SWMHD_example.jl:47-61: time, iteration, max|u|, max|A|, min h, wal
 sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the fields incl. halos as .npy (the JLD2 writer's role, :80-84).
 --frames T collects the reference's output frames on the device (swmhd_amd.FieldTimeSeries: the fields (u, v, A, s) every T time units,
 :80-84, or those of --frame-fields out of u v h A s B_x B_y, as --frame-dtype f32|f64) and writes them to <out>/frames.npz at the end.
+--zonal-means T collects x-averaged profiles on the device (swmhd_amd.ZonalMeanTimeSeries: Oceananigans' Average(u, dims = 1) in an
+output writer; every T time units the float64 row means of --zonal-names out of u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA, one
+launch per sample and no frame) and writes them to <out>/zonal_means.npz at the end; in single, --amps and --channel --gradients runs.
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
 --dye adds one passive tracer c = tanh(y) to the run (ShallowWaterModel(tracers=("c",)): the reference's `tracers = (:A)` with a second
 name): its min / max join the progress line and the field goes into the --dump-every dumps.  With --amps, --coriolis, --gravity or
@@ -61,6 +64,8 @@ def main():
     ap.add_argument("--frames", type=float, default=0.0, help="model time between output frames (0 = none); written to <out>/frames.npz")
     ap.add_argument("--frame-fields", default="u,v,A,s", help="comma-separated fields of a frame: u v h A s B_x B_y")
     ap.add_argument("--frame-dtype", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--zonal-means", type=float, default=0.0, help="model time between zonal-mean samples (0 = none); written to <out>/zonal_means.npz")
+    ap.add_argument("--zonal-names", default="u,v,A,uv,B_xB_y,vA", help="comma-separated profiles: u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA")
     ap.add_argument("--dye", action="store_true", help="advect one passive tracer c = tanh(y) with the flow")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
@@ -79,6 +84,8 @@ def main():
     a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts))
     if a.dts and a.frames > 0:
         ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
+    if a.dts and a.zonal_means > 0:
+        ap.error("--zonal-means is a schedule in time units: not with a per-member time step (--dts)")
     if a.dye and a.channel:
         ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
     if a.amps or a.channel or a.sweep:
@@ -116,9 +123,12 @@ def main():
     report(0.0)
     e0 = rows[0][4]
     series, fevery = frame_writer(a, model, nsteps)
+    zonal, zevery = zonal_writer(a, model, nsteps)
     model.time_step(a.dt)
     if fevery == 1:
         series.write()
+    if zevery == 1:
+        zonal.write()
     model.capture_graph(a.dt)
     next_dump = a.dump_every
     t_start = time.perf_counter()
@@ -128,9 +138,13 @@ def main():
         n = min(a.every - model.iteration % a.every, nsteps - model.iteration)
         if fevery:
             n = min(n, fevery - model.iteration % fevery)
+        if zevery:
+            n = min(n, zevery - model.iteration % zevery)
         model.time_steps(n, a.dt)
         if fevery and model.iteration % fevery == 0:
             series.write(time=model.iteration * a.dt)         # one launch, no synchronisation
+        if zevery and model.iteration % zevery == 0:
+            zonal.write(time=model.iteration * a.dt)          # likewise
         if model.iteration % a.every != 0 and model.iteration != nsteps:
             continue
         model.synchronize()
@@ -144,6 +158,7 @@ def main():
     print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations, {N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); "
           f"energy drift abs(E - E0) * 100 = {abs(rows[-1][4] - e0) * 100:.4f}")
     save_frames(a, series)
+    save_zonal(a, zonal)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
@@ -168,6 +183,26 @@ def save_frames(a, series):
         os.makedirs(a.out, exist_ok=True)
         series.save(os.path.join(a.out, "frames.npz"))
         print(f"{len(series)} frames of ({', '.join(series.names)}) -> {os.path.join(a.out, 'frames.npz')}")
+
+
+def zonal_writer(a, model, nsteps):
+    """--zonal-means: (ZonalMeanTimeSeries, steps between samples), or (None, 0)"""
+    if a.zonal_means <= 0:
+        return None, 0
+    import swmhd_amd as S
+    sched = S.TimeInterval(a.zonal_means)
+    every = sched.steps(a.dt)
+    zonal = S.ZonalMeanTimeSeries(model, names=tuple(n.strip() for n in a.zonal_names.split(",") if n.strip()), schedule=sched,
+                                  capacity=nsteps // every + 1)
+    zonal.write()           # the initial state, as the frames
+    return zonal, every
+
+
+def save_zonal(a, zonal):
+    if zonal is not None:
+        os.makedirs(a.out, exist_ok=True)
+        zonal.save(os.path.join(a.out, "zonal_means.npz"))
+        print(f"{len(zonal)} samples of the zonal means ({', '.join(zonal.names)}) -> {os.path.join(a.out, 'zonal_means.npz')}")
 
 
 def run_ensemble(a):
@@ -227,9 +262,12 @@ def run_ensemble(a):
     report(0.0)
     e0 = [r[-1] for r in rows]
     series, fevery = frame_writer(a, ens, nsteps)
+    zonal, zevery = zonal_writer(a, ens, nsteps)
     ens.time_step(dt)
     if fevery == 1:
         series.write()
+    if zevery == 1:
+        zonal.write()
     ens.capture_graph(dt)
     t_start = time.perf_counter()
     t0 = None
@@ -238,9 +276,13 @@ def run_ensemble(a):
         n = min(a.every - ens.iteration % a.every, nsteps - ens.iteration)
         if fevery:
             n = min(n, fevery - ens.iteration % fevery)
+        if zevery:
+            n = min(n, zevery - ens.iteration % zevery)
         ens.time_steps(n, dt)
         if fevery and ens.iteration % fevery == 0:
             series.write(time=ens.iteration * a.dt)           # all members in one launch, no synchronisation
+        if zevery and ens.iteration % zevery == 0:
+            zonal.write(time=ens.iteration * a.dt)            # likewise
         if ens.iteration % a.every != 0 and ens.iteration != nsteps:
             continue
         ens.synchronize()
@@ -251,6 +293,7 @@ def run_ensemble(a):
     print(f"Simulation took {total:.2f} s to finish running ({nsteps} iterations of {len(amps)} members, "
           f"{len(amps) * N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); energy drift abs(E - E0) * 100 per member = {drift}")
     save_frames(a, series)
+    save_zonal(a, zonal)
     if a.dye:
         os.makedirs(a.out, exist_ok=True)
         np.savez(os.path.join(a.out, "tracers.npz"), c=ens.tracers["c"][(slice(None),) + grid.interior].cpu().numpy(),

@@ -757,4 +757,8 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #ifdef __cplusplus
 }
 #endif
+
+/* zonal means (swmhd_zonal_means_*, swmhd_ensemble_zonal_means_*, SWMHD_ZM_*): x-averaged profiles of the output fields and their products */
+#include "swmhd_zonal.h"
+
 #endif /* SWMHD_H */

@@ -23,6 +23,8 @@ HALO_X, HALO_Y = 1, 2
 DIAG_NOUT, DIAG_WORKSPACE = 7, 1024 * 7
 # SWMHD_OUT_*: the output fields of swmhd_output_fields_*, by the names of the reference's writer, in bit (= frame) order
 OUT_BITS = {"u": 1, "v": 2, "h": 4, "A": 8, "s": 16, "B_x": 32, "B_y": 64}
+# SWMHD_ZM_*: the profiles of swmhd_zonal_means_*, in bit (= profile) order: the seven fields of OUT_BITS, then the second moments
+ZM_BITS = {**OUT_BITS, "uu": 128, "vv": 256, "uv": 512, "B_xB_x": 1024, "B_yB_y": 2048, "B_xB_y": 4096, "vA": 8192}
 ENSEMBLE_MAX_MEMBERS = 65535
 ENSEMBLE_NPARAMS = 3    # SWMHD_ENSEMBLE_NPARAMS: (g, f, dt) per member in the table of the swmhd_ensemble_*_params calls
 MAX_TRACERS = 8         # SWMHD_MAX_TRACERS: passive tracers per swmhd_tracers_rk3_* launch
@@ -157,6 +159,12 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_output_fields_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, i, i, i, p, i, i64, i64, i64, i, p]
         f.restype = i
+        f = getattr(lib, f"swmhd_zonal_means_{sfx}")
+        f.argtypes = [p, p, p, p, i, i, i, i, i64, ft, ft, i, i, i, i, p, i64, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_zonal_means_{sfx}")
+        f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, i, i, i, p, i64, i64, i, p]
+        f.restype = i
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
     lib.swmhd_tendency_launch_geometry.restype = i
     lib.swmhd_ring_available.argtypes = [C.c_char_p]
@@ -193,6 +201,8 @@ EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", 
         "ensemble_tracers_rk3_params")] + [
     "swmhd_ring_" + name for name in ("available", "unique_id", "create", "create_loopback", "destroy", "last_error", "comm_stream", "join", "time_launches",
                                       "launch_times")]
+# the symbols include/swmhd_zonal.h declares (swmhd.h includes it; tests/test_zonal_abi.py checks the .so exports each of them)
+ZONAL_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("zonal_means", "ensemble_zonal_means")]
 RING_ID_BYTES = 128
 
 

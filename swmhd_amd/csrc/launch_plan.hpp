@@ -1,5 +1,5 @@
-// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels and the tracer stage kernel: what a call will
-// enqueue, decided as data before anything is launched.
+// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel and the zonal-mean
+// kernel: what a call will enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
 #pragma once
@@ -404,6 +404,42 @@ inline TracerTiles tracer_tiles(int Nx, int rows, int K, int members) {
     t.blocks = (long)t.ntx * t.nty * members;
     t.too_many = t.blocks >= (1L << 31);
     return t;
+}
+
+// ---- the rows of one zonal-mean call (zonal.hip) -------------------------------------------------------------------------------------
+// One wavefront reduces one row: lane l takes the 4-cell chunks l, l + 64, l + 128, ... of the row (ZONAL_TRIP = 256 cells per trip of
+// the wave), adds their terms serially in x order, and a 6-level butterfly adds the 64 lane sums.  Four rows per 256-thread workgroup,
+// the workgroups of member m after those of member m - 1 in blockIdx.x.  The summation order is zonal_depth's: a function of Nx alone.
+constexpr int ZONAL_NT = 256, ZONAL_WAVE = 64, ZONAL_VEC = 4;
+constexpr int ZONAL_ROWS = ZONAL_NT / ZONAL_WAVE, ZONAL_TRIP = ZONAL_WAVE * ZONAL_VEC;
+struct ZonalPlan {
+    int rows_per_block;
+    long row_blocks;  // workgroups of one member
+    long blocks;      // row_blocks * members: every row of every member in one launch
+    bool none;        // nothing to compute: no rows or no members
+    bool too_many;    // 2^31 blocks or more: beyond the grid of one launch
+};
+// members: 1 for a single grid
+inline ZonalPlan zonal_plan(int rows, int members) {
+    ZonalPlan p{};
+    p.rows_per_block = ZONAL_ROWS;
+    p.none = rows <= 0 || members <= 0;
+    if (p.none) return p;
+    p.row_blocks = ((long)rows + ZONAL_ROWS - 1) / ZONAL_ROWS;
+    p.blocks = p.row_blocks * members;
+    p.too_many = p.blocks >= (1L << 31);
+    return p;
+}
+// Additions on the longest path from a term to the row sum: lane 0 has the most terms, 4 per full trip and min(4, cells left) of the
+// ragged one, added one after the other (terms - 1 additions); then one butterfly level per bit of (lanes with terms - 1) -- a level
+// whose partner lane has no term adds 0.0, which is exact.  The bound of tests/zonal_cases.py.
+inline int zonal_depth(int Nx) {
+    if (Nx <= 0) return 0;
+    const int rem = Nx % ZONAL_TRIP, terms0 = ZONAL_VEC * (Nx / ZONAL_TRIP) + (rem < ZONAL_VEC ? rem : ZONAL_VEC);
+    const int chunks = (Nx + ZONAL_VEC - 1) / ZONAL_VEC, lanes = chunks < ZONAL_WAVE ? chunks : ZONAL_WAVE;
+    int levels = 0;
+    while ((1 << levels) < lanes) ++levels;
+    return terms0 - 1 + levels;
 }
 
 }  // namespace swmhd

@@ -384,6 +384,13 @@ class ShallowWaterEnsemble:
         from .output import enqueue_frame
         return enqueue_frame(self, names, out, array_type)
 
+    # --- zonal means of all members in one launch (swmhd_ensemble_zonal_means_*) -------------------------------------
+    def zonal_means(self, names=("u", "v", "A"), out=None):
+        """ShallowWaterModel.zonal_means for every member: the float64 device tensor (members, len(names), Ny); member m of it is
+        bitwise member(m).zonal_means(...).  One launch, no host synchronisation."""
+        from .zonal import enqueue_zonal_means
+        return enqueue_zonal_means(self, names, out)
+
     # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
     def member(self, m):
         """A ShallowWaterModel holding a copy of member m (state and tracers with halos, their G-, the member's g, f, clock and

@@ -555,6 +555,18 @@ class ShallowWaterModel:
         from .output import enqueue_frame
         return enqueue_frame(self, names, out, array_type)
 
+    # --- zonal means (Oceananigans: Average(u, dims = 1)): one launch, no frame-sized buffer, no host synchronisation ----
+    def zonal_means(self, names=("u", "v", "A"), out=None):
+        """Enqueue the x-averaged profiles of the current state: the float64 device tensor (len(names), Ny), row j of profile k =
+        (sum over i = 1..Nx of term_k(i, j)) / Nx -- the frame fields u v h A s B_x B_y and the second moments uu vv uv B_xB_x B_yB_y
+        B_xB_y vA (swmhd_zonal_means_* in include/swmhd_zonal.h; uv is the Reynolds stress, B_xB_y the Maxwell stress, -d(vA)/dy the whole
+        right-hand side of the mean potential).  The points averaged are the frame's, on Bounded directions too.  On a y-slab: this
+        rank's rows.  The summation order depends on Nx alone, so a profile is reproducible bit for bit.  Eddy quantities are the
+        caller's subtraction: <u'v'> = <uv> - <u><v> cancels where the eddies are weak, and loses that many digits.  See
+        swmhd_amd.zonal for the writer (ZonalMeanTimeSeries)."""
+        from .zonal import enqueue_zonal_means
+        return enqueue_zonal_means(self, names, out)
+
     # --- checkpoint: prognostic fields with halos + G⁻ + clock, one .npz per rank ---------------------------------
     def save_checkpoint(self, path):
         import numpy as np
