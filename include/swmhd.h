@@ -368,6 +368,13 @@ int swmhd_step_rk3_f32(float *const *q, float *const *q_alt, float *const *Ga, f
  * out[3] = segments (workgroups along y), out[4] = rows per segment, out[5] = resident workgroups per CU the kernel is built
  * for, out[6] = halo lanes per strip side, out[7] = compute units of the device.  elem_size 8 (f64) or 4 (f32); flags as above. */
 int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_size, int flags, int out[8]);
+/* The same for the fused stage of an ensemble (swmhd_ensemble_tendencies_rk3*, swmhd_ensemble_step_rk3*: all Ny rows of `members`
+ * members of an Nx x Ny grid in one launch of the LDS-tiled kernel), as the launcher plans it, its measurement knobs SWMHD_ENS_RY and
+ * SWMHD_ENS_MAP included.  out[0] = 1, out[1] = threads per workgroup, out[2] = tile columns, out[3] = tile rows, out[4] = rows per tile,
+ * out[5] = member mapping (1: the member is folded into blockIdx.x, 2: it is blockIdx.y), out[6] = grid.x, out[7] = grid.y.
+ * flags: SWMHD_STRICT, SWMHD_TILE_KERNEL, SWMHD_WRAP_X / _Y, SWMHD_RK3_ANCHOR, SWMHD_BOUNDED_X / _Y (the stage of
+ * swmhd_ensemble_step_rk3_bc); anything else, members outside 1 .. 65535 or a launch beyond 2^31 - 1 workgroups: SWMHD_EINVAL. */
+int swmhd_ensemble_launch_geometry(int Nx, int Ny, int formulation, int elem_size, int flags, int members, int out[8]);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU: one process per GPU, the domain cut into y-slabs (rank r owns global rows [r*Ny, (r+1)*Ny), all x).  A Periodic y
@@ -577,8 +584,8 @@ int swmhd_ensemble_diagnostics_f32(const float *q1, const float *q2, const float
  * Results: SWMHD_STRICT members are bit-identical to the oracle's time_step with that member's gradients (and so to the single-grid
  * Bounded schedule, swmhd_tendencies_rk3 with the BOUNDED flags + swmhd_fill_halo per stage, as ShallowWaterModel.time_step runs it).
  * Fast members run the single grid's 64 x 8 wall-tile kernel body in its ensemble instantiation, within the fast tolerances of that
- * schedule but not bitwise: the compiler groups the uniform factors of the fused substep differently there (last-bit differences in
- * a few cells per stage).  Larger fast members run that kernel where a single grid takes the marching kernel plus a wall frame.
+ * schedule; bitwise equality is not promised: the fused substep rounds alike in every instantiation of the kernel (explicit fused
+ * multiply-adds), but the tendencies are compiled with reassociation, instantiation by instantiation.  Larger fast members run that kernel where a single grid takes the marching kernel plus a wall frame.
  * The boundary-condition fill is bitwise swmhd_fill_halo in both builds.  A non-finite member does not affect the others.
  * ---------------------------------------------------------------------------------------------- */
 /* swmhd_ensemble_fill_halo: swmhd_fill_halo of every member (two launches for all members), with the checks of that call and of the
@@ -621,7 +628,7 @@ int swmhd_ensemble_step_rk3_bc_f32(float *const *q, float *const *q_alt, float *
  * and *state_in_alt are exactly those of the counterpart.  A non-finite parameter poisons that member only.
  * Results: SWMHD_STRICT members are bit-identical to the oracle's time_step / tendencies called with that member's (g, f, dt), and so
  * to the scalar call when all rows are equal.  Fast members are within the fast tolerances of a fast single model built with the
- * member's parameters, not bitwise: as for Bounded members, the compiler groups uniform factors differently between instantiations.
+ * member's parameters; as for Bounded members, bitwise equality is not promised (profiles/stage_matrix/ records that it was observed).
  * Out of scope: per-member formulation or forcing kind, and output schedules in time units across members whose clocks diverge.
  * ---------------------------------------------------------------------------------------------- */
 #define SWMHD_ENSEMBLE_NPARAMS 3

@@ -167,6 +167,8 @@ def _declare(lib):
         f.restype = i
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
     lib.swmhd_tendency_launch_geometry.restype = i
+    lib.swmhd_ensemble_launch_geometry.argtypes = [i, i, i, i, i, i, C.POINTER(i)]
+    lib.swmhd_ensemble_launch_geometry.restype = i
     lib.swmhd_ring_available.argtypes = [C.c_char_p]
     lib.swmhd_ring_available.restype = i
     lib.swmhd_ring_unique_id.argtypes = [C.c_char_p, p]
@@ -190,7 +192,7 @@ def _declare(lib):
 
 
 # every symbol include/swmhd.h declares (tests/test_abi.py checks the .so exports each of them)
-EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", "swmhd_probe_fp64_issue", "swmhd_probe_copy"] + ["swmhd_event_" + n for n in ("create", "record", "elapsed_ms", "destroy")] + [
+EXPORTS = ["swmhd_version", "swmhd_strerror", "swmhd_tendency_launch_geometry", "swmhd_ensemble_launch_geometry", "swmhd_probe_fp64_issue", "swmhd_probe_copy"] + ["swmhd_event_" + n for n in ("create", "record", "elapsed_ms", "destroy")] + [
     f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in (
         "lorentz_jacobian", "lorentz_jacobian_rows", "lorentz_divergence", "lorentz_divergence_rows",
         "fill_halo", "fill_halo_periodic", "fill_halo_periodic_multi", "tendencies", "tendencies_rk3", "rk3_substep", "step_rk3", "diagnostics",
@@ -252,6 +254,14 @@ def tendency_launch_geometry(Nx, rows, formulation, elem_size=8, flags=0):
     out = (C.c_int * 8)()
     check(lib().swmhd_tendency_launch_geometry(Nx, rows, formulation, elem_size, flags, out), "swmhd_tendency_launch_geometry")
     keys = ("kind", "threads", "nstrips", "nseg", "rows_per_segment", "wg_per_cu", "halo_lanes", "cus")
+    return dict(zip(keys, list(out)))
+
+
+def ensemble_launch_geometry(Nx, Ny, formulation, members, elem_size=8, flags=0):
+    """dict(kind, threads, tile_columns, tile_rows, rows_per_tile, member_map, grid_x, grid_y) of a fused ensemble stage (swmhd.h)."""
+    out = (C.c_int * 8)()
+    check(lib().swmhd_ensemble_launch_geometry(Nx, Ny, formulation, elem_size, flags, members, out), "swmhd_ensemble_launch_geometry")
+    keys = ("kind", "threads", "tile_columns", "tile_rows", "rows_per_tile", "member_map", "grid_x", "grid_y")
     return dict(zip(keys, list(out)))
 
 

@@ -285,6 +285,32 @@ inline TendPlan plan_tendency(TendPlanIn a) {
     return p;
 }
 
+// How an ensemble stage maps members onto the grid (launch_ensemble_stage): folded into blockIdx.x (1, the default) or blockIdx.y (2).
+// Knob (read once; measurement only): SWMHD_ENS_MAP = 1 | 2.
+inline int ensemble_member_map() {
+    static int cache = 0;
+    return env_knob("SWMHD_ENS_MAP", cache) == 2 ? 2 : 1;
+}
+// swmhd_ensemble_launch_geometry: the launch of a fused ensemble stage over all Ny rows of `members` members, from the planner and
+// the knob reader that launch_ensemble_stage asks.  out: kind (1 LDS-tiled), threads, tile columns, tile rows, rows per tile, member
+// mapping (1 blockIdx.x, 2 blockIdx.y), grid.x, grid.y.  1: not one tile launch (nothing to do, or no plan).
+inline int ensemble_launch_geometry(int Nx, int Ny, int formulation, int elem_size, bool strict, int wrap, int topo_x, int topo_y,
+                                    int members, int out[8]) {
+    TendPlanIn in{};
+    in.Nx = Nx; in.Ny = Ny; in.elem_size = elem_size; in.j1 = Ny; in.formulation = formulation; in.strict = strict;
+    in.kernel_variant = 1; in.wrap = wrap; in.topo_x = topo_x; in.topo_y = topo_y;
+    in.fuse = 1; in.store_G = 1; in.members = members;
+    const TendPlan p = plan_tendency(in);
+    if (p.n != 1 || !p.e[0].tile()) return 1;
+    const TendLaunch &l = p.e[0];
+    const int map = ensemble_member_map();
+    const long tiles = (long)l.ntx * l.nty, gx = map == 2 ? tiles : tiles * members;
+    if (gx >= (1L << 31)) return 1;
+    out[0] = 1; out[1] = 256; out[2] = l.ntx; out[3] = l.nty; out[4] = l.kernel == TendKernel::TILE_RY1 ? 4 : 8;
+    out[5] = map; out[6] = (int)gx; out[7] = map == 2 ? members : 1;
+    return 0;
+}
+
 // swmhd_tendency_launch_geometry: the first launch of the plan of a periodic single-range stage of MODE 7 (a fused middle stage that
 // stores G) on a parent below 4 GiB.  out: kind (1 LDS-tiled, 2 row-marching, 3 packed fp32), threads, strips | tile columns, segments |
 // tile rows, rows per segment | tile, workgroups per CU (0: tiles), halo lanes a side, CUs.

@@ -376,6 +376,14 @@ int swmhd_tendency_launch_geometry(int Nx, int rows, int formulation, int elem_s
     return tendency_launch_geometry(Nx, rows, formulation, elem_size, fl.strict, fl.kernel_variant, fl.leave_room, fl.wrap, out);
 }
 
+int swmhd_ensemble_launch_geometry(int Nx, int Ny, int formulation, int elem_size, int flags, int members, int out[8]) {
+    if (!out || Nx <= 0 || Ny <= 0 || (elem_size != 4 && elem_size != 8)) return SWMHD_EINVAL;
+    if (!formulation_ok(formulation) || members < 1 || members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
+    if ((flags & ~(ENS_FLAGS | BOUNDED_FLAGS)) || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
+    const Flags fl = decode_flags(flags);
+    return ensemble_launch_geometry(Nx, Ny, formulation, elem_size, fl.strict, fl.wrap, fl.topo_x, fl.topo_y, members, out) ? SWMHD_EINVAL : SWMHD_OK;
+}
+
 // The exported wrappers: each packs its C scalars into a Grid, a Physics (stage scalars by name; the *_params calls leave out what
 // their table holds) and, for ensembles, an Ens, and makes one call.
 #define SWMHD_DEF_API(sfx, T)                                                                                                                         \

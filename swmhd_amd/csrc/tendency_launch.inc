@@ -100,20 +100,20 @@ hipError_t LAUNCH_NAME(launch_tendency_, LAUNCH_SFX)(const TendArgs<T> &a, int f
 // Ensemble stage: the LDS-tiled kernel over every tile of every member (one row range), at the tile height of the plan -- that of a
 // single model of the member's size, so the compiled body is that model's and a periodic member's results are bitwise the single
 // model's.  Bounded members always take the wall kernel, where a large single model takes the marching kernel plus the wall frame.
-// Strict members are bitwise single models.  Fast Bounded members are not: with reassociation the compiler groups the uniform factors of
-// the fused substep differently in this instantiation (an ulp in a few cells per stage), within the fast tolerances.
+// Strict members are bitwise single models.  Fast Bounded members and members with their own parameters are promised the fast tolerances
+// only: the fused substep rounds alike in every instantiation (substep_pinned), the tendencies are reassociated per instantiation.
 // Members are folded into blockIdx.x by default.  Tile height and mapping were measured (tools/time_ensemble.py, profiles/ensemble/).
-// Knob (read once; measurement only): SWMHD_ENS_MAP = 1 folds the member into blockIdx.x, 2 makes it blockIdx.y.
+// Knob (read once; measurement only): SWMHD_ENS_MAP = 1 folds the member into blockIdx.x, 2 makes it blockIdx.y (launch_plan.hpp
+// ensemble_member_map, which swmhd_ensemble_launch_geometry reports).
 template <typename T, bool PAR>
 static hipError_t launch_ensemble_stage(const TileArgs<T, true, PAR> &a, int formulation, int lorentz, hipStream_t s) {
-    static int map_cache = 0;
     if (a.j1 <= a.j0 || a.members <= 0) return hipSuccess;
     TendPlanIn in = plan_input<T>(a, formulation, a.members);
     in.j0b = in.j1b = in.edge_cols = 0;
     const TendPlan plan = plan_tendency(in);
     if (plan.n != 1 || !plan.e[0].tile()) return plan.n ? hipErrorInvalidValue : hipSuccess;
     const TendLaunch &l = plan.e[0];
-    const int map = env_knob("SWMHD_ENS_MAP", map_cache);
+    const int map = ensemble_member_map();
     const long blocks = (long)l.ntx * l.nty * a.members;
     if (blocks >= (1L << 31) || (map == 2 && a.members > 65535)) return hipErrorInvalidConfiguration;
     TileArgs<T, true, PAR> e = a;

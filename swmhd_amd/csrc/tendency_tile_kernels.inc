@@ -58,6 +58,29 @@ __device__ __forceinline__ void ens_member_params(EnsParTendArgs<T> &a, unsigned
     a.dtw = a.dt * a.zeta;
 }
 
+// The G- forms of the fused substep in fast builds, U + dt (gamma G [+ zeta Gm]), with their rounding written down as explicit fused
+// multiply-adds in T: c1 = dt gamma and c2 = dt zeta (one multiply each, of uniform operands), then fma(c1, G, U) for a first stage and
+// fma(c2, Gm, fma(c1, G, U)) with a G- operand -- one v_fma per addend, no separate add.  Written as U + (dt gamma) G the expression
+// was regrouped under -fassociative-math and contracted under -ffp-contract=fast as the compiler liked, and differently in the
+// single-grid and the ensemble instantiation of the kernel below (last bits of the new state: tests/test_ensemble_stage_matrix_gpu.py).
+// An fma intrinsic is neither split nor regrouped, and reassociate(off) keeps the two multiplies that feed it as written, so every
+// instantiation rounds alike and an ensemble member is bitwise the single grid in these forms, as it is in the anchor form, whose
+// products come from the host.  (#pragma clang fp contract(off) would NOT do: with -ffp-contract=fast the backend still fuses.)
+__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template <typename T>
+__device__ __forceinline__ T substep_pinned(T U, T dt, T gamma, T G) {   // first stage
+#pragma clang fp reassociate(off)
+    const T c1 = dt * gamma;
+    return fma_t(c1, G, U);
+}
+template <typename T>
+__device__ __forceinline__ T substep_pinned(T U, T dt, T gamma, T G, T zeta, T Gm) {
+#pragma clang fp reassociate(off)
+    const T c1 = dt * gamma, c2 = dt * zeta;
+    return fma_t(c2, Gm, fma_t(c1, G, U));
+}
+
 // FORM: 0 conservative, 1 vector invariant.  LOR: 0 none, 1 Jacobian (FORM 1 only), 2 divergence (FORM 0 only).
 // BND: at least one direction is Bounded -- reconstructions near walls drop to the boundary schemes (sw_device.inc) and the divergence-
 // form Lorentz fluxes take the reference's wall branches (sw_mhd_divergence_functions.jl:42-53,66-77,90-101,114-125).  With
@@ -302,11 +325,12 @@ __global__ __launch_bounds__(TX *TYB) void k_tendency_tile(TileArgs<T, ENS, PAR>
                         }
                     } else if (a.first) {
                         if constexpr (STRICT) un = Us[f] + a.dt * a.gamma * Gs[f];
-                        else un = Us[f] + (a.dt * a.gamma) * Gs[f];
+                        else un = substep_pinned<T>(Us[f], a.dt, a.gamma, Gs[f]);
                     } else if (!STRICT && a.gm_prev) {
                         un = Us[f] + (a.dt * a.gamma) * Gs[f] + a.zeta * (Us[f] - a.Gm[f][o]);
                     } else {
-                        un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * a.Gm[f][o]);
+                        if constexpr (STRICT) un = Us[f] + a.dt * (a.gamma * Gs[f] + a.zeta * a.Gm[f][o]);
+                        else un = substep_pinned<T>(Us[f], a.dt, a.gamma, Gs[f], a.zeta, a.Gm[f][o]);
                     }
                     a.Unew[f][o] = un;
                 }

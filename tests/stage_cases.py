@@ -6,6 +6,11 @@ matrices of calls made through every kernel path of those entry points (PATHS):
                  the LDS-tiled kernel k_tendency_tile in its fast 64 x 4 and 64 x 8 bodies, the strict 64 x 8 body and the fast and
                  strict wall bodies (Bounded directions): tile_matrix(), run by tests/test_tile_stage_matrix_gpu.py and
                  tools/stage_matrix_report.py --tile
+    ens4, ens8, ens-strict, par4, par-strict
+                 the ensemble instantiations of k_tendency_tile behind swmhd_ensemble_tendencies_rk3_* and, with a device table of
+                 (g, f, dt) per member, swmhd_ensemble_tendencies_rk3_params_*: ens_matrix(), every member a StageData of its own in
+                 pitched family buffers, run by tests/test_ensemble_stage_matrix_gpu.py, its forced-layout child processes and
+                 tools/stage_matrix_report.py --ensemble (last section of this file)
 
 Fast paths: the tendencies G come from the CPU oracle in float64 (fp32 inputs widened exactly); the substep is evaluated in
 np.longdouble from the formulas of the header.  Strict paths: G is the oracle's in the precision of the call and the substep is
@@ -137,12 +142,15 @@ class StageData:
     # defaults of a subclass that builds its own (periodic) inputs without this constructor (tests/test_weno_arith_gpu.py)
     topo, wall_failures, _G_strict = (P, P), (), None
 
-    def __init__(self, oracle, Nx, Ny, form, lor, dtype, seed=None, topo=(P, P)):
+    def __init__(self, oracle, Nx, Ny, form, lor, dtype, seed=None, topo=(P, P), grav=None, fcor=None):
         self.Nx, self.Ny, self.form, self.lor, self.dtype, self.topo = Nx, Ny, form, lor, np.dtype(dtype), tuple(topo)
         seed = 1000 * Nx + Ny if seed is None else seed
         self.q, self.aux = random_fields(Nx, Ny, form, dtype, seed)
-        # spacings and constants as the call receives them (c_float rounds 0.11, 0.13 and 9.81)
-        self.dx, self.dy, self.grav, self.fcor = (float(self.dtype.type(x)) for x in (DX, DY, GRAV, FCOR))
+        # spacings and constants as the call receives them (c_float rounds 0.11, 0.13 and 9.81); grav, fcor: the g and f of a member of
+        # an ensemble with per-member parameters (None: the constants of every other case)
+        own = grav is not None or fcor is not None
+        self.dx, self.dy, self.grav, self.fcor = (float(self.dtype.type(x)) for x in (DX, DY, GRAV if grav is None else grav,
+                                                                                      FCOR if fcor is None else fcor))
         kw = {}
         if self.topo != (P, P):
             TC.fill_state(oracle, self.q, Nx, Ny, self.topo, TC.grad_A(self.topo), self.dx, self.dy)
@@ -155,7 +163,9 @@ class StageData:
             w = (oracle.lorentz_jacobian(q64[3], q64[2], Nx, Ny, H, H, self.dx, self.dy, nthreads=NTHREADS) if lor == 1 else
                  oracle.lorentz_divergence(q64[3], q64[2], Nx, Ny, H, H, self.dx, self.dy, nthreads=NTHREADS, **kw))
             force = max(float(np.abs(Hh.interior(x, Nx, Ny, H, H)).max()) for x in w)
-        self.scales = [float(s) for s in Hh.term_scales(FORM[form], q64, self.dx, self.dy, force)]
+        # (the S of a member with its own g and f is formed with them: a smaller g must not keep the bound of 9.81)
+        own = dict(g=self.grav, f=abs(self.fcor)) if own else {}
+        self.scales = [float(s) for s in Hh.term_scales(FORM[form], q64, self.dx, self.dy, force, **own)]
         self.Gmax = [float(np.abs(g).max()) for g in self.G]
         self.Umax = [float(np.abs(Hh.interior(a, Nx, Ny, H, H)).max()) for a in q64]
         self._oracle, self._G_strict = oracle, None
@@ -532,18 +542,19 @@ def _same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(np.ascontiguousarray(a).view(u), np.ascontiguousarray(b).view(u))
 
 
-def run_stage(S, data, variant, cset, flags=0, rows=None, path="march", expect_rc=0):
+def run_stage(S, data, variant, cset, flags=0, rows=None, path="march", expect_rc=0, dt=None):
     """One call through the C-ABI with the flags of `path` (SWMHD_MARCH_KERNEL by default; the Bounded flags of data.topo) | flags.
     Inputs: data.q with NaN in the halos of every wrapped direction; the operand data.aux (sentinel halos).  Every output buffer starts
     as the sentinel (qnew of P*: as Uprev).  The return code must be expect_rc.  Returns the parents before and after:
-    {"q": (before, after), "operand": ..., "qnew": ..., "Gn": ...} (None where the call has no such buffer)."""
+    {"q": (before, after), "operand": ..., "qnew": ..., "Gn": ...} (None where the call has no such buffer).  dt: the time step of the
+    call where it is not data.dt(gamma) (a member of an ensemble that steps at the ensemble's dt)."""
     import torch
     L = S._lib
     v = VARIANTS[variant]
     Nx, Ny = data.Nx, data.Ny
     j0, j1 = (0, Ny) if rows is None else rows
     gam, zet = COEFFS[cset][variant]
-    dt = data.dt(gam)
+    dt = data.dt(gam) if dt is None else dt
     sfx = "f64" if data.dtype == np.float64 else "f32"
     q_in = [a.copy() for a in data.q]
     for a in q_in:
@@ -726,5 +737,429 @@ def forced_main(name, out_path):
     return 1 if failures else 0
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the ensemble matrix: k_tendency_tile<..., ENS = true, PAR = false | true> through swmhd_ensemble_tendencies_rk3[_params]_*, member
+# by member against the single-grid reference above (numpy only down to run_ens_stage)
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Ensemble paths.  par: the *_params entry points (a device table of (g, f, dt) per member); ty: rows of a tile -- that of a single
+# model of the member's size; refused: SWMHD_GM_IS_PREV_STATE everywhere, the anchor forms where SWMHD_STRICT refuses them for a single
+# grid ("semantics ... as there").  There is no ensemble form of T.
+NO_PREV_STATE = ("P2g", "P3n")
+ENS_PATHS = {
+    "ens4": dict(flags=TILE_KERNEL, strict=False, par=False, ty=4, refused=NO_PREV_STATE),
+    "ens8": dict(flags=TILE_KERNEL, strict=False, par=False, ty=8, refused=NO_PREV_STATE),
+    "ens-strict": dict(flags=STRICT, strict=True, par=False, ty=8, refused=FAST_ONLY),
+    "par4": dict(flags=TILE_KERNEL, strict=False, par=True, ty=4, refused=NO_PREV_STATE),
+    "par-strict": dict(flags=STRICT, strict=True, par=True, ty=8, refused=FAST_ONLY),
+}
+ENS_PAD, ENS_GAP = 5, 37            # columns after every row and elements after every member of a pitched family (ensemble_tracer_cases)
+# members per shape: with 64 x 4 | 64 x 8 tiles the launches have 15 | 10, 18 | 12, 9 | 6, 4 | 2 and 72 | 36 workgroups -- none but
+# 72 a multiple of 8, below and above 8 on both tile heights (xcd_remap deals ntiles * members blocks over 8 XCDs)
+ENS_SHAPES = {(3, 9): 5, (65, 9): 3, (129, 9): 1, (65, 5): 1, (129, 31): 3}
+ENS_DENSE_SHAPE = (65, 9)           # also run dense: stride_y = Nx + 2 H, stride_m = (Ny + 2 H) stride_y, with WRAP_X | WRAP_Y
+ENS8_MEMBERS = 2
+# g and f of member m of a par* path (rounded to the precision of the call by StageData): pairwise distinct, two f negative; dt is the
+# member's own StageData.dt
+PAR_G = (9.81, 1.0, 4.0, 20.0, 2.5)
+PAR_F = (1.0, -0.5, 2.0, 0.25, -1.5)
+
+
+def ens_calls():
+    return [(v, c) for v, c in calls() if v != "T"]
+
+
+def ens_matrix():
+    """Every (path, Nx, Ny, members, form, lor, dtype, flags, dense) of the ensemble matrix, grouped so that consecutive entries share
+    their members' StageData."""
+    XY = WRAP_X | WRAP_Y
+    for (Nx, Ny), members in ENS_SHAPES.items():
+        layouts = [(0, False), (XY, False)] + ([(WRAP_X, False), (WRAP_Y, False), (XY, True)] if (Nx, Ny) == ENS_DENSE_SHAPE else [])
+        for form, lor in FORMS:
+            for dtype in DTYPES:
+                for path in ("ens4", "ens-strict", "par4", "par-strict"):
+                    for flags, dense in layouts:
+                        yield path, Nx, Ny, members, form, lor, dtype, flags, dense
+    for form, lor in FORMS:
+        for dtype in DTYPES:
+            for flags in (0, XY):
+                yield ("ens8",) + TILE8_SHAPE + (ENS8_MEMBERS, form, lor, dtype, flags, False)
+
+
+def ens_case_id(path, Nx, Ny, members, form, lor, dtype, flags, dense):
+    return f"{path}-m{members}-{'dense' if dense else 'pitched'}-{case_id(Nx, Ny, None, form, lor, dtype, flags)}"
+
+
+def ens_workgroups(path, Nx, Ny, members, ty=None):
+    """Workgroups of the launch: tile columns x tile rows x members."""
+    return tiles(Nx, TILE_X)[0] * tiles(Ny, ty or ENS_PATHS[path]["ty"])[0] * members
+
+
+def ens_layout(Nx, Ny, dense):
+    """(stride_y, stride_m) of a family."""
+    sy = Nx + 2 * H + (0 if dense else ENS_PAD)
+    return sy, (Ny + 2 * H) * sy + (0 if dense else ENS_GAP)
+
+
+def ens_view(flat, m, Nx, Ny, dense):
+    """Member m's parent inside a flat family buffer (a view)."""
+    sy, sm = ens_layout(Nx, Ny, dense)
+    return flat[m * sm:m * sm + (Ny + 2 * H) * sy].reshape(Ny + 2 * H, sy)[:, :Nx + 2 * H]
+
+
+def ens_pack(parents, Nx, Ny, dense, fill):
+    """One flat family buffer: member m's parent from parents[m], `fill` in the row padding and the member gaps."""
+    flat = np.full(len(parents) * ens_layout(Nx, Ny, dense)[1], fill, dtype=parents[0].dtype)
+    for m, a in enumerate(parents):
+        ens_view(flat, m, Nx, Ny, dense)[...] = a
+    return flat
+
+
+_REGIONS = {}
+INTERIOR, HALO, PADDING, GAP = 0, 1, 2, 3
+REGION_NAME = {HALO: "halo", PADDING: "row padding", GAP: "member gap"}
+
+
+def ens_regions(Nx, Ny, members, dense):
+    """What every element of a family buffer is: INTERIOR | HALO | PADDING | GAP."""
+    key = (Nx, Ny, members, dense)
+    if key not in _REGIONS:
+        _REGIONS.clear()
+        sy, sm = ens_layout(Nx, Ny, dense)
+        reg = np.full(members * sm, GAP, dtype=np.int8)
+        for m in range(members):
+            reg[m * sm:m * sm + (Ny + 2 * H) * sy] = PADDING
+            v = ens_view(reg, m, Nx, Ny, dense)
+            v[...] = HALO
+            Hh.interior(v, Nx, Ny, H, H)[...] = INTERIOR
+        _REGIONS[key] = reg
+    return _REGIONS[key]
+
+
+_ENS_DATA = {}
+
+
+def ens_members(oracle, Nx, Ny, members, form, lor, dtype, par, row=None):
+    """The members of a case: one StageData each, from a seed of its own (no two members share a field, the operand aux included);
+    with par, member m carries (PAR_G[m], PAR_F[m]).  row: form every member's reference with that row of the table instead (what a
+    kernel that read one row for all members would compute).  Computed once per shape and shared: do not modify."""
+    out = []
+    for m in range(members):
+        r = m if row is None else row
+        key = (Nx, Ny, form, lor, np.dtype(dtype).name, m, r if par else None)
+        if key not in _ENS_DATA:
+            for k in [k for k in _ENS_DATA if k[:2] != (Nx, Ny)]:
+                del _ENS_DATA[k]
+            kw = dict(grav=PAR_G[r], fcor=PAR_F[r]) if par else {}
+            _ENS_DATA[key] = StageData(oracle, Nx, Ny, form, lor, dtype, seed=1000 * Nx + Ny + 7919 * (m + 1), **kw)
+            _ENS_DATA[key]._ens_ref = {}
+        out.append(_ENS_DATA[key])
+    return out
+
+
+def ens_dts(members, variant, cset, par):
+    """dt of every member: its own StageData.dt with a table, member 0's for all where the call has one dt."""
+    gam = COEFFS[cset][variant][0]
+    return [d.dt(gam) for d in members] if par else [members[0].dt(gam)] * len(members)
+
+
+def ens_expected(oracle, members, variant, cset, dts, strict):
+    """[(reference, bounds | None)] per member: reference_stage + stage_bounds of that member with its dt, or reference_stage_strict
+    (whose G is the oracle's with the member's g and f).  Kept per member for the other layouts of the shape (small shapes only)."""
+    v, coeffs, out = VARIANTS[variant], COEFFS[cset][variant], []
+    for d, dt in zip(members, dts):
+        key = (variant, cset, dt, strict)
+        if key not in d._ens_ref:
+            operand = d.aux if v["operand"] else None
+            if strict:
+                ref, bounds = reference_stage_strict(d, variant, coeffs, dt), None
+            else:
+                ref = reference_stage(oracle, d.q, operand, variant, coeffs, d.Nx, d.Ny, d.dx, d.dy, d.form, d.lor, dt, G=d.G)
+                bounds = stage_bounds(d, d.q, operand, variant, coeffs, dt, ref)
+            if d.Nx * d.Ny > 20000:
+                out.append((ref, bounds))
+                continue
+            d._ens_ref[key] = (ref, bounds)
+        out.append(d._ens_ref[key])
+    return out
+
+
+def ens_buffers(members, variant, flags, dense):
+    """The host buffers of one call, {"q", "operand", "qnew", "Gn"}: lists of 4 flat family buffers (None: the call has none).  Inputs:
+    every member's q with NaN in the halos of every wrapped direction, its own operand aux (sentinel halos), NaN in the row padding
+    and the member gaps.  Outputs: the sentinel everywhere.  qnew of P* IS the operand (it holds Uprev), Gn of A2a IS the operand."""
+    v, d0 = VARIANTS[variant], members[0]
+    Nx, Ny = d0.Nx, d0.Ny
+    qs = []
+    for d in members:
+        q_in = [a.copy() for a in d.q]
+        for a in q_in:
+            Hh.poison_halo(a, Nx, Ny, H, H, x=bool(flags & WRAP_X), y=bool(flags & WRAP_Y))
+        qs.append(q_in)
+    sent = np.full_like(d0.q[0], SENTINEL)
+    fam = lambda per_member, fill: [ens_pack([p[f] for p in per_member], Nx, Ny, dense, fill) for f in range(4)]
+    out = {"q": fam(qs, np.nan), "operand": None, "qnew": None, "Gn": None}
+    if v["operand"]:
+        out["operand"] = fam([d.aux for d in members], np.nan)
+    out["qnew"] = out["operand"] if v["operand"] == "Uprev" else fam([[sent] * 4] * len(members), SENTINEL)
+    out["Gn"] = out["operand"] if v["alias"] else fam([[sent] * 4] * len(members), SENTINEL)
+    return out
+
+
+def ens_copy(bufs):
+    """A deep copy of ens_buffers' result that keeps its aliases."""
+    out = {k: None if bufs[k] is None else [a.copy() for a in bufs[k]] for k in ("q", "operand")}
+    for k in ("qnew", "Gn"):
+        out[k] = out["operand"] if bufs[k] is bufs["operand"] and bufs[k] is not None else [a.copy() for a in bufs[k]]
+    return out
+
+
+def ens_fabricate(members, variant, dense, before, expected):
+    """What a correct kernel leaves behind, built from `expected` (rounded to the precision of the call) on a copy of `before`: for the
+    CPU pin of check_ens_outputs, which then spoils it."""
+    after, d0 = ens_copy(before), members[0]
+    for m, (ref, _) in enumerate(expected):
+        for name in ("qnew", "Gn"):
+            if ref[name] is None or ref[name] is KEEP:
+                continue
+            for f in range(4):
+                Hh.interior(ens_view(after[name][f], m, d0.Nx, d0.Ny, dense), d0.Nx, d0.Ny, H, H)[...] = ref[name][f].astype(d0.dtype)
+    return after
+
+
+def check_ens_refusal(before, after):
+    """A refused call left every buffer bitwise as it was: the failures."""
+    fails = []
+    for name in ("q", "operand", "qnew", "Gn"):
+        for f in range(4 if before[name] is not None else 0):
+            if not _same_bits(before[name][f], after[name][f]):
+                fails.append(f"refused call changed {name}[{f}]")
+    return fails
+
+
+def check_ens_outputs(members, variant, flags, dense, before, after, expected, singles=None):
+    """check_case for every member of an ensemble call: (failures, ratios).  before / after: ens_buffers and what the call made of them;
+    expected: ens_expected; singles: per member {"qnew", "Gn"} parents of the same call made on the member alone, to be equal bit for bit.
+      1. every written output finite and within its member's bounds (bounds None: bitwise its member's strict reference)
+      2. an output with KEEP, every halo, the row padding and the member gaps of every output family, every input and operand: bitwise
+         as before
+      3. with a WRAP flag the halos of that direction of all four inputs of every member are NaN on entry"""
+    v, d0 = VARIANTS[variant], members[0]
+    Nx, Ny, M = d0.Nx, d0.Ny, len(members)
+    reg = ens_regions(Nx, Ny, M, dense)
+    fails, ratios = [], {}
+    for f in range(4):
+        if not _same_bits(before["q"][f], after["q"][f]):
+            fails.append(f"input field {f} was changed")
+        if v["operand"] and v["operand"] != "Uprev" and not _same_bits(before["operand"][f], after["operand"][f]):
+            fails.append(f"operand {v['operand']} field {f} was changed")
+        for m in range(M):
+            a = ens_view(before["q"][f], m, Nx, Ny, dense)
+            if (flags & WRAP_X and not (np.isnan(a[:, :H]).all() and np.isnan(a[:, H + Nx:]).all())) or \
+               (flags & WRAP_Y and not (np.isnan(a[:H]).all() and np.isnan(a[H + Ny:]).all())):
+                fails.append(f"member {m} input field {f}: the halos of a wrapped direction are not NaN on entry")
+    for name in ("qnew", "Gn"):
+        if after[name] is None or (name == "Gn" and v["alias"]):
+            continue
+        for f in range(4):
+            b, a = before[name][f], after[name][f]
+            if expected[0][0][name] is KEEP:
+                if not _same_bits(a, b):
+                    fails.append(f"{name}[{f}] must keep its sentinel: {int((a != b).sum())} cells written")
+                continue
+            changed = (a.view(np.uint8).reshape(a.size, -1) != b.view(np.uint8).reshape(b.size, -1)).any(axis=1)
+            for r, what in REGION_NAME.items():
+                n = int((changed & (reg == r)).sum())
+                if n:
+                    fails.append(f"{name}[{f}]: {n} cells of the {what} written")
+            for m, (ref, bounds) in enumerate(expected):
+                got_t = Hh.interior(ens_view(a, m, Nx, Ny, dense), Nx, Ny, H, H)
+                got = got_t.astype(np.longdouble)
+                if not np.isfinite(got).all():
+                    fails.append(f"member {m} {name}[{f}]: {int((~np.isfinite(got)).sum())} non-finite cells")
+                    ratios[name] = float("inf")
+                    continue
+                if singles is not None:
+                    alone = Hh.interior(singles[m][name][f], Nx, Ny, H, H)
+                    if not _same_bits(np.ascontiguousarray(got_t), np.ascontiguousarray(alone)):
+                        fails.append(f"member {m} {name}[{f}]: {int((got_t != alone).sum())} cells differ from the single-grid call on the member alone")
+                if bounds is None:      # strict: the bits of the oracle's (a -0 for a +0 is a difference)
+                    want = np.ascontiguousarray(ref[name][f])
+                    u = np.uint64 if want.dtype.itemsize == 8 else np.uint32
+                    same = (np.ascontiguousarray(got_t).view(u) == want.view(u)) if want.dtype == got_t.dtype else np.zeros(want.shape, bool)
+                    ratios[name] = max(ratios.get(name, 0.0), 0.0 if same.all() else float("inf"))
+                    if not same.all():
+                        fails.append(f"member {m} {name}[{f}]: {int((~same).sum())} cells differ from the oracle's, max |difference| "
+                                     f"{float(np.abs(got - ref[name][f]).max()):.3e}")
+                    continue
+                err, bound = float(np.abs(got - ref[name][f]).max()), bounds[name][f]
+                ratios[name] = max(ratios.get(name, 0.0), err / bound)
+                if not err <= bound:
+                    fails.append(f"member {m} {name}[{f}]: max error {err:.3e} > bound {bound:.3e}")
+    return fails, ratios
+
+
+def check_ens_layout(L, path, Nx, Ny, members, form, dtype, flags, ty=None, member_map=1):
+    """The layout the case is there for, as check_tile_layout: tile columns, tile rows and rows of a tile from the planner's answer
+    for a single grid of the member's shape (swmhd_tendency_launch_geometry) -- the ensemble's plan by the header -- and the
+    ensemble launch itself from swmhd_ensemble_launch_geometry, which reads the launcher's knobs: the same tiles, the member mapping
+    (1: folded into blockIdx.x, 2: blockIdx.y) and the grid.  ty | member_map: what a SWMHD_ENS_RY | SWMHD_ENS_MAP child forces; the
+    ensemble query must then report the forced layout, not the default."""
+    p = ENS_PATHS[path]
+    q = TILE_KERNEL | (STRICT if p["strict"] else 0) | (flags & (WRAP_X | WRAP_Y))
+    elem = np.dtype(dtype).itemsize
+    geo = L.tendency_launch_geometry(Nx, Ny, form, elem, q)
+    ntx, lastx = tiles(Nx, TILE_X)
+    assert (geo["kind"], geo["nstrips"]) == (1, ntx), (path, Nx, Ny, geo)
+    assert (geo["rows_per_segment"], geo["nseg"]) == (p["ty"], tiles(Ny, p["ty"])[0]), (path, Nx, Ny, geo)
+    ty = ty or p["ty"]
+    nty, lasty = tiles(Ny, ty)
+    ens = L.ensemble_launch_geometry(Nx, Ny, form, members, elem, q)
+    grid = (ntx * nty * members, 1) if member_map == 1 else (ntx * nty, members)
+    want = dict(kind=1, threads=256, tile_columns=ntx, tile_rows=nty, rows_per_tile=ty, member_map=member_map, grid_x=grid[0], grid_y=grid[1])
+    assert ens == want, (path, Nx, Ny, members, ens, want)
+    note = f" (forced from {p['ty']})" if ty != p["ty"] else ""
+    return (f"kind 1, {ntx} tile columns, last {lastx} wide, {nty} tile rows of {ty}, last {lasty}{note}, "
+            f"member in blockIdx.{'xy'[member_map - 1]}, grid {grid[0]} x {grid[1]}")
+
+
+def run_ens_stage(S, members, variant, cset, flags, dense, path, before, dts, expect_rc=0):
+    """One call of swmhd_ensemble_tendencies_rk3[_params]_* on copies of `before` on the device; returns what they hold afterwards
+    (ens_buffers' structure).  The return code must be expect_rc."""
+    import torch
+    L, p, v, d0 = S._lib, ENS_PATHS[path], VARIANTS[variant], members[0]
+    Nx, Ny, M = d0.Nx, d0.Ny, len(members)
+    sy, sm = ens_layout(Nx, Ny, dense)
+    gam, zet = COEFFS[cset][variant]
+    sfx = "f64" if d0.dtype == np.float64 else "f32"
+    dev = lambda arrs: None if arrs is None else [torch.from_numpy(a).cuda() for a in arrs]
+    PA = lambda ts: L.ptr_array([t.data_ptr() for t in ts])
+    t = {"q": dev(before["q"]), "operand": dev(before["operand"])}
+    for k in ("qnew", "Gn"):
+        t[k] = t["operand"] if before[k] is before["operand"] and before[k] is not None else dev(before[k])
+    fl = p["flags"] | flags | (GM_IS_PREV_STATE if v["operand"] == "Uprev" else 0) | (RK3_ANCHOR if v["anchor"] else 0)
+    gm = PA(t["operand"]) if t["operand"] is not None else None
+    head = (PA(t["q"]), PA(t["qnew"]), PA(t["Gn"]), gm, M, sm, Nx, Ny, H, H, sy, d0.dx, d0.dy)
+    if p["par"]:
+        table = torch.from_numpy(np.array([[d.grav, d.fcor, dt] for d, dt in zip(members, dts)], dtype=d0.dtype)).cuda()
+        rc = getattr(L.lib(), f"swmhd_ensemble_tendencies_rk3_params_{sfx}")(*head, table.data_ptr(), d0.form, d0.lor, gam, zet, v["store_G"], fl, None)
+    else:
+        assert len(set(dts)) == 1 and len({(d.grav, d.fcor) for d in members}) == 1
+        rc = getattr(L.lib(), f"swmhd_ensemble_tendencies_rk3_{sfx}")(*head, d0.grav, d0.fcor, d0.form, d0.lor, dts[0], gam, zet, v["store_G"], fl, None)
+    if expect_rc == 0:
+        L.check(rc, f"{variant}/{cset}")
+    assert rc == expect_rc, f"{variant}/{cset}: rc={rc}, expected {expect_rc}"
+    torch.cuda.synchronize()
+    return {k: None if t[k] is None else [x.cpu().numpy() for x in t[k]] for k in t}
+
+
+def ens_singles(S, members, variant, cset, flags, dts):
+    """The same call through swmhd_tendencies_rk3_* with SWMHD_TILE_KERNEL on every member alone, as a dense copy with the member's
+    g, f and dt: [{"qnew", "Gn"}] parents afterwards."""
+    out = []
+    for d, dt in zip(members, dts):
+        r = run_stage(S, d, variant, cset, flags, None, path="tile4", dt=dt)
+        out.append({k: r[k][1] for k in ("qnew", "Gn")})
+    return out
+
+
+def check_ens_case(S, oracle, members, variant, cset, flags, dense, path, single=None):
+    """One call of an ensemble case: (failures, ratios, observed).  single: "assert" -- every member bitwise the single-grid call on
+    the member alone (the header's promise for fast members below ~0.33 Mcell without a table); "observe" -- only report whether that
+    holds, as observed["bitwise_single"]."""
+    p = ENS_PATHS[path]
+    dts = ens_dts(members, variant, cset, p["par"])
+    before = ens_buffers(members, variant, flags, dense)
+    if variant in p["refused"]:
+        try:
+            after = run_ens_stage(S, members, variant, cset, flags, dense, path, before, dts, expect_rc=ENOTSUP)
+        except AssertionError as e:
+            return [str(e)], {}, {}
+        return check_ens_refusal(before, after), {}, {}
+    expected = ens_expected(oracle, members, variant, cset, dts, p["strict"])
+    after = run_ens_stage(S, members, variant, cset, flags, dense, path, before, dts)
+    singles = ens_singles(S, members, variant, cset, flags, dts) if single else None
+    fails, ratios = check_ens_outputs(members, variant, flags, dense, before, after, expected, singles if single == "assert" else None)
+    observed = {}
+    if single == "observe":
+        lines, _ = check_ens_outputs(members, variant, flags, dense, before, after, expected, singles)
+        observed["bitwise_single"] = not any("single-grid call" in m for m in lines)
+    return fails, ratios, observed
+
+
+def run_ens_cases(S, oracle, path, Nx, Ny, members, form, lor, dtype, flags, dense, worst=None, stop_at_first=False, single="default",
+                  observed=None):
+    """All call forms and coefficient sets of one entry of the ensemble matrix: the failures, each prefixed with its call.  single:
+    "default" asserts the bitwise single-grid promise on ens4 and nowhere else; observed: {path/precision: [calls bitwise the
+    single-grid call, calls]} filled where single is "observe"."""
+    if single == "default":
+        single = "assert" if path == "ens4" else None
+    data = ens_members(oracle, Nx, Ny, members, form, lor, dtype, ENS_PATHS[path]["par"])
+    prec = "f64" if np.dtype(dtype) == np.float64 else "f32"
+    cid = ens_case_id(path, Nx, Ny, members, form, lor, dtype, flags, dense)
+    failures = []
+    for variant, cset in ens_calls():
+        fails, ratios, obs = check_ens_case(S, oracle, data, variant, cset, flags, dense, path, single)
+        refused = "refused (SWMHD_ENOTSUP), nothing written" if variant in ENS_PATHS[path]["refused"] and not fails else ""
+        print(f"  {cid} {variant}/{cset}: {refused}" + ", ".join(f"{k} {r:.3g}" for k, r in ratios.items())
+              + (f", bitwise the single-grid call: {obs['bitwise_single']}" if obs else "") + (f"  FAILED: {fails}" if fails else ""))
+        if worst is not None and ratios:
+            key = f"{path}/{prec}/{variant}"
+            worst[key] = max(worst.get(key, 0.0), max(ratios.values()))
+        if observed is not None and obs:
+            n = observed.setdefault(f"{path}/{prec}", [0, 0])
+            n[0] += int(obs["bitwise_single"]); n[1] += 1
+        failures += [f"{variant}/{cset}: {m}" for m in fails]
+        if failures and stop_at_first:
+            break
+    return failures
+
+
+# The ensemble launcher's read-once knobs, each in a child process of its own (test_ensemble_stage_matrix_gpu.test_forced_layouts).
+# ty | member_map: the tile height of the fast paths | the member mapping under the knob, which the child reads back from the library
+# (swmhd_ensemble_launch_geometry in check_ens_layout): a knob the launcher did not take would fail there.
+ENS_FORCED = {
+    # the member in blockIdx.y: a 2-D grid of ntiles x members workgroups; the scalar fast and the table strict path between them run
+    # the member decoding with and without a table, in the fast and the strict object
+    "ens-map2": dict(env={"SWMHD_ENS_MAP": "2"}, paths=("ens4", "par-strict"), ty=None, member_map=2),
+    # 64 x 8 fast tiles at small shapes: last tiles of one row (9 rows) and one column (65, 129 columns) of that body; no bitwise
+    # promise against the single grid's 64 x 4 tiles
+    "ens-ry2": dict(env={"SWMHD_ENS_RY": "2"}, paths=("ens4", "par4"), ty=8, member_map=1),
+}
+ENS_FORCED_SHAPES = [(65, 9), (129, 31)]
+ENS_FORCED_MEMBERS = 3
+
+
+def ens_forced_cases(name):
+    cfg = ENS_FORCED[name]
+    return [(path, Nx, Ny, ENS_FORCED_MEMBERS, form, lor, dtype, flags, False) for Nx, Ny in ENS_FORCED_SHAPES for form, lor in ((1, 1), (0, 2))
+            for dtype in DTYPES for path in cfg["paths"] for flags in (WRAP_X | WRAP_Y,)]
+
+
+def ens_forced_main(name, out_path):
+    """Child process: ens_forced_cases(name) under the knob `name` (set by the parent in the environment).  Writes {"ok", "failed",
+    "layouts", "worst", "observed"} and exits non-zero at the first failure."""
+    assert "swmhd_amd" not in sys.modules, "the knobs are read once: the library must not have been used in this process"
+    cfg = ENS_FORCED[name]
+    for k, val in cfg["env"].items():
+        assert os.environ.get(k) == val, f"{k} must be {val} in the environment of this process"
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import swmhd_amd as S
+    from oracle import oracle as O
+    worst, layouts, failures, observed = {}, {}, [], {}
+    for case in ens_forced_cases(name):
+        path, Nx, Ny, members, form, lor, dtype, flags, dense = case
+        cid = ens_case_id(*case)
+        layouts[cid] = check_ens_layout(S._lib, path, Nx, Ny, members, form, dtype, flags, ty=cfg["ty"], member_map=cfg["member_map"])
+        single = "default" if cfg["ty"] is None else ("observe" if path == "ens4" else None)
+        failures = run_ens_cases(S, O, *case, worst=worst, stop_at_first=True, single=single, observed=observed)
+        if failures:
+            break
+    with open(out_path, "w") as fh:
+        json.dump({"ok": not failures, "failed": [f"{cid} {m}" for m in failures], "layouts": layouts, "worst": worst, "observed": observed,
+                   "env": cfg["env"]}, fh, indent=1, sort_keys=True)
+    return 1 if failures else 0
+
+
 if __name__ == "__main__":
-    sys.exit(forced_main(sys.argv[1], sys.argv[2]))
+    sys.exit((ens_forced_main if sys.argv[1] in ENS_FORCED else forced_main)(sys.argv[1], sys.argv[2]))

@@ -1,8 +1,8 @@
 """GPU tests of Bounded ensembles (BoundedShallowWaterEnsemble, swmhd_ensemble_fill_halo_*, swmhd_ensemble_step_rk3_bc_*): every
 member, with its own boundary conditions, computes what the same grid computes alone -- the boundary-condition fill bitwise against the
 oracle (f64) and the single-grid fill (f32), strict members bitwise against the oracle's Bounded time_step and a strict
-ShallowWaterModel, fast members within the fast tolerance of a fast ShallowWaterModel (the ensemble instantiation of the wall kernel
-groups the uniform factors of the fused substep differently: last bits in a few cells) -- member by member independent,
+ShallowWaterModel, fast members within the fast tolerance of a fast ShallowWaterModel (bitwise equality is not promised: the tendencies of the ensemble
+instantiation of the wall kernel are reassociated on their own) -- member by member independent,
 graph-replayable, handed over to a ShallowWaterModel mid-run, with per-member diagnostics; and the example runs the reference's
 commented channel experiment as a sweep over the gradient of A."""
 import csv
@@ -306,3 +306,103 @@ def test_example_runs_a_channel_gradient_sweep(tmp_path):
     # the imposed field B_x = -g / h: the magnetic energy grows with the gradient squared
     me = [float([row for row in rows if row["member"] == str(m)][0]["magnetic"]) for m in range(len(grads))]
     assert me[0] < me[1] < me[2]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the wall body of the ensemble kernel (BND + ENS has no stage entry point: it runs under swmhd_ensemble_step_rk3_bc* only) at the
+# shapes of the single grid's wall matrix
+# ---------------------------------------------------------------------------------------------------------------------------------
+import stage_cases as SC      # noqa: E402
+
+PAD, GAP, FILL = 5, 37, 777.0
+# distinct GradientBoundaryCondition values of A per member (west, east, south, north), cut to the Bounded sides of a topology
+WALL_GRADS = [(0.03, -0.04, -0.05, -0.05), (-0.11, 0.1, 0.125, -0.02), (0.2, 0.07, -0.3, 0.3)]
+
+
+def wall_grads(topo):
+    return [tuple(v if topo[k // 2] == B else None for k, v in enumerate(gr)) for gr in WALL_GRADS]
+
+
+def step_pitched_members(S, Nx, Ny, topo, form, states, grads, dtype, strict, dx, dy, dt, params=None):
+    """ONE RK3 step of swmhd_ensemble_step_rk3_bc_* (params: rows (g, f, dt) -> swmhd_ensemble_step_rk3_bc_params_*) through the C-ABI
+    on members pitched in rows and between members (stride_y = Nx + 6 + 5, stride_m = (Ny + 6) stride_y + 37), all four buffer
+    families prefilled with FILL.  Asserts that the row padding and the member gaps of all 16 buffers still hold FILL and returns every
+    member's four parents."""
+    L, M = S._lib, len(states)
+    sy = Nx + 6 + PAD
+    sm = (Ny + 6) * sy + GAP
+    sfx, tdt = ("f64", torch.float64) if dtype == np.float64 else ("f32", torch.float32)
+    outside = np.ones(M * sm, dtype=bool)
+    view = lambda flat, m: flat[m * sm:m * sm + (Ny + 6) * sy].reshape(Ny + 6, sy)[:, :Nx + 6]
+    for m in range(M):
+        view(outside, m)[...] = False
+    fams = []
+    for fam in range(4):
+        flats = [np.full(M * sm, FILL, dtype=dtype) for _ in range(4)]
+        if fam == 0:
+            for k in range(4):
+                for m in range(M):
+                    view(flats[k], m)[...] = states[m][k]
+        fams.append([torch.from_numpy(a).cuda() for a in flats])
+    table = np.full((M, 4, 4), np.nan)
+    for m, gr in enumerate(grads):
+        table[m, 3] = [np.nan if v is None else v for v in (gr or (None,) * 4)]
+    gt = torch.from_numpy(table).to(tdt).cuda()
+    flags = (L.STRICT if strict else 0) | (L.BOUNDED_X if topo[0] == B else 0) | (L.BOUNDED_Y if topo[1] == B else 0)
+    swapped = ctypes.c_int(-1)
+    head = [L.ptr_array([t.data_ptr() for t in ts]) for ts in fams] + [M, sm, Nx, Ny, 3, 3, sy, dx, dy]
+    if params is None:
+        rc = getattr(L.lib(), f"swmhd_ensemble_step_rk3_bc_{sfx}")(*head, G, F, form, 2 - form, dt, 1, gt.data_ptr(), flags, ctypes.byref(swapped), None)
+    else:
+        pt = torch.from_numpy(np.asarray(params, dtype=np.float64)).to(tdt).cuda()
+        rc = getattr(L.lib(), f"swmhd_ensemble_step_rk3_bc_params_{sfx}")(*head, pt.data_ptr(), form, 2 - form, 1, gt.data_ptr(), flags,
+                                                                          ctypes.byref(swapped), None)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert swapped.value in (0, 1)
+    host = [[t.cpu().numpy() for t in ts] for ts in fams]
+    for fam in host:
+        for a in fam:
+            assert bool((a[outside] == FILL).all()), "row padding or a gap between members was written"
+    return [[view(a, m).copy() for a in host[swapped.value]] for m in range(M)]
+
+
+def check_wall_shape(S, O, shape, topo, form, dtype, strict, params=None):
+    """One step of 3 pitched members with distinct states and distinct gradients of A: strict members bitwise the oracle's time_step
+    with that member's gradients (and (g, f, dt)), fast members within the fast tolerance of a fast single Bounded model of the member."""
+    Nx, Ny = shape
+    g = grid_for(S, Nx, Ny, topo)
+    grads = wall_grads(topo)
+    states = member_states(O, Nx, Ny, topo, form, grads, 100 * Nx + Ny, g.dx, g.dy, dtype)
+    assert all(not np.array_equal(states[i][k], states[j][k]) for k in range(4) for i in range(3) for j in range(i))
+    got = step_pitched_members(S, Nx, Ny, topo, form, states, grads, dtype, strict, g.dx, g.dy, DT, params)
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    for m, (q, gr) in enumerate(zip(states, grads)):
+        gm, fm, dtm = (G, F, DT) if params is None else params[m]
+        if strict:
+            want = [a.copy() for a in q]
+            O.time_step(*want, Nx, Ny, 3, 3, g.dx, g.dy, dtm, form, 2 - form, gm, fm, nthreads=4, topo=topo, gradA=gr)
+            for k, (w, a) in enumerate(zip(want, got[m])):
+                assert bitwise(w, a), f"member {m} field {k}: strict != oracle by {np.abs(w.astype(np.float64) - a).max()} with (g, f, dt) = {gm, fm, dtm}"
+        else:
+            model = S.ShallowWaterModel(g, gm, fm, formulation=FORM[form], dtype=tdt, strict=False, boundary_conditions=bcs_for(S, gr))
+            for f, a in zip(model._raw_fields, q):
+                f.data.copy_(torch.from_numpy(a))
+            model.update_state()
+            model.time_step(dtm)
+            model.synchronize()
+            for k, (s, a) in enumerate(zip(model.fields, got[m])):
+                err = np.abs(s.numpy().astype(np.float64) - a).max()
+                print(f"member {m} field {k}: fast ensemble - fast model = {err:.3e}, bitwise: {bitwise(s.numpy(), a)}")
+                assert close(s.numpy(), a, dtype), f"member {m} field {k}: fast ensemble off the fast model by {err}"
+
+
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("form", [1, 0], ids=["vi", "cons"])
+@pytest.mark.parametrize("topo", SC.WALL_TOPOS, ids=["PB", "BP", "BB"])
+@pytest.mark.parametrize("shape", SC.WALL_SHAPES, ids=[f"{a}x{b}" for a, b in SC.WALL_SHAPES])
+def test_wall_shapes_on_pitched_members(swmhd, oracle, shape, topo, form, dtype, strict):
+    """The wall body of the ensemble kernel at the shapes of the single grid's wall matrix (a tile edge 1 and 3 cells from a wall, on
+    it, both walls in one tile, several tiles a side), one RK3 step on every Bounded topology."""
+    check_wall_shape(swmhd, oracle, shape, topo, form, dtype, strict)

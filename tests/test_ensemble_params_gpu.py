@@ -21,7 +21,8 @@ if __name__ == "__main__":
 
 import helpers as Hh
 from test_bounded_oracle import state, P, B
-from test_ensemble_bounded_gpu import GRADS_PB, bcs_for, bitwise, close, grid_for, member_arrays, member_states
+import stage_cases as SC
+from test_ensemble_bounded_gpu import GRADS_PB, bcs_for, bitwise, check_wall_shape, close, grid_for, member_arrays, member_states
 
 pytestmark = pytest.mark.gpu
 FORM = {0: "Conservative", 1: "VectorInvariant"}
@@ -111,6 +112,18 @@ def test_strict_periodic_members_equal_oracle(swmhd, oracle, form, shape):
 def test_strict_bounded_members_equal_oracle(swmhd, oracle, form, topo):
     """Per-member gradients combined with per-member parameters."""
     check_strict(swmhd, oracle, grid_for(swmhd, 48, 40, topo), topo, form, 9)
+
+
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("form", [1, 0], ids=["vi", "cons"])
+@pytest.mark.parametrize("topo", SC.WALL_TOPOS, ids=["PB", "BP", "BB"])
+@pytest.mark.parametrize("shape", SC.WALL_SHAPES, ids=[f"{a}x{b}" for a, b in SC.WALL_SHAPES])
+def test_wall_shapes_on_pitched_members_with_their_own_parameters(swmhd, oracle, shape, topo, form, dtype, strict):
+    """The wall body of the PAR ensemble kernel at the shapes of the single grid's wall matrix: one RK3 step of 3 pitched members with
+    distinct states, gradients and (g, f, dt) (one f negative) -- strict bitwise the oracle's time_step with the member's gradients and
+    parameters, fast within the fast tolerance of a fast single Bounded model with them; row padding and gaps untouched."""
+    check_wall_shape(swmhd, oracle, shape, topo, form, dtype, strict, params=list(zip(GS, FS, DTS))[:3])
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])

@@ -10,6 +10,12 @@ wall-strict) x precision x call form, with the number of cases per path and the 
 
     python tools/stage_matrix_report.py --tile [out.json] (default: profiles/stage_matrix/achieved_tile.json)
 
+And for the ensemble matrix (the calls of tests/test_ensemble_stage_matrix_gpu.py) per ensemble path (ens4, ens8, ens-strict, par4,
+par-strict) x precision x call form, over all members, with the observation the test does not assert: in how many calls of par4 and
+ens8 every member happened to be bitwise the single-grid call on the member alone (the header promises that for ens4 only):
+
+    python tools/stage_matrix_report.py --ensemble [out.json] (default: profiles/stage_matrix/achieved_ensemble.json)
+
 The strict paths are compared bitwise: their ratio is 0 (every written cell equal to the oracle's) or inf."""
 import json
 import os
@@ -71,8 +77,39 @@ def main_tile(out_path):
     return 1 if failures else 0
 
 
+def main_ensemble(out_path):
+    import torch
+    import swmhd_amd as S
+    from oracle import oracle as O
+    worst, layouts, failures, ncases, refusals, observed, workgroups = {}, {}, [], {}, 0, {}, {}
+    t0 = time.perf_counter()
+    for case in SC.ens_matrix():
+        path, Nx, Ny, members, form, lor, dtype, flags, dense = case
+        ncases[path] = ncases.get(path, 0) + 1
+        refusals += sum(1 for v, _ in SC.ens_calls() if v in SC.ENS_PATHS[path]["refused"])
+        layouts[f"{Nx} x {Ny} x {members} members {path}"] = SC.check_ens_layout(S._lib, path, Nx, Ny, members, form, dtype, flags)
+        workgroups.setdefault(path, set()).add(SC.ens_workgroups(path, Nx, Ny, members))
+        single = {"ens4": "assert", "par4": "observe", "ens8": "observe"}.get(path)
+        failures += [f"{SC.ens_case_id(*case)} {m}" for m in SC.run_ens_cases(S, O, *case, worst=worst, single=single, observed=observed)]
+    seconds = time.perf_counter() - t0
+    rec = {"device": torch.cuda.get_device_name(0), "kernel_source_hash": S._lib.source_hash(), "cases": sum(ncases.values()),
+           "cases_per_path": ncases, "calls_per_case": len(SC.ens_calls()), "refused_calls": refusals, "seconds": float(f"{seconds:.1f}"),
+           "workgroups_per_launch": {k: sorted(v) for k, v in workgroups.items()}, "failures": failures,
+           "max_error_over_bound": {k: float(f"{v:.3g}") for k, v in sorted(worst.items())},
+           "calls_bitwise_the_single_grid_call": {k: {"bitwise": v[0], "calls": v[1]} for k, v in sorted(observed.items())}, "layouts": layouts}
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+    print(json.dumps(rec["max_error_over_bound"], indent=1))
+    print(json.dumps(rec["calls_bitwise_the_single_grid_call"], indent=1))
+    print(f"{rec['cases']} cases x {len(SC.ens_calls())} calls ({refusals} of them refusals) in {seconds:.1f} s, {len(failures)} failures -> {out_path}")
+    return 1 if failures else 0
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--ensemble":
+        sys.exit(main_ensemble(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "stage_matrix", "achieved_ensemble.json")))
     if args and args[0] == "--tile":
         sys.exit(main_tile(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "stage_matrix", "achieved_tile.json")))
     sys.exit(main(args[0] if args else os.path.join(ROOT, "profiles", "stage_matrix", "achieved.json")))
