@@ -10,7 +10,8 @@ g = 9.81, f = 1, RK3, A = 0.5|y| ("uniform B_x") or the two Gaussians, h = 1, th
 reference's (SWMHD_example.jl:47-61: time, iteration, max|u|, max|A|, min h, wall time) and one row of the energies the reference
 sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the fields incl. halos as .npy (the JLD2 writer's role, :80-84).
 --frames T collects the reference's output frames on the device (swmhd_amd.FieldTimeSeries: the fields (u, v, A, s) every T time units,
-:80-84, or those of --frame-fields out of u v h A s B_x B_y, as --frame-dtype f32|f64) and writes them to <out>/frames.npz at the end.
+:80-84, or those of --frame-fields out of u v h A s B_x B_y and the derived vorticity divergence current potential_vorticity, as
+--frame-dtype f32|f64) and writes them to <out>/frames.npz at the end.
 --zonal-means T collects x-averaged profiles on the device (swmhd_amd.ZonalMeanTimeSeries: Oceananigans' Average(u, dims = 1) in an
 output writer; every T time units the float64 row means of --zonal-names out of u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA, one
 launch per sample and no frame) and writes them to <out>/zonal_means.npz at the end; in single, --amps and --channel --gradients runs.
@@ -62,7 +63,7 @@ def main():
     ap.add_argument("--energies", default=None, help="CSV file for (time, KE, ME, PE, total)")
     ap.add_argument("--dump-every", type=float, default=0.0, help="model time between field dumps (0 = none)")
     ap.add_argument("--frames", type=float, default=0.0, help="model time between output frames (0 = none); written to <out>/frames.npz")
-    ap.add_argument("--frame-fields", default="u,v,A,s", help="comma-separated fields of a frame: u v h A s B_x B_y")
+    ap.add_argument("--frame-fields", default="u,v,A,s", help="comma-separated fields of a frame: u v h A s B_x B_y vorticity divergence current potential_vorticity")
     ap.add_argument("--frame-dtype", choices=["f32", "f64"], default="f32")
     ap.add_argument("--zonal-means", type=float, default=0.0, help="model time between zonal-mean samples (0 = none); written to <out>/zonal_means.npz")
     ap.add_argument("--zonal-names", default="u,v,A,uv,B_xB_y,vA", help="comma-separated profiles: u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA")

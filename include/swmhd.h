@@ -767,5 +767,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 
 /* zonal means (swmhd_zonal_means_*, swmhd_ensemble_zonal_means_*, SWMHD_ZM_*): x-averaged profiles of the output fields and their products */
 #include "swmhd_zonal.h"
+/* derived frames (swmhd_derived_fields_*, swmhd_ensemble_derived_fields[_params]_*, SWMHD_DRV_*): vorticity, divergence, current, PV */
+#include "swmhd_derived.h"
 
 #endif /* SWMHD_H */

@@ -102,6 +102,26 @@ function diagnostics(q, grid; formulation = VECTOR_INVARIANT, g = 9.81, h_ref = 
     return Array(out)
 end
 
+const DRV_VORTICITY, DRV_DIVERGENCE, DRV_CURRENT, DRV_PV = Cint(1), Cint(2), Cint(4), Cint(8)      # SWMHD_DRV_* (include/swmhd_derived.h)
+
+"""
+    derived_fields!(frame, q, grid; which = DRV_VORTICITY | DRV_CURRENT, f = 1.0, formulation = VECTOR_INVARIANT)
+
+What a writer given `∂x(v) - ∂y(u)` would store, made on the device in one launch (swmhd_derived_fields_f64): the fields of `which` in bit
+order -- vorticity and potential vorticity `(ζ + f) / h` at the corners, divergence and current `∇²A` at the centres -- halo-stripped
+into `frame`, a Float32 or Float64 device array (Nx, Ny, number of fields).  q = (u|uh, v|vh, h, A).  Periodic directions are read
+through their periodic images (no halo fill needed); Bounded directions from the halos as `fill_halos!` left them.
+"""
+function derived_fields!(frame, q, grid; which = DRV_VORTICITY | DRV_CURRENT, f = 1.0, formulation = VECTOR_INVARIANT)
+    fl = (topology(grid, 1) == Periodic ? SWMHD_WRAP_X : Cint(0)) | (topology(grid, 2) == Periodic ? SWMHD_WRAP_Y : Cint(0))
+    check(ccall((:swmhd_derived_fields_f64, libswmhd), Cint,
+                (Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cint, Cint, Cint, Int64, Float64, Float64, Cint, Float64,
+                 Cint, Cint, Cint, Ptr{Cvoid}, Cint, Int64, Int64, Cint, Ptr{Cvoid}),
+                pp(q[1]), pp(q[2]), pp(q[3]), pp(q[4]), grid.Nx, grid.Ny, grid.Hx, grid.Hy, stride_y(q[1]), grid.Δxᶜᵃᵃ, grid.Δyᵃᶜᵃ,
+                formulation, f, 0, grid.Ny, which, pointer(frame), sizeof(eltype(frame)), grid.Nx, grid.Nx * grid.Ny, fl, hipstream()))
+    return frame
+end
+
 "Topology flags of a grid for the tendency entry points (the reference tests `topology(grid, d) == Bounded`, sw_mhd_divergence_functions.jl:42)."
 topology_flags(grid) = (topology(grid, 1) == Bounded ? SWMHD_BOUNDED_X : Cint(0)) | (topology(grid, 2) == Bounded ? SWMHD_BOUNDED_Y : Cint(0))
 

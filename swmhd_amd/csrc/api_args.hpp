@@ -95,6 +95,7 @@ constexpr int LORENTZ_FLAGS = SWMHD_STRICT | KERNEL_FLAGS;
 constexpr int SUBSTEP_FLAGS = SWMHD_STRICT;
 constexpr int OUTPUT_FLAGS = WRAP_FLAGS;
 constexpr int ZONAL_FLAGS = WRAP_FLAGS;   // swmhd_zonal_means: the frame's
+constexpr int DERIVED_FLAGS = WRAP_FLAGS; // swmhd_derived_fields: the frame's
 // swmhd_tendencies[_rk3], swmhd_step_rk3 and the slab drivers' stages
 constexpr int TEND_FLAGS = SWMHD_STRICT | KERNEL_FLAGS | WRAP_FLAGS | SWMHD_LEAVE_ROOM | BOUNDED_FLAGS | SWMHD_GM_IS_PREV_STATE |
                            SWMHD_RK3_ANCHOR | OPEN_FLAGS;

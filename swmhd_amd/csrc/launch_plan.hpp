@@ -1,5 +1,5 @@
-// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel and the zonal-mean
-// kernel: what a call will enqueue, decided as data before anything is launched.
+// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the zonal-mean
+// kernel and the derived-frame kernel: what a call will enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
 #pragma once
@@ -466,6 +466,31 @@ inline int zonal_depth(int Nx) {
     int levels = 0;
     while ((1 << levels) < lanes) ++levels;
     return terms0 - 1 + levels;
+}
+
+// ---- the chunks of one derived-frame call (derived.hip) -----------------------------------------------------------------------------
+// One-shot workgroups in address order, as the output frames: a thread takes one 4-cell chunk of one row, a 256-thread workgroup 256
+// consecutive chunks of the row-major list of (row, chunk); the member is blockIdx.y.
+constexpr int DERIVED_NT = 256, DERIVED_VEC = 4;
+struct DerivedPlan {
+    int nchunk;       // chunks of one row: the last may be ragged
+    long threads;     // rows * nchunk: chunks of one member
+    long blocks;      // workgroups of one member (grid x); grid y = members
+    int members;
+    bool none;        // nothing to compute: no rows or no members
+    bool too_many;    // 2^31 workgroups or more: beyond the grid of one launch
+};
+// members: 1 for a single grid
+inline DerivedPlan derived_plan(int Nx, int rows, int members) {
+    DerivedPlan p{};
+    p.none = Nx <= 0 || rows <= 0 || members <= 0;
+    if (p.none) return p;
+    p.members = members;
+    p.nchunk = (int)(((long)Nx + DERIVED_VEC - 1) / DERIVED_VEC);
+    p.threads = (long)rows * p.nchunk;
+    p.blocks = (p.threads + DERIVED_NT - 1) / DERIVED_NT;
+    p.too_many = p.blocks >= (1L << 31) || p.blocks * members >= (1L << 31);   // (in this order: the product cannot overflow)
+    return p;
 }
 
 }  // namespace swmhd

@@ -1,0 +1,81 @@
+"""Derived frames: relative vorticity, velocity divergence, vertical current and potential vorticity, made on the device.
+
+A 2-D MHD turbulence run is read by zeta = dv/dx - du/dy, J = laplace(A), the divergence (the gravity-wave part, and the first thing to
+look at when a run goes unstable) and the shallow-water potential vorticity q = (zeta + f) / h.  In Oceananigans each is one line handed
+to the writer; here `derived_fields` (a method of ShallowWaterModel and of the ensembles) enqueues ONE kernel (swmhd_derived_fields_*,
+include/swmhd_derived.h) that differences the four parents into a halo-stripped device tensor in the writer's element type, for all
+members of an ensemble, without a halo fill in front and without a host synchronisation.  The writer is swmhd_amd.output's
+FieldTimeSeries, which takes these names mixed with the seven of the frame.  Zonal means and integrals of these fields are out of scope
+(DESIGN.md section 7).
+"""
+import torch
+
+from . import _lib
+from .fields import _stream_ptr
+
+DEFAULT_NAMES = ("vorticity", "current")
+_ELEM = {torch.float32: 4, torch.float64: 8}
+
+
+def _runs(names, tracers=()):
+    """The fields as launches: the kernel writes the fields of a mask in bit order (vorticity divergence current potential_vorticity),
+    so `names` is cut into runs that ascend in that order, as output._runs cuts a frame."""
+    runs = []
+    for n in names:
+        if n in tracers:
+            raise _lib.SwmhdError(f"output field {n!r} is a tracer: frames hold {' '.join(_lib.OUT_BITS)} only; read model.tracers[{n!r}]")
+        if n not in _lib.DRV_BITS:
+            raise _lib.SwmhdError(f"derived field {n!r}: one of {' '.join(_lib.DRV_BITS)}")
+        bit = _lib.DRV_BITS[n]
+        if runs and bit > runs[-1][-1]:
+            runs[-1].append(bit)
+        else:
+            runs.append([bit])
+    if not runs:
+        raise _lib.SwmhdError("derived_fields: no field names")
+    return runs
+
+
+def state_pointers(model):
+    """(the four parents' device pointers, row stride, device, is an ensemble) of the state as it stands now"""
+    if getattr(model, "members", None) is not None:
+        q = model._state                  # (whichever set of tensors is the state NOW: the ping-pong roles flip every stage)
+        return [t.data_ptr() for t in q], q[0].stride(1), q[0].device, True
+    model._join()                         # a ring exchange of this state may still be in flight
+    q = model._raw_fields
+    return [f.ptr for f in q], q[0].stride_y, q[0].data.device, False
+
+
+def launch(model, ptrs, sy, ens, which, first, out):
+    """One swmhd_[ensemble_]derived_fields[_params]_* launch: the fields of mask `which` into `out` from its field `first` on."""
+    g, sfx = model.grid, model.sfx
+    frame = (0, g.Ny, which, first.data_ptr(), out.element_size(), out.stride(-2), out.stride(-3))
+    if not ens:
+        f = getattr(model._L, f"swmhd_derived_fields_{sfx}")
+        rc = f(*ptrs, g.Nx, g.Ny, g.Hx, g.Hy, sy, g.dx, g.dy, model.form_code, model.f, *frame, model._rwrap, _stream_ptr())
+    else:
+        par = model.parameters is not None      # each member's f, from the table
+        f = getattr(model._L, f"swmhd_ensemble_derived_fields_{'params_' if par else ''}{sfx}")
+        rc = f(*ptrs, model.members, model.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, sy, g.dx, g.dy, model.form_code,
+               model.parameters.data_ptr() if par else model.f, *frame, out.stride(0), model._rwrap, _stream_ptr())
+    _lib.check(rc, "swmhd_derived_fields")
+
+
+def enqueue_derived(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32):
+    """ShallowWaterModel.derived_fields / ShallowWaterEnsemble.derived_fields: see there."""
+    names = tuple(names)
+    runs = _runs(names, getattr(model, "tracer_names", ()))
+    ptrs, sy, dev, ens = state_pointers(model)
+    g = model.grid
+    shape = ((model.members,) if ens else ()) + (len(names), g.Ny, g.Nx)
+    if out is None:
+        if array_type not in _ELEM:
+            raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
+        out = torch.empty(shape, dtype=array_type, device=dev)
+    elif not (out.is_cuda and out.dtype in _ELEM and tuple(out.shape) == shape and out.stride(-1) == 1):
+        raise _lib.SwmhdError(f"derived_fields: out must be a float32 / float64 CUDA tensor of shape {shape} with unit stride in x")
+    k = 0
+    for bits in runs:
+        launch(model, ptrs, sy, ens, sum(bits), out.select(-3, k), out)
+        k += len(bits)
+    return out

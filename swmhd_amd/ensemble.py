@@ -384,6 +384,14 @@ class ShallowWaterEnsemble:
         from .output import enqueue_frame
         return enqueue_frame(self, names, out, array_type)
 
+    # --- derived frames of all members in one launch (swmhd_ensemble_derived_fields[_params]_*) ----------------------
+    def derived_fields(self, names=("vorticity", "current"), out=None, array_type=torch.float32):
+        """ShallowWaterModel.derived_fields for every member: the device tensor (members, len(names), Ny, Nx); member m of it is
+        bitwise member(m).derived_fields(...), the potential vorticity with member m's coriolis_f (from the parameter table where the
+        ensemble has one).  One launch, no host synchronisation."""
+        from .derived import enqueue_derived
+        return enqueue_derived(self, names, out, array_type)
+
     # --- zonal means of all members in one launch (swmhd_ensemble_zonal_means_*) -------------------------------------
     def zonal_means(self, names=("u", "v", "A"), out=None):
         """ShallowWaterModel.zonal_means for every member: the float64 device tensor (members, len(names), Ny); member m of it is

@@ -555,6 +555,17 @@ class ShallowWaterModel:
         from .output import enqueue_frame
         return enqueue_frame(self, names, out, array_type)
 
+    # --- derived frames (Oceananigans: ∂x(v) - ∂y(u) handed to the writer): one launch, no halo fill, no host synchronisation ----
+    def derived_fields(self, names=("vorticity", "current"), out=None, array_type=torch.float32):
+        """Enqueue the differenced fields of the current state: the device tensor (len(names), Ny, Nx) of vorticity (dv/dx - du/dy at
+        the corners), divergence (du/dx + dv/dy at the centres), current (J = laplace(A) at the centres) and potential_vorticity
+        ((vorticity + coriolis_f) / h at the corners) -- swmhd_derived_fields_* in include/swmhd_derived.h; u, v are the frame's
+        velocities for the conservative model too -- halo-stripped, in `array_type` (or into `out`, float32 or float64 of that shape),
+        any order and repetition of names.  Points: i = 1..Nx, j = 1..Ny, on Bounded directions too.  On a y-slab: this rank's rows.
+        Reads the periodic images where the step leaves the halos stale.  FieldTimeSeries takes these names among the frame's."""
+        from .derived import enqueue_derived
+        return enqueue_derived(self, names, out, array_type)
+
     # --- zonal means (Oceananigans: Average(u, dims = 1)): one launch, no frame-sized buffer, no host synchronisation ----
     def zonal_means(self, names=("u", "v", "A"), out=None):
         """Enqueue the x-averaged profiles of the current state: the float64 device tensor (len(names), Ny), row j of profile k =

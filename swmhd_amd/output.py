@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from .derived import launch as launch_derived, state_pointers
 from .fields import _stream_ptr
 
 DEFAULT_NAMES = ("u", "v", "A", "s")    # the reference's writer
@@ -30,7 +31,8 @@ def _runs(names, tracers=()):
         if n in tracers:
             raise _lib.SwmhdError(f"output field {n!r} is a tracer: frames hold {' '.join(_lib.OUT_BITS)} only; read model.tracers[{n!r}]")
         if n not in _lib.OUT_BITS:
-            raise _lib.SwmhdError(f"output field {n!r}: one of {' '.join(_lib.OUT_BITS)} (velocities u, v also for the conservative model)")
+            raise _lib.SwmhdError(f"output field {n!r}: one of {' '.join(_lib.OUT_BITS)} (velocities u, v also for the conservative model); "
+                                  f"frames also take the derived fields {' '.join(_lib.DRV_BITS)}")
         bit = _lib.OUT_BITS[n]
         if runs and bit > runs[-1][-1]:
             runs[-1].append(bit)
@@ -38,6 +40,25 @@ def _runs(names, tracers=()):
             runs.append([bit])
     if not runs:
         raise _lib.SwmhdError("output_fields: no field names")
+    return runs
+
+
+def _frame_runs(names, tracers=()):
+    """[(derived, bits)]: `names` as launches where the derived fields of swmhd_amd.derived (vorticity divergence current
+    potential_vorticity) stand among the seven of the frame: a run also ends where the kernel changes.  Without a derived name these
+    are the runs of _runs, refusals included."""
+    if not any(n in _lib.DRV_BITS and n not in tracers for n in names):
+        return [(False, bits) for bits in _runs(names, tracers)]
+    runs = []
+    for n in names:
+        drv = n in _lib.DRV_BITS and n not in tracers
+        if not drv:
+            _runs((n,), tracers)          # (refuses a tracer or an unknown name, with the frame's message)
+        bit = (_lib.DRV_BITS if drv else _lib.OUT_BITS)[n]
+        if runs and runs[-1][0] == drv and bit > runs[-1][1][-1]:
+            runs[-1][1].append(bit)
+        else:
+            runs.append((drv, [bit]))
     return runs
 
 
@@ -49,16 +70,9 @@ def frame_shape(model, names):
 def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32):
     """ShallowWaterModel.output_fields / ShallowWaterEnsemble.output_fields: see there."""
     names = tuple(names)
-    runs = _runs(names, getattr(model, "tracer_names", ()))
-    ens = getattr(model, "members", None) is not None
+    runs = _frame_runs(names, getattr(model, "tracer_names", ()))
     g = model.grid
-    if ens:
-        q = model._state                  # (whichever set of tensors is the state NOW: the ping-pong roles flip every stage)
-        ptrs, sy, dev = [t.data_ptr() for t in q], q[0].stride(1), q[0].device
-    else:
-        model._join()                     # a ring exchange of this state may still be in flight
-        q = model._raw_fields
-        ptrs, sy, dev = [f.ptr for f in q], q[0].stride_y, q[0].data.device
+    ptrs, sy, dev, ens = state_pointers(model)
     shape = frame_shape(model, names)
     if out is None:
         if array_type not in _ELEM:
@@ -71,9 +85,13 @@ def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32
     flags = model._rwrap
     sfx = model.sfx
     k = 0
-    for bits in runs:
+    for derived, bits in runs:
         which = sum(bits)
         first = out.select(-3, k)
+        if derived:                       # (the kernel of swmhd_amd.derived: same frame layout, same flags)
+            launch_derived(model, ptrs, sy, ens, which, first, out)
+            k += len(bits)
+            continue
         if ens:
             f = getattr(model._L, f"swmhd_ensemble_output_fields_{sfx}")
             rc = f(*ptrs, model.members, model.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, sy, g.dx, g.dy, model.form_code, 0, g.Ny, which,
@@ -124,7 +142,9 @@ def frame_iterations(schedule, dt, nsteps):
 class FieldTimeSeries:
     """The reference's field writer on the device: `capacity` frames of `names` in one tensor, plus the host lists `times` and
     `iterations`.  frames: (capacity, len(names), Ny, Nx); for an ensemble (capacity, members, len(names), Ny, Nx); on a y-slab the
-    rank's own rows.  Names: u v h A s B_x B_y (velocities also for the conservative model, which stores uh, vh).
+    rank's own rows.  Names: u v h A s B_x B_y (velocities also for the conservative model, which stores uh, vh) and, in any mixture
+    with them, the derived fields vorticity divergence current potential_vorticity (swmhd_amd.derived: a kernel of their own, so a
+    launch ends where the kernel changes).
 
     array_type defaults to float32.  That default is this library's: the reference's field writer was given no array type and its
     NetCDF writer (the energies) is the one that asks for Array{Float64}; what Oceananigans' JLD2 writer stores unasked is
@@ -135,7 +155,7 @@ class FieldTimeSeries:
 
     def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None, array_type=torch.float32):
         self.model, self.names, self.schedule = model, tuple(names), schedule
-        _runs(self.names, getattr(model, "tracer_names", ()))
+        _frame_runs(self.names, getattr(model, "tracer_names", ()))
         if array_type not in _ELEM:
             raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
         if capacity is None or int(capacity) < 1:
