@@ -164,13 +164,38 @@ def _check_anchor(out, ref_terms, w, tol_scale, eps, tag):
     assert np.isfinite(out).all() and err <= bound, (tag, err, bound)
 
 
+def _check_update(out, c, G, Gm, dt, t, tol_scale, tag):
+    """out = c + dt (gamma G + zeta Gm) (Gm None: c + dt gamma G) of a fast classic stage with COEF's gamma and zeta against the same
+    expression in longdouble with the strict G and the coefficients as the kernel receives them.  Bound: that of the single-grid stage
+    matrix (stage_cases.stage_bounds): dt weight (tendency bound) + 4 eps max|addends and result|, weight = |gamma| + |zeta| with Gm,
+    |gamma| without."""
+    LD = np.longdouble
+    eps = float(np.finfo(t).eps)
+    gam, zet, dtl = LD(t(COEF["gamma"])), LD(t(COEF["zeta"])), LD(t(dt))
+    ga, za, dta = abs(float(gam)), abs(float(zet)), float(dtl)
+    amax = lambda a: float(np.abs(a).max())
+    terms = [dta * ga * amax(G), amax(c)]
+    if Gm is None:
+        ref, weight = c.astype(LD) + dtl * gam * G.astype(LD), ga
+    else:
+        ref, weight = c.astype(LD) + dtl * (gam * G.astype(LD) + zet * Gm.astype(LD)), ga + za
+        terms.append(dta * za * amax(Gm))
+    err = float(np.abs(out.astype(LD) - ref).max())
+    bound = dta * weight * tol_scale + 4 * eps * max(terms + [amax(ref)])
+    print(f"update {tag}: err {err:.3e}, bound {bound:.3e}, ratio {err / bound:.3g}")
+    assert np.isfinite(out).all() and err <= bound, (tag, err, bound)
+
+
 @pytest.mark.parametrize("sfx,rough", [("f64", False), ("f64", True), ("f32", True), ("f32", False)])
 @pytest.mark.parametrize("form", [1, 0])
 @pytest.mark.parametrize("Nx,Ny", EC.SHAPES + [(96, 96)])
 def test_fast_stages_within_the_tolerance_of_A(swmhd, oracle, Nx, Ny, form, sfx, rough):
     """Fast ensemble stages, 2 members x 3 tracers, with a scalar dt and with the table (two different dt): the classic stage's stored
     Gn against the strict ensemble launch in the norm and with the bound of the single-grid test; the anchored stages' outputs
-    (cnew and W of the first, cnew of a later one) with that bound carried through the update (module docstring)."""
+    (cnew and W of the first, cnew of a later one) with that bound carried through the update (module docstring).  The classic
+    stages' new state: cnew of the G- stage, and cnew of the first stage (Gm == NULL; store_G 1 and 0, the latter leaving Gn alone) with
+    the scalar dt and with the table, per member and tracer within the G--stage | first-stage bound of the single-grid stage matrix
+    (_check_update) with the strict tendency as G and the member's dt."""
     L = swmhd._lib
     M, K = 2, 3
     d = EC.StageInputs(oracle, Nx, Ny, form, sfx, rough, members=M, K=K, reference=False)
@@ -191,9 +216,23 @@ def test_fast_stages_within_the_tolerance_of_A(swmhd, oracle, Nx, Ny, form, sfx,
     launch(L, d, q_d, c_d, a2, junk, Gm_d, M, 0, wrap | L.RK3_ANCHOR, dt=COEF["dt"], gamma=gamma, zeta=0.0)    # anchored later stage: Gm is W
     launch(L, d, q_d, c_d, p1, pW, None, M, 0, wrap | L.RK3_ANCHOR, gamma=gamma, zeta=wz, params=table)
     launch(L, d, q_d, c_d, p2, pjunk, Gm_d, M, 0, wrap | L.RK3_ANCHOR, gamma=gamma, zeta=0.0, params=table)
+    # fast first stage (Gm == NULL), G stored and not, with the scalar dt and with the table; the zeta passed must be ignored
+    firsts = {}
+    for how in ("scalar", "table"):
+        for store in (1, 0):
+            cn, gn = [sentinel(d, M) for _ in range(K)], [sentinel(d, M) for _ in range(K)]
+            kw = dict(params=table) if how == "table" else dict(dt=COEF["dt"])
+            launch(L, d, q_d, c_d, cn, gn, None, M, store, wrap, gamma=COEF["gamma"], zeta=COEF["zeta"], **kw)
+            firsts[how, store] = (cn, gn)
     torch.cuda.synchronize()
     host = lambda ts: [_members_interior(x.cpu().numpy(), d, M) for x in ts]
     Gs_h, Gf_h, a1_h, W_h, a2_h, p1_h, pW_h, p2_h = (host(x) for x in (Gs, Gf, a1, W, a2, p1, pW, p2))
+    cf_h = host(cf)
+    firsts_h = {key: (host(cn), host(gn)) for key, (cn, gn) in firsts.items()}
+    for (how, store), (cn, gn) in firsts.items():
+        if not store:             # store_G = 0 leaves Gn alone, pad columns, halos and member gaps included
+            for x in gn:
+                assert np.array_equal(x.cpu().numpy(), np.full(x.numel(), TC.SENTINEL, dtype=t)), (how, store)
     for x in junk + pjunk:        # an anchored later stage writes nothing through Gn
         assert np.array_equal(x.cpu().numpy(), np.full(x.numel(), TC.SENTINEL, dtype=t))
     dt64 = float(t(COEF["dt"]))
@@ -215,6 +254,14 @@ def test_fast_stages_within_the_tolerance_of_A(swmhd, oracle, Nx, Ny, form, sfx,
             _check_anchor(p1_h[k][m], (c, G), dts[m] * g_t, tol * scale, eps, ("params first cnew",) + tag)
             _check_anchor(pW_h[k][m], (c, G), dts[m] * wz, tol * scale, eps, ("params first W",) + tag)
             _check_anchor(p2_h[k][m], (Wop, G), dts[m] * g_t, tol * scale, eps, ("params later cnew",) + tag)
+            # the classic updates: the G- stage (Wop is its Gm) and the first stage, the latter with the member's dt of the table
+            _check_update(cf_h[k][m], c, G, Wop, dt64, t, tol * scale, ("later cnew",) + tag)
+            for (how, store), (cn_h, gn_h) in firsts_h.items():
+                dt_m = dts[m] if how == "table" else dt64
+                _check_update(cn_h[k][m], c, G, None, dt_m, t, tol * scale, (f"first cnew {how} store_G={store}",) + tag)
+                if store:
+                    errG = np.abs(gn_h[k][m] - G).max()
+                    assert np.isfinite(gn_h[k][m]).all() and errG <= tol * scale, (how, m, k, errG / scale)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -16,6 +16,11 @@ ens8 every member happened to be bitwise the single-grid call on the member alon
 
     python tools/stage_matrix_report.py --ensemble [out.json] (default: profiles/stage_matrix/achieved_ensemble.json)
 
+And for the tracer stage matrix (the calls of tests/test_tracer_stage_matrix_gpu.py, tests/tracer_stage_cases.py) per path (fast,
+wall, wall-strict) x precision x call form, with the call in which the worst ratio of every path and precision occurred:
+
+    python tools/stage_matrix_report.py --tracers [out.json] (default: profiles/tracer_stage_matrix/achieved.json)
+
 The strict paths are compared bitwise: their ratio is 0 (every written cell equal to the oracle's) or inf."""
 import json
 import os
@@ -106,8 +111,47 @@ def main_ensemble(out_path):
     return 1 if failures else 0
 
 
+def main_tracers(out_path):
+    import torch
+    import swmhd_amd as S
+    from oracle import oracle as O
+    import tracer_stage_cases as TS
+    worst, layouts, failures, ncases, refusals, ncalls = {}, {}, [], {}, 0, 0
+    t0 = time.perf_counter()
+    for case in TS.matrix():
+        path, Nx, Ny, topo, form, dtype, wrap = case
+        ncases[path] = ncases.get(path, 0) + 1
+        for rows in TS.row_ranges(Ny):
+            ncalls += len(TS.calls())
+            refusals += sum(1 for v, _, _ in TS.calls() if v in TS.PATHS[path]["refused"])
+            nrows = Ny if rows is None else rows[1] - rows[0]
+            layouts[f"{Nx} x {nrows} rows"] = TS.check_layout(Nx, Ny, rows)
+        failures += [f"{TS.case_id(*case)} {m}" for m in TS.run_cases(S, O, *case, worst=worst)]
+    seconds = time.perf_counter() - t0
+    # the worst ratio per path and precision, with the call it occurred in
+    per_path = {}
+    for key, (ratio, where) in worst.items():
+        pp = key.rsplit("/", 1)[0]
+        if ratio >= per_path.get(pp, (-1.0, ""))[0]:
+            per_path[pp] = (ratio, where)
+    rec = {"device": torch.cuda.get_device_name(0), "kernel_source_hash": S._lib.source_hash(), "cases": sum(ncases.values()),
+           "cases_per_path": ncases, "calls": ncalls, "refused_calls": refusals, "seconds": float(f"{seconds:.1f}"), "failures": failures,
+           "max_error_over_bound": {k: float(f"{v[0]:.3g}") for k, v in sorted(worst.items())},
+           "worst_per_path_and_precision": {k: {"ratio": float(f"{v[0]:.3g}"), "call": v[1]} for k, v in sorted(per_path.items())},
+           "layouts": layouts}
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+    print(json.dumps(rec["max_error_over_bound"], indent=1))
+    print(json.dumps(rec["worst_per_path_and_precision"], indent=1))
+    print(f"{rec['cases']} cases, {ncalls} calls ({refusals} of them refusals) in {seconds:.1f} s, {len(failures)} failures -> {out_path}")
+    return 1 if failures else 0
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--tracers":
+        sys.exit(main_tracers(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "tracer_stage_matrix", "achieved.json")))
     if args and args[0] == "--ensemble":
         sys.exit(main_ensemble(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "stage_matrix", "achieved_ensemble.json")))
     if args and args[0] == "--tile":
