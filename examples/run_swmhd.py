@@ -15,6 +15,9 @@ sends to NetCDF (:74-77) into --energies (CSV).  --dump-every T writes the field
 --zonal-means T collects x-averaged profiles on the device (swmhd_amd.ZonalMeanTimeSeries: Oceananigans' Average(u, dims = 1) in an
 output writer; every T time units the float64 row means of --zonal-names out of u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA, one
 launch per sample and no frame) and writes them to <out>/zonal_means.npz at the end; in single, --amps and --channel --gradients runs.
+--zonal-spectra T collects zonal wavenumber spectra on the device (swmhd_amd.ZonalSpectrumTimeSeries: every T time units the row-averaged
+power spectra along x of --spectra-names out of u v h A s B_x B_y, by a double-precision row FFT in LDS; --size must be a power of two
+from 4 to 4096) and writes them to <out>/zonal_spectra.npz at the end, with the wavenumbers k and kx = 2 pi k / Lx.
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
 --dye adds one passive tracer c = tanh(y) to the run (ShallowWaterModel(tracers=("c",)): the reference's `tracers = (:A)` with a second
 name): its min / max join the progress line and the field goes into the --dump-every dumps.  With --amps, --coriolis, --gravity or
@@ -67,6 +70,8 @@ def main():
     ap.add_argument("--frame-dtype", choices=["f32", "f64"], default="f32")
     ap.add_argument("--zonal-means", type=float, default=0.0, help="model time between zonal-mean samples (0 = none); written to <out>/zonal_means.npz")
     ap.add_argument("--zonal-names", default="u,v,A,uv,B_xB_y,vA", help="comma-separated profiles: u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA")
+    ap.add_argument("--zonal-spectra", type=float, default=0.0, help="model time between zonal-spectrum samples (0 = none); written to <out>/zonal_spectra.npz")
+    ap.add_argument("--spectra-names", default="u,v,A", help="comma-separated spectra: u v h A s B_x B_y")
     ap.add_argument("--dye", action="store_true", help="advect one passive tracer c = tanh(y) with the flow")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
@@ -87,6 +92,8 @@ def main():
         ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
     if a.dts and a.zonal_means > 0:
         ap.error("--zonal-means is a schedule in time units: not with a per-member time step (--dts)")
+    if a.dts and a.zonal_spectra > 0:
+        ap.error("--zonal-spectra is a schedule in time units: not with a per-member time step (--dts)")
     if a.dye and a.channel:
         ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
     if a.amps or a.channel or a.sweep:
@@ -125,11 +132,14 @@ def main():
     e0 = rows[0][4]
     series, fevery = frame_writer(a, model, nsteps)
     zonal, zevery = zonal_writer(a, model, nsteps)
+    spectra, severy = spectra_writer(a, model, nsteps)
     model.time_step(a.dt)
     if fevery == 1:
         series.write()
     if zevery == 1:
         zonal.write()
+    if severy == 1:
+        spectra.write()
     model.capture_graph(a.dt)
     next_dump = a.dump_every
     t_start = time.perf_counter()
@@ -141,11 +151,15 @@ def main():
             n = min(n, fevery - model.iteration % fevery)
         if zevery:
             n = min(n, zevery - model.iteration % zevery)
+        if severy:
+            n = min(n, severy - model.iteration % severy)
         model.time_steps(n, a.dt)
         if fevery and model.iteration % fevery == 0:
             series.write(time=model.iteration * a.dt)         # one launch, no synchronisation
         if zevery and model.iteration % zevery == 0:
             zonal.write(time=model.iteration * a.dt)          # likewise
+        if severy and model.iteration % severy == 0:
+            spectra.write(time=model.iteration * a.dt)        # two launches, no synchronisation
         if model.iteration % a.every != 0 and model.iteration != nsteps:
             continue
         model.synchronize()
@@ -160,6 +174,7 @@ def main():
           f"energy drift abs(E - E0) * 100 = {abs(rows[-1][4] - e0) * 100:.4f}")
     save_frames(a, series)
     save_zonal(a, zonal)
+    save_spectra(a, spectra)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
@@ -204,6 +219,26 @@ def save_zonal(a, zonal):
         os.makedirs(a.out, exist_ok=True)
         zonal.save(os.path.join(a.out, "zonal_means.npz"))
         print(f"{len(zonal)} samples of the zonal means ({', '.join(zonal.names)}) -> {os.path.join(a.out, 'zonal_means.npz')}")
+
+
+def spectra_writer(a, model, nsteps):
+    """--zonal-spectra: (ZonalSpectrumTimeSeries, steps between samples), or (None, 0)"""
+    if a.zonal_spectra <= 0:
+        return None, 0
+    import swmhd_amd as S
+    sched = S.TimeInterval(a.zonal_spectra)
+    every = sched.steps(a.dt)
+    spectra = S.ZonalSpectrumTimeSeries(model, names=tuple(n.strip() for n in a.spectra_names.split(",") if n.strip()), schedule=sched,
+                                        capacity=nsteps // every + 1)
+    spectra.write()         # the initial state, as the frames
+    return spectra, every
+
+
+def save_spectra(a, spectra):
+    if spectra is not None:
+        os.makedirs(a.out, exist_ok=True)
+        spectra.save(os.path.join(a.out, "zonal_spectra.npz"))
+        print(f"{len(spectra)} samples of the zonal spectra ({', '.join(spectra.names)}) -> {os.path.join(a.out, 'zonal_spectra.npz')}")
 
 
 def run_ensemble(a):
@@ -264,11 +299,14 @@ def run_ensemble(a):
     e0 = [r[-1] for r in rows]
     series, fevery = frame_writer(a, ens, nsteps)
     zonal, zevery = zonal_writer(a, ens, nsteps)
+    spectra, severy = spectra_writer(a, ens, nsteps)
     ens.time_step(dt)
     if fevery == 1:
         series.write()
     if zevery == 1:
         zonal.write()
+    if severy == 1:
+        spectra.write()
     ens.capture_graph(dt)
     t_start = time.perf_counter()
     t0 = None
@@ -279,11 +317,15 @@ def run_ensemble(a):
             n = min(n, fevery - ens.iteration % fevery)
         if zevery:
             n = min(n, zevery - ens.iteration % zevery)
+        if severy:
+            n = min(n, severy - ens.iteration % severy)
         ens.time_steps(n, dt)
         if fevery and ens.iteration % fevery == 0:
             series.write(time=ens.iteration * a.dt)           # all members in one launch, no synchronisation
         if zevery and ens.iteration % zevery == 0:
             zonal.write(time=ens.iteration * a.dt)            # likewise
+        if severy and ens.iteration % severy == 0:
+            spectra.write(time=ens.iteration * a.dt)          # likewise
         if ens.iteration % a.every != 0 and ens.iteration != nsteps:
             continue
         ens.synchronize()
@@ -295,6 +337,7 @@ def run_ensemble(a):
           f"{len(amps) * N * N * nsteps / total / 1e6:.1f} Mcell-steps/s); energy drift abs(E - E0) * 100 per member = {drift}")
     save_frames(a, series)
     save_zonal(a, zonal)
+    save_spectra(a, spectra)
     if a.dye:
         os.makedirs(a.out, exist_ok=True)
         np.savez(os.path.join(a.out, "tracers.npz"), c=ens.tracers["c"][(slice(None),) + grid.interior].cpu().numpy(),

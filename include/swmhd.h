@@ -769,5 +769,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_zonal.h"
 /* derived frames (swmhd_derived_fields_*, swmhd_ensemble_derived_fields[_params]_*, SWMHD_DRV_*): vorticity, divergence, current, PV */
 #include "swmhd_derived.h"
+/* zonal spectra (swmhd_zonal_spectra_*, swmhd_ensemble_zonal_spectra_*, SWMHD_ZS_*): row-averaged power spectra along x of the output fields */
+#include "swmhd_spectra.h"
 
 #endif /* SWMHD_H */

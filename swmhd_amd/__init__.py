@@ -12,8 +12,9 @@ from .distributed import SlabDecomposition, exchange_y_halos
 from .ensemble import ShallowWaterEnsemble, BoundedShallowWaterEnsemble
 from .output import FieldTimeSeries, TimeInterval, IterationInterval, run
 from .zonal import ZonalMeanTimeSeries
+from .spectra import ZonalSpectrumTimeSeries
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
            "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble",
-           "BoundedShallowWaterEnsemble", "FieldTimeSeries", "ZonalMeanTimeSeries", "TimeInterval", "IterationInterval", "run", "_lib"]
+           "BoundedShallowWaterEnsemble", "FieldTimeSeries", "ZonalMeanTimeSeries", "ZonalSpectrumTimeSeries", "TimeInterval", "IterationInterval", "run", "_lib"]

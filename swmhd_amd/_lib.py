@@ -27,6 +27,9 @@ OUT_BITS = {"u": 1, "v": 2, "h": 4, "A": 8, "s": 16, "B_x": 32, "B_y": 64}
 ZM_BITS = {**OUT_BITS, "uu": 128, "vv": 256, "uv": 512, "B_xB_x": 1024, "B_yB_y": 2048, "B_xB_y": 4096, "vA": 8192}
 # SWMHD_DRV_*: the fields of swmhd_derived_fields_* (include/swmhd_derived.h), in bit (= frame) order
 DRV_BITS = {"vorticity": 1, "divergence": 2, "current": 4, "potential_vorticity": 8}
+# SWMHD_ZS_*: the fields of swmhd_zonal_spectra_* (include/swmhd_spectra.h): those of OUT_BITS; Nx = 2^p, p = 2 .. 12
+ZS_BITS = dict(OUT_BITS)
+SPECTRA_MIN_NX, SPECTRA_MAX_NX = 4, 4096
 ENSEMBLE_MAX_MEMBERS = 65535
 ENSEMBLE_NPARAMS = 3    # SWMHD_ENSEMBLE_NPARAMS: (g, f, dt) per member in the table of the swmhd_ensemble_*_params calls
 MAX_TRACERS = 8         # SWMHD_MAX_TRACERS: passive tracers per swmhd_tracers_rk3_* launch
@@ -174,9 +177,18 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_derived_fields_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, ft, i, i, i, p, i, i64, i64, i64, i, p]
         f.restype = i
+        # zonal spectra: the arguments of the zonal means with the workspace in front of `out`
+        f = getattr(lib, f"swmhd_zonal_spectra_{sfx}")
+        f.argtypes = [p, p, p, p, i, i, i, i, i64, ft, ft, i, i, i, i, p, p, i64, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_zonal_spectra_{sfx}")
+        f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, i, i, i, p, p, i64, i64, i, p]
+        f.restype = i
         f = getattr(lib, f"swmhd_ensemble_derived_fields_params_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, p, i, i, i, p, i, i64, i64, i64, i, p]
         f.restype = i
+    lib.swmhd_zonal_spectra_workspace.argtypes = [i, i, i, i]
+    lib.swmhd_zonal_spectra_workspace.restype = i64
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
     lib.swmhd_tendency_launch_geometry.restype = i
     lib.swmhd_ensemble_launch_geometry.argtypes = [i, i, i, i, i, i, C.POINTER(i)]
@@ -220,6 +232,9 @@ ZONAL_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("z
 # the symbols include/swmhd_derived.h declares (swmhd.h includes it; tests/test_derived_abi.py checks the .so exports each of them)
 DERIVED_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
                    for name in ("derived_fields", "ensemble_derived_fields", "ensemble_derived_fields_params")]
+# the symbols include/swmhd_spectra.h declares (swmhd.h includes it; tests/test_spectra_abi.py checks the .so exports each of them)
+SPECTRA_EXPORTS = ["swmhd_zonal_spectra_workspace"] + [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
+                                                       for name in ("zonal_spectra", "ensemble_zonal_spectra")]
 RING_ID_BYTES = 128
 
 

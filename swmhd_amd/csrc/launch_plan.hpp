@@ -1,5 +1,5 @@
 // Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the zonal-mean
-// kernel and the derived-frame kernel: what a call will enqueue, decided as data before anything is launched.
+// kernel, the derived-frame kernel and the zonal-spectrum kernels: what a call will enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
 #pragma once
@@ -466,6 +466,71 @@ inline int zonal_depth(int Nx) {
     int levels = 0;
     while ((1 << levels) < lanes) ++levels;
     return terms0 - 1 + levels;
+}
+
+// ---- the two launches of one zonal-spectrum call (spectra.hip) -----------------------------------------------------------------------
+// Pass 1: W units per (member, field); unit w transforms the rows w, w + W, w + 2W, ... of the range one after the other in LDS and adds
+// their p_j[k] to per-thread accumulators in that order, then stores its partial spectrum of Nx/2 + 1 doubles to the workspace at
+// ((member * nfields + field) * W + w) * (Nx/2 + 1).  W = min(rows, SPECTRA_WMAX): a function of the row count alone, never of the
+// device, so the summation order depends on (Nx, rows) only.  A unit is a workgroup of SPECTRA_NT threads from Nx = 512 on; up to
+// Nx = 256 a stage has at most 64 butterflies, a unit is one wave, and a workgroup holds SPECTRA_UNITS_SMALL units of consecutive w.
+// Pass 2: one thread group per (member, field, k): SPECTRA_P2_G lanes, lane g adds the partials g, g + G, g + 2G, ... one after the
+// other, a tree of log2(G) levels through LDS adds the lane sums, the result is divided by rows.  SPECTRA_P2_K values of k per workgroup.
+// LDS of a unit: the row (Nx doubles = Nx/2 complex) and the twiddle quarter table (Nx/4 complex): 12 Nx bytes, 48 KiB at Nx = 4096,
+// 12 KiB for the four units of a workgroup at Nx = 256.
+constexpr int SPECTRA_NT = 256, SPECTRA_WMAX = 256, SPECTRA_MIN_LOG2 = 2, SPECTRA_MAX_LOG2 = 12;
+constexpr int SPECTRA_P2_G = 16, SPECTRA_P2_K = 16;
+constexpr int SPECTRA_SMALL_NX = 256, SPECTRA_UNITS_SMALL = 4;   // up to SMALL_NX: one wave per row, UNITS_SMALL rows per workgroup
+constexpr int SPECTRA_ACC = ((1 << (SPECTRA_MAX_LOG2 - 1)) + SPECTRA_NT) / SPECTRA_NT;   // accumulators of a thread: ceil((Nx/2 + 1) / NT)
+struct SpectraPlan {
+    int log2n;        // Nx = 2^log2n; -1: Nx is not a supported size
+    int W;            // units of pass 1 per (member, field)
+    int units;        // units per workgroup: 1, or SPECTRA_UNITS_SMALL up to SPECTRA_SMALL_NX
+    int nk;           // Nx/2 + 1
+    long blocks1;     // ceil(W / units) * nfields * members
+    long blocks2;     // ceil(nk / SPECTRA_P2_K) * nfields * members
+    long lds_bytes;   // dynamic LDS of a pass-1 workgroup
+    long workspace;   // doubles: W * nfields * members * nk
+    int depth;        // D_rows (spectra_depth)
+    bool none;        // nothing to compute: no rows, no fields or no members
+    bool unsupported; // Nx is not 2^p with SPECTRA_MIN_LOG2 <= p <= SPECTRA_MAX_LOG2
+    bool too_many;    // 2^31 workgroups or more in one of the launches
+};
+inline int spectra_log2(int Nx) {
+    for (int p = SPECTRA_MIN_LOG2; p <= SPECTRA_MAX_LOG2; ++p)
+        if (Nx == (1 << p)) return p;
+    return -1;
+}
+inline int spectra_W(int rows) { return rows <= 0 ? 0 : (rows < SPECTRA_WMAX ? rows : SPECTRA_WMAX); }
+// Rounded additions on the longest path from a p_j[k] to the row sum: workgroup 0 has ceil(rows / W) rows, added one after the other
+// starting from 0.0 (the first addition is exact); lane 0 of pass 2 adds ceil(W / G) partials the same way; then one tree level per bit
+// of (lanes with a partial - 1) -- a level whose partner holds no partial adds 0.0, which is exact.  The bound of tests/spectra_cases.py.
+inline int spectra_depth(int rows) {
+    if (rows <= 0) return 0;
+    const int W = spectra_W(rows);
+    const int serial1 = (int)(((long)rows + W - 1) / W) - 1, serial2 = (W + SPECTRA_P2_G - 1) / SPECTRA_P2_G - 1;
+    const int lanes = W < SPECTRA_P2_G ? W : SPECTRA_P2_G;
+    int levels = 0;
+    while ((1 << levels) < lanes) ++levels;
+    return serial1 + serial2 + levels;
+}
+// members: 1 for a single grid
+inline SpectraPlan spectra_plan(int Nx, int rows, int nfields, int members) {
+    SpectraPlan p{};
+    p.log2n = spectra_log2(Nx);
+    p.unsupported = p.log2n < 0;
+    p.none = rows <= 0 || nfields <= 0 || members <= 0;
+    if (p.unsupported || p.none) return p;
+    p.W = spectra_W(rows);
+    p.nk = Nx / 2 + 1;
+    p.units = Nx <= SPECTRA_SMALL_NX ? SPECTRA_UNITS_SMALL : 1;
+    p.blocks1 = (long)((p.W + p.units - 1) / p.units) * nfields * members;
+    p.blocks2 = (long)((p.nk + SPECTRA_P2_K - 1) / SPECTRA_P2_K) * nfields * members;
+    p.lds_bytes = 12L * Nx * p.units;
+    p.workspace = (long)p.W * nfields * members * p.nk;
+    p.depth = spectra_depth(rows);
+    p.too_many = p.blocks1 >= (1L << 31) || p.blocks2 >= (1L << 31);
+    return p;
 }
 
 // ---- the chunks of one derived-frame call (derived.hip) -----------------------------------------------------------------------------

@@ -399,6 +399,13 @@ class ShallowWaterEnsemble:
         from .zonal import enqueue_zonal_means
         return enqueue_zonal_means(self, names, out)
 
+    # --- zonal spectra of all members in two launches (swmhd_ensemble_zonal_spectra_*) --------------------------------
+    def zonal_spectra(self, names=("u", "v", "A"), out=None):
+        """ShallowWaterModel.zonal_spectra for every member: the float64 device tensor (members, len(names), Nx/2 + 1); member m of it
+        is bitwise member(m).zonal_spectra(...).  No host synchronisation."""
+        from .spectra import enqueue_zonal_spectra
+        return enqueue_zonal_spectra(self, names, out)
+
     # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
     def member(self, m):
         """A ShallowWaterModel holding a copy of member m (state and tracers with halos, their G-, the member's g, f, clock and

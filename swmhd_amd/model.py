@@ -578,6 +578,17 @@ class ShallowWaterModel:
         from .zonal import enqueue_zonal_means
         return enqueue_zonal_means(self, names, out)
 
+    # --- zonal spectra: a row FFT in LDS and a row average, two launches, no frame-sized buffer, no host synchronisation ----
+    def zonal_spectra(self, names=("u", "v", "A"), out=None):
+        """Enqueue the zonal power spectra of the current state: the float64 device tensor (len(names), Nx/2 + 1), entry k of spectrum
+        F = the mean over the rows of c_k |F^_j[k]|^2, F^_j the DFT along x of row j of the float64 frame field F (u v h A s B_x B_y)
+        divided by Nx, c_k = 1 at k = 0 and k = Nx/2 and 2 between, so that the entries sum to the mean of F^2
+        (swmhd_zonal_spectra_* in include/swmhd_spectra.h).  Nx must be a power of two from 4 to 4096 and the x direction Periodic.  On a
+        y-slab: the spectrum of this rank's rows.  The summation order depends on (Nx, Ny) alone, so a spectrum is reproducible bit for
+        bit.  See swmhd_amd.spectra for the writer (ZonalSpectrumTimeSeries)."""
+        from .spectra import enqueue_zonal_spectra
+        return enqueue_zonal_spectra(self, names, out)
+
     # --- checkpoint: prognostic fields with halos + G⁻ + clock, one .npz per rank ---------------------------------
     def save_checkpoint(self, path):
         import numpy as np
