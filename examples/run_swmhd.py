@@ -23,6 +23,11 @@ The step loop runs through HIP-graph replays (two RK3 steps per replay).
 name): its min / max join the progress line and the field goes into the --dump-every dumps.  With --amps, --coriolis, --gravity or
 --dts every member of the ensemble carries the dye (ShallowWaterEnsemble(tracers=("c",)): one more launch per RK3 stage for all of
 them); the interiors of all members go to <out>/tracers.npz at the end.  Not with --channel (Bounded ensembles carry no tracers).
+--viscosity NU and --diffusivity ETA add Oceananigans' closure = ScalarDiffusivity(nu = NU, kappa = ETA) (swmhd_amd.ScalarDiffusivity:
+NU on u and v, ETA -- the magnetic diffusivity -- on A and on the dye; one more launch per RK3 stage).  --viscosity needs
+--formulation jacobian; neither goes with --channel.  In an ensemble run both take comma lists like --coriolis (a sweep of the Reynolds
+or of the magnetic Prandtl number), and a list of several values starts one.  dt is not limited by the closure: the line printed at the
+start gives ScalarDiffusivity.max_stable_dt.
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
@@ -73,6 +78,8 @@ def main():
     ap.add_argument("--zonal-spectra", type=float, default=0.0, help="model time between zonal-spectrum samples (0 = none); written to <out>/zonal_spectra.npz")
     ap.add_argument("--spectra-names", default="u,v,A", help="comma-separated spectra: u v h A s B_x B_y")
     ap.add_argument("--dye", action="store_true", help="advect one passive tracer c = tanh(y) with the flow")
+    ap.add_argument("--viscosity", default=None, help="nu of ScalarDiffusivity, on u and v (ensemble runs: a comma list, one member per entry)")
+    ap.add_argument("--diffusivity", default=None, help="kappa of ScalarDiffusivity, on A and the dye (ensemble runs: a comma list)")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -87,7 +94,12 @@ def main():
         ap.error("--channel and --gradients go together")
     if a.channel and a.amps:
         ap.error("--channel sweeps --gradients, not --amps")
-    a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts))
+    a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts)) or any("," in (x or "") for x in (a.viscosity, a.diffusivity))
+    a.closure = a.viscosity is not None or a.diffusivity is not None
+    if a.closure and a.channel:
+        ap.error("--viscosity / --diffusivity: not with --channel (the closure runs on periodic grids)")
+    if a.viscosity is not None and a.formulation != "jacobian":
+        ap.error("--viscosity needs --formulation jacobian (the conservative viscous stress is another operator)")
     if a.dts and a.frames > 0:
         ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
     if a.dts and a.zonal_means > 0:
@@ -105,7 +117,10 @@ def main():
     N, L = a.size, 10.0
     grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
     form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
-    model = S.ShallowWaterModel(grid, configs.G, configs.F, formulation=form, tracers=("c",) if a.dye else ())
+    closure = S.ScalarDiffusivity(nu=float(a.viscosity or 0.0), kappa=float(a.diffusivity or 0.0)) if a.closure else None
+    if closure is not None:
+        print(f"closure: {closure}, max_stable_dt = {closure.max_stable_dt(grid):.4g} (dt = {a.dt:g})")
+    model = S.ShallowWaterModel(grid, configs.G, configs.F, formulation=form, tracers=("c",) if a.dye else (), closure=closure)
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)
     A0 = (lambda X, Y: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp)
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
@@ -253,7 +268,8 @@ def run_ensemble(a):
         amps = floats(a.gradients if a.channel else a.amps)
     else:
         amps = [a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)]
-    lists = {"--coriolis": floats(a.coriolis or ""), "--gravity": floats(a.gravity or ""), "--dts": floats(a.dts or "")}
+    lists = {"--coriolis": floats(a.coriolis or ""), "--gravity": floats(a.gravity or ""), "--dts": floats(a.dts or ""),
+             "--viscosity": floats(a.viscosity or ""), "--diffusivity": floats(a.diffusivity or "")}
     B = max([len(amps)] + [len(v) for v in lists.values()])
     for name, v in [("--gradients" if a.channel else "--amps", amps)] + [(k, v) for k, v in lists.items() if v]:
         if len(v) not in (1, B):
@@ -270,7 +286,11 @@ def run_ensemble(a):
         A0 = [lambda X, Y, gr=gr: gr * Y for gr in amps]
     else:
         grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
-        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form, tracers=("c",) if a.dye else ())
+        closure = None
+        if a.closure:
+            closure = S.ScalarDiffusivity(nu=per(lists["--viscosity"], 0.0), kappa=per(lists["--diffusivity"], 0.0))
+            print(f"closure: {closure}, max_stable_dt = {closure.max_stable_dt(grid):.4g}")
+        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form, tracers=("c",) if a.dye else (), closure=closure)
         A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
     label = "gradient" if a.channel else "amp"
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))

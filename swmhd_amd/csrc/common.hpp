@@ -278,6 +278,27 @@ template <typename T> hipError_t launch_tracers_ensemble_strict(const EnsTracerA
 template <typename T> hipError_t launch_tracers_ensemble_params_fast(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s);
 template <typename T> hipError_t launch_tracers_ensemble_params_strict(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s);
 
+// ScalarDiffusivity closure (swmhd_diffusion_rk3_*, diffusion.hip): D_k = coef_k laplace(old_k) of up to 3 + MAX_TRACERS fields in ONE
+// launch, added to what the stage kernels have written: nw[k] += a D_k and, where acc[k] != nullptr, acc[k] += w D_k.  Pointers address
+// interior cell (1,1) like TendArgs; wrap as there.  members > 0: an ensemble -- member m of every parent at ptr + m * stride_m, its
+// coefficients in the DEVICE table coef_tab[m * nfields + k] (coef is not read); with params != nullptr its dt is params[3 m + 2] and
+// the kernel forms a_m = dt a (a: gamma) and, with `anchor`, w_m = dt w (w: the anchor's weight), else w_m = w.
+constexpr int DIFFUSION_MAX_FIELDS = 3 + MAX_TRACERS;   // = SWMHD_DIFFUSION_MAX_FIELDS
+template <typename T>
+struct DiffusionArgs {
+    const T *old[DIFFUSION_MAX_FIELDS];
+    T *nw[DIFFUSION_MAX_FIELDS], *acc[DIFFUSION_MAX_FIELDS];
+    T coef[DIFFUSION_MAX_FIELDS];
+    int nfields, Nx, Ny, j0, j1, wrap;
+    long sy;
+    T dx, dy, a, w;
+    int members, anchor;
+    long stride_m;
+    const T *coef_tab, *params;
+};
+template <typename T> hipError_t launch_diffusion_fast(const DiffusionArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_diffusion_strict(const DiffusionArgs<T> &a, hipStream_t s);
+
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
 // (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read

@@ -224,6 +224,58 @@ int tracers_common(const T *const *q, const T *const *c, T *const *cnew, T *cons
     return hiprc(fl.strict ? launch_tracers_strict<T>(a, form, s) : launch_tracers_fast<T>(a, form, s));
 }
 
+// swmhd_diffusion_rk3: nw[k] += a coef[k] laplace(old[k]), acc[k] += w coef[k] laplace(old[k]) of up to SWMHD_DIFFUSION_MAX_FIELDS fields in
+// one launch (diffusion.hip).  Every check precedes the first HIP call.  With `ens` (swmhd_ensemble_diffusion_rk3): `coef` is the DEVICE
+// table of members x nfields values and is not looked at; ens->params (optional) brings every member's dt.  The ensemble's own
+// argument errors come first.  One grid: the fields with coef == 0 are left out of the launch here.
+template <typename T>
+int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, const Grid &g, T a, T w, const Rows &r,
+                     int flags, void *stream, const Ens *ens = nullptr) {
+    if (ens) {
+        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
+        if (g.Ny <= 0 || g.Hy < 0 || g.sy <= 0 || ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
+    }
+    if (!old || !nw || !coef) return SWMHD_EINVAL;
+    if (nfields < 1 || nfields > SWMHD_DIFFUSION_MAX_FIELDS) return SWMHD_EINVAL;
+    if (!g.extents_ok() || !g.spacing_ok() || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
+    if (flags & ~(DIFFUSION_FLAGS | DIFFUSION_NOTSUP)) return SWMHD_EINVAL;
+    for (int k = 0; k < nfields; ++k)
+        if (!old[k] || !nw[k]) return SWMHD_EINVAL;
+    for (int k = 0; k < nfields; ++k) {
+        const T *const ak = acc ? acc[k] : nullptr;
+        if (ak == nw[k]) return SWMHD_EINVAL;
+        for (int m = 0; m < nfields; ++m) {
+            if (nw[k] == old[m] || (ak && ak == old[m])) return SWMHD_EINVAL;   // other workgroups still read old around their rows
+            if (m != k && (nw[k] == nw[m] || (ak && (ak == nw[m] || ak == acc[m])))) return SWMHD_EINVAL;
+        }
+    }
+    if (!ens)
+        for (int k = 0; k < nfields; ++k)
+            if (!isfinite((double)coef[k]) || coef[k] < T(0)) return SWMHD_EINVAL;
+    if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
+    if (flags & DIFFUSION_NOTSUP) return SWMHD_ENOTSUP;
+    const Flags fl = decode_flags(flags);
+    if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
+    if (r.j0 == r.j1) return SWMHD_OK;
+    DiffusionArgs<T> d;
+    int n = 0;
+    for (int k = 0; k < nfields; ++k) {
+        if (!ens && coef[k] == T(0)) continue;
+        d.old[n] = g.interior(old[k]); d.nw[n] = g.interior(nw[k]);
+        d.acc[n] = (acc && acc[k]) ? g.interior(acc[k]) : nullptr;
+        d.coef[n] = ens ? T(0) : coef[k];
+        ++n;
+    }
+    if (n == 0) return SWMHD_OK;
+    for (int k = n; k < DIFFUSION_MAX_FIELDS; ++k) { d.old[k] = nullptr; d.nw[k] = nullptr; d.acc[k] = nullptr; d.coef[k] = T(0); }
+    d.nfields = n; d.Nx = g.Nx; d.Ny = g.Ny; d.j0 = r.j0; d.j1 = r.j1; d.wrap = fl.wrap; d.sy = (long)g.sy;
+    d.dx = T(g.dx); d.dy = T(g.dy); d.a = a; d.w = w;
+    d.members = ens ? ens->members : 0; d.anchor = fl.anchor; d.stride_m = ens ? (long)ens->stride_m : 0;
+    d.coef_tab = ens ? coef : nullptr; d.params = ens ? static_cast<const T *>(ens->params) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    return hiprc(fl.strict ? launch_diffusion_strict<T>(d, s) : launch_diffusion_fast<T>(d, s));
+}
+
 // The RK3 step driver.  Periodic: stages in anchor form (fast) and a periodic fill of whatever the kernel does not wrap.  Bounded
 // ensembles (ens->bc, swmhd_ensemble_step_rk3_bc): ShallowWaterModel.time_step's Bounded schedule -- every stage in G- form, then the
 // boundary-condition fill of the four fields, gradient values from the DEVICE table bc_gradient.  ph: the model and dt.
@@ -540,5 +592,21 @@ int swmhd_ensemble_launch_geometry(int Nx, int Ny, int formulation, int elem_siz
 
 SWMHD_DEF_API(f64, double)
 SWMHD_DEF_API(f32, float)
+
+// include/swmhd_diffusion.h
+#define SWMHD_DEF_DIFFUSION(sfx, T)                                                                                                                    \
+    int swmhd_diffusion_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, int Nx, int Ny, int Hx, int Hy,       \
+                                  int64_t sy, T dx, T dy, T a, T w, int j0, int j1, int flags, void *stream) {                                        \
+        return diffusion_common<T>(old, nw, acc, coef, nfields, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, a, w, Rows{j0, j1}, flags, stream);                 \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_diffusion_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, int members,                 \
+                                           int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, const T *params, T a, T w,       \
+                                           int j0, int j1, int flags, void *stream) {                                                                 \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return diffusion_common<T>(old, nw, acc, coef, nfields, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, a, w, Rows{j0, j1}, flags, stream, &e);             \
+    }
+
+SWMHD_DEF_DIFFUSION(f64, double)
+SWMHD_DEF_DIFFUSION(f32, float)
 
 }  // extern "C"

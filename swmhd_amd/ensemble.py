@@ -16,9 +16,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .closure import check_closure
 from .fields import _SFX, _stream_ptr
 from .grid import Center, Face
-from .model import ShallowWaterModel, rk3_operands, tracer_names
+from .model import RK3_ANCHOR_WEIGHT, ShallowWaterModel, rk3_operands, rk3_stage, tracer_names
 from .shared import (VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups, finish_stage,
                      formulation_codes, gradient_values)
 
@@ -54,12 +55,21 @@ class ShallowWaterEnsemble:
     Passive tracers: `tracers=("c", "d")` gives every member those centre fields (ShallowWaterModel's argument, same names and limit),
     laid out like the state.  Such an ensemble steps stage by stage: swmhd_ensemble_tendencies_rk3[_params], then
     swmhd_ensemble_tracers_rk3[_params] on the state the stage started from -- six launches per step for all tracers of all members
-    with fused halos -- and its four state fields come out bitwise what the native driver gives the ensemble without tracers."""
+    with fused halos -- and its four state fields come out bitwise what the native driver gives the ensemble without tracers.
+
+    Closure: `closure=ScalarDiffusivity(nu=..., kappa=...)` (ShallowWaterModel's argument) with a scalar or one value per member for
+    every coefficient -- a sweep of the Reynolds or the magnetic Prandtl number.  `diffusion_coefficients` is the (members, fields
+    with a coefficient) device table; such an ensemble steps stage by stage as one with tracers does, with one more launch per stage
+    for all members (swmhd_ensemble_diffusion_rk3_*), under a scalar or a per-member dt.  Without a closure, or with coefficients
+    that are all 0, the ensemble calls exactly what it calls without the argument."""
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, tracers=()):
+                 fuse_halo=True, tracers=(), closure=None):
         self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
+        self.closure = closure
+        coefs = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
+                              formulation != VectorInvariantFormulation)      # (a Bounded grid: _check_topology, below)
         if decomp is not None or grid.Ny_global != grid.Ny or grid.j_offset != 0:
             raise _lib.SwmhdError("ShallowWaterEnsemble runs on one GPU: no slab decomposition")
         self._check_topology(grid)
@@ -71,6 +81,9 @@ class ShallowWaterEnsemble:
         if not 1 <= self.members <= _lib.ENSEMBLE_MAX_MEMBERS:
             raise _lib.SwmhdError(f"members = {members}: 1 .. {_lib.ENSEMBLE_MAX_MEMBERS}")
         # checked before anything touches a device
+        # the closure's coefficients: a scalar or one value per member each; the fields all of whose values are 0 have no launch
+        coefs = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs or {}).items()}
+        self._diffusion = {n: c for n, c in coefs.items() if np.any(c != 0.0)} or None
         self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
         self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
         self.grid = grid
@@ -104,6 +117,11 @@ class ShallowWaterEnsemble:
         self.clock_time, self.iteration = 0.0, 0
         self._L = _lib.lib()
         self.parameters, self._table_dt = None, None
+        # (members, fields with a coefficient) on the device, in the ensemble's dtype: the table of swmhd_ensemble_diffusion_rk3_*
+        self.diffusion_coefficients = None
+        if self._diffusion is not None:
+            host = np.stack([self._diffusion[n] for n in self._diffusion_names()], axis=1)
+            self.diffusion_coefficients = torch.from_numpy(np.ascontiguousarray(host)).to(device=self._state[0].device, dtype=dtype)
         if g_seq or f_seq:
             self._make_parameters()
 
@@ -261,6 +279,31 @@ class ShallowWaterEnsemble:
         f = getattr(self._L, f"swmhd_ensemble_tracers_rk3_{'params_' if par else ''}{self.sfx}")
         _lib.check(f(*head, self.parameters.data_ptr() if par else dt, *tail), "swmhd_ensemble_tracers_rk3" + ("_params" if par else ""))
 
+    def _diffusion_names(self):
+        return [n for n in self.names + self.tracer_names if n in self._diffusion]
+
+    def _diffusion_stage(self, dt, stage):
+        """The closure's launch of RK3 stage `stage` for every member (swmhd_ensemble_diffusion_rk3_*; with dt None every member's dt
+        comes from the table): ShallowWaterModel._diffusion_stage with the coefficients of member m in row m of the device table."""
+        g = self.grid
+        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        names = self._diffusion_names()
+        cur = {**dict(zip(self.names, self._state)), **self._tr}
+        new = {**dict(zip(self.names, self._alt)), **self._tr_alt}
+        Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
+        par = dt is None
+        acc, w, flag = None, 0.0, 0
+        if anchor and stage == 0:     # with the table the kernel forms dt_m / 4 (SWMHD_RK3_ANCHOR: w is a weight of dt)
+            acc, w, flag = self._ptrs([Gn[n] for n in names]), (RK3_ANCHOR_WEIGHT if par else dt * RK3_ANCHOR_WEIGHT), _lib.RK3_ANCHOR
+        elif not anchor and store:
+            acc, w = self._ptrs([Gn[n] for n in names]), 1.0
+        f = getattr(self._L, f"swmhd_ensemble_diffusion_rk3_{self.sfx}")
+        rc = f(self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc, self.diffusion_coefficients.data_ptr(),
+               len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy,
+               self.parameters.data_ptr() if par else None, gamma if par else dt * gamma, w, 0, g.Ny,
+               self._flags | self._rwrap | flag, _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_diffusion_rk3")
+
     def _stage_steps(self, dt, n):
         """n steps stage by stage (dt: the scalar, or None for the table).  Without fused halos every stage ends with the periodic fill
         of the state and of the tracers, as the native driver fills the state."""
@@ -290,7 +333,7 @@ class ShallowWaterEnsemble:
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        if self._tr:        # (the native step driver steps the four fields only)
+        if self._tr or self._diffusion is not None:        # (the native step driver steps the four fields only)
             self._stage_steps(dt if dts is None else None, n)
         else:
             self._enqueue_steps(dt if dts is None else None, n, swapped)
@@ -427,7 +470,7 @@ class ShallowWaterEnsemble:
     def _member_model(self, m):
         return ShallowWaterModel(self.grid, float(self.g_values[m]), float(self.f_values[m]), formulation=self.formulation,
                                  lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
-                                 tracers=self.tracer_names)
+                                 tracers=self.tracer_names, closure=self.closure.for_member(m) if self.closure is not None else None)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
@@ -446,7 +489,10 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, boundary_conditions=None, tracers=()):
+                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None):
+        if closure is not None:       # before anything is allocated
+            raise _lib.SwmhdError("closure on a Bounded ensemble is not supported (SWMHD_ENOTSUP): the wall faces of u and v and the "
+                                  "gradient conditions need a kernel body of their own")
         if tracer_names(tracers):     # before anything is allocated
             raise _lib.SwmhdError("tracers on a Bounded ensemble are not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc steps the "
                                   "four fields only and that schedule has no per-stage entry point")

@@ -8,9 +8,12 @@ Reference call sites being mirrored:
 One `time_step(dt)` == Oceananigans' RK3 `time_step!`: 3 x {calculate_tendencies!, rk3_substep!, store_tendencies!
 (pointer swap), update_state! (halo fill)}.  All arithmetic happens in libswmhd.so; there is no CPU path.
 """
+import ctypes
+
 import torch
 
 from . import _lib
+from .closure import check_closure
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
 from .grid import Center, Face
@@ -79,7 +82,7 @@ class ShallowWaterModel:
     def __init__(self, grid, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, device="cuda", strict=False, decomp=None, group=None,
                  overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None,
-                 tracers=()):
+                 tracers=(), closure=None):
         # passive tracers (swmhd_tracers_rk3_*): names and what they cannot be combined with are checked before anything is allocated
         self.tracer_names = tracer_names(tracers)
         if self.tracer_names:
@@ -89,6 +92,14 @@ class ShallowWaterModel:
                 raise _lib.SwmhdError("tracers with ring= are not supported (SWMHD_ENOTSUP): the slab driver steps the four fields only")
             if not fused:
                 raise _lib.SwmhdError("tracers need the fused stage kernel (SWMHD_ENOTSUP): fused=False has no tracer substep")
+        # closure = ScalarDiffusivity(...): its names and refusals are checked before anything is allocated too.  _diffusion: the
+        # coefficient of every field that has one; None without a closure and with one whose coefficients are all 0, and then the
+        # model makes exactly the calls it makes without the argument
+        self.closure = closure
+        coefs = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
+                              formulation != VectorInvariantFormulation, any(c == _lib.BOUNDED for c in grid.topo_codes()),
+                              decomp is not None and decomp.world_size > 1, ring is not None, fused)
+        self._diffusion = {n: float(c) for n, c in (coefs or {}).items() if float(c) != 0.0} or None
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code, self.lorentz_code, self.names = formulation_codes(formulation, lorentz_forcing)
@@ -383,6 +394,31 @@ class ShallowWaterModel:
                dt, gamma, zeta, store, 0, g.Ny, flags, _stream_ptr())
         _lib.check(rc, "swmhd_tracers_rk3")
 
+    def _diffusion_stage(self, dt, stage):
+        """The closure's launch of RK3 stage `stage` (swmhd_diffusion_rk3_*): D = coef laplace(field) on the state the stage started
+        from, for every field with a coefficient, added with dt gamma to the new state (and tracers) and, where the stage stores an
+        operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
+        the anchor form).  After _stage_fused and _tracer_stage and BEFORE the swaps (finish_stage)."""
+        g = self.grid
+        P = _lib.ptr_array
+        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        names = [n for n in self.names + self.tracer_names if n in self._diffusion]
+        cur = {**self._state, **self._tr}
+        new = {**self._alt, **self._tr_alt}
+        Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
+        acc, w = None, 0.0
+        if anchor and stage == 0:
+            acc, w = P([Gn[n].ptr for n in names]), dt * RK3_ANCHOR_WEIGHT
+        elif not anchor and store:
+            acc, w = P([Gn[n].ptr for n in names]), 1.0
+        ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
+        coef = (ft * len(names))(*[self._diffusion[n] for n in names])
+        f = getattr(self._L, f"swmhd_diffusion_rk3_{self.sfx}")
+        rc = f(P([cur[n].ptr for n in names]), P([new[n].ptr for n in names]), acc, coef, len(names), g.Nx, g.Ny, g.Hx, g.Hy,
+               self._raw_fields[0].stride_y, g.dx, g.dy, dt * gamma, w, 0, g.Ny,
+               (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap, _stream_ptr())
+        _lib.check(rc, "swmhd_diffusion_rk3")
+
     # --- time_step!(model, dt): RungeKutta3 ------------------------------------------------------------------
     def _native_steps(self, dt, n):
         """n RK3 steps in ONE C call that enqueues every launch: the native ring driver (swmhd_ring_step_rk3_*) on a slab, the step
@@ -515,7 +551,7 @@ class ShallowWaterModel:
 
     def _driver_steps(self, dt, n):
         if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)
-                                      and not self._tr):     # (the native step driver steps the four fields only)
+                                      and not self._tr and self._diffusion is None):     # (the native step driver steps the four fields only)
             return self._native_steps(dt, n)
         for _ in range(n):
             self.time_step(dt)
