@@ -23,6 +23,10 @@ The step loop runs through HIP-graph replays (two RK3 steps per replay).
 name): its min / max join the progress line and the field goes into the --dump-every dumps.  With --amps, --coriolis, --gravity or
 --dts every member of the ensemble carries the dye (ShallowWaterEnsemble(tracers=("c",)): one more launch per RK3 stage for all of
 them); the interiors of all members go to <out>/tracers.npz at the end.  Not with --channel (Bounded ensembles carry no tracers).
+--beta B adds Oceananigans' coriolis = BetaPlane(f₀ = F0, β = B) with --coriolis as F0 (swmhd_amd.BetaPlane: f = F0 + B y, y = 0 in
+mid-domain; the stage kernels run with f = 0 and one more launch per RK3 stage adds f(y) (v̄, -ū)): Rossby and magneto-Rossby waves.  Comma
+lists give one ensemble member per entry, like --coriolis.  With --channel it runs ONE Bounded model (one --gradients entry: Bounded
+ensembles take no f(y)).  Frames of potential_vorticity are not available under --beta; vorticity is.
 --viscosity NU and --diffusivity ETA add Oceananigans' closure = ScalarDiffusivity(nu = NU, kappa = ETA) (swmhd_amd.ScalarDiffusivity:
 NU on u and v, ETA -- the magnetic diffusivity -- on A and on the dye; one more launch per RK3 stage).  --viscosity needs
 --formulation jacobian; neither goes with --channel.  In an ensemble run both take comma lists like --coriolis (a sweep of the Reynolds
@@ -65,6 +69,7 @@ def main():
     ap.add_argument("--channel", action="store_true", help="(Periodic, Bounded) channel with gradient boundary conditions on A")
     ap.add_argument("--gradients", default=None, help="with --channel: comma-separated gradients of A, one ensemble member each")
     ap.add_argument("--coriolis", default=None, help="comma-separated Coriolis parameters f: one ensemble member per entry")
+    ap.add_argument("--beta", default=None, help="beta of coriolis = BetaPlane(f0, beta), with --coriolis as f0 (ensemble runs: a comma list, one member per entry)")
     ap.add_argument("--gravity", default=None, help="comma-separated gravitational accelerations g: one ensemble member per entry")
     ap.add_argument("--dts", default=None, help="comma-separated time steps: one ensemble member per entry (overrides --dt)")
     ap.add_argument("--every", type=int, default=100, help="iterations between progress lines / energy rows")
@@ -83,10 +88,11 @@ def main():
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
-    for k in range(len(argv) - 1):   # "--gradients -0.01,-0.05": argparse would read the negative list as an option
-        if argv[k] in ("--gradients", "--coriolis"):
+    k = 0
+    while k < len(argv) - 1:         # "--gradients -0.01,-0.05": argparse would read the negative list as an option
+        if argv[k] in ("--gradients", "--coriolis", "--beta"):
             argv[k] = argv[k] + "=" + argv.pop(k + 1)
-            break
+        k += 1
     a = ap.parse_args(argv)
     if a.plot_case:
         return plot_case(a)
@@ -108,21 +114,37 @@ def main():
         ap.error("--zonal-spectra is a schedule in time units: not with a per-member time step (--dts)")
     if a.dye and a.channel:
         ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
-    if a.amps or a.channel or a.sweep:
+    a.sweep = a.sweep or "," in (a.beta or "")
+    # --channel with --beta: ONE Bounded model (Bounded ensembles take no f(y)), so one gradient, one f0 and one beta
+    one_channel = a.channel and a.beta is not None
+    if one_channel and (a.gravity or a.dts or any("," in (x or "") for x in (a.gradients, a.beta, a.coriolis))):
+        ap.error("--channel with --beta runs one model: one --gradients entry, one --coriolis, one --beta, no --gravity or --dts")
+    if (a.amps or a.channel or a.sweep) and not one_channel:
         return run_ensemble(a)
+    a.sweep = False
 
     import torch
     import swmhd_amd as S
     from swmhd_amd import configs
     N, L = a.size, 10.0
-    grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
+    grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2),
+                             topology=("Periodic", "Bounded" if a.channel else "Periodic", "Flat"))
     form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
     closure = S.ScalarDiffusivity(nu=float(a.viscosity or 0.0), kappa=float(a.diffusivity or 0.0)) if a.closure else None
     if closure is not None:
         print(f"closure: {closure}, max_stable_dt = {closure.max_stable_dt(grid):.4g} (dt = {a.dt:g})")
-    model = S.ShallowWaterModel(grid, configs.G, configs.F, formulation=form, tracers=("c",) if a.dye else (), closure=closure)
+    # --beta B [--coriolis F0]: coriolis = BetaPlane(f0 = F0, beta = B), f = F0 + B y with y = 0 in mid-domain; one more launch per stage
+    coriolis = S.BetaPlane(float(a.coriolis) if a.coriolis else configs.F, float(a.beta)) if a.beta is not None else S.FPlane(configs.F)
+    if a.beta is not None:
+        print(f"coriolis: {coriolis}")
+    gr = float(a.gradients) if a.channel else None
+    bcs = {"A": S.FieldBoundaryConditions(north=S.GradientBoundaryCondition(gr), south=S.GradientBoundaryCondition(gr))} if a.channel else None
+    model = S.ShallowWaterModel(grid, configs.G, formulation=form, tracers=("c",) if a.dye else (), closure=closure, coriolis=coriolis,
+                                boundary_conditions=bcs)
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)
     A0 = (lambda X, Y: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp)
+    if a.channel:
+        A0 = lambda X, Y: gr * Y
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
     v0 = lambda X, Y: -5 * X * np.exp(-(X ** 2 + Y ** 2))
     n1, n2 = model.names[:2]
@@ -269,7 +291,7 @@ def run_ensemble(a):
     else:
         amps = [a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)]
     lists = {"--coriolis": floats(a.coriolis or ""), "--gravity": floats(a.gravity or ""), "--dts": floats(a.dts or ""),
-             "--viscosity": floats(a.viscosity or ""), "--diffusivity": floats(a.diffusivity or "")}
+             "--viscosity": floats(a.viscosity or ""), "--diffusivity": floats(a.diffusivity or ""), "--beta": floats(a.beta or "")}
     B = max([len(amps)] + [len(v) for v in lists.values()])
     for name, v in [("--gradients" if a.channel else "--amps", amps)] + [(k, v) for k, v in lists.items() if v]:
         if len(v) not in (1, B):
@@ -290,7 +312,12 @@ def run_ensemble(a):
         if a.closure:
             closure = S.ScalarDiffusivity(nu=per(lists["--viscosity"], 0.0), kappa=per(lists["--diffusivity"], 0.0))
             print(f"closure: {closure}, max_stable_dt = {closure.max_stable_dt(grid):.4g}")
-        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, fs, formulation=form, tracers=("c",) if a.dye else (), closure=closure)
+        # --beta: coriolis = BetaPlane(f0, beta) with --coriolis as f0, a scalar or one value per member each
+        fkw = {"coriolis_f": fs}
+        if a.beta is not None:
+            fkw = {"coriolis": S.BetaPlane(fs, per(lists["--beta"], 0.0))}
+            print(f"coriolis: {fkw['coriolis']}")
+        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, formulation=form, tracers=("c",) if a.dye else (), closure=closure, **fkw)
         A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
     label = "gradient" if a.channel else "amp"
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
@@ -313,7 +340,8 @@ def run_ensemble(a):
                   f"PE {d['potential_energy']:.3e} total {d['total_energy']:.6f}", flush=True)
             rows.append((m,) + (params(m) if a.sweep else ()) + (t, d["kinetic_energy"], d["magnetic_energy"], d["potential_energy"], d["total_energy"]))
 
-    params = lambda m: (float(ens.g_values[m]), float(ens.f_values[m]), dt[m] if a.dts else a.dt)
+    f0 = np.broadcast_to(np.asarray(fs, dtype=float), (len(amps),))        # (with --beta: f0; the stage kernels then run with f = 0)
+    params = lambda m: (float(ens.g_values[m]), float(f0[m]), dt[m] if a.dts else a.dt)
     sweep = lambda m: ", g {:g}, f {:g}, dt {:g}".format(*params(m)) if a.sweep else ""
     report(0.0)
     e0 = [r[-1] for r in rows]

@@ -773,5 +773,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_spectra.h"
 /* ScalarDiffusivity closure (swmhd_diffusion_rk3_*, swmhd_ensemble_diffusion_rk3_*): nu laplace(u, v), kappa laplace(A, tracers) per RK3 stage */
 #include "swmhd_diffusion.h"
+/* BetaPlane Coriolis (swmhd_coriolis_rk3_*, swmhd_ensemble_coriolis_rk3_*): f(y) (vbar, -ubar) added to (u, v) or (uh, vh) per RK3 stage */
+#include "swmhd_coriolis.h"
 
 #endif /* SWMHD_H */

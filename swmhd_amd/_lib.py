@@ -35,6 +35,7 @@ ENSEMBLE_NPARAMS = 3    # SWMHD_ENSEMBLE_NPARAMS: (g, f, dt) per member in the t
 MAX_TRACERS = 8         # SWMHD_MAX_TRACERS: passive tracers per swmhd_tracers_rk3_* launch
 DIFFUSION_MAX_FIELDS = 3 + MAX_TRACERS    # SWMHD_DIFFUSION_MAX_FIELDS: fields per swmhd_diffusion_rk3_* launch
 DIFFUSION_TILE_ROWS = 64                  # SWMHD_DIFFUSION_TILE_ROWS: rows of a workgroup of the diffusion kernel (four waves)
+CORIOLIS_TILE_ROWS = 64                   # SWMHD_CORIOLIS_TILE_ROWS: rows of a workgroup of the Coriolis kernel (four waves)
 
 
 def ensemble_diag_workspace(members, Nx, Ny):
@@ -196,6 +197,13 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_diffusion_rk3_{sfx}")
         f.argtypes = [C.POINTER(p)] * 3 + [p, i, i, i64, i, i, i, i, i64, ft, ft, p, ft, ft, i, i, i, p]
         f.restype = i
+        # BetaPlane Coriolis: q1, q2 old, new, acc, frow (device table), ...
+        f = getattr(lib, f"swmhd_coriolis_rk3_{sfx}")
+        f.argtypes = [p] * 7 + [i, i, i, i, i64, ft, ft, i, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_coriolis_rk3_{sfx}")
+        f.argtypes = [p] * 7 + [i, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
+        f.restype = i
     lib.swmhd_zonal_spectra_workspace.argtypes = [i, i, i, i]
     lib.swmhd_zonal_spectra_workspace.restype = i64
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
@@ -246,6 +254,8 @@ SPECTRA_EXPORTS = ["swmhd_zonal_spectra_workspace"] + [f"swmhd_{name}_{sfx}" for
                                                        for name in ("zonal_spectra", "ensemble_zonal_spectra")]
 # the symbols include/swmhd_diffusion.h declares (swmhd.h includes it; tests/test_diffusion_abi.py checks the .so exports each of them)
 DIFFUSION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("diffusion_rk3", "ensemble_diffusion_rk3")]
+# the symbols include/swmhd_coriolis.h declares (swmhd.h includes it; tests/test_coriolis_abi.py checks the .so exports each of them)
+CORIOLIS_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("coriolis_rk3", "ensemble_coriolis_rk3")]
 RING_ID_BYTES = 128
 
 

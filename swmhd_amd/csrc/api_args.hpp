@@ -106,6 +106,10 @@ constexpr int TRACER_NOTSUP = SWMHD_MARCH_KERNEL | SWMHD_GM_IS_PREV_STATE | OPEN
 // swmhd_diffusion_rk3 and its ensemble form (periodic grids only; SWMHD_RK3_ANCHOR: what `w` means to the ensemble call with a table)
 constexpr int DIFFUSION_FLAGS = SWMHD_STRICT | WRAP_FLAGS | SWMHD_RK3_ANCHOR;
 constexpr int DIFFUSION_NOTSUP = BOUNDED_FLAGS | KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLAGS | SWMHD_LEAVE_ROOM;
+// swmhd_coriolis_rk3 and its ensemble form: the Bounded flags say only that the direction is not wrapped (the filled halo carries the
+// wall), so a direction with both its flags is an argument error; SWMHD_RK3_ANCHOR as for the diffusion calls
+constexpr int CORIOLIS_FLAGS = SWMHD_STRICT | WRAP_FLAGS | BOUNDED_FLAGS | SWMHD_RK3_ANCHOR;
+constexpr int CORIOLIS_NOTSUP = KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLAGS | SWMHD_LEAVE_ROOM;
 // swmhd_ensemble_*: the periodic family, and the boundary-condition family (swmhd_ensemble_fill_halo, swmhd_ensemble_step_rk3_bc),
 // which accepts Bounded directions and runs the stage in G- form
 constexpr int ENS_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | WRAP_FLAGS | SWMHD_RK3_ANCHOR;

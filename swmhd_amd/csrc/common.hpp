@@ -299,6 +299,26 @@ struct DiffusionArgs {
 template <typename T> hipError_t launch_diffusion_fast(const DiffusionArgs<T> &a, hipStream_t s);
 template <typename T> hipError_t launch_diffusion_strict(const DiffusionArgs<T> &a, hipStream_t s);
 
+// BetaPlane Coriolis (swmhd_coriolis_rk3_*, coriolis.hip): D1 = fc[j] vbar, D2 = -(ff[j] ubar) of the two momentum-like fields q1, q2 in
+// ONE launch, added to what the stage kernels (run with f = 0) have written: n1 += a D1, n2 += a D2 and, where a1 != nullptr (then a2
+// too), a1 += w D1, a2 += w D2.  Pointers address interior cell (1,1) like TendArgs; wrap as there.  frow: the DEVICE table fc[0..Ny)
+// then ff[0..Ny).  members > 0: an ensemble -- member m of every parent at ptr + m * stride_m, its table at frow + m * 2 Ny; params,
+// anchor as in DiffusionArgs.
+template <typename T>
+struct CoriolisArgs {
+    const T *q1, *q2;
+    T *n1, *n2, *a1, *a2;
+    const T *frow;
+    int Nx, Ny, j0, j1, wrap;
+    long sy;
+    T a, w;
+    int members, anchor;
+    long stride_m;
+    const T *params;
+};
+template <typename T> hipError_t launch_coriolis_fast(const CoriolisArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_coriolis_strict(const CoriolisArgs<T> &a, hipStream_t s);
+
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
 // (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read

@@ -1,4 +1,4 @@
-// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the zonal-mean
+// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the Coriolis correction, the zonal-mean
 // kernel, the derived-frame kernel and the zonal-spectrum kernels: what a call will enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
@@ -430,6 +430,35 @@ inline TracerTiles tracer_tiles(int Nx, int rows, int K, int members) {
     t.blocks = (long)t.ntx * t.nty * members;
     t.too_many = t.blocks >= (1L << 31);
     return t;
+}
+
+// ---- the strips of one Coriolis correction (coriolis.hip) ----------------------------------------------------------------------------
+// A wave owns a strip of CORIOLIS_WAVE lanes x vec columns and marches down CORIOLIS_WAVE_ROWS rows of it; the CORIOLIS_WAVES waves of
+// a workgroup are consecutive row segments of one strip.  vec = 16 bytes of elements where `phase` >= 0: the 16-byte phase (in elements)
+// that the interior pointers of all six parents share and the pitches keep -- then the vector groups start `lead` = phase columns left
+// of x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  phase < 0: one element per lane.
+// blockIdx.x = (m nsb + sb) nstrips + strip.
+constexpr int CORIOLIS_WAVE = 64, CORIOLIS_WAVES = 4, CORIOLIS_WAVE_ROWS = 16;   // CORIOLIS_WAVES CORIOLIS_WAVE_ROWS = SWMHD_CORIOLIS_TILE_ROWS
+struct CoriolisPlan {
+    int vec, lead;
+    int nstrips, nsb; // strips of 64 vec columns x blocks of CORIOLIS_WAVES row segments, of one member
+    long blocks;      // nstrips * nsb * members
+    bool none;        // nothing to compute: no rows or no members
+    bool too_many;    // 2^31 blocks or more: beyond the grid of one launch
+};
+// members: 1 for a single grid
+inline CoriolisPlan coriolis_plan(int Nx, int rows, int elem_size, int phase, int members) {
+    CoriolisPlan p{};
+    p.none = Nx <= 0 || rows <= 0 || members <= 0;
+    if (p.none) return p;
+    p.vec = phase >= 0 ? 16 / elem_size : 1;
+    p.lead = phase >= 0 ? phase : 0;
+    const long cols = (long)CORIOLIS_WAVE * p.vec, tile_rows = (long)CORIOLIS_WAVES * CORIOLIS_WAVE_ROWS;
+    const long nstrips = ((long)Nx + p.lead + cols - 1) / cols, nsb = ((long)rows + tile_rows - 1) / tile_rows;
+    p.nstrips = (int)nstrips; p.nsb = (int)nsb;
+    p.blocks = nstrips * nsb * members;
+    p.too_many = p.blocks >= (1L << 31);
+    return p;
 }
 
 // ---- the rows of one zonal-mean call (zonal.hip) -------------------------------------------------------------------------------------

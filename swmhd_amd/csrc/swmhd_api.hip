@@ -276,6 +276,44 @@ int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *
     return hiprc(fl.strict ? launch_diffusion_strict<T>(d, s) : launch_diffusion_fast<T>(d, s));
 }
 
+// swmhd_coriolis_rk3: n1 += a fc vbar, n2 -= a ff ubar (and a1, a2 with w) in one launch (coriolis.hip).  Every check precedes the first
+// HIP call, in the order include/swmhd_coriolis.h states.  With `ens` (swmhd_ensemble_coriolis_rk3): frow holds one table per member;
+// ens->params (optional) brings every member's dt.
+template <typename T>
+int coriolis_common(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const T *frow, const Grid &g, T a, T w, const Rows &r, int flags,
+                    void *stream, const Ens *ens = nullptr) {
+    if (!q1 || !q2 || !n1 || !n2 || !frow) return SWMHD_EINVAL;
+    if ((a1 == nullptr) != (a2 == nullptr)) return SWMHD_EINVAL;
+    if (!g.extents_ok() || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
+    if ((flags & ~(CORIOLIS_FLAGS | CORIOLIS_NOTSUP)) || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
+    const T *const in[2] = {q1, q2};
+    const T *const out[4] = {n1, n2, a1, a2};
+    for (int k = 0; k < 4; ++k) {
+        if (!out[k]) continue;
+        if (out[k] == in[0] || out[k] == in[1]) return SWMHD_EINVAL;   // other workgroups still read old around their rows
+        for (int m = 0; m < k; ++m)
+            if (out[k] == out[m]) return SWMHD_EINVAL;
+    }
+    if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
+    if (ens) {
+        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
+        if (ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
+    }
+    if (flags & CORIOLIS_NOTSUP) return SWMHD_ENOTSUP;
+    const Flags fl = decode_flags(flags);
+    if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
+    if (r.j0 == r.j1) return SWMHD_OK;
+    CoriolisArgs<T> c;
+    c.q1 = g.interior(q1); c.q2 = g.interior(q2); c.n1 = g.interior(n1); c.n2 = g.interior(n2);
+    c.a1 = a1 ? g.interior(a1) : nullptr; c.a2 = a2 ? g.interior(a2) : nullptr;
+    c.frow = frow;
+    c.Nx = g.Nx; c.Ny = g.Ny; c.j0 = r.j0; c.j1 = r.j1; c.wrap = fl.wrap; c.sy = (long)g.sy; c.a = a; c.w = w;
+    c.members = ens ? ens->members : 0; c.anchor = fl.anchor; c.stride_m = ens ? (long)ens->stride_m : 0;
+    c.params = ens ? static_cast<const T *>(ens->params) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    return hiprc(fl.strict ? launch_coriolis_strict<T>(c, s) : launch_coriolis_fast<T>(c, s));
+}
+
 // The RK3 step driver.  Periodic: stages in anchor form (fast) and a periodic fill of whatever the kernel does not wrap.  Bounded
 // ensembles (ens->bc, swmhd_ensemble_step_rk3_bc): ShallowWaterModel.time_step's Bounded schedule -- every stage in G- form, then the
 // boundary-condition fill of the four fields, gradient values from the DEVICE table bc_gradient.  ph: the model and dt.
@@ -608,5 +646,21 @@ SWMHD_DEF_API(f32, float)
 
 SWMHD_DEF_DIFFUSION(f64, double)
 SWMHD_DEF_DIFFUSION(f32, float)
+
+// include/swmhd_coriolis.h
+#define SWMHD_DEF_CORIOLIS(sfx, T)                                                                                                                     \
+    int swmhd_coriolis_rk3_##sfx(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const T *frow, int Nx, int Ny, int Hx, int Hy, int64_t sy,     \
+                                 T a, T w, int j0, int j1, int flags, void *stream) {                                                                 \
+        return coriolis_common<T>(q1, q2, n1, n2, a1, a2, frow, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags, stream);                         \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_coriolis_rk3_##sfx(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const T *frow, int members, int64_t stride_m,         \
+                                          int Nx, int Ny, int Hx, int Hy, int64_t sy, const T *params, T a, T w, int j0, int j1, int flags,           \
+                                          void *stream) {                                                                                             \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return coriolis_common<T>(q1, q2, n1, n2, a1, a2, frow, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags, stream, &e);                     \
+    }
+
+SWMHD_DEF_CORIOLIS(f64, double)
+SWMHD_DEF_CORIOLIS(f32, float)
 
 }  // extern "C"

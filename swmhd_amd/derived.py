@@ -36,6 +36,13 @@ def _runs(names, tracers=()):
     return runs
 
 
+def check_coriolis_names(model, names):
+    """SwmhdError for potential_vorticity of a model whose Coriolis parameter varies with y: the kernel takes one scalar f."""
+    if getattr(model, "_coriolis", None) is not None and "potential_vorticity" in names:
+        raise _lib.SwmhdError(f"potential_vorticity under coriolis = {model.coriolis!r} is not supported (SWMHD_ENOTSUP): "
+                              "swmhd_derived_fields_* takes a scalar f; vorticity is available")
+
+
 def state_pointers(model):
     """(the four parents' device pointers, row stride, device, is an ensemble) of the state as it stands now"""
     if getattr(model, "members", None) is not None:
@@ -65,6 +72,7 @@ def enqueue_derived(model, names=DEFAULT_NAMES, out=None, array_type=torch.float
     """ShallowWaterModel.derived_fields / ShallowWaterEnsemble.derived_fields: see there."""
     names = tuple(names)
     runs = _runs(names, getattr(model, "tracer_names", ()))
+    check_coriolis_names(model, names)
     ptrs, sy, dev, ens = state_pointers(model)
     g = model.grid
     shape = ((model.members,) if ens else ()) + (len(names), g.Ny, g.Nx)

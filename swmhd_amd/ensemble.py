@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from .closure import check_closure
+from .coriolis import check_coriolis, row_table
 from .fields import _SFX, _stream_ptr
 from .grid import Center, Face
 from .model import RK3_ANCHOR_WEIGHT, ShallowWaterModel, rk3_operands, rk3_stage, tracer_names
@@ -57,6 +58,11 @@ class ShallowWaterEnsemble:
     swmhd_ensemble_tracers_rk3[_params] on the state the stage started from -- six launches per step for all tracers of all members
     with fused halos -- and its four state fields come out bitwise what the native driver gives the ensemble without tracers.
 
+    Coriolis: `coriolis=BetaPlane(f0=..., beta=...)` (ShallowWaterModel's argument; swmhd_amd.coriolis) with a scalar or one value per
+    member for f0 and for beta -- a sweep of beta.  `coriolis_rows` is the (members, 2, Ny) device table of f at the centres and the
+    faces of every member's rows; such an ensemble steps stage by stage with one more launch per stage for all members
+    (swmhd_ensemble_coriolis_rk3_*), under a scalar or a per-member dt.  FPlane(f) is coriolis_f=f and changes no call.
+
     Closure: `closure=ScalarDiffusivity(nu=..., kappa=...)` (ShallowWaterModel's argument) with a scalar or one value per member for
     every coefficient -- a sweep of the Reynolds or the magnetic Prandtl number.  `diffusion_coefficients` is the (members, fields
     with a coefficient) device table; such an ensemble steps stage by stage as one with tracers does, with one more launch per stage
@@ -65,8 +71,12 @@ class ShallowWaterEnsemble:
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, tracers=(), closure=None):
+                 fuse_halo=True, tracers=(), closure=None, coriolis=None):
         self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
+        # coriolis = FPlane | BetaPlane | CoriolisProfile (ShallowWaterModel's argument; values may be per member).  None and FPlane: the
+        # f of the stage kernels.  Otherwise they get f = 0 and _coriolis holds the parameter whose rows _coriolis_stage adds
+        self.coriolis = coriolis
+        coriolis_f, self._coriolis = check_coriolis(coriolis, coriolis_f, 1.0)
         self.closure = closure
         coefs = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
                               formulation != VectorInvariantFormulation)      # (a Bounded grid: _check_topology, below)
@@ -84,6 +94,7 @@ class ShallowWaterEnsemble:
         # the closure's coefficients: a scalar or one value per member each; the fields all of whose values are 0 have no launch
         coefs = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs or {}).items()}
         self._diffusion = {n: c for n, c in coefs.items() if np.any(c != 0.0)} or None
+        rows = row_table(self._coriolis, grid, self.members) if self._coriolis is not None else None
         self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
         self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
         self.grid = grid
@@ -122,6 +133,11 @@ class ShallowWaterEnsemble:
         if self._diffusion is not None:
             host = np.stack([self._diffusion[n] for n in self._diffusion_names()], axis=1)
             self.diffusion_coefficients = torch.from_numpy(np.ascontiguousarray(host)).to(device=self._state[0].device, dtype=dtype)
+        # (members, 2, Ny) on the device, in the ensemble's dtype and rounded to it: fc then ff of every member, the table of
+        # swmhd_ensemble_coriolis_rk3_*; built once
+        self.coriolis_rows = None
+        if rows is not None:
+            self.coriolis_rows = torch.from_numpy(rows).to(device=self._state[0].device, dtype=dtype)
         if g_seq or f_seq:
             self._make_parameters()
 
@@ -279,6 +295,24 @@ class ShallowWaterEnsemble:
         f = getattr(self._L, f"swmhd_ensemble_tracers_rk3_{'params_' if par else ''}{self.sfx}")
         _lib.check(f(*head, self.parameters.data_ptr() if par else dt, *tail), "swmhd_ensemble_tracers_rk3" + ("_params" if par else ""))
 
+    def _coriolis_stage(self, dt, stage):
+        """The Coriolis launch of RK3 stage `stage` for every member (swmhd_ensemble_coriolis_rk3_*; with dt None every member's dt comes
+        from the table): ShallowWaterModel._coriolis_stage with the rows of member m in block m of the device table."""
+        g = self.grid
+        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        q, new = self._state, self._alt
+        par = dt is None
+        acc, w, flag = (None, None), 0.0, 0
+        if anchor and stage == 0:     # with the table the kernel forms dt_m / 4 (SWMHD_RK3_ANCHOR: w is a weight of dt)
+            acc, w, flag = (self.Gn[0].data_ptr(), self.Gn[1].data_ptr()), (RK3_ANCHOR_WEIGHT if par else dt * RK3_ANCHOR_WEIGHT), _lib.RK3_ANCHOR
+        elif not anchor and store:
+            acc, w = (self.Gn[0].data_ptr(), self.Gn[1].data_ptr()), 1.0
+        f = getattr(self._L, f"swmhd_ensemble_coriolis_rk3_{self.sfx}")
+        rc = f(q[0].data_ptr(), q[1].data_ptr(), new[0].data_ptr(), new[1].data_ptr(), acc[0], acc[1], self.coriolis_rows.data_ptr(),
+               self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride(1), self.parameters.data_ptr() if par else None,
+               gamma if par else dt * gamma, w, 0, g.Ny, self._flags | self._rwrap | flag, _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_coriolis_rk3")
+
     def _diffusion_names(self):
         return [n for n in self.names + self.tracer_names if n in self._diffusion]
 
@@ -333,7 +367,7 @@ class ShallowWaterEnsemble:
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        if self._tr or self._diffusion is not None:        # (the native step driver steps the four fields only)
+        if self._tr or self._diffusion is not None or self._coriolis is not None:        # (the native step driver steps the four fields only, with a scalar f)
             self._stage_steps(dt if dts is None else None, n)
         else:
             self._enqueue_steps(dt if dts is None else None, n, swapped)
@@ -468,9 +502,10 @@ class ShallowWaterEnsemble:
         return model
 
     def _member_model(self, m):
-        return ShallowWaterModel(self.grid, float(self.g_values[m]), float(self.f_values[m]), formulation=self.formulation,
+        f = {"coriolis_f": float(self.f_values[m])} if self._coriolis is None else {"coriolis": self._coriolis.for_member(m)}
+        return ShallowWaterModel(self.grid, float(self.g_values[m]), formulation=self.formulation,
                                  lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
-                                 tracers=self.tracer_names, closure=self.closure.for_member(m) if self.closure is not None else None)
+                                 tracers=self.tracer_names, closure=self.closure.for_member(m) if self.closure is not None else None, **f)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
@@ -489,7 +524,11 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None):
+                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None):
+        coriolis_f, varying = check_coriolis(coriolis, coriolis_f, 1.0)       # before anything is allocated
+        if varying is not None:
+            raise _lib.SwmhdError("coriolis = f(y) on a Bounded ensemble is not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is "
+                                  "one native call and has no per-stage entry point for the correction launch")
         if closure is not None:       # before anything is allocated
             raise _lib.SwmhdError("closure on a Bounded ensemble is not supported (SWMHD_ENOTSUP): the wall faces of u and v and the "
                                   "gradient conditions need a kernel body of their own")
@@ -512,6 +551,7 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
             check_boundary_conditions(bcs, self._bounded, names)
         super().__init__(grid, members, gravitational_acceleration, coriolis_f, formulation, lorentz_forcing, dtype, strict, device,
                          member_stride, decomp, fuse_halo)
+        self.coriolis = coriolis      # (None or an FPlane: its f went to the base class as coriolis_f)
         self._member_bcs = per_member
         # (members, 4 fields, 4 sides: west, east, south, north), NaN = default; in the ensemble's dtype (f32: rounded to nearest as the
         # single model's ctypes.c_float values are)

@@ -10,10 +10,12 @@ One `time_step(dt)` == Oceananigans' RK3 `time_step!`: 3 x {calculate_tendencies
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
 from .closure import check_closure
+from .coriolis import check_coriolis, row_table
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
 from .grid import Center, Face
@@ -82,7 +84,16 @@ class ShallowWaterModel:
     def __init__(self, grid, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, device="cuda", strict=False, decomp=None, group=None,
                  overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None,
-                 tracers=(), closure=None):
+                 tracers=(), closure=None, coriolis=None):
+        # coriolis = FPlane | BetaPlane | CoriolisProfile (swmhd_amd.coriolis), checked before anything is allocated.  None and FPlane:
+        # the scalar f of the stage kernels, exactly the calls made without the argument.  Otherwise the stage kernels get f = 0 and
+        # _coriolis holds the parameter whose rows _coriolis_stage adds after every stage
+        self.coriolis = coriolis
+        coriolis_f, self._coriolis = check_coriolis(coriolis, coriolis_f, 1.0, decomp is not None and decomp.world_size > 1,
+                                                    ring is not None, fused)
+        if np.ndim(coriolis_f) or (self._coriolis is not None and self._coriolis.per_member is not None):
+            raise _lib.SwmhdError(f"coriolis = {coriolis!r}: per-member values belong to an ensemble")
+        rows = row_table(self._coriolis, grid) if self._coriolis is not None else None
         # passive tracers (swmhd_tracers_rk3_*): names and what they cannot be combined with are checked before anything is allocated
         self.tracer_names = tracer_names(tracers)
         if self.tracer_names:
@@ -155,6 +166,10 @@ class ShallowWaterModel:
         self.tendency_events = None   # bench.py: list collecting (start, end) HIP events around every tendency launch
         if any(not f.data.is_cuda for f in self._state.values()):
             raise _lib.SwmhdError("ShallowWaterModel runs on the GPU only (no CPU fallback)")
+        # (2, Ny) on the device, in the model's dtype and rounded to it: fc then ff, the table of swmhd_coriolis_rk3_*; built once
+        self.coriolis_rows = None
+        if rows is not None:
+            self.coriolis_rows = torch.from_numpy(rows).to(device=self._raw_fields[0].data.device, dtype=dtype)
         # y-slab ring: the native RCCL ring (swmhd_ring_*) when the process group is RCCL; torch.distributed p2p otherwise
         # (gloo rehearsals).  The ring's step driver needs the fused stage kernel and a slab taller than its two strips.
         # `ring`: a swmhd_ring handle created by the caller -- one of swmhd_ring_create_loopback's (loopback_rings below): several
@@ -394,6 +409,26 @@ class ShallowWaterModel:
                dt, gamma, zeta, store, 0, g.Ny, flags, _stream_ptr())
         _lib.check(rc, "swmhd_tracers_rk3")
 
+    def _coriolis_stage(self, dt, stage):
+        """The Coriolis launch of RK3 stage `stage` under a parameter that varies with y (swmhd_coriolis_rk3_*): D = f(y_j) (vbar, -ubar)
+        on the state the stage started from, added with dt gamma to the two new momentum-like fields and, where the stage stores an
+        operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
+        the anchor form) -- as _diffusion_stage chooses them.  Order (finish_stage): after _stage_fused and _tracer_stage, BEFORE
+        _diffusion_stage and the swaps; with a closure as well the new u is ((stage + a D_coriolis) + a D_closure), and that order
+        decides the last bits.  Bounded directions pass no WRAP flag and read the halos the previous fill left current."""
+        g = self.grid
+        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        q, new = self._raw_fields, [self._alt[n] for n in self.names]
+        acc, w = (None, None), 0.0
+        if anchor and stage == 0:
+            acc, w = (self.Gn[0].ptr, self.Gn[1].ptr), dt * RK3_ANCHOR_WEIGHT
+        elif not anchor and store:
+            acc, w = (self.Gn[0].ptr, self.Gn[1].ptr), 1.0
+        f = getattr(self._L, f"swmhd_coriolis_rk3_{self.sfx}")
+        rc = f(q[0].ptr, q[1].ptr, new[0].ptr, new[1].ptr, acc[0], acc[1], self.coriolis_rows.data_ptr(), g.Nx, g.Ny, g.Hx, g.Hy,
+               q[0].stride_y, dt * gamma, w, 0, g.Ny, (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap, _stream_ptr())
+        _lib.check(rc, "swmhd_coriolis_rk3")
+
     def _diffusion_stage(self, dt, stage):
         """The closure's launch of RK3 stage `stage` (swmhd_diffusion_rk3_*): D = coef laplace(field) on the state the stage started
         from, for every field with a coefficient, added with dt gamma to the new state (and tracers) and, where the stage stores an
@@ -551,7 +586,8 @@ class ShallowWaterModel:
 
     def _driver_steps(self, dt, n):
         if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)
-                                      and not self._tr and self._diffusion is None):     # (the native step driver steps the four fields only)
+                                      and not self._tr and self._diffusion is None
+                                      and self._coriolis is None):     # (the native step driver steps the four fields only, with a scalar f)
             return self._native_steps(dt, n)
         for _ in range(n):
             self.time_step(dt)

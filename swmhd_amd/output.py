@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .derived import launch as launch_derived, state_pointers
+from .derived import check_coriolis_names, launch as launch_derived, state_pointers
 from .fields import _stream_ptr
 
 DEFAULT_NAMES = ("u", "v", "A", "s")    # the reference's writer
@@ -71,6 +71,7 @@ def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32
     """ShallowWaterModel.output_fields / ShallowWaterEnsemble.output_fields: see there."""
     names = tuple(names)
     runs = _frame_runs(names, getattr(model, "tracer_names", ()))
+    check_coriolis_names(model, names)
     g = model.grid
     ptrs, sy, dev, ens = state_pointers(model)
     shape = frame_shape(model, names)
@@ -156,6 +157,7 @@ class FieldTimeSeries:
     def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None, array_type=torch.float32):
         self.model, self.names, self.schedule = model, tuple(names), schedule
         _frame_runs(self.names, getattr(model, "tracer_names", ()))
+        check_coriolis_names(model, self.names)
         if array_type not in _ELEM:
             raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
         if capacity is None or int(capacity) < 1:

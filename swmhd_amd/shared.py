@@ -42,11 +42,15 @@ def diagnostics_dict(v):
 def finish_stage(o, dt, stage, fused=True):
     """What follows the state's launch of RK3 stage `stage` of `o` (a ShallowWaterModel or a ShallowWaterEnsemble), before its halo
     fill: the tracers through the same stage in one launch (o._tracer_stage), advected by the state the stage STARTED from -- still
-    o._state here -- then, with a closure, its one diffusion launch on that same state, correcting what the two launches have written
-    (o._diffusion_stage) -- then the pointer swaps: the new tracers and the new state become current, and G- <- Gn for both
+    o._state here -- then, under a Coriolis parameter that varies with y, its one launch on that same state, correcting the two
+    momentum-like fields the stage kernel wrote with f = 0 (o._coriolis_stage) -- then, with a closure, its one diffusion launch on that
+    same state, correcting what the launches before it have written (o._diffusion_stage); in this order, which decides the last bits
+    where both are present -- then the pointer swaps: the new tracers and the new state become current, and G- <- Gn for both
     (store_tendencies!, 0 bytes).  fused=False: the state was advanced in place by a substep, only its G sets swap."""
     if o._tr:
         o._tracer_stage(dt, stage)
+    if getattr(o, "_coriolis", None) is not None:
+        o._coriolis_stage(dt, stage)
     if getattr(o, "_diffusion", None) is not None:
         o._diffusion_stage(dt, stage)
     if o._tr:
