@@ -2,7 +2,7 @@
 // checks the dispatch sequence of each case against what the launchers enqueued before the plans existed (read off those launchers; the
 // same cases were traced on an MI355X, profiles/launch_plan/ and profiles/op_launch_plan/).  Launches nothing and allocates no device
 // memory; without a device the CU count is taken as 256, which is the MI355X's, so the numbers hold either way.  Compiled and run by
-// tests/test_launch_plan_cpu.py with the SWMHD_* knobs unset, and once more as `launch_plan_check op_ly 5` with SWMHD_OP_LY=5.
+// tests/test_launch_plan_cpu.py with the SWMHD_* knobs unset, and again as `launch_plan_check op_ly 5` with SWMHD_OP_LY=5 and `op_ly 13` with 13.
 #include "launch_plan.hpp"
 #include <stdio.h>
 #include <string.h>
@@ -377,11 +377,76 @@ static void operators_bounded() {
     CHECK(p.n == 2 && p.e[0].kernel == OpKernel::MARCH && op_tile_is(p.e[1], 21, 1) && op_args_are(p.e[1], 792, 800, 0, B | TOPO_OPEN_SOUTH, 0));
 }
 
-// SWMHD_OP_LY = ly (a process of its own: the knob is read once): that many rows per segment, even below the minimum of 8
+// ---- the shapes of the operator call matrix (tests/operator_cases.py) -------------------------------------------------------------
+// What every shape of the matrix lands on, so that "one column and one row below, at and above a workgroup" is a fact about the plan:
+// strips of 252 | 250 output columns x segments of 8 rows on the march path (SWMHD_MARCH_KERNEL: kernel_variant 2), tiles of
+// 64 x 16 | 64 x 8 on the tile, strict and wall paths.
+struct MatrixShape { int Nx, Ny, nx, ny, ny_inner; };   // strips | tile columns, segments | tile rows over all rows and over rows [1, Ny - 1)
+static OpPlanIn matrix_op(int Nx, int Ny, bool div, int variant, bool strict, int tx, int ty, int j0, int j1) {
+    OpPlanIn a = op(Nx, Ny, div, tx, ty);
+    a.kernel_variant = variant; a.strict = strict; a.j0 = j0; a.j1 = j1;
+    return a;
+}
+static void operators_matrix() {
+    CHECK(OP_MARCH_NT == 256 && OP_MARCH_LY_MIN == 8 && TILE_X == 64 && OP_JAC_TILE_Y == 16 && OP_DIV_TILE_Y == 8);
+    // march: (1,1) (2,3) (5,4) (W-1,R-1) (W,R) (W+1,R+1) (2W+1,2R+1), W = 252 | 250, R = 8: a small grid forced onto the marching
+    // kernels has segments of the minimum of 8 rows
+    const MatrixShape jm[7] = {{1, 1, 1, 1, 0}, {2, 3, 1, 1, 1}, {5, 4, 1, 1, 1}, {251, 7, 1, 1, 1}, {252, 8, 1, 1, 1}, {253, 9, 2, 2, 1}, {505, 17, 3, 3, 2}};
+    const MatrixShape dm[7] = {{1, 1, 1, 1, 0}, {2, 3, 1, 1, 1}, {5, 4, 1, 1, 1}, {249, 7, 1, 1, 1}, {250, 8, 1, 1, 1}, {251, 9, 2, 2, 1}, {501, 17, 3, 3, 2}};
+    for (int div = 0; div <= 1; ++div) {
+        for (int k = 0; k < 7; ++k) {
+            const MatrixShape &m = div ? dm[k] : jm[k];
+            OpPlan p = plan_lorentz(matrix_op(m.Nx, m.Ny, div != 0, 2, false, 0, 0, 0, m.Ny));
+            CHECK(p.n == 1 && op_march_is(p.e[0], m.nx, m.ny, 8, div ? 5 : 6) && op_args_are(p.e[0], 0, m.Ny, 0, 0, 0));
+            p = plan_lorentz(matrix_op(m.Nx, m.Ny, div != 0, 2, false, 0, 0, 1, m.Ny - 1 > 1 ? m.Ny - 1 : 1));
+            CHECK(m.ny_inner ? p.n == 1 && op_march_is(p.e[0], m.nx, m.ny_inner, 8, div ? 5 : 6) : p.n == 0);
+        }
+        // the phase sweep: (W + 1, 21), rows [j0, j0 + 9): two strips, the second one column wide; a full segment and one of one row
+        for (int j0 = 0; j0 < 12; ++j0) {
+            const OpPlan p = plan_lorentz(matrix_op(div ? 251 : 253, 21, div != 0, 2, false, 0, 0, j0, j0 + 9));
+            CHECK(p.n == 1 && op_march_is(p.e[0], 2, 2, 8, div ? 5 : 6) && op_args_are(p.e[0], j0, j0 + 9, 0, 0, 0));
+        }
+    }
+    // tile and strict: the same seven around 64 x 16 | 64 x 8, and (129, 9)
+    const MatrixShape jt[8] = {{1, 1, 1, 1, 0}, {2, 3, 1, 1, 1}, {5, 4, 1, 1, 1}, {63, 15, 1, 1, 1}, {64, 16, 1, 1, 1}, {65, 17, 2, 2, 1}, {129, 33, 3, 3, 2}, {129, 9, 3, 1, 1}};
+    const MatrixShape dt[8] = {{1, 1, 1, 1, 0}, {2, 3, 1, 1, 1}, {5, 4, 1, 1, 1}, {63, 7, 1, 1, 1}, {64, 8, 1, 1, 1}, {65, 9, 2, 2, 1}, {129, 17, 3, 3, 2}, {129, 9, 3, 2, 1}};
+    for (int div = 0; div <= 1; ++div) {
+        for (int strict = 0; strict <= 1; ++strict) {
+            for (int k = 0; k < 8; ++k) {
+                const MatrixShape &m = div ? dt[k] : jt[k];
+                OpPlan p = plan_lorentz(matrix_op(m.Nx, m.Ny, div != 0, strict ? 0 : 1, strict != 0, 0, 0, 0, m.Ny));
+                CHECK(p.n == 1 && op_tile_is(p.e[0], m.nx, m.ny) && op_args_are(p.e[0], 0, m.Ny, 0, 0, 0));
+                p = plan_lorentz(matrix_op(m.Nx, m.Ny, div != 0, strict ? 0 : 1, strict != 0, 0, 0, 1, m.Ny - 1 > 1 ? m.Ny - 1 : 1));
+                CHECK(m.ny_inner ? p.n == 1 && op_tile_is(p.e[0], m.nx, m.ny_inner) : p.n == 0);
+            }
+        }
+    }
+    // wall and wall-strict: (4,3) and (7,9) in place of the three tiny shapes; the wall tile kernel alone with the caller's topology
+    const MatrixShape dw[7] = {{4, 3, 1, 1, 1}, {7, 9, 1, 2, 1}, {63, 7, 1, 1, 1}, {64, 8, 1, 1, 1}, {65, 9, 2, 2, 1}, {129, 17, 3, 3, 2}, {129, 9, 3, 2, 1}};
+    const int topos[3][2] = {{1, 1}, {1, 0}, {0, 1}};
+    for (int t = 0; t < 3; ++t) {
+        for (int strict = 0; strict <= 1; ++strict) {
+            for (int k = 0; k < 7; ++k) {
+                const MatrixShape &m = dw[k];
+                const OpPlanIn a = matrix_op(m.Nx, m.Ny, true, strict ? 0 : 1, strict != 0, topos[t][0], topos[t][1], 0, m.Ny);
+                CHECK(wall_tile_alone(a, m.nx) && plan_lorentz(a).e[0].nty == m.ny);
+                const OpPlanIn b = matrix_op(m.Nx, m.Ny, true, strict ? 0 : 1, strict != 0, topos[t][0], topos[t][1], 1, m.Ny - 1);
+                CHECK(wall_tile_alone(b, m.nx) && plan_lorentz(b).e[0].nty == m.ny_inner);
+            }
+        }
+    }
+}
+
+// SWMHD_OP_LY = ly (a process of its own: the knob is read once): that many rows per segment, even below the minimum of 8 -- on a large
+// grid and on the sweep grid of the operator matrix (all 21 rows and rows [j0, j0 + 9))
 static void operators_forced_ly(int ly) {
     for (int div = 0; div <= 1; ++div) {
-        const OpPlan p = plan_lorentz(op(4096, 4096, div != 0));
+        OpPlan p = plan_lorentz(op(4096, 4096, div != 0));
         CHECK(p.n == 1 && op_march_is(p.e[0], 17, (4096 + ly - 1) / ly, ly, div ? 5 : 6));
+        p = plan_lorentz(matrix_op(div ? 251 : 253, 21, div != 0, 2, false, 0, 0, 0, 21));
+        CHECK(p.n == 1 && op_march_is(p.e[0], 2, (21 + ly - 1) / ly, ly, div ? 5 : 6));
+        p = plan_lorentz(matrix_op(div ? 251 : 253, 21, div != 0, 2, false, 0, 0, 7, 16));
+        CHECK(p.n == 1 && op_march_is(p.e[0], 2, (9 + ly - 1) / ly, ly, div ? 5 : 6));
     }
 }
 
@@ -421,6 +486,7 @@ int main(int argc, char **argv) {
     query();
     operators_periodic();
     operators_bounded();
+    operators_matrix();
     tracers();
     printf(failures ? "%d plan checks FAILED\n" : "launch plans OK\n", failures);
     return failures ? 1 : 0;

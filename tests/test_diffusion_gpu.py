@@ -148,28 +148,56 @@ def test_parents_of_different_phase_and_null_acc_entries(swmhd):
 # ----------------------------------------------------------------------------------------------------------------------------------
 # ensembles through the ABI
 # ----------------------------------------------------------------------------------------------------------------------------------
+# (Nx by precision, Ny, stride_y by precision, elements added to stride_m): the launch of three members and three fields has
+# 9 x strips x row blocks workgroups
+ENS_GEOMETRIES = {
+    # one strip, one row block; the 16-byte path (stride_y and stride_m multiples of four): 9 workgroups
+    "one-tile": dict(Nx={"f64": 65, "f32": 65}, Ny=17, sy={"f64": 72, "f32": 72}, gap=8, vec=True),
+    # the 16-byte path with two strips (128 doubles | 256 floats each) and two row blocks of 64 rows: 36 workgroups, no multiple of 8
+    "vec-2x2": dict(Nx={"f64": 129, "f32": 257}, Ny=65, sy={"f64": 136, "f32": 264}, gap=8, vec=True),
+    # an odd stride_m: one element per lane, two strips of 64 columns, two row blocks: 36 workgroups
+    "elem-2x2": dict(Nx={"f64": 65, "f32": 65}, Ny=65, sy={"f64": 72, "f32": 72}, gap=9, vec=False),
+}
+
+
 @pytest.mark.parametrize("members", [1, 3])
 @pytest.mark.parametrize("sfx", ["f64", "f32"])
 def test_ensemble_members_are_single_grid_calls(swmhd, sfx, members):
-    """Strict, 65 x 17, three fields, stride_m pitched with the sentinel in the gap; per-member coefficients (one of them 0) in the
-    device table; dt: one for all (params NULL; w = 1), and per member from the (g, f, dt) table, with w = 1 (the stored tendency) and
-    with SWMHD_RK3_ANCHOR (w = 1/4 of each member's dt).  Member m is bitwise the single-grid call with coef[m], a = dt_m gamma formed
-    in the element type as the kernel forms it, and its w.  Then a member full of NaN leaves the others bitwise what they were."""
+    """Three fields, stride_m pitched with the sentinel in the gap; per-member coefficients (one of them 0) in the device table; dt: one
+    for all (params NULL; w = 1), and per member from the (g, f, dt) table, with w = 1 (the stored tendency) and with SWMHD_RK3_ANCHOR
+    (w = 1/4 of each member's dt).  Geometries (ENS_GEOMETRIES): 65 x 17, one tile per member and field; two strips x two row blocks on
+    the 16-byte path and on the one-element path (an odd stride_m), where the kernel's decode of blockIdx into (member, field, tile)
+    has more than one tile to tell apart.  Rows: all, and [1, Ny - 1), where rows 0 and Ny - 1 of every member stay bitwise what they
+    were.  Strict: member m is bitwise the single-grid call with coef[m], a = dt_m gamma formed in the element type as the kernel
+    forms it, and its w.  Fast: member m is held to the derived bound of the single-grid stage matrix (check_outputs, against the
+    longdouble value with the coefficients of the table as rounded to the precision of the call) -- not bitwise to the fast
+    single-grid call: two instantiations need not contract alike.  Then (strict) a member full of NaN leaves the others bitwise what
+    they were."""
     L = swmhd._lib
     t = NPDT[sfx]
-    Nx, Ny, Hx, Hy, n = 65, 17, 3, 3, 3
-    sy = 72
+    for name, geo in ENS_GEOMETRIES.items():
+        for strict in (True, False):
+            _ensemble_abi_case(L, sfx, t, members, name, geo, strict)
+
+
+def _ensemble_abi_case(L, sfx, t, members, name, geo, strict):
+    Nx, Ny, Hx, Hy, n = geo["Nx"][sfx], geo["Ny"], 3, 3, 3
+    sy = geo["sy"][sfx]
     size = (Ny + 2 * Hy) * sy
-    stride_m = size + 8
+    stride_m = size + geo["gap"]
+    V = 16 // np.dtype(t).itemsize
+    assert (sy % V == 0 and stride_m % V == 0) == geo["vec"]
     ft = ctypes.c_double if sfx == "f64" else ctypes.c_float
     cases = [Case(Nx, Ny, Hx, Hy, sy, t, True, 20 + m) for m in range(members)]
     table = np.array([[0.011 * (m + 1) + 0.002 * k if (m + k) % 4 != 1 else 0.0 for k in range(n)] for m in range(members)], dtype=t)
+    for m, c in enumerate(cases):      # the references of check_outputs take the member's coefficients of the table
+        c.coef[:n] = [float(x) for x in table[m]]
     dts = np.array([0.013 * (1 + 0.5 * m) for m in range(members)], dtype=t)
     gamma = t(0.37)
     params = np.stack([np.full(members, 9.81), np.ones(members), dts], axis=1).astype(t)
     single = getattr(L.lib(), f"swmhd_diffusion_rk3_{sfx}")
     ens = getattr(L.lib(), f"swmhd_ensemble_diffusion_rk3_{sfx}")
-    flags = L.STRICT | L.WRAP_X | L.WRAP_Y
+    flags = (L.STRICT if strict else 0) | L.WRAP_X | L.WRAP_Y
 
     def pack(arrs):        # (n, members * stride_m): field k of member m at [k, m * stride_m:]
         out = np.full((n, members * stride_m), DC.SENTINEL, dtype=t)
@@ -177,46 +205,59 @@ def test_ensemble_members_are_single_grid_calls(swmhd, sfx, members):
             out[:, m * stride_m:m * stride_m + size] = a[:n].reshape(n, size)
         return torch.from_numpy(out).cuda()
 
-    def run_ensemble(olds, par, w, anchor):
+    def run_ensemble(olds, par, w, anchor, rows):
         old_d, new_d, acc_d = pack(olds), pack([c.new for c in cases]), pack([c.acc for c in cases])
         tab_d, par_d = torch.from_numpy(table).cuda(), torch.from_numpy(params).cuda()
         rc = ens(ptrs(old_d, n), ptrs(new_d, n), ptrs(acc_d, n), tab_d.data_ptr(), n, members, stride_m, Nx, Ny, Hx, Hy, sy, cases[0].dx,
-                 cases[0].dy, par_d.data_ptr() if par else None, float(gamma) if par else float(dts[0] * gamma), w, 0, Ny,
+                 cases[0].dy, par_d.data_ptr() if par else None, float(gamma) if par else float(dts[0] * gamma), w, rows[0], rows[1],
                  flags | (L.RK3_ANCHOR if anchor else 0), None)
         L.check(rc, "swmhd_ensemble_diffusion_rk3")
         torch.cuda.synchronize()
         return new_d.cpu().numpy(), acc_d.cpu().numpy()
 
-    def run_single(m, a, w):
+    def run_single(m, a, w, rows):
         c = cases[m]
         old_d, new_d, acc_d = torch.from_numpy(c.old).cuda(), torch.from_numpy(c.new).cuda(), torch.from_numpy(c.acc).cuda()
         coef = (ft * n)(*[float(x) for x in table[m]])
         rc = single(ptrs(old_d, n), ptrs(new_d, n), ptrs(acc_d, n), ctypes.cast(coef, ctypes.c_void_p), n, Nx, Ny, Hx, Hy, sy, c.dx, c.dy,
-                    a, w, 0, Ny, flags, None)
+                    a, w, rows[0], rows[1], flags, None)
         L.check(rc, "swmhd_diffusion_rk3")
         torch.cuda.synchronize()
         return new_d.cpu().numpy()[:n].reshape(n, size), acc_d.cpu().numpy()[:n].reshape(n, size)
 
     u = np.uint64 if sfx == "f64" else np.uint32
     quarter = t(0.25)
-    for par, w, anchor in ((False, 1.0, False), (True, 1.0, False), (True, float(quarter), True)):
-        got_new, got_acc = run_ensemble([c.old for c in cases], par, w, anchor)
-        for m in range(members):
-            a_m = float((dts[m] if par else dts[0]) * gamma)
-            w_m = float(dts[m] * quarter) if anchor else w
-            one_new, one_acc = run_single(m, a_m, w_m)
-            lo = m * stride_m
-            assert np.array_equal(got_new[:, lo:lo + size].view(u), one_new.view(u)), (par, anchor, m)
-            assert np.array_equal(got_acc[:, lo:lo + size].view(u), one_acc.view(u)), (par, anchor, m)
-            assert np.all(got_new[:, lo + size:lo + stride_m] == DC.SENTINEL) and np.all(got_acc[:, lo + size:lo + stride_m] == DC.SENTINEL)
-            k0 = [k for k in range(n) if table[m, k] == 0]
-            for k in k0:        # a zero of the device table: that field of that member is untouched
-                assert np.array_equal(one_new[k].view(u), cases[m].new[k].reshape(-1).view(u))
-    if members > 1:
-        clean = run_ensemble([c.old for c in cases], True, 1.0, False)
+    outer = [Hy, Hy + Ny - 1]      # parent rows of the rows 0 and Ny - 1
+    for rows in ((0, Ny), (1, Ny - 1)):
+        for par, w, anchor in ((False, 1.0, False), (True, 1.0, False), (True, float(quarter), True)):
+            got_new, got_acc = run_ensemble([c.old for c in cases], par, w, anchor, rows)
+            for m in range(members):
+                tag = (name, strict, rows, par, anchor, m)
+                a_m = float((dts[m] if par else dts[0]) * gamma)
+                w_m = float(dts[m] * quarter) if anchor else w
+                lo = m * stride_m
+                mine = [g[:, lo:lo + size] for g in (got_new, got_acc)]
+                assert np.all(got_new[:, lo + size:lo + stride_m] == DC.SENTINEL) and np.all(got_acc[:, lo + size:lo + stride_m] == DC.SENTINEL), tag
+                k0 = [k for k in range(n) if table[m, k] == 0]
+                if strict:
+                    one_new, one_acc = run_single(m, a_m, w_m, rows)
+                    assert np.array_equal(mine[0].view(u), one_new.view(u)), tag
+                    assert np.array_equal(mine[1].view(u), one_acc.view(u)), tag
+                    for k in k0:        # a zero of the device table: that field of that member is untouched
+                        assert np.array_equal(one_new[k].view(u), cases[m].new[k].reshape(-1).view(u))
+                else:
+                    for got, start, scalar, what in ((mine[0], cases[m].new, a_m, "new"), (mine[1], cases[m].acc, w_m, "acc")):
+                        full = start.copy()
+                        full[:n] = got.reshape(n, Ny + 2 * Hy, sy)
+                        check_outputs(cases[m], full, start, range(n), k0[0] if k0 else -1, scalar, rows, False, (what,) + tag)
+                if rows[0] > 0:         # rows 0 and Ny - 1 of every member and field: bitwise what they were
+                    for got, start in ((mine[0], cases[m].new), (mine[1], cases[m].acc)):
+                        assert np.array_equal(got.reshape(n, Ny + 2 * Hy, sy)[:, outer].view(u), start[:n][:, outer].view(u)), tag
+    if members > 1 and strict:
+        clean = run_ensemble([c.old for c in cases], True, 1.0, False, (0, Ny))
         olds = [c.old for c in cases]
         olds[1] = np.full_like(olds[1], np.nan)
-        bad = run_ensemble(olds, True, 1.0, False)
+        bad = run_ensemble(olds, True, 1.0, False, (0, Ny))
         for x, y in zip(clean, bad):
             for m in (0, 2):
                 assert np.array_equal(x[:, m * stride_m:(m + 1) * stride_m].view(u), y[:, m * stride_m:(m + 1) * stride_m].view(u))

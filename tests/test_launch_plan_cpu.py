@@ -55,8 +55,9 @@ def test_geometry_query_reproduces_recorded_table(swmhd, table):
 def test_plan_dispatch_sequences(tmp_path):
     """launch_plan_check.cpp as a host program: the plans of periodic stages in every RK3 stage form, Bounded hybrids with and without
     open sides, two-range and empty-range launches, parents beyond 4 GiB, Bounded grids below the hybrid thresholds, ensembles; the
-    plans of the Lorentz operators (cross-overs, the Bounded hybrid and its thresholds, the round cap) and the tiles of a tracer stage.
-    Then once more in a fresh process with SWMHD_OP_LY=5 (read once): 5 rows per segment, below the minimum of 8."""
+    plans of the Lorentz operators (cross-overs, the Bounded hybrid and its thresholds, the round cap, and what every shape of the
+    operator call matrix of tests/operator_cases.py lands on) and the tiles of a tracer stage.  Then in fresh processes with
+    SWMHD_OP_LY=5 and =13 (read once): that many rows per segment, below and above the minimum of 8, also on the matrix's sweep grid."""
     exe = str(tmp_path / "launch_plan_check")
     rocm = os.path.dirname(os.path.dirname(os.path.realpath(HIPCC)))
     cc = subprocess.run([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
@@ -65,8 +66,9 @@ def test_plan_dispatch_sequences(tmp_path):
     assert cc.returncode == 0, cc.stderr[-3000:]
     r = subprocess.run([exe], env=_clean_env({}), capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "launch plans OK" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
-    r = subprocess.run([exe, "op_ly", "5"], env=_clean_env({"SWMHD_OP_LY": "5"}), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "launch plans OK" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
+    for ly in ("5", "13"):
+        r = subprocess.run([exe, "op_ly", ly], env=_clean_env({"SWMHD_OP_LY": ly}), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and "launch plans OK" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
 
 
 def test_launchers_do_not_reenter():

@@ -21,6 +21,12 @@ wall, wall-strict) x precision x call form, with the call in which the worst rat
 
     python tools/stage_matrix_report.py --tracers [out.json] (default: profiles/tracer_stage_matrix/achieved.json)
 
+And for the call matrix of the Lorentz operator kernels (the calls of tests/test_operator_matrix_gpu.py, tests/operator_cases.py) per path
+(march, tile, wall) x form x precision -- max|got - oracle64| / (tol max|oracle64|) over the rows written, tol = 1e-13 | 2e-5 -- with
+the forced segment lengths SWMHD_OP_LY = 5 and 13 in child processes of their own (march-ly5, march-ly13):
+
+    python tools/stage_matrix_report.py --operators [out.json] (default: profiles/operator_matrix/achieved.json)
+
 The strict paths are compared bitwise: their ratio is 0 (every written cell equal to the oracle's) or inf."""
 import json
 import os
@@ -148,8 +154,56 @@ def main_tracers(out_path):
     return 1 if failures else 0
 
 
+def main_operators(out_path):
+    import subprocess
+    import tempfile
+    import torch
+    import swmhd_amd as S
+    from oracle import oracle as O
+    import operator_cases as OC
+    import test_operator_matrix_gpu as TM
+    worst, failures, ncases, ncalls = {}, [], {}, 0
+    t0 = time.perf_counter()
+    for case in OC.matrix():
+        path, form = case[:2]
+        ncases[path] = ncases.get(path, 0) + 1
+        ncalls += len(OC.calls(path, form))
+        failures += [f"{OC.case_id(*case)} {m}" for m in TM.run_case(S, O, *case, worst=worst)]
+    seconds = time.perf_counter() - t0
+    for path, cfg in OC.PATHS.items():      # strict paths: bitwise, 0 or inf
+        for form in cfg["forms"] if cfg["strict"] else ():
+            for dtype in OC.DTYPES:
+                bad = any(f.startswith(f"{path}-{form}-{OC.SFX[dtype]}-") and "bitwise" in f for f in failures)
+                worst[f"{path}/{form}/{OC.SFX[dtype]}"] = float("inf") if bad else 0.0
+    forced = {}
+    for ly in TM.FORCED_LY:                 # one child at a time; the second only if the first passed
+        env = {k: v for k, v in os.environ.items() if k != "SWMHD_OP_LY"}
+        env["SWMHD_OP_LY"] = str(ly)
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "forced.json")
+            r = subprocess.run([sys.executable, TM.__file__, str(ly), out], env=env, capture_output=True, text=True, timeout=300)
+            res = json.load(open(out)) if os.path.exists(out) else {"ok": False, "failed": [r.stderr[-1000:]], "worst": {}}
+        forced[f"SWMHD_OP_LY={ly}"] = {"cases": res.get("cases"), "calls_per_case": len(TM.forced_calls("jacobian"))}
+        worst.update({k.replace("march/", f"march-ly{ly}/"): v for k, v in res["worst"].items()})
+        failures += [f"SWMHD_OP_LY={ly} {m}" for m in res["failed"]]
+        if not res["ok"]:
+            break
+    rec = {"device": torch.cuda.get_device_name(0), "kernel_source_hash": S._lib.source_hash(), "cases": sum(ncases.values()),
+           "cases_per_path": ncases, "calls": ncalls, "seconds": float(f"{seconds:.1f}"), "forced_layouts": forced, "failures": failures,
+           "tolerance": {OC.SFX[t]: OC.TOL[t] for t in OC.DTYPES},
+           "max_error_over_bound": {k: float(f"{v:.3g}") for k, v in sorted(worst.items())}}
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        json.dump(rec, fh, indent=1)
+    print(json.dumps(rec["max_error_over_bound"], indent=1))
+    print(f"{rec['cases']} cases, {ncalls} calls in {seconds:.1f} s, {len(failures)} failures -> {out_path}")
+    return 1 if failures else 0
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--operators":
+        sys.exit(main_operators(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "operator_matrix", "achieved.json")))
     if args and args[0] == "--tracers":
         sys.exit(main_tracers(args[1] if len(args) > 1 else os.path.join(ROOT, "profiles", "tracer_stage_matrix", "achieved.json")))
     if args and args[0] == "--ensemble":
