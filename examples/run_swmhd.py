@@ -18,6 +18,9 @@ launch per sample and no frame) and writes them to <out>/zonal_means.npz at the 
 --zonal-spectra T collects zonal wavenumber spectra on the device (swmhd_amd.ZonalSpectrumTimeSeries: every T time units the row-averaged
 power spectra along x of --spectra-names out of u v h A s B_x B_y, by a double-precision row FFT in LDS; --size must be a power of two
 from 4 to 4096) and writes them to <out>/zonal_spectra.npz at the end, with the wavenumbers k and kx = 2 pi k / Lx.
+--isotropic-spectra T collects isotropic power spectra E(|k|) on the device (swmhd_amd.IsotropicSpectrumTimeSeries: every T time units the
+shell sums of the 2-D power spectra of --spectra-names, by a row FFT, a column FFT in LDS and a shell sum; periodic runs whose --size is a
+power of two from 4 to 4096) and writes them to <out>/isotropic_spectra.npz at the end, with the shell wavenumbers k and mode counts.
 The step loop runs through HIP-graph replays (two RK3 steps per replay).
 --dye adds one passive tracer c = tanh(y) to the run (ShallowWaterModel(tracers=("c",)): the reference's `tracers = (:A)` with a second
 name): its min / max join the progress line and the field goes into the --dump-every dumps.  With --amps, --coriolis, --gravity or
@@ -81,6 +84,7 @@ def main():
     ap.add_argument("--zonal-means", type=float, default=0.0, help="model time between zonal-mean samples (0 = none); written to <out>/zonal_means.npz")
     ap.add_argument("--zonal-names", default="u,v,A,uv,B_xB_y,vA", help="comma-separated profiles: u v h A s B_x B_y uu vv uv B_xB_x B_yB_y B_xB_y vA")
     ap.add_argument("--zonal-spectra", type=float, default=0.0, help="model time between zonal-spectrum samples (0 = none); written to <out>/zonal_spectra.npz")
+    ap.add_argument("--isotropic-spectra", type=float, default=0.0, help="model time between isotropic-spectrum samples (0 = none); written to <out>/isotropic_spectra.npz")
     ap.add_argument("--spectra-names", default="u,v,A", help="comma-separated spectra: u v h A s B_x B_y")
     ap.add_argument("--dye", action="store_true", help="advect one passive tracer c = tanh(y) with the flow")
     ap.add_argument("--viscosity", default=None, help="nu of ScalarDiffusivity, on u and v (ensemble runs: a comma list, one member per entry)")
@@ -112,6 +116,8 @@ def main():
         ap.error("--zonal-means is a schedule in time units: not with a per-member time step (--dts)")
     if a.dts and a.zonal_spectra > 0:
         ap.error("--zonal-spectra is a schedule in time units: not with a per-member time step (--dts)")
+    if a.dts and a.isotropic_spectra > 0:
+        ap.error("--isotropic-spectra is a schedule in time units: not with a per-member time step (--dts)")
     if a.dye and a.channel:
         ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
     a.sweep = a.sweep or "," in (a.beta or "")
@@ -170,6 +176,7 @@ def main():
     series, fevery = frame_writer(a, model, nsteps)
     zonal, zevery = zonal_writer(a, model, nsteps)
     spectra, severy = spectra_writer(a, model, nsteps)
+    iso, ievery = isotropic_writer(a, model, nsteps)
     model.time_step(a.dt)
     if fevery == 1:
         series.write()
@@ -177,6 +184,8 @@ def main():
         zonal.write()
     if severy == 1:
         spectra.write()
+    if ievery == 1:
+        iso.write()
     model.capture_graph(a.dt)
     next_dump = a.dump_every
     t_start = time.perf_counter()
@@ -190,6 +199,8 @@ def main():
             n = min(n, zevery - model.iteration % zevery)
         if severy:
             n = min(n, severy - model.iteration % severy)
+        if ievery:
+            n = min(n, ievery - model.iteration % ievery)
         model.time_steps(n, a.dt)
         if fevery and model.iteration % fevery == 0:
             series.write(time=model.iteration * a.dt)         # one launch, no synchronisation
@@ -197,6 +208,8 @@ def main():
             zonal.write(time=model.iteration * a.dt)          # likewise
         if severy and model.iteration % severy == 0:
             spectra.write(time=model.iteration * a.dt)        # two launches, no synchronisation
+        if ievery and model.iteration % ievery == 0:
+            iso.write(time=model.iteration * a.dt)            # three launches, no synchronisation
         if model.iteration % a.every != 0 and model.iteration != nsteps:
             continue
         model.synchronize()
@@ -212,6 +225,7 @@ def main():
     save_frames(a, series)
     save_zonal(a, zonal)
     save_spectra(a, spectra)
+    save_isotropic(a, iso)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
@@ -276,6 +290,26 @@ def save_spectra(a, spectra):
         os.makedirs(a.out, exist_ok=True)
         spectra.save(os.path.join(a.out, "zonal_spectra.npz"))
         print(f"{len(spectra)} samples of the zonal spectra ({', '.join(spectra.names)}) -> {os.path.join(a.out, 'zonal_spectra.npz')}")
+
+
+def isotropic_writer(a, model, nsteps):
+    """--isotropic-spectra: (IsotropicSpectrumTimeSeries, steps between samples), or (None, 0)"""
+    if a.isotropic_spectra <= 0:
+        return None, 0
+    import swmhd_amd as S
+    sched = S.TimeInterval(a.isotropic_spectra)
+    every = sched.steps(a.dt)
+    iso = S.IsotropicSpectrumTimeSeries(model, names=tuple(n.strip() for n in a.spectra_names.split(",") if n.strip()), schedule=sched,
+                                        capacity=nsteps // every + 1)
+    iso.write()             # the initial state, as the frames
+    return iso, every
+
+
+def save_isotropic(a, iso):
+    if iso is not None:
+        os.makedirs(a.out, exist_ok=True)
+        iso.save(os.path.join(a.out, "isotropic_spectra.npz"))
+        print(f"{len(iso)} samples of the isotropic spectra ({', '.join(iso.names)}) -> {os.path.join(a.out, 'isotropic_spectra.npz')}")
 
 
 def run_ensemble(a):
@@ -348,6 +382,7 @@ def run_ensemble(a):
     series, fevery = frame_writer(a, ens, nsteps)
     zonal, zevery = zonal_writer(a, ens, nsteps)
     spectra, severy = spectra_writer(a, ens, nsteps)
+    iso, ievery = isotropic_writer(a, ens, nsteps)
     ens.time_step(dt)
     if fevery == 1:
         series.write()
@@ -355,6 +390,8 @@ def run_ensemble(a):
         zonal.write()
     if severy == 1:
         spectra.write()
+    if ievery == 1:
+        iso.write()
     ens.capture_graph(dt)
     t_start = time.perf_counter()
     t0 = None
@@ -367,6 +404,8 @@ def run_ensemble(a):
             n = min(n, zevery - ens.iteration % zevery)
         if severy:
             n = min(n, severy - ens.iteration % severy)
+        if ievery:
+            n = min(n, ievery - ens.iteration % ievery)
         ens.time_steps(n, dt)
         if fevery and ens.iteration % fevery == 0:
             series.write(time=ens.iteration * a.dt)           # all members in one launch, no synchronisation
@@ -374,6 +413,8 @@ def run_ensemble(a):
             zonal.write(time=ens.iteration * a.dt)            # likewise
         if severy and ens.iteration % severy == 0:
             spectra.write(time=ens.iteration * a.dt)          # likewise
+        if ievery and ens.iteration % ievery == 0:
+            iso.write(time=ens.iteration * a.dt)              # likewise
         if ens.iteration % a.every != 0 and ens.iteration != nsteps:
             continue
         ens.synchronize()
@@ -386,6 +427,7 @@ def run_ensemble(a):
     save_frames(a, series)
     save_zonal(a, zonal)
     save_spectra(a, spectra)
+    save_isotropic(a, iso)
     if a.dye:
         os.makedirs(a.out, exist_ok=True)
         np.savez(os.path.join(a.out, "tracers.npz"), c=ens.tracers["c"][(slice(None),) + grid.interior].cpu().numpy(),

@@ -771,6 +771,8 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_derived.h"
 /* zonal spectra (swmhd_zonal_spectra_*, swmhd_ensemble_zonal_spectra_*, SWMHD_ZS_*): row-averaged power spectra along x of the output fields */
 #include "swmhd_spectra.h"
+/* 2-D and isotropic spectra (swmhd_spectra2d_*, swmhd_ensemble_spectra2d_*): P2[kx,ky] and the shell sums E(|k|) of the output fields */
+#include "swmhd_spectra2d.h"
 /* ScalarDiffusivity closure (swmhd_diffusion_rk3_*, swmhd_ensemble_diffusion_rk3_*): nu laplace(u, v), kappa laplace(A, tracers) per RK3 stage */
 #include "swmhd_diffusion.h"
 /* BetaPlane Coriolis (swmhd_coriolis_rk3_*, swmhd_ensemble_coriolis_rk3_*): f(y) (vbar, -ubar) added to (u, v) or (uh, vh) per RK3 stage */

@@ -187,6 +187,13 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_zonal_spectra_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, i, i, i, p, p, i64, i64, i, p]
         f.restype = i
+        # 2-D and isotropic spectra: the zonal spectra without the rows; wx, wy; out_shell and out_2d with their strides
+        f = getattr(lib, f"swmhd_spectra2d_{sfx}")
+        f.argtypes = [p, p, p, p, i, i, i, i, i64, ft, ft, i, i, C.c_double, C.c_double, p, p, i64, p, i64, i64, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_spectra2d_{sfx}")
+        f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, i, C.c_double, C.c_double, p, p, i64, i64, p, i64, i64, i64, i, p]
+        f.restype = i
         f = getattr(lib, f"swmhd_ensemble_derived_fields_params_{sfx}")
         f.argtypes = [p, p, p, p, i, i64, i, i, i, i, i64, ft, ft, i, p, i, i, i, p, i, i64, i64, i64, i, p]
         f.restype = i
@@ -206,6 +213,10 @@ def _declare(lib):
         f.restype = i
     lib.swmhd_zonal_spectra_workspace.argtypes = [i, i, i, i]
     lib.swmhd_zonal_spectra_workspace.restype = i64
+    lib.swmhd_spectra2d_shells.argtypes = [i, i, C.c_double, C.c_double]
+    lib.swmhd_spectra2d_shells.restype = i
+    lib.swmhd_spectra2d_workspace.argtypes = [i, i, i, i, C.c_double, C.c_double]
+    lib.swmhd_spectra2d_workspace.restype = i64
     lib.swmhd_tendency_launch_geometry.argtypes = [i, i, i, i, i, C.POINTER(i)]
     lib.swmhd_tendency_launch_geometry.restype = i
     lib.swmhd_ensemble_launch_geometry.argtypes = [i, i, i, i, i, i, C.POINTER(i)]
@@ -252,6 +263,9 @@ DERIVED_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
 # the symbols include/swmhd_spectra.h declares (swmhd.h includes it; tests/test_spectra_abi.py checks the .so exports each of them)
 SPECTRA_EXPORTS = ["swmhd_zonal_spectra_workspace"] + [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
                                                        for name in ("zonal_spectra", "ensemble_zonal_spectra")]
+# the symbols include/swmhd_spectra2d.h declares (swmhd.h includes it; tests/test_spectra2d_abi.py checks the .so exports each of them)
+SPECTRA2D_EXPORTS = ["swmhd_spectra2d_shells", "swmhd_spectra2d_workspace"] + [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
+                                                                               for name in ("spectra2d", "ensemble_spectra2d")]
 # the symbols include/swmhd_diffusion.h declares (swmhd.h includes it; tests/test_diffusion_abi.py checks the .so exports each of them)
 DIFFUSION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("diffusion_rk3", "ensemble_diffusion_rk3")]
 # the symbols include/swmhd_coriolis.h declares (swmhd.h includes it; tests/test_coriolis_abi.py checks the .so exports each of them)

@@ -1,4 +1,4 @@
-// Host-only argument layer of the C ABI (swmhd_api.hip, ring.hip, the host tails of output.hip, zonal.hip and spectra.hip): what a valid halo-padded grid is,
+// Host-only argument layer of the C ABI (swmhd_api.hip, ring.hip, the host tails of output.hip, zonal.hip, spectra.hip and spectra2d.hip): what a valid halo-padded grid is,
 // what the physics arguments may be, what the SWMHD_* flag bits mean and which of them each family of entry points takes -- each said
 // once.  No kernel, no launch.  Internal, like common.hpp.
 #pragma once
@@ -97,6 +97,7 @@ constexpr int OUTPUT_FLAGS = WRAP_FLAGS;
 constexpr int ZONAL_FLAGS = WRAP_FLAGS;   // swmhd_zonal_means: the frame's
 constexpr int DERIVED_FLAGS = WRAP_FLAGS; // swmhd_derived_fields: the frame's
 constexpr int SPECTRA_FLAGS = WRAP_FLAGS; // swmhd_zonal_spectra: the frame's
+constexpr int SPECTRA2D_FLAGS = WRAP_FLAGS; // swmhd_spectra2d: the frame's
 // swmhd_tendencies[_rk3], swmhd_step_rk3 and the slab drivers' stages
 constexpr int TEND_FLAGS = SWMHD_STRICT | KERNEL_FLAGS | WRAP_FLAGS | SWMHD_LEAVE_ROOM | BOUNDED_FLAGS | SWMHD_GM_IS_PREV_STATE |
                            SWMHD_RK3_ANCHOR | OPEN_FLAGS;

@@ -562,6 +562,84 @@ inline SpectraPlan spectra_plan(int Nx, int rows, int nfields, int members) {
     return p;
 }
 
+// ---- the three launches of one 2-D / isotropic spectrum call (spectra2d.hip) ---------------------------------------------------------
+// Workspace: the complex half-plane, (member, field, kx, j) with j contiguous (2 nkx Ny doubles per member and field, nkx = Nx/2 + 1),
+// then, when shells are asked for, the column partials (member, field, kx, s) (nkx NS doubles per member and field).
+// Pass 1 (rows): a workgroup of SPECTRA_NT threads takes R consecutive rows of one (member, field), transforms them as the zonal spectra
+// do -- one row at a time from Nx = 512 on, SPECTRA_UNITS_SMALL rows side by side, a wave each, up to Nx = 256 -- keeps all R transformed
+// rows in LDS and then stores the modes transposed, R x 16 B of one line per store.  R: the largest power of two <= min(S2D_RMAX, Ny)
+// whose LDS -- R rows of 8 Nx bytes (+ 16 bytes of padding each where R > 2: the transposed read takes the same element of R rows) and
+// one twiddle quarter table of 4 Nx bytes -- stays within min(lds_limit, S2D_ROWS_LDS): 16 rows up to Nx = 512, 8, 4, 2 at 1024, 2048,
+// 4096 (80 KiB: two workgroups per CU).
+// Pass 2 (columns): one unit per (member, field, kx): a wave up to Ny = 256 (SPECTRA_UNITS_SMALL to a workgroup; the last workgroup may
+// hold idle units), a workgroup from Ny = 512 on.  LDS of a unit: the column (16 Ny bytes) and the twiddle quarter table (4 Ny bytes):
+// 80 KiB at Ny = 4096.  Fallback, where the device admits less than that per workgroup (lds_limit: its attribute, asked once per
+// process): no table, sincospi per butterfly -- the same values bit for bit -- and 16 Ny bytes = 64 KiB.
+// Pass 3 (shells): as pass 2 of the zonal spectra: SPECTRA_P2_G lanes per (member, field, s), lane g adds the partials of kx = g, g + G,
+// ... one after the other, then a tree; SPECTRA_P2_K shells per workgroup.  Not launched when no shells are asked for.
+constexpr int S2D_RMAX = 16;
+constexpr long S2D_ROWS_LDS = 80L * 1024, S2D_LDS_MAX = 160L * 1024;
+struct Spectra2dPlan {
+    int log2nx, log2ny;   // -1: not a supported size
+    int nkx, NS;          // Nx/2 + 1; shells (spectra2d_shells)
+    int R, pad;           // rows of a pass-1 workgroup; doubles of padding behind each of its rows in LDS
+    int units1, units2;   // rows side by side in pass 1; units per workgroup of pass 2
+    bool table;           // pass 2 holds a twiddle table in LDS
+    long blocks1, blocks2, blocks3;
+    long lds1, lds2;      // dynamic LDS of a workgroup of pass 1, pass 2
+    long modes, partials; // doubles of the two parts of the workspace (partials: 0 without shells)
+    long workspace;       // modes + partials
+    bool none;            // nothing to compute: no fields or no members
+    bool unsupported;     // Nx or Ny is not 2^p with SPECTRA_MIN_LOG2 <= p <= SPECTRA_MAX_LOG2
+    bool too_many;        // 2^31 workgroups or more in one of the launches
+};
+// the shell of mode (mx, my): include/swmhd_spectra2d.h; two products, one sum, in this order, no contraction
+inline int spectra2d_shell(int mx, int my, double wx, double wy) {
+    const double a = wx * (double)(mx * mx);
+    const double b = wy * (double)(my * my);
+    const double r2 = a + b;
+    return (int)__builtin_floor(__builtin_sqrt(r2) + 0.5);
+}
+// NS: one more than the shell of the corner mode (Nx/2, Ny/2); 0 for extents or metrics that are not positive and finite
+inline int spectra2d_shells(int Nx, int Ny, double wx, double wy) {
+    if (Nx <= 0 || Ny <= 0 || !(wx > 0.0) || !(wy > 0.0) || wx > 1.7e308 || wy > 1.7e308) return 0;
+    const double a = wx * ((double)(Nx / 2) * (double)(Nx / 2));   // (as spectra2d_shell; the squares in double: any Nx)
+    const double b = wy * ((double)(Ny / 2) * (double)(Ny / 2));
+    const double r2 = a + b;
+    const double r = __builtin_sqrt(r2) + 0.5;
+    return r < 2147483646.0 ? (int)__builtin_floor(r) + 1 : 0;
+}
+// members: 1 for a single grid; lds_limit: bytes of LDS a workgroup may take on the device
+inline Spectra2dPlan spectra2d_plan(int Nx, int Ny, int nfields, int members, double wx, double wy, bool shells, long lds_limit = S2D_LDS_MAX) {
+    Spectra2dPlan p{};
+    p.log2nx = spectra_log2(Nx);
+    p.log2ny = spectra_log2(Ny);
+    p.unsupported = p.log2nx < 0 || p.log2ny < 0;
+    p.none = nfields <= 0 || members <= 0;
+    if (p.unsupported || p.none) return p;
+    p.nkx = Nx / 2 + 1;
+    p.NS = spectra2d_shells(Nx, Ny, wx, wy);
+    const long mf = (long)nfields * members;
+    const long budget = lds_limit < S2D_ROWS_LDS ? lds_limit : S2D_ROWS_LDS;
+    p.units1 = Nx <= SPECTRA_SMALL_NX ? SPECTRA_UNITS_SMALL : 1;
+    for (p.R = S2D_RMAX < Ny ? S2D_RMAX : Ny; ; p.R >>= 1) {
+        p.pad = p.R > 2 ? 2 : 0;
+        p.lds1 = (long)p.R * 8 * (Nx + p.pad) + 4L * Nx;
+        if (p.lds1 <= budget || p.R == 1) break;
+    }
+    p.blocks1 = (long)(Ny / p.R) * mf;
+    p.units2 = Ny <= SPECTRA_SMALL_NX ? SPECTRA_UNITS_SMALL : 1;
+    p.table = 20L * Ny * p.units2 <= lds_limit;
+    p.lds2 = (p.table ? 20L : 16L) * Ny * p.units2;
+    p.blocks2 = (p.nkx * mf + p.units2 - 1) / p.units2;
+    p.blocks3 = shells ? (long)((p.NS + SPECTRA_P2_K - 1) / SPECTRA_P2_K) * mf : 0;
+    p.modes = 2L * p.nkx * Ny * mf;
+    p.partials = shells ? (long)p.nkx * p.NS * mf : 0;
+    p.workspace = p.modes + p.partials;
+    p.too_many = p.blocks1 >= (1L << 31) || p.blocks2 >= (1L << 31) || p.blocks3 >= (1L << 31);
+    return p;
+}
+
 // ---- the chunks of one derived-frame call (derived.hip) -----------------------------------------------------------------------------
 // One-shot workgroups in address order, as the output frames: a thread takes one 4-cell chunk of one row, a 256-thread workgroup 256
 // consecutive chunks of the row-major list of (row, chunk); the member is blockIdx.y.

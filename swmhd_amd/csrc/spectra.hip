@@ -36,35 +36,7 @@ struct SpectraArgs {
     long stride_m, osm;
 };
 
-struct alignas(16) cplx { double re, im; };
-__device__ __forceinline__ cplx cmul(cplx a, cplx w) { return cplx{a.re * w.re - a.im * w.im, a.re * w.im + a.im * w.re}; }
-// w_Nx^idx, 0 <= idx < Nx/2, from the quarter table: w^(idx) = −i w^(idx − Nx/4) beyond it
-__device__ __forceinline__ cplx twiddle(const cplx *tw, int idx, int Q) {
-    if (idx < Q) return tw[idx];
-    const cplx t = tw[idx - Q];
-    return cplx{t.im, -t.re};
-}
-
-// the frame value of field `bit` at cell x of row y (0-based interior indices): the statements of zonal.hip for one cell
-template <typename T>
-__device__ __forceinline__ double frame_value(const SpectraArgs<T> &a, int bit, bool cons, long r0, long rm, long rp, int x, int xl) {
-    auto ld = [](const T *p, long o) { return (double)p[o]; };
-    auto U = [&](int i, int il) { return cons ? ld(a.q1, r0 + i) / (0.5 * (ld(a.h, r0 + il) + ld(a.h, r0 + i))) : ld(a.q1, r0 + i); };
-    auto V0 = [&](int i) { return cons ? ld(a.q2, r0 + i) / (0.5 * (ld(a.h, rm + i) + ld(a.h, r0 + i))) : ld(a.q2, r0 + i); };
-    auto Vp = [&](int i) { return cons ? ld(a.q2, rp + i) / (0.5 * (ld(a.h, r0 + i) + ld(a.h, rp + i))) : ld(a.q2, rp + i); };
-    switch (bit) {
-    case SWMHD_ZS_U: return U(x, xl);
-    case SWMHD_ZS_V: return V0(x);
-    case SWMHD_ZS_H: return ld(a.h, r0 + x);
-    case SWMHD_ZS_A: return ld(a.A, r0 + x);
-    case SWMHD_ZS_SPEED: {
-        const double u = U(x, xl), g00 = V0(xl), g10 = V0(x), g01 = Vp(xl), g11 = Vp(x);
-        return sqrt(u * u + 0.5 * (0.5 * (g00 * g00 + g10 * g10) + 0.5 * (g01 * g01 + g11 * g11)));
-    }
-    case SWMHD_ZS_BX: return -((ld(a.A, r0 + x) - ld(a.A, rm + x)) / a.dy) / (0.5 * (ld(a.h, rm + x) + ld(a.h, r0 + x)));
-    default: return ((ld(a.A, r0 + x) - ld(a.A, r0 + xl)) / a.dx) / (0.5 * (ld(a.h, r0 + xl) + ld(a.h, r0 + x)));   // SWMHD_ZS_BY
-    }
-}
+#include "spectra_device.inc"   // cplx, twiddle, frame_value, load_row, dif_stage, untangle: shared with spectra2d.hip
 
 // TPR: threads of one row.  SPECTRA_NT (one row per workgroup) from Nx = 512 on; 64 (one wave per row, SPECTRA_NT / 64 rows of
 // consecutive w side by side in one workgroup) up to Nx = 256, where a row has at most 64 butterflies per stage (spectra_plan: units).
@@ -91,21 +63,10 @@ __global__ __launch_bounds__(SPECTRA_NT, 3) void k_spectra_rows(SpectraArgs<T> a
         const long o = (long)m * a.stride_m;
         a.q1 += o; a.q2 += o; a.h += o; a.A += o;
     }
-    // field number f of the mask: its bit
-    int bit = 0;
-    for (int p = 0, n = 0; p < 7; ++p) {
-        if (a.which & (1 << p)) {
-            if (n == f) bit = 1 << p;
-            ++n;
-        }
-    }
+    const int bit = field_bit(a.which, f);
     const bool cons = a.form == SWMHD_CONSERVATIVE;
 
-    for (int k = lane; k < Q; k += TPR) {
-        double s, c;
-        sincospi((double)(2 * k) / (double)N, &s, &c);   // (2k/N: exact, N is a power of two)
-        tw[k] = cplx{c, -s};
-    }
+    for (int k = lane; k < Q; k += TPR) tw[k] = twiddle_entry(k, N);
 
     double acc[ACC];
 #pragma unroll
@@ -117,48 +78,12 @@ __global__ __launch_bounds__(SPECTRA_NT, 3) void k_spectra_rows(SpectraArgs<T> a
     for (int trip = 0; trip < trips; ++trip) {
         const int row = w + trip * a.W;
         const bool active = w < a.W && row < rows;
-        if (active) {
-            const int y = a.j0 + row;
-            const int ym = (y == 0 && (a.wrap & 2)) ? a.Ny - 1 : y - 1;
-            const int yp = (y == a.Ny - 1 && (a.wrap & 2)) ? 0 : y + 1;
-            const long r0 = (long)y * a.sy, rm = (long)ym * a.sy, rp = (long)yp * a.sy;
-#pragma unroll 4
-            for (int x = lane; x < N; x += TPR) {
-                const int xl = (x == 0 && (a.wrap & 1)) ? N - 1 : x - 1;
-                x_row[x] = frame_value(a, bit, cons, r0, rm, rp, x, xl);
-            }
-        }
+        if (active) load_row<TPR>(a, x_row, bit, cons, a.j0 + row, lane);
         __syncthreads();   // (also: the twiddles of the first row)
 
         // decimation in frequency: half-span hs = M/2 .. 1; butterfly t: block t / hs, offset j = t mod hs; twiddle w_M^(j M/(2 hs)) = w_Nx^(j M/hs)
         for (int lh = LM - 1; lh >= 0; --lh) {
-            const int hs = 1 << lh, sh = LM - lh;
-            if (active) {
-                // NB butterflies of the thread at a time: all their operands are read before the first is written
-                for (int base = lane; base < (M >> 1); base += TPR * NB) {
-                    cplx p[NB], q[NB], wv[NB];
-                    int i0[NB];
-#pragma unroll
-                    for (int n = 0; n < NB; ++n) {
-                        const int t = base + n * TPR;
-                        if (t < (M >> 1)) {
-                            const int j = t & (hs - 1);
-                            i0[n] = ((t >> lh) << (lh + 1)) + j;
-                            p[n] = z[i0[n]];
-                            q[n] = z[i0[n] + hs];
-                            wv[n] = twiddle(tw, j << sh, Q);
-                        }
-                    }
-#pragma unroll
-                    for (int n = 0; n < NB; ++n) {
-                        if (base + n * TPR < (M >> 1)) {
-                            const cplx d{p[n].re - q[n].re, p[n].im - q[n].im};
-                            z[i0[n]] = cplx{p[n].re + q[n].re, p[n].im + q[n].im};
-                            z[i0[n] + hs] = cmul(d, wv[n]);
-                        }
-                    }
-                }
-            }
+            if (active) dif_stage<TPR, NB>(z, tw, lane, M >> 1, lh, LM - lh, Q);
             __syncthreads();
         }
 
@@ -168,23 +93,8 @@ __global__ __launch_bounds__(SPECTRA_NT, 3) void k_spectra_rows(SpectraArgs<T> a
             for (int r = 0; r < ACC; ++r) {
                 const int k = lane + r * TPR;
                 if (k <= M) {
-                    double xr, xi, ck = 2.0;
-                    if (k == 0 || k == M) {
-                        const cplx z0 = z[0];
-                        xr = k == 0 ? z0.re + z0.im : z0.re - z0.im;
-                        xi = 0.0;
-                        ck = 1.0;
-                    } else {
-                        const cplx p = z[__brev((unsigned)k) >> (32 - LM)], q = z[__brev((unsigned)(M - k)) >> (32 - LM)];
-                        const cplx E{0.5 * (p.re + q.re), 0.5 * (p.im - q.im)};
-                        const cplx O{0.5 * (p.im + q.im), -(0.5 * (p.re - q.re))};
-                        const cplx wo = cmul(O, twiddle(tw, k, Q));
-                        xr = E.re + wo.re;
-                        xi = E.im + wo.im;
-                    }
-                    xr *= inv;
-                    xi *= inv;
-                    acc[r] += ck * (xr * xr + xi * xi);
+                    const cplx X = untangle(z, tw, k, M, LM, Q, inv);
+                    acc[r] += ((k == 0 || k == M) ? 1.0 : 2.0) * (X.re * X.re + X.im * X.im);
                 }
             }
         }

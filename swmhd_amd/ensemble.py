@@ -483,6 +483,18 @@ class ShallowWaterEnsemble:
         from .spectra import enqueue_zonal_spectra
         return enqueue_zonal_spectra(self, names, out)
 
+    # --- 2-D and isotropic spectra of all members in three launches (swmhd_ensemble_spectra2d_*) --------------------
+    def isotropic_spectra(self, names=("u", "v", "A"), out=None):
+        """ShallowWaterModel.isotropic_spectra for every member: the float64 device tensor (members, len(names), NS); member m of it is
+        bitwise member(m).isotropic_spectra(...).  No host synchronisation."""
+        from .spectra2d import enqueue_isotropic_spectra
+        return enqueue_isotropic_spectra(self, names, out)
+
+    def power_spectra_2d(self, names=("u", "v", "A"), out=None):
+        """ShallowWaterModel.power_spectra_2d for every member: (members, len(names), Nx/2 + 1, Ny)."""
+        from .spectra2d import enqueue_power_spectra_2d
+        return enqueue_power_spectra_2d(self, names, out)
+
     # --- one member as a ShallowWaterModel (checkpoints, inspection) ------------------------------------------------
     def member(self, m):
         """A ShallowWaterModel holding a copy of member m (state and tracers with halos, their G-, the member's g, f, clock and

@@ -661,6 +661,24 @@ class ShallowWaterModel:
         from .spectra import enqueue_zonal_spectra
         return enqueue_zonal_spectra(self, names, out)
 
+    # --- 2-D and isotropic spectra: the row FFT keeping its modes, a column FFT in LDS and the shell sum, three launches ----
+    def isotropic_spectra(self, names=("u", "v", "A"), out=None):
+        """Enqueue the isotropic power spectra of the current state: the float64 device tensor (len(names), NS), entry s of spectrum F =
+        the sum of P2[kx, ky] over the modes whose shell floor(sqrt(wx kx^2 + wy my^2) + 1/2) is s, P2 = c_kx |F^[kx, ky]|^2 of the 2-D
+        DFT of the float64 frame field F divided by Nx Ny, so that the entries sum to the mean of F^2 (swmhd_spectra2d_* in
+        include/swmhd_spectra2d.h).  The shell width is max(2 pi/Lx, 2 pi/Ly); swmhd_amd.spectra2d.isotropic_shells(grid) gives the
+        wavenumbers and the mode counts.  Both sizes must be powers of two from 4 to 4096 and both directions Periodic; a model on a
+        y-slab of several ranks is refused (a 2-D transform needs every row).  Bit-reproducible.  See swmhd_amd.spectra2d for the
+        writer (IsotropicSpectrumTimeSeries)."""
+        from .spectra2d import enqueue_isotropic_spectra
+        return enqueue_isotropic_spectra(self, names, out)
+
+    def power_spectra_2d(self, names=("u", "v", "A"), out=None):
+        """Enqueue the 2-D power spectra P2[kx, ky] of the current state: the float64 device tensor (len(names), Nx/2 + 1, Ny), ky in
+        FFT order (0 .. Ny/2, then -Ny/2 + 1 .. -1); its entries sum to the mean of F^2.  What isotropic_spectra sums over shells."""
+        from .spectra2d import enqueue_power_spectra_2d
+        return enqueue_power_spectra_2d(self, names, out)
+
     # --- checkpoint: prognostic fields with halos + G⁻ + clock, one .npz per rank ---------------------------------
     def save_checkpoint(self, path):
         import numpy as np

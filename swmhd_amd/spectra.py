@@ -14,7 +14,7 @@ butterfly y1 = (a - b) w -- one rounding of the difference, sqrt(2) gamma_2 of t
 sincospi of the exact fraction 2k/Nx (2 ulp per component: mu = 4 * 2^-53), never from a recurrence; the half-length transform's two
 trivial stages, the untangling pass and re^2 + im^2 fit into the log2(Nx) stages counted (include/swmhd_spectra.h has the account).
 
-Not built: 2-D and isotropic spectra, spectra along y, cross- and co-spectra, per-row spectra, sizes other than 2^p (4 .. 4096),
+2-D and isotropic spectra: swmhd_amd.spectra2d.  Not built: spectra along y alone, cross- and co-spectra, per-row spectra, sizes other than 2^p (4 .. 4096),
 tracers, and the slab-global average -- on y-slabs each rank gets the spectrum of its own rows, and the global one is the row-weighted
 mean of the ranks', the caller's to form.  The kinetic-energy spectrum (P_u + P_v)/2 and the magnetic one are the user's sums.
 """
