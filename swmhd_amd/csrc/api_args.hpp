@@ -1,4 +1,4 @@
-// Host-only argument layer of the C ABI (swmhd_api.hip, ring.hip, the host tails of output.hip, zonal.hip, spectra.hip and spectra2d.hip): what a valid halo-padded grid is,
+// Host-only argument layer of the C ABI (swmhd_api.hip, ring.hip, the host tails of output.hip, derived.hip, zonal.hip, spectra.hip and spectra2d.hip): what a valid halo-padded grid is,
 // what the physics arguments may be, what the SWMHD_* flag bits mean and which of them each family of entry points takes -- each said
 // once.  No kernel, no launch.  Internal, like common.hpp.
 #pragma once
@@ -93,11 +93,8 @@ constexpr int KERNEL_FLAGS = SWMHD_TILE_KERNEL | SWMHD_MARCH_KERNEL, WRAP_FLAGS 
 constexpr int BOUNDED_FLAGS = SWMHD_BOUNDED_X | SWMHD_BOUNDED_Y, OPEN_FLAGS = SWMHD_OPEN_SOUTH | SWMHD_OPEN_NORTH;
 constexpr int LORENTZ_FLAGS = SWMHD_STRICT | KERNEL_FLAGS;
 constexpr int SUBSTEP_FLAGS = SWMHD_STRICT;
-constexpr int OUTPUT_FLAGS = WRAP_FLAGS;
-constexpr int ZONAL_FLAGS = WRAP_FLAGS;   // swmhd_zonal_means: the frame's
-constexpr int DERIVED_FLAGS = WRAP_FLAGS; // swmhd_derived_fields: the frame's
-constexpr int SPECTRA_FLAGS = WRAP_FLAGS; // swmhd_zonal_spectra: the frame's
-constexpr int SPECTRA2D_FLAGS = WRAP_FLAGS; // swmhd_spectra2d: the frame's
+// swmhd_output_fields, swmhd_derived_fields, swmhd_zonal_means, swmhd_zonal_spectra, swmhd_spectra2d: the diagnostics that read a frame
+constexpr int FRAME_FLAGS = WRAP_FLAGS;
 // swmhd_tendencies[_rk3], swmhd_step_rk3 and the slab drivers' stages
 constexpr int TEND_FLAGS = SWMHD_STRICT | KERNEL_FLAGS | WRAP_FLAGS | SWMHD_LEAVE_ROOM | BOUNDED_FLAGS | SWMHD_GM_IS_PREV_STATE |
                            SWMHD_RK3_ANCHOR | OPEN_FLAGS;
@@ -154,6 +151,46 @@ void set_grid(Args &a, const Grid &g, int topo_x, int topo_y) {
     a.Nx = g.Nx; a.Ny = g.Ny; a.Hx = g.Hx; a.Hy = g.Hy; a.sy = (long)g.sy;
     a.dx = T(g.dx); a.dy = T(g.dy); a.rdx = T(1) / a.dx; a.rdy = T(1) / a.dy;
     a.topo_x = topo_x; a.topo_y = topo_y;
+}
+
+// ---- what the diagnostics that read a frame share (output.hip, derived.hip, zonal.hip, spectra.hip, spectra2d.hip) -----------------
+// Every check here answers SWMHD_EINVAL, and every SWMHD_EINVAL check of those calls precedes their other answers (SWMHD_EHALO, then
+// SWMHD_ENOTSUP, then "nothing to do"), so the order among these is not observable (tests/golden/*return_codes.json hold the rest).
+// the four parents, the grid and the formulation
+inline bool frame_source_ok(const void *q1, const void *q2, const void *h, const void *A, const Grid &g, int form) {
+    return q1 && q2 && h && A && g.extents_ok() && g.spacing_ok() && formulation_ok(form);
+}
+// member count and member stride of the parents; none: a single grid
+inline bool frame_members_ok(const Ens *ens, const Grid &g) {
+    return !ens || (ens->members >= 1 && ens->members <= SWMHD_ENSEMBLE_MAX_MEMBERS && ens->stride_m >= g.min_member_stride());
+}
+// Two halo rules, each kept as it was: the frames, the derived frames and the zonal means ask for one halo cell whatever the wrap
+// flags; the two spectra ask for it only in a direction that is not wrapped.  Both answer SWMHD_EHALO.
+inline bool frame_halo_ok(const Grid &g) { return g.halo_at_least(1); }
+inline bool spectra_halo_ok(const Grid &g, int flags) { return (g.Hx >= 1 || (flags & SWMHD_WRAP_X)) && (g.Hy >= 1 || (flags & SWMHD_WRAP_Y)); }
+// a frame (swmhd_output_fields, swmhd_derived_fields): `which` fields of `elem`-byte elements at out; row, field and (ensembles) member
+// stride in elements.  frame_ok: rows r of the fields of mask `all` fit it
+struct Frame {
+    int which;
+    void *out;
+    int elem;
+    int64_t osy, osf, osm = 0;
+};
+inline bool frame_ok(const Frame &o, int all, const Grid &g, const Rows &r, const Ens *ens) {
+    if (!o.out || !g.rows_ok(r.j0, r.j1) || o.which <= 0 || (o.which & ~all) || (o.elem != 4 && o.elem != 8)) return false;
+    if (o.osy < g.Nx || o.osf < (int64_t)(r.j1 - r.j0) * o.osy) return false;
+    return !ens || o.osm >= (int64_t)__builtin_popcount((unsigned)o.which) * o.osf;
+}
+// what OutArgs, DrvArgs, ZonalArgs, SpectraArgs and S2dArgs share: the parents at interior cell (1,1), extents, stride, spacings,
+// formulation, mask, wrap bits and member stride
+template <typename Args, typename T>
+void set_frame_source(Args &a, const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, int which, int flags, const Ens *ens) {
+    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = g.interior(h); a.A = g.interior(A);
+    a.Nx = g.Nx; a.Ny = g.Ny; a.sy = (long)g.sy;
+    a.dx = g.dx; a.dy = g.dy;
+    a.form = form; a.which = which;
+    a.wrap = decode_flags(flags).wrap;
+    a.stride_m = ens ? (long)ens->stride_m : 0;
 }
 
 // ---- what the slab driver (ring.hip) shares with the exported calls of the same names: same checks, same return codes --------------

@@ -11,10 +11,11 @@
 // This object is built without FMA contraction and with IEEE divide (Makefile: STRICT), so a frame is reproducible against a plain
 // numpy restatement (tests/derived_cases.py).
 //
-// The shape is k_output_fields' (output.hip), which this file restates: one-shot workgroups in address order (launch_plan.hpp:
-// derived_plan), four cells of a row per thread (32 B of an fp64 parent, one 16-byte store of a float32 frame), the member in
-// blockIdx.y, a chunk that crosses the end of a row falls back to single elements, under-aligned vector types.  A row window here has
-// the east neighbour x0+4 as well as the west neighbour x0−1, each a single element, loaded only where the mask needs it.
+// The shape is k_output_fields' (output.hip): one-shot workgroups in address order (launch_plan.hpp: derived_plan), four cells of a
+// row per thread (32 B of an fp64 parent, one 16-byte store of a float32 frame), the member in blockIdx.y, a chunk that crosses the
+// end of a row falls back to single elements; the velocities, the vector types and the chunk store are those of frame_device.inc.  A
+// row window here has the east neighbour x0+4 as well as the west neighbour x0−1, each a single element, loaded only where the mask
+// needs it, so this file keeps a load_row of its own.
 // Reach: one cell (x±1, y±1) and the (x−1, y−1) corner.  With SWMHD_WRAP_X / _Y those neighbours are taken at (x mod Nx, y mod Ny):
 // no halo cell of that direction is read.
 #include "api_args.hpp"
@@ -23,13 +24,10 @@
 namespace swmhd {
 namespace {
 
-constexpr int DRV_W = DERIVED_VEC + 2;   // a row window: values x0-1, x0 .. x0+3, x0+4
+#include "frame_device.inc"   // frame_vel, frame_xy_mean, frame_rows, frame_west, FrameVec, store_chunk: shared with output.hip and zonal.hip
 
-typedef double drv_d4 __attribute__((ext_vector_type(4), aligned(8)));
-typedef float drv_f4 __attribute__((ext_vector_type(4), aligned(4)));
-template <typename T> struct DrvVec;
-template <> struct DrvVec<double> { typedef drv_d4 type; };
-template <> struct DrvVec<float> { typedef drv_f4 type; };
+constexpr int DRV_W = DERIVED_VEC + 2;   // a row window: values x0-1, x0 .. x0+3, x0+4
+static_assert(DERIVED_VEC == FRAME_VEC, "a thread's cells are one chunk of the frame");
 
 template <typename T>
 struct DrvArgs {
@@ -55,7 +53,7 @@ template <typename T>
 __device__ __forceinline__ void load_row(const T *__restrict__ row, const DrvCols &c, bool west, bool east, double (&r)[DRV_W]) {
     if (west) r[0] = (double)row[c.xl];
     if (c.full) {
-        const typename DrvVec<T>::type v = *reinterpret_cast<const typename DrvVec<T>::type *>(row + c.x0);
+        const typename FrameVec<T>::type v = *reinterpret_cast<const typename FrameVec<T>::type *>(row + c.x0);
 #pragma unroll
         for (int k = 0; k < DERIVED_VEC; ++k) r[1 + k] = (double)v[k];
         if (east) r[1 + DERIVED_VEC] = (double)row[c.nvalid == DERIVED_VEC ? c.xe : c.x0 + DERIVED_VEC];
@@ -66,20 +64,6 @@ __device__ __forceinline__ void load_row(const T *__restrict__ row, const DrvCol
             r[1 + k] = (inside || behind) ? (double)row[inside ? c.x0 + k : c.xe] : 0.0;   // (0: never stored)
         }
         r[1 + DERIVED_VEC] = 0.0;
-    }
-}
-
-template <typename O>
-__device__ __forceinline__ void store_chunk(O *__restrict__ p, const double (&v)[DERIVED_VEC], bool full, int nvalid) {
-    if (full) {
-        typename DrvVec<O>::type w;
-#pragma unroll
-        for (int k = 0; k < DERIVED_VEC; ++k) w[k] = (O)v[k];
-        *reinterpret_cast<typename DrvVec<O>::type *>(p) = w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < DERIVED_VEC; ++k)
-            if (k < nvalid) p[k] = (O)v[k];
     }
 }
 
@@ -103,11 +87,9 @@ __global__ __launch_bounds__(DERIVED_NT) void k_derived_fields(DrvArgs<T> a) {
     out += (long)row * a.osy + c.x0;
     c.nvalid = a.Nx - c.x0;
     c.full = c.nvalid >= DERIVED_VEC;
-    c.xl = (c.x0 == 0 && (a.wrap & 1)) ? a.Nx - 1 : c.x0 - 1;
+    c.xl = frame_west(c.x0, a.Nx, a.wrap);
     c.xe = (a.wrap & 1) ? 0 : a.Nx;
-    const int ym = (y == 0 && (a.wrap & 2)) ? a.Ny - 1 : y - 1;
-    const int yp = (y == a.Ny - 1 && (a.wrap & 2)) ? 0 : y + 1;
-    const long r0 = (long)y * a.sy, rm = (long)ym * a.sy, rp = (long)yp * a.sy;
+    const auto [r0, rm, rp] = frame_rows(y, a.Ny, a.sy, a.wrap);
     const bool full = c.full;
     const int nvalid = c.nvalid;
 
@@ -135,20 +117,20 @@ __global__ __launch_bounds__(DERIVED_NT) void k_derived_fields(DrvArgs<T> a) {
     double Um[DRV_W], U0[DRV_W], V0[DRV_W], Vp[DRV_W], res[DERIVED_VEC], zeta[DERIVED_VEC];
     if (wantZ) {
 #pragma unroll
-        for (int p = 1; p <= DERIVED_VEC; ++p) Um[p] = cons ? q1_m[p] / (0.5 * (h_m[p - 1] + h_m[p])) : q1_m[p];
+        for (int p = 1; p <= DERIVED_VEC; ++p) Um[p] = frame_vel(cons, q1_m[p], h_m[p - 1], h_m[p]);
     }
     if (wantZ || wantD) {
 #pragma unroll
         for (int p = 1; p <= DERIVED_VEC; ++p) {
-            U0[p] = cons ? q1_0[p] / (0.5 * (h_0[p - 1] + h_0[p])) : q1_0[p];
-            V0[p] = cons ? q2_0[p] / (0.5 * (h_m[p] + h_0[p])) : q2_0[p];
+            U0[p] = frame_vel(cons, q1_0[p], h_0[p - 1], h_0[p]);
+            V0[p] = frame_vel(cons, q2_0[p], h_m[p], h_0[p]);
         }
     }
-    if (wantZ) V0[0] = cons ? q2_0[0] / (0.5 * (h_m[0] + h_0[0])) : q2_0[0];
+    if (wantZ) V0[0] = frame_vel(cons, q2_0[0], h_m[0], h_0[0]);
     if (wantD) {
-        U0[DERIVED_VEC + 1] = cons ? q1_0[DERIVED_VEC + 1] / (0.5 * (h_0[DERIVED_VEC] + h_0[DERIVED_VEC + 1])) : q1_0[DERIVED_VEC + 1];
+        U0[DERIVED_VEC + 1] = frame_vel(cons, q1_0[DERIVED_VEC + 1], h_0[DERIVED_VEC], h_0[DERIVED_VEC + 1]);
 #pragma unroll
-        for (int p = 1; p <= DERIVED_VEC; ++p) Vp[p] = cons ? q2_p[p] / (0.5 * (h_0[p] + h_p[p])) : q2_p[p];
+        for (int p = 1; p <= DERIVED_VEC; ++p) Vp[p] = frame_vel(cons, q2_p[p], h_0[p], h_p[p]);
     }
 
     if (wantZ) {
@@ -175,18 +157,10 @@ __global__ __launch_bounds__(DERIVED_NT) void k_derived_fields(DrvArgs<T> a) {
     }
     if (wantQ) {
 #pragma unroll
-        for (int k = 0; k < DERIVED_VEC; ++k) res[k] = (zeta[k] + f) / (0.5 * (0.5 * (h_m[k] + h_m[k + 1]) + 0.5 * (h_0[k] + h_0[k + 1])));
+        for (int k = 0; k < DERIVED_VEC; ++k) res[k] = (zeta[k] + f) / frame_xy_mean(h_m[k], h_m[k + 1], h_0[k], h_0[k + 1]);
         store_chunk(out, res, full, nvalid);
     }
 }
-
-// the frame: `which` fields of `elem`-byte elements at out; row, field and (ensembles) member stride in elements
-struct DrvFrame {
-    int which;
-    void *out;
-    int elem;
-    int64_t osy, osf, osm = 0;
-};
 
 template <typename T, int MODE>
 void launch(const DrvArgs<T> &a, int elem, dim3 grid, hipStream_t s) {
@@ -194,35 +168,21 @@ void launch(const DrvArgs<T> &a, int elem, dim3 grid, hipStream_t s) {
     else hipLaunchKernelGGL((k_derived_fields<T, double, MODE>), grid, dim3(DERIVED_NT), 0, s, a);
 }
 
-// the checks of output_common (output.hip), in its order, with SWMHD_DRV_ALL for the mask; f: the scalar (ens->par: the table instead)
+// the checks of output_common (output.hip) with SWMHD_DRV_ALL for the mask; f: the scalar (ens->par: the table instead)
 template <typename T>
-int derived_common(const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, T f, const Rows &r, const DrvFrame &o,
+int derived_common(const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, T f, const Rows &r, const Frame &o,
                    int flags, void *stream, const Ens *ens = nullptr) {
-    if (!q1 || !q2 || !h || !A || !o.out) return SWMHD_EINVAL;
-    if (!g.extents_ok() || !g.spacing_ok() || !formulation_ok(form) || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
-    if (o.which <= 0 || (o.which & ~SWMHD_DRV_ALL)) return SWMHD_EINVAL;
-    if (o.elem != 4 && o.elem != 8) return SWMHD_EINVAL;
-    if (flags & ~DERIVED_FLAGS) return SWMHD_EINVAL;
-    const int nf = __builtin_popcount((unsigned)o.which);
-    if (o.osy < g.Nx || o.osf < (int64_t)(r.j1 - r.j0) * o.osy) return SWMHD_EINVAL;
-    if (ens) {
-        if (ens->par && !ens->params) return SWMHD_EINVAL;
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (ens->stride_m < g.min_member_stride() || o.osm < (int64_t)nf * o.osf) return SWMHD_EINVAL;
-    }
-    if (!g.halo_at_least(1)) return SWMHD_EHALO;
+    if (!frame_source_ok(q1, q2, h, A, g, form) || !frame_ok(o, SWMHD_DRV_ALL, g, r, ens)) return SWMHD_EINVAL;
+    if ((flags & ~FRAME_FLAGS) || !frame_members_ok(ens, g) || (ens && ens->par && !ens->params)) return SWMHD_EINVAL;
+    if (!frame_halo_ok(g)) return SWMHD_EHALO;
     const DerivedPlan p = derived_plan(g.Nx, r.j1 - r.j0, ens ? ens->members : 1);
     if (p.none) return SWMHD_OK;
     if (p.too_many) return hiprc(hipErrorInvalidConfiguration);
     DrvArgs<T> a;
-    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = g.interior(h); a.A = g.interior(A);
+    set_frame_source(a, q1, q2, h, A, g, form, o.which, flags, ens);
     a.out = o.out;
-    a.Nx = g.Nx; a.Ny = g.Ny; a.j0 = r.j0; a.j1 = r.j1; a.nchunk = p.nchunk;
-    a.sy = (long)g.sy; a.osy = (long)o.osy; a.osf = (long)o.osf;
-    a.dx = g.dx; a.dy = g.dy; a.f = (double)f;
-    a.form = form; a.which = o.which;
-    a.wrap = decode_flags(flags).wrap;
-    a.stride_m = ens ? (long)ens->stride_m : 0; a.ostride_m = ens ? (long)o.osm : 0;
+    a.j0 = r.j0; a.j1 = r.j1; a.nchunk = p.nchunk; a.f = (double)f;
+    a.osy = (long)o.osy; a.osf = (long)o.osf; a.ostride_m = ens ? (long)o.osm : 0;
     a.params = ens && ens->par ? static_cast<const T *>(ens->params) : nullptr;
     const dim3 grid((unsigned)p.blocks, (unsigned)p.members);
     hipStream_t s = (hipStream_t)stream;
@@ -242,7 +202,7 @@ extern "C" {
                                    T dx, T dy, int formulation, T coriolis_f, int j0, int j1, int which, void *out,                 \
                                    int out_elem_size, int64_t out_stride_y, int64_t out_stride_f, int flags, void *stream) {        \
         return swmhd::derived_common<T>(q1, q2, h, A, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, formulation, coriolis_f,             \
-                                        swmhd::Rows{j0, j1}, swmhd::DrvFrame{which, out, out_elem_size, out_stride_y, out_stride_f}, \
+                                        swmhd::Rows{j0, j1}, swmhd::Frame{which, out, out_elem_size, out_stride_y, out_stride_f}, \
                                         flags, stream);                                                                              \
     }                                                                                                                                \
     int swmhd_ensemble_derived_fields_##sfx(const T *q1, const T *q2, const T *h, const T *A, int members, int64_t stride_m,        \
@@ -252,7 +212,7 @@ extern "C" {
         const swmhd::Ens e{members, stride_m};                                                                                       \
         return swmhd::derived_common<T>(q1, q2, h, A, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, formulation, coriolis_f,             \
                                         swmhd::Rows{j0, j1},                                                                         \
-                                        swmhd::DrvFrame{which, out, out_elem_size, out_stride_y, out_stride_f, out_stride_m}, flags, \
+                                        swmhd::Frame{which, out, out_elem_size, out_stride_y, out_stride_f, out_stride_m}, flags, \
                                         stream, &e);                                                                                 \
     }                                                                                                                                \
     int swmhd_ensemble_derived_fields_params_##sfx(const T *q1, const T *q2, const T *h, const T *A, int members, int64_t stride_m, \
@@ -263,7 +223,7 @@ extern "C" {
         const swmhd::Ens e{members, stride_m, false, true, params};                                                                  \
         return swmhd::derived_common<T>(q1, q2, h, A, swmhd::Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, formulation, T(0),                   \
                                         swmhd::Rows{j0, j1},                                                                         \
-                                        swmhd::DrvFrame{which, out, out_elem_size, out_stride_y, out_stride_f, out_stride_m}, flags, \
+                                        swmhd::Frame{which, out, out_elem_size, out_stride_y, out_stride_f, out_stride_m}, flags, \
                                         stream, &e);                                                                                 \
     }
 

@@ -2,9 +2,9 @@
 // the four prognostic parents (swmhd_zonal_spectra_*, include/swmhd_spectra.h).
 //
 //   P_F[k] = (1/rows) Σ_j c_k |(1/Nx) Σ_i F(i,j) exp(−2πi k (i−1)/Nx)|²,  k = 0 .. Nx/2,  c_k = 1 at the two ends, else 2
-// F(i,j): the float64 frame values u v h A s B_x B_y (mask bits = SWMHD_OUT_*), per cell the statements of zonal.hip and output.hip, which
-// this file restates for one cell of one field; the object is built without FMA contraction and with IEEE divide / sqrt (Makefile:
-// STRICT), so the input of the transform is bitwise the float64 frame (tests/output_cases.np_output_fields).
+// F(i,j): the float64 frame values u v h A s B_x B_y (mask bits = SWMHD_OUT_*), per cell the frame definitions of frame_device.inc as
+// spectra_device.inc::frame_value states them for one cell of one field; the object is built without FMA contraction and with IEEE
+// divide / sqrt (Makefile: STRICT), so the input of the transform is bitwise the float64 frame (tests/output_cases.np_output_fields).
 //
 // Pass 1 (k_spectra_rows): unit (member, field, w) takes the rows j0 + w, j0 + w + W, ... (launch_plan.hpp: spectra_plan) one after the
 // other.  A unit is a workgroup of SPECTRA_NT threads from Nx = 512 on and one wave up to Nx = 256 (four units of consecutive w per
@@ -146,32 +146,22 @@ struct SpectraOut {
 template <typename T>
 int spectra_common(const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, const Rows &r, const SpectraOut &o, int flags,
                    void *stream, const Ens *ens = nullptr) {
-    if (!q1 || !q2 || !h || !A || !o.out || !o.ws) return SWMHD_EINVAL;
-    if (!g.extents_ok() || !g.spacing_ok() || !formulation_ok(form) || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
-    if (o.which <= 0 || (o.which & ~SWMHD_ZS_ALL)) return SWMHD_EINVAL;
-    if (flags & ~SPECTRA_FLAGS) return SWMHD_EINVAL;
+    if (!frame_source_ok(q1, q2, h, A, g, form) || !o.out || !o.ws || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
+    if (o.which <= 0 || (o.which & ~SWMHD_ZS_ALL) || (flags & ~FRAME_FLAGS)) return SWMHD_EINVAL;
     const int nf = __builtin_popcount((unsigned)o.which);
-    if (o.osk < (int64_t)g.Nx / 2 + 1) return SWMHD_EINVAL;
-    if (ens) {
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (ens->stride_m < g.min_member_stride() || o.osm < (int64_t)nf * o.osk) return SWMHD_EINVAL;
-    }
-    if ((g.Hx < 1 && !(flags & SWMHD_WRAP_X)) || (g.Hy < 1 && !(flags & SWMHD_WRAP_Y))) return SWMHD_EHALO;
+    if (o.osk < (int64_t)g.Nx / 2 + 1 || !frame_members_ok(ens, g) || (ens && o.osm < (int64_t)nf * o.osk)) return SWMHD_EINVAL;
+    if (!spectra_halo_ok(g, flags)) return SWMHD_EHALO;
     const int members = ens ? ens->members : 1;
     const SpectraPlan p = spectra_plan(g.Nx, r.j1 - r.j0, nf, members);
     if (p.unsupported) return SWMHD_ENOTSUP;
     if (p.none) return SWMHD_OK;
     if (p.too_many) return hiprc(hipErrorInvalidConfiguration);
     SpectraArgs<T> a;
-    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = g.interior(h); a.A = g.interior(A);
+    set_frame_source(a, q1, q2, h, A, g, form, o.which, flags, ens);
     a.ws = o.ws; a.out = o.out;
-    a.Nx = g.Nx; a.Ny = g.Ny; a.j0 = r.j0; a.j1 = r.j1;
-    a.sy = (long)g.sy; a.osk = (long)o.osk;
-    a.dx = g.dx; a.dy = g.dy;
-    a.form = form; a.which = o.which;
-    a.wrap = decode_flags(flags).wrap;
+    a.j0 = r.j0; a.j1 = r.j1;
+    a.osk = (long)o.osk; a.osm = ens ? (long)o.osm : 0;
     a.W = p.W; a.nf = nf; a.log2n = p.log2n;
-    a.stride_m = ens ? (long)ens->stride_m : 0; a.osm = ens ? (long)o.osm : 0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid1((unsigned)p.blocks1), grid2((unsigned)p.blocks2);
     constexpr int WAVE = 64;

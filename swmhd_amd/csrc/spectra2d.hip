@@ -247,10 +247,8 @@ struct S2dOut {
 template <typename T>
 int spectra2d_common(const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, const S2dOut &o, int flags, void *stream,
                      const Ens *ens = nullptr) {
-    if (!q1 || !q2 || !h || !A || !o.ws || (!o.shell && !o.out2)) return SWMHD_EINVAL;
-    if (!g.extents_ok() || !g.spacing_ok() || !formulation_ok(form)) return SWMHD_EINVAL;
-    if (o.which <= 0 || (o.which & ~SWMHD_ZS_ALL)) return SWMHD_EINVAL;
-    if (flags & ~SPECTRA2D_FLAGS) return SWMHD_EINVAL;
+    if (!frame_source_ok(q1, q2, h, A, g, form) || !o.ws || (!o.shell && !o.out2)) return SWMHD_EINVAL;
+    if (o.which <= 0 || (o.which & ~SWMHD_ZS_ALL) || (flags & ~FRAME_FLAGS) || !frame_members_ok(ens, g)) return SWMHD_EINVAL;
     if (!(o.wx > 0.0) || !(o.wy > 0.0) || !std::isfinite(o.wx) || !std::isfinite(o.wy)) return SWMHD_EINVAL;
     const int nf = __builtin_popcount((unsigned)o.which);
     const int NS = spectra2d_shells(g.Nx, g.Ny, o.wx, o.wy);
@@ -258,13 +256,8 @@ int spectra2d_common(const T *q1, const T *q2, const T *h, const T *A, const Gri
     const int64_t nkx = (int64_t)g.Nx / 2 + 1;
     if (o.shell && o.oss < NS) return SWMHD_EINVAL;
     if (o.out2 && (o.o2kx < g.Ny || o.o2f / nkx < o.o2kx)) return SWMHD_EINVAL;   // (a >= n b  <=>  a / n >= b: no overflow)
-    if (ens) {
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
-        if (o.shell && o.osm / nf < o.oss) return SWMHD_EINVAL;
-        if (o.out2 && o.o2m / nf < o.o2f) return SWMHD_EINVAL;
-    }
-    if ((g.Hx < 1 && !(flags & SWMHD_WRAP_X)) || (g.Hy < 1 && !(flags & SWMHD_WRAP_Y))) return SWMHD_EHALO;
+    if (ens && ((o.shell && o.osm / nf < o.oss) || (o.out2 && o.o2m / nf < o.o2f))) return SWMHD_EINVAL;
+    if (!spectra_halo_ok(g, flags)) return SWMHD_EHALO;
     const int members = ens ? ens->members : 1;
     if (spectra_log2(g.Nx) < 0 || spectra_log2(g.Ny) < 0) return SWMHD_ENOTSUP;
     const Spectra2dPlan p = spectra2d_plan(g.Nx, g.Ny, nf, members, o.wx, o.wy, o.shell != nullptr, device_lds_limit());
@@ -272,17 +265,11 @@ int spectra2d_common(const T *q1, const T *q2, const T *h, const T *A, const Gri
     if (p.none) return SWMHD_OK;
     if (p.too_many) return hiprc(hipErrorInvalidConfiguration);
     S2dArgs<T> a;
-    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = g.interior(h); a.A = g.interior(A);
+    set_frame_source(a, q1, q2, h, A, g, form, o.which, flags, ens);
     a.ws = o.ws;
-    a.Nx = g.Nx; a.Ny = g.Ny;
-    a.sy = (long)g.sy;
-    a.dx = g.dx; a.dy = g.dy;
-    a.form = form; a.which = o.which;
-    a.wrap = decode_flags(flags).wrap;
     a.nf = nf; a.log2n = p.log2nx; a.R = p.R; a.pad = p.pad;
     a.log2r = 0;
     while ((1 << a.log2r) < p.R) ++a.log2r;
-    a.stride_m = ens ? (long)ens->stride_m : 0;
     hipStream_t s = (hipStream_t)stream;
     constexpr int WAVE = 64;
     static_assert(SPECTRA_UNITS_SMALL == SPECTRA_NT / WAVE, "a small row or column is one wave's");

@@ -29,7 +29,9 @@ __device__ __forceinline__ cplx twiddle_at(const cplx *tw, int idx, int Q) {
     }
 }
 
-// the frame value of field `bit` at cell x of row y (0-based interior indices): the statements of zonal.hip for one cell
+// the frame value of field `bit` at cell x of row y (0-based interior indices): the definitions of frame_device.inc, with which these
+// statements must agree bit for bit (the spectra tests hold them to the frame), written out for one cell of one field: routed through
+// frame_device.inc's helpers the two row kernels compile to other code objects, and a listing that changes is a change to measure.
 // (Args: q1 q2 h A at interior cell (1,1), dx, dy)
 template <typename Args>
 __device__ __forceinline__ double frame_value(const Args &a, int bit, bool cons, long r0, long rm, long rp, int x, int xl) {

@@ -2,8 +2,7 @@
 // one launch over the four prognostic parents (swmhd_zonal_means_*, include/swmhd_zonal.h).
 //
 //   profile[k][j] = (Σ_{i=1..Nx} term_k(i, j)) / Nx
-// Per-cell terms: the definitions of output.hip (a binary operation sits at its FIRST operand's location, the second operand is
-// interpolated there, a divisor field is interpolated; all arithmetic in double), with U V BX BY the frame values:
+// Per-cell terms: the frame definitions and their placement rule (frame_device.inc), with U V BX BY the frame values:
 //   u v h A s B_x B_y   the frame fields themselves (mask bits = SWMHD_OUT_*)
 //   uu    @fc  U·U             vv    @cf  V·V             uv    @fc  U · ℑxyᶠᶜ(V)     0.5*(0.5*(V(i−1,j)+V(i,j)) + 0.5*(V(i−1,j+1)+V(i,j+1)))
 //   B_xB_x @cf BX·BX           B_yB_y @fc BY·BY           B_xB_y @fc BY · ℑxyᶠᶜ(BX)   same grouping
@@ -14,7 +13,7 @@
 //
 // Shape: one wave64 per row, four rows per 256-thread workgroup (launch_plan.hpp: zonal_plan) -- no LDS, no barrier, no atomics.  Lane l
 // takes the 4-cell chunks l, l + 64, ... of its row (32 B of an fp64 parent per load where the chunk lies inside the row, single elements
-// where it crosses the end, as load_row of output.hip, which this file restates), adds their terms serially in x order, and a butterfly
+// where it crosses the end: load_row of frame_device.inc, shared with output.hip), adds their terms serially in x order, and a butterfly
 // (__shfl_xor, 32 .. 1) adds the 64 lane sums; both operands of a butterfly level are the same pair in both lanes and addition commutes,
 // so every lane ends with the same bits and lane 0 stores.  The order is a function of Nx alone (zonal_depth): not of the row range, the
 // member count, the strides or the grid.  64-wide members: 256 x 64 rows = 16 384 waves; a 4096-wide row: 16 trips per lane.
@@ -27,13 +26,10 @@
 namespace swmhd {
 namespace {
 
-constexpr int NPROF = 14;
+#include "frame_device.inc"   // frame_vel .. frame_xy_mean, frame_west, load_row: shared with output.hip and derived.hip
 
-typedef double zm_d4 __attribute__((ext_vector_type(4), aligned(8)));
-typedef float zm_f4 __attribute__((ext_vector_type(4), aligned(4)));
-template <typename T> struct ZmVec;
-template <> struct ZmVec<double> { typedef zm_d4 type; };
-template <> struct ZmVec<float> { typedef zm_f4 type; };
+constexpr int NPROF = 14;
+static_assert(ZONAL_VEC == FRAME_VEC, "a trip of a lane is one chunk of the frame");
 
 template <typename T>
 struct ZonalArgs {
@@ -45,20 +41,6 @@ struct ZonalArgs {
     int form, which, wrap;      // wrap: bit 0 = x, bit 1 = y
     long row_blocks, stride_m, osm;   // ensembles: member blockIdx.x / row_blocks
 };
-
-// values x0-1, x0 .. x0+3 of one row: r[0] is the west neighbour of the chunk, r[1 + k] cell x0 + k
-template <typename T>
-__device__ __forceinline__ void load_row(const T *__restrict__ row, int x0, int xl, bool full, int Nx, double (&r)[ZONAL_VEC + 1]) {
-    r[0] = (double)row[xl];
-    if (full) {
-        const typename ZmVec<T>::type v = *reinterpret_cast<const typename ZmVec<T>::type *>(row + x0);
-#pragma unroll
-        for (int k = 0; k < ZONAL_VEC; ++k) r[1 + k] = (double)v[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < ZONAL_VEC; ++k) r[1 + k] = (double)row[k < Nx - x0 ? x0 + k : Nx - 1];   // (beyond the row: never added)
-    }
-}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -87,6 +69,7 @@ __global__ __launch_bounds__(ZONAL_NT, M == ZM_ROW ? 4 : 2) void k_zonal_means(Z
     const long row = rb * ZONAL_ROWS + wave;
     if (row >= (long)(a.j1 - a.j0)) return;   // (the whole wave)
     const int y = a.j0 + (int)row;
+    // (frame_device.inc: frame_rows, written out: through the function this kernel's scalar code is scheduled differently)
     const int ym = (y == 0 && (a.wrap & 2)) ? a.Ny - 1 : y - 1;
     const int yp = (y == a.Ny - 1 && (a.wrap & 2)) ? 0 : y + 1;
     const long r0 = (long)y * a.sy, rm = (long)ym * a.sy, rp = (long)yp * a.sy;
@@ -114,43 +97,43 @@ __global__ __launch_bounds__(ZONAL_NT, M == ZM_ROW ? 4 : 2) void k_zonal_means(Z
     for (int x0 = lane * ZONAL_VEC; x0 < a.Nx;) {
         const int nvalid = a.Nx - x0;
         const bool full = nvalid >= ZONAL_VEC;
-        const int xl = (x0 == 0 && (a.wrap & 1)) ? a.Nx - 1 : x0 - 1;
+        const int xl = frame_west(x0, a.Nx, a.wrap);
         double q1_0[R], q2_0[R], q2_p[R], h_m[R], h_0[R], h_p[R], A_m[R], A_0[R], A_p[R];
-        if (needU) load_row(a.q1 + r0, x0, xl, full, a.Nx, q1_0);
-        if (needV0) load_row(a.q2 + r0, x0, xl, full, a.Nx, q2_0);
-        if (needVp) load_row(a.q2 + rp, x0, xl, full, a.Nx, q2_p);
-        if (ld_h0) load_row(a.h + r0, x0, xl, full, a.Nx, h_0);
-        if (ld_hm) load_row(a.h + rm, x0, xl, full, a.Nx, h_m);
-        if (ld_hp) load_row(a.h + rp, x0, xl, full, a.Nx, h_p);
-        if (ld_A0) load_row(a.A + r0, x0, xl, full, a.Nx, A_0);
-        if (ld_Am) load_row(a.A + rm, x0, xl, full, a.Nx, A_m);
-        if (ld_Ap) load_row(a.A + rp, x0, xl, full, a.Nx, A_p);
+        if (needU) load_row<true>(a.q1 + r0, x0, xl, full, a.Nx, q1_0);
+        if (needV0) load_row<true>(a.q2 + r0, x0, xl, full, a.Nx, q2_0);
+        if (needVp) load_row<true>(a.q2 + rp, x0, xl, full, a.Nx, q2_p);
+        if (ld_h0) load_row<true>(a.h + r0, x0, xl, full, a.Nx, h_0);
+        if (ld_hm) load_row<true>(a.h + rm, x0, xl, full, a.Nx, h_m);
+        if (ld_hp) load_row<true>(a.h + rp, x0, xl, full, a.Nx, h_p);
+        if (ld_A0) load_row<true>(a.A + r0, x0, xl, full, a.Nx, A_0);
+        if (ld_Am) load_row<true>(a.A + rm, x0, xl, full, a.Nx, A_m);
+        if (ld_Ap) load_row<true>(a.A + rp, x0, xl, full, a.Nx, A_p);
 
         // frame values: U and BY at the chunk's faces; V and BX on rows y and y + 1 from the west neighbour on (ℑxyᶠᶜ reads it)
         double U[ZONAL_VEC], BY[ZONAL_VEC], V0[R], Vp[R], BX0[R], BXp[R];
         if (needU) {
 #pragma unroll
-            for (int k = 0; k < ZONAL_VEC; ++k) U[k] = cons ? q1_0[k + 1] / (0.5 * (h_0[k] + h_0[k + 1])) : q1_0[k + 1];
+            for (int k = 0; k < ZONAL_VEC; ++k) U[k] = frame_vel(cons, q1_0[k + 1], h_0[k], h_0[k + 1]);
         }
         if (needV0) {
 #pragma unroll
-            for (int i = 0; i < R; ++i) V0[i] = cons ? q2_0[i] / (0.5 * (h_m[i] + h_0[i])) : q2_0[i];
+            for (int i = 0; i < R; ++i) V0[i] = frame_vel(cons, q2_0[i], h_m[i], h_0[i]);
         }
         if (needVp) {
 #pragma unroll
-            for (int i = 0; i < R; ++i) Vp[i] = cons ? q2_p[i] / (0.5 * (h_0[i] + h_p[i])) : q2_p[i];
+            for (int i = 0; i < R; ++i) Vp[i] = frame_vel(cons, q2_p[i], h_0[i], h_p[i]);
         }
         if (needBX0) {
 #pragma unroll
-            for (int i = 0; i < R; ++i) BX0[i] = -((A_0[i] - A_m[i]) / a.dy) / (0.5 * (h_m[i] + h_0[i]));
+            for (int i = 0; i < R; ++i) BX0[i] = frame_bx(A_0[i], A_m[i], a.dy, h_m[i], h_0[i]);
         }
         if (needBXp) {
 #pragma unroll
-            for (int i = 0; i < R; ++i) BXp[i] = -((A_p[i] - A_0[i]) / a.dy) / (0.5 * (h_0[i] + h_p[i]));
+            for (int i = 0; i < R; ++i) BXp[i] = frame_bx(A_p[i], A_0[i], a.dy, h_0[i], h_p[i]);
         }
         if (needBY) {
 #pragma unroll
-            for (int k = 0; k < ZONAL_VEC; ++k) BY[k] = ((A_0[k + 1] - A_0[k]) / a.dx) / (0.5 * (h_0[k] + h_0[k + 1]));
+            for (int k = 0; k < ZONAL_VEC; ++k) BY[k] = frame_by(A_0[k + 1], A_0[k], a.dx, h_0[k], h_0[k + 1]);
         }
 
         // the terms of cell x0 + k, added in x order (acc[p]: bit p of the mask)
@@ -161,18 +144,15 @@ __global__ __launch_bounds__(ZONAL_NT, M == ZM_ROW ? 4 : 2) void k_zonal_means(Z
                 if (w & SWMHD_ZM_V) acc[1] += V0[k + 1];
                 if (w & SWMHD_ZM_H) acc[2] += h_0[k + 1];
                 if (w & SWMHD_ZM_A) acc[3] += A_0[k + 1];
-                if (wantS) {
-                    const double g00 = V0[k], g10 = V0[k + 1], g01 = Vp[k], g11 = Vp[k + 1];
-                    acc[4] += sqrt(U[k] * U[k] + 0.5 * (0.5 * (g00 * g00 + g10 * g10) + 0.5 * (g01 * g01 + g11 * g11)));
-                }
+                if (wantS) acc[4] += frame_speed(U[k], V0[k], V0[k + 1], Vp[k], Vp[k + 1]);
                 if (w & SWMHD_ZM_BX) acc[5] += BX0[k + 1];
                 if (w & SWMHD_ZM_BY) acc[6] += BY[k];
                 if (w & SWMHD_ZM_UU) acc[7] += U[k] * U[k];
                 if (w & SWMHD_ZM_VV) acc[8] += V0[k + 1] * V0[k + 1];
-                if (wantUV) acc[9] += U[k] * (0.5 * (0.5 * (V0[k] + V0[k + 1]) + 0.5 * (Vp[k] + Vp[k + 1])));
+                if (wantUV) acc[9] += U[k] * frame_xy_mean(V0[k], V0[k + 1], Vp[k], Vp[k + 1]);
                 if (w & SWMHD_ZM_BXBX) acc[10] += BX0[k + 1] * BX0[k + 1];
                 if (w & SWMHD_ZM_BYBY) acc[11] += BY[k] * BY[k];
-                if (wantBB) acc[12] += BY[k] * (0.5 * (0.5 * (BX0[k] + BX0[k + 1]) + 0.5 * (BXp[k] + BXp[k + 1])));
+                if (wantBB) acc[12] += BY[k] * frame_xy_mean(BX0[k], BX0[k + 1], BXp[k], BXp[k + 1]);
                 if (wantVA) acc[13] += V0[k + 1] * (0.5 * (A_m[k + 1] + A_0[k + 1]));
             }
         }
@@ -203,29 +183,19 @@ struct ZonalOut {
 template <typename T>
 int zonal_common(const T *q1, const T *q2, const T *h, const T *A, const Grid &g, int form, const Rows &r, const ZonalOut &o, int flags,
                  void *stream, const Ens *ens = nullptr) {
-    if (!q1 || !q2 || !h || !A || !o.out) return SWMHD_EINVAL;
-    if (!g.extents_ok() || !g.spacing_ok() || !formulation_ok(form) || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
-    if (o.which <= 0 || (o.which & ~SWMHD_ZM_ALL)) return SWMHD_EINVAL;
-    if (flags & ~ZONAL_FLAGS) return SWMHD_EINVAL;
-    const int np = __builtin_popcount((unsigned)o.which);
-    if (o.osk < (int64_t)(r.j1 - r.j0)) return SWMHD_EINVAL;
-    if (ens) {
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (ens->stride_m < g.min_member_stride() || o.osm < (int64_t)np * o.osk) return SWMHD_EINVAL;
-    }
-    if (!g.halo_at_least(1)) return SWMHD_EHALO;
+    if (!frame_source_ok(q1, q2, h, A, g, form) || !o.out || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
+    if (o.which <= 0 || (o.which & ~SWMHD_ZM_ALL) || (flags & ~FRAME_FLAGS)) return SWMHD_EINVAL;
+    if (o.osk < (int64_t)(r.j1 - r.j0) || !frame_members_ok(ens, g)) return SWMHD_EINVAL;
+    if (ens && o.osm < (int64_t)__builtin_popcount((unsigned)o.which) * o.osk) return SWMHD_EINVAL;
+    if (!frame_halo_ok(g)) return SWMHD_EHALO;
     const ZonalPlan p = zonal_plan(r.j1 - r.j0, ens ? ens->members : 1);
     if (p.none) return SWMHD_OK;
     if (p.too_many) return hiprc(hipErrorInvalidConfiguration);
     ZonalArgs<T> a;
-    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = g.interior(h); a.A = g.interior(A);
+    set_frame_source(a, q1, q2, h, A, g, form, o.which, flags, ens);
     a.out = o.out;
-    a.Nx = g.Nx; a.Ny = g.Ny; a.j0 = r.j0; a.j1 = r.j1;
-    a.sy = (long)g.sy; a.osk = (long)o.osk;
-    a.dx = g.dx; a.dy = g.dy;
-    a.form = form; a.which = o.which;
-    a.wrap = decode_flags(flags).wrap;
-    a.row_blocks = p.row_blocks; a.stride_m = ens ? (long)ens->stride_m : 0; a.osm = ens ? (long)o.osm : 0;
+    a.j0 = r.j0; a.j1 = r.j1;
+    a.osk = (long)o.osk; a.row_blocks = p.row_blocks; a.osm = ens ? (long)o.osm : 0;
     const dim3 grid((unsigned)p.blocks);
     hipStream_t s = (hipStream_t)stream;
     const bool lean = !(o.which & ~ZM_ROW);

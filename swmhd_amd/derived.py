@@ -11,29 +11,19 @@ FieldTimeSeries, which takes these names mixed with the seven of the frame.  Zon
 import torch
 
 from . import _lib
+from ._series import cut_runs, lead_shape, out_tensor, state_pointers    # (state_pointers: also for those who import it from here)
 from .fields import _stream_ptr
 
 DEFAULT_NAMES = ("vorticity", "current")
-_ELEM = {torch.float32: 4, torch.float64: 8}
+ELEM_TYPES = (torch.float32, torch.float64)      # the element types of a frame
+# a tracer among the names of a frame, derived or not: the frame's answer
+TRACER_MESSAGE = f"output field {{n!r}} is a tracer: frames hold {' '.join(_lib.OUT_BITS)} only; read model.tracers[{{n!r}}]"
+_MESSAGES = (TRACER_MESSAGE, f"derived field {{n!r}}: one of {' '.join(_lib.DRV_BITS)}", "derived_fields: no field names")
 
 
 def _runs(names, tracers=()):
-    """The fields as launches: the kernel writes the fields of a mask in bit order (vorticity divergence current potential_vorticity),
-    so `names` is cut into runs that ascend in that order, as output._runs cuts a frame."""
-    runs = []
-    for n in names:
-        if n in tracers:
-            raise _lib.SwmhdError(f"output field {n!r} is a tracer: frames hold {' '.join(_lib.OUT_BITS)} only; read model.tracers[{n!r}]")
-        if n not in _lib.DRV_BITS:
-            raise _lib.SwmhdError(f"derived field {n!r}: one of {' '.join(_lib.DRV_BITS)}")
-        bit = _lib.DRV_BITS[n]
-        if runs and bit > runs[-1][-1]:
-            runs[-1].append(bit)
-        else:
-            runs.append([bit])
-    if not runs:
-        raise _lib.SwmhdError("derived_fields: no field names")
-    return runs
+    """The fields as launches (cut_runs): bit order vorticity divergence current potential_vorticity."""
+    return cut_runs(names, _lib.DRV_BITS, tracers, _MESSAGES)
 
 
 def check_coriolis_names(model, names):
@@ -41,16 +31,6 @@ def check_coriolis_names(model, names):
     if getattr(model, "_coriolis", None) is not None and "potential_vorticity" in names:
         raise _lib.SwmhdError(f"potential_vorticity under coriolis = {model.coriolis!r} is not supported (SWMHD_ENOTSUP): "
                               "swmhd_derived_fields_* takes a scalar f; vorticity is available")
-
-
-def state_pointers(model):
-    """(the four parents' device pointers, row stride, device, is an ensemble) of the state as it stands now"""
-    if getattr(model, "members", None) is not None:
-        q = model._state                  # (whichever set of tensors is the state NOW: the ping-pong roles flip every stage)
-        return [t.data_ptr() for t in q], q[0].stride(1), q[0].device, True
-    model._join()                         # a ring exchange of this state may still be in flight
-    q = model._raw_fields
-    return [f.ptr for f in q], q[0].stride_y, q[0].data.device, False
 
 
 def launch(model, ptrs, sy, ens, which, first, out):
@@ -74,14 +54,7 @@ def enqueue_derived(model, names=DEFAULT_NAMES, out=None, array_type=torch.float
     runs = _runs(names, getattr(model, "tracer_names", ()))
     check_coriolis_names(model, names)
     ptrs, sy, dev, ens = state_pointers(model)
-    g = model.grid
-    shape = ((model.members,) if ens else ()) + (len(names), g.Ny, g.Nx)
-    if out is None:
-        if array_type not in _ELEM:
-            raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
-        out = torch.empty(shape, dtype=array_type, device=dev)
-    elif not (out.is_cuda and out.dtype in _ELEM and tuple(out.shape) == shape and out.stride(-1) == 1):
-        raise _lib.SwmhdError(f"derived_fields: out must be a float32 / float64 CUDA tensor of shape {shape} with unit stride in x")
+    out = out_tensor(out, lead_shape(model) + (len(names), model.grid.Ny, model.grid.Nx), ELEM_TYPES, dev, "derived_fields", "x", array_type)
     k = 0
     for bits in runs:
         launch(model, ptrs, sy, ens, sum(bits), out.select(-3, k), out)

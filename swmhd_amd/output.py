@@ -16,31 +16,18 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .derived import check_coriolis_names, launch as launch_derived, state_pointers
+from ._series import DeviceTimeSeries, cut_runs, lead_shape, out_tensor, state_pointers
+from .derived import ELEM_TYPES, TRACER_MESSAGE, check_coriolis_names, launch as launch_derived
 from .fields import _stream_ptr
 
 DEFAULT_NAMES = ("u", "v", "A", "s")    # the reference's writer
-_ELEM = {torch.float32: 4, torch.float64: 8}
+_MESSAGES = (TRACER_MESSAGE, f"output field {{n!r}}: one of {' '.join(_lib.OUT_BITS)} (velocities u, v also for the conservative model); "
+             f"frames also take the derived fields {' '.join(_lib.DRV_BITS)}", "output_fields: no field names")
 
 
 def _runs(names, tracers=()):
-    """The frame's fields as launches: the kernel writes the fields of a mask in bit order (u v h A s B_x B_y), so `names` is cut into
-    runs that ascend in that order -- one launch for the default frame, and any order or repetition of names is honoured."""
-    runs = []
-    for n in names:
-        if n in tracers:
-            raise _lib.SwmhdError(f"output field {n!r} is a tracer: frames hold {' '.join(_lib.OUT_BITS)} only; read model.tracers[{n!r}]")
-        if n not in _lib.OUT_BITS:
-            raise _lib.SwmhdError(f"output field {n!r}: one of {' '.join(_lib.OUT_BITS)} (velocities u, v also for the conservative model); "
-                                  f"frames also take the derived fields {' '.join(_lib.DRV_BITS)}")
-        bit = _lib.OUT_BITS[n]
-        if runs and bit > runs[-1][-1]:
-            runs[-1].append(bit)
-        else:
-            runs.append([bit])
-    if not runs:
-        raise _lib.SwmhdError("output_fields: no field names")
-    return runs
+    """The frame's fields as launches (cut_runs): bit order u v h A s B_x B_y -- one launch for the default frame."""
+    return cut_runs(names, _lib.OUT_BITS, tracers, _MESSAGES)
 
 
 def _frame_runs(names, tracers=()):
@@ -63,8 +50,7 @@ def _frame_runs(names, tracers=()):
 
 
 def frame_shape(model, names):
-    g, members = model.grid, getattr(model, "members", None)
-    return ((members,) if members is not None else ()) + (len(names), g.Ny, g.Nx)
+    return lead_shape(model) + (len(names), model.grid.Ny, model.grid.Nx)
 
 
 def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32):
@@ -74,13 +60,7 @@ def enqueue_frame(model, names=DEFAULT_NAMES, out=None, array_type=torch.float32
     check_coriolis_names(model, names)
     g = model.grid
     ptrs, sy, dev, ens = state_pointers(model)
-    shape = frame_shape(model, names)
-    if out is None:
-        if array_type not in _ELEM:
-            raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
-        out = torch.empty(shape, dtype=array_type, device=dev)
-    elif not (out.is_cuda and out.dtype in _ELEM and tuple(out.shape) == shape and out.stride(-1) == 1):
-        raise _lib.SwmhdError(f"output_fields: out must be a float32 / float64 CUDA tensor of shape {shape} with unit stride in x")
+    out = out_tensor(out, frame_shape(model, names), ELEM_TYPES, dev, "output_fields", "x", array_type)
     # The model steps with SWMHD_WRAP_* exactly where its halos may be stale (_rwrap): the kernel then reads the periodic image
     # itself, so a frame needs no halo fill in front of it.  Everywhere else the halos are kept current by the step.
     flags = model._rwrap
@@ -140,7 +120,7 @@ def frame_iterations(schedule, dt, nsteps):
     return list(range(0, nsteps + 1, n))
 
 
-class FieldTimeSeries:
+class FieldTimeSeries(DeviceTimeSeries):
     """The reference's field writer on the device: `capacity` frames of `names` in one tensor, plus the host lists `times` and
     `iterations`.  frames: (capacity, len(names), Ny, Nx); for an ensemble (capacity, members, len(names), Ny, Nx); on a y-slab the
     rank's own rows.  Names: u v h A s B_x B_y (velocities also for the conservative model, which stores uh, vh) and, in any mixture
@@ -154,50 +134,31 @@ class FieldTimeSeries:
     The tensor (capacity x frame bytes: 268 MB per 4096^2 float32 frame of four fields) is allocated when the first frame is written.
     `write` only enqueues; `numpy` and `save` are the calls that synchronise."""
 
+    _data, _unit = "frames", "frames"
+    frames = DeviceTimeSeries.tensor
+
     def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None, array_type=torch.float32):
-        self.model, self.names, self.schedule = model, tuple(names), schedule
-        _frame_runs(self.names, getattr(model, "tracer_names", ()))
-        check_coriolis_names(model, self.names)
-        if array_type not in _ELEM:
-            raise _lib.SwmhdError(f"array_type {array_type}: torch.float32 or torch.float64")
-        if capacity is None or int(capacity) < 1:
-            raise _lib.SwmhdError("FieldTimeSeries: capacity (frames) must be given: the frames stay on the device")
-        self.capacity, self.array_type = int(capacity), array_type
-        self.times, self.iterations = [], []
-        self._frames = None
+        self.array_type = self.dtype = array_type
+        super().__init__(model, names, schedule, capacity)
 
-    def __len__(self):
-        return len(self.times)
+    def _check_names(self):
+        _frame_runs(self.names, getattr(self.model, "tracer_names", ()))
+        check_coriolis_names(self.model, self.names)
+        if self.array_type not in ELEM_TYPES:
+            raise _lib.SwmhdError(f"array_type {self.array_type}: torch.float32 or torch.float64")
 
-    @property
-    def frames(self):
-        """The device tensor of all `capacity` slots; the first len(self) hold frames."""
-        if self._frames is None:
-            m = self.model
-            dev = m._state[0].device if getattr(m, "members", None) is not None else m._raw_fields[0].data.device
-            self._frames = torch.empty((self.capacity,) + frame_shape(m, self.names), dtype=self.array_type, device=dev)
-        return self._frames
+    def _sample_shape(self):
+        return frame_shape(self.model, self.names)
 
-    def write(self, time=None):
-        """Enqueue one frame of the model's current state into the next slot."""
-        k = len(self.times)
-        if k >= self.capacity:
-            raise _lib.SwmhdError(f"FieldTimeSeries: all {self.capacity} slots are written")
-        enqueue_frame(self.model, self.names, out=self.frames[k])
-        self.times.append(self.model.clock_time if time is None else time)
-        self.iterations.append(self.model.iteration)
-
-    def numpy(self):
-        """The frames written so far as a host array (synchronises)."""
-        return self.frames[:len(self.times)].cpu().numpy()
+    def _enqueue(self, out):
+        enqueue_frame(self.model, self.names, out=out)
 
     def save(self, path):
         """One .npz: frames, names, times, iterations and the grid extents (synchronises)."""
         import numpy as np
         g = self.model.grid
-        np.savez(path, frames=self.numpy(), names=np.array(self.names), times=np.array(self.times, dtype=np.float64),
-                 iterations=np.array(self.iterations, dtype=np.int64), size=np.array([g.Nx, g.Ny]),
-                 x=np.array(g.x, dtype=np.float64), y=np.array(g.y, dtype=np.float64), j_offset=g.j_offset, Ny_global=g.Ny_global)
+        self._savez(path, size=np.array([g.Nx, g.Ny]), x=np.array(g.x, dtype=np.float64), y=np.array(g.y, dtype=np.float64),
+                    j_offset=g.j_offset, Ny_global=g.Ny_global)
 
 
 def run(model, dt, stop_time=None, stop_iteration=None, writers=()):

@@ -23,29 +23,18 @@ import math
 import torch
 
 from . import _lib
+from ._series import DeviceTimeSeries, cached_workspace, cut_runs, lead_shape, out_tensor, state_pointers
 from .fields import _stream_ptr
 from .output import TimeInterval
 
 DEFAULT_NAMES = ("u", "v", "A")
+_MESSAGES = (f"zonal spectrum {{n!r}} is a tracer: spectra are {' '.join(_lib.ZS_BITS)} only",
+             f"zonal spectrum {{n!r}}: one of {' '.join(_lib.ZS_BITS)} (velocities u, v also for the conservative model)", "zonal_spectra: no names")
 
 
 def _runs(names, tracers=()):
-    """The spectra as launches: the kernels write the spectra of a mask in bit order (u v h A s B_x B_y), so `names` is cut into runs
-    that ascend in that order, as zonal._runs cuts the profiles: any order or repetition of names is honoured."""
-    runs = []
-    for n in names:
-        if n in tracers:
-            raise _lib.SwmhdError(f"zonal spectrum {n!r} is a tracer: spectra are {' '.join(_lib.ZS_BITS)} only")
-        if n not in _lib.ZS_BITS:
-            raise _lib.SwmhdError(f"zonal spectrum {n!r}: one of {' '.join(_lib.ZS_BITS)} (velocities u, v also for the conservative model)")
-        bit = _lib.ZS_BITS[n]
-        if runs and bit > runs[-1][-1]:
-            runs[-1].append(bit)
-        else:
-            runs.append([bit])
-    if not runs:
-        raise _lib.SwmhdError("zonal_spectra: no names")
-    return runs
+    """The spectra as launches (cut_runs): bit order u v h A s B_x B_y."""
+    return cut_runs(names, _lib.ZS_BITS, tracers, _MESSAGES)
 
 
 def _check(model, names):
@@ -61,40 +50,19 @@ def _check(model, names):
 
 
 def spectrum_shape(model, names):
-    members = getattr(model, "members", None)
-    return ((members,) if members is not None else ()) + (len(names), model.grid.Nx // 2 + 1)
-
-
-def _workspace(model, nfields, dev):
-    """The cached device workspace of a model: grown to what the C function states for the largest run asked for so far."""
-    g = model.grid
-    need = model._L.swmhd_zonal_spectra_workspace(g.Nx, g.Ny, nfields, getattr(model, "members", None) or 1)
-    ws = getattr(model, "_spectra_ws", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = torch.empty((need,), dtype=torch.float64, device=dev)
-        model._spectra_ws = ws
-    return ws
+    return lead_shape(model) + (len(names), model.grid.Nx // 2 + 1)
 
 
 def enqueue_zonal_spectra(model, names=DEFAULT_NAMES, out=None):
     """ShallowWaterModel.zonal_spectra / ShallowWaterEnsemble.zonal_spectra: see there."""
     names = tuple(names)
     runs = _check(model, names)
-    ens = getattr(model, "members", None) is not None
     g = model.grid
-    if ens:
-        q = model._state                  # (whichever set of tensors is the state NOW: the ping-pong roles flip every stage)
-        ptrs, sy, dev = [t.data_ptr() for t in q], q[0].stride(1), q[0].device
-    else:
-        model._join()                     # a ring exchange of this state may still be in flight
-        q = model._raw_fields
-        ptrs, sy, dev = [f.ptr for f in q], q[0].stride_y, q[0].data.device
-    shape = spectrum_shape(model, names)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == shape and out.stride(-1) == 1):
-        raise _lib.SwmhdError(f"zonal_spectra: out must be a float64 CUDA tensor of shape {shape} with unit stride in k")
-    ws = _workspace(model, max(len(bits) for bits in runs), dev)
+    ptrs, sy, dev, ens = state_pointers(model)
+    out = out_tensor(out, spectrum_shape(model, names), (torch.float64,), dev, "zonal_spectra", "k")
+    # (the workspace: what the C function states for the largest run asked for so far)
+    need = model._L.swmhd_zonal_spectra_workspace(g.Nx, g.Ny, max(len(bits) for bits in runs), getattr(model, "members", None) or 1)
+    ws = cached_workspace(model, "_spectra_ws", need, dev)
     flags = model._rwrap                  # as enqueue_frame: the periodic images where the step leaves the halos stale
     sfx = model.sfx
     k = 0
@@ -114,7 +82,7 @@ def enqueue_zonal_spectra(model, names=DEFAULT_NAMES, out=None):
     return out
 
 
-class ZonalSpectrumTimeSeries:
+class ZonalSpectrumTimeSeries(DeviceTimeSeries):
     """A writer of zonal spectra for run(): `capacity` samples of `names` in one float64 device tensor, plus the host lists `times` and
     `iterations`.  spectra: (capacity, len(names), Nx/2 + 1); for an ensemble (capacity, members, len(names), Nx/2 + 1); on a y-slab the
     spectrum of the rank's own rows.  Names: u v h A s B_x B_y (include/swmhd_spectra.h).
@@ -122,44 +90,24 @@ class ZonalSpectrumTimeSeries:
     The tensor is allocated when the first sample is written.  `write` only enqueues; `numpy` and `save` are the calls that
     synchronise."""
 
+    _data, _unit = "spectra", "samples"
+    spectra = DeviceTimeSeries.tensor
+
     def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None):
-        self.model, self.names, self.schedule = model, tuple(names), schedule
-        _check(model, self.names)
-        if capacity is None or int(capacity) < 1:
-            raise _lib.SwmhdError("ZonalSpectrumTimeSeries: capacity (samples) must be given: the spectra stay on the device")
-        self.capacity = int(capacity)
-        self.times, self.iterations = [], []
-        self._spectra = None
+        super().__init__(model, names, schedule, capacity)
 
-    def __len__(self):
-        return len(self.times)
+    def _check_names(self):
+        _check(self.model, self.names)
 
-    @property
-    def spectra(self):
-        """The device tensor of all `capacity` slots; the first len(self) hold samples."""
-        if self._spectra is None:
-            m = self.model
-            dev = m._state[0].device if getattr(m, "members", None) is not None else m._raw_fields[0].data.device
-            self._spectra = torch.empty((self.capacity,) + spectrum_shape(m, self.names), dtype=torch.float64, device=dev)
-        return self._spectra
+    def _sample_shape(self):
+        return spectrum_shape(self.model, self.names)
 
-    def write(self, time=None):
-        """Enqueue the spectra of the model's current state into the next slot."""
-        k = len(self.times)
-        if k >= self.capacity:
-            raise _lib.SwmhdError(f"ZonalSpectrumTimeSeries: all {self.capacity} slots are written")
-        enqueue_zonal_spectra(self.model, self.names, out=self.spectra[k])
-        self.times.append(self.model.clock_time if time is None else time)
-        self.iterations.append(self.model.iteration)
-
-    def numpy(self):
-        """The samples written so far as a host array (synchronises)."""
-        return self.spectra[:len(self.times)].cpu().numpy()
+    def _enqueue(self, out):
+        enqueue_zonal_spectra(self.model, self.names, out=out)
 
     def save(self, path):
         """One .npz: spectra, names, times, iterations, the integer wavenumbers k = 0 .. Nx/2 and kx = 2 pi k / Lx (synchronises)."""
         import numpy as np
         g = self.model.grid
         k = np.arange(g.Nx // 2 + 1, dtype=np.int64)
-        np.savez(path, spectra=self.numpy(), names=np.array(self.names), times=np.array(self.times, dtype=np.float64),
-                 iterations=np.array(self.iterations, dtype=np.int64), k=k, kx=2.0 * math.pi * k / g.Lx)
+        self._savez(path, k=k, kx=2.0 * math.pi * k / g.Lx)

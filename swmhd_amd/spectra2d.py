@@ -24,6 +24,7 @@ import math
 import torch
 
 from . import _lib
+from ._series import DeviceTimeSeries, cached_workspace, lead_shape, out_tensor, state_pointers
 from .fields import _stream_ptr
 from .output import TimeInterval
 from .spectra import DEFAULT_NAMES, _runs
@@ -79,11 +80,6 @@ def _check(model, names, what):
     return runs
 
 
-def _lead(model):
-    members = getattr(model, "members", None)
-    return (members,) if members is not None else ()
-
-
 def shells(grid):
     """NS of the grid, from the statement of the header (no library call)."""
     _, wx, wy = metric(grid)
@@ -92,46 +88,23 @@ def shells(grid):
     return int(math.floor(math.sqrt(a + b) + 0.5)) + 1
 
 
-def _workspace(model, nfields, dev, wx, wy):
-    """The cached device workspace of a model: grown to what the C function states for the largest run asked for so far."""
-    g = model.grid
-    need = model._L.swmhd_spectra2d_workspace(g.Nx, g.Ny, nfields, getattr(model, "members", None) or 1, wx, wy)
-    ws = getattr(model, "_spectra2d_ws", None)
-    if ws is None or ws.numel() < need or ws.device != dev:
-        ws = torch.empty((need,), dtype=torch.float64, device=dev)
-        model._spectra2d_ws = ws
-    return ws
-
-
 def _enqueue(model, names, shell_out, plane_out, what):
     names = tuple(names)
     runs = _check(model, names, what)
-    ens = getattr(model, "members", None) is not None
     g = model.grid
     _, wx, wy = metric(g)
     NS, nkx = shells(g), g.Nx // 2 + 1
-    if ens:
-        q = model._state                  # (whichever set of tensors is the state NOW: the ping-pong roles flip every stage)
-        ptrs, sy, dev = [t.data_ptr() for t in q], q[0].stride(1), q[0].device
-    else:
-        model._join()
-        q = model._raw_fields
-        ptrs, sy, dev = [f.ptr for f in q], q[0].stride_y, q[0].data.device
-    lead = _lead(model)
+    ptrs, sy, dev, ens = state_pointers(model)
     outs = []
-    for out, tail, unit in ((shell_out, (len(names), NS), 1), (plane_out, (len(names), nkx, g.Ny), 2)):
-        if out is None:
-            outs.append(None)
-            continue
-        shape = lead + tail
-        if out is True:
-            out = torch.empty(shape, dtype=torch.float64, device=dev)
-        elif not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == shape and out.stride(-1) == 1
-                  and (unit == 1 or out.stride(-2) >= g.Ny)):
-            raise _lib.SwmhdError(f"{what}: out must be a float64 CUDA tensor of shape {shape} with unit stride in its last axis")
+    for out, tail, row_stride in ((shell_out, (len(names), NS), 0), (plane_out, (len(names), nkx, g.Ny), g.Ny)):
+        if out is not None:      # (True: allocate)
+            out = out_tensor(None if out is True else out, lead_shape(model) + tail, (torch.float64,), dev, what, "its last axis",
+                             row_stride=row_stride)
         outs.append(out)
     eo, po = outs
-    ws = _workspace(model, max(len(bits) for bits in runs), dev, wx, wy)
+    # (the workspace: what the C function states for the largest run asked for so far)
+    need = model._L.swmhd_spectra2d_workspace(g.Nx, g.Ny, max(len(bits) for bits in runs), getattr(model, "members", None) or 1, wx, wy)
+    ws = cached_workspace(model, "_spectra2d_ws", need, dev)
     flags = model._rwrap                  # as enqueue_frame: the periodic images where the step leaves the halos stale
     sfx = model.sfx
     k = 0
@@ -166,10 +139,10 @@ def enqueue_power_spectra_2d(model, names=DEFAULT_NAMES, out=None):
 
 
 def isotropic_shape(model, names):
-    return _lead(model) + (len(names), shells(model.grid))
+    return lead_shape(model) + (len(names), shells(model.grid))
 
 
-class IsotropicSpectrumTimeSeries:
+class IsotropicSpectrumTimeSeries(DeviceTimeSeries):
     """A writer of isotropic spectra for run(): `capacity` samples of `names` in one float64 device tensor, plus the host lists `times`
     and `iterations`.  spectra: (capacity, len(names), NS); for an ensemble (capacity, members, len(names), NS).  Names: u v h A s B_x
     B_y (include/swmhd_spectra2d.h).
@@ -177,43 +150,23 @@ class IsotropicSpectrumTimeSeries:
     The tensor is allocated when the first sample is written.  `write` only enqueues; `numpy` and `save` are the calls that
     synchronise."""
 
+    _data, _unit = "spectra", "samples"
+    spectra = DeviceTimeSeries.tensor
+
     def __init__(self, model, names=DEFAULT_NAMES, schedule=TimeInterval(0.1), capacity=None):
-        self.model, self.names, self.schedule = model, tuple(names), schedule
-        _check(model, self.names, "IsotropicSpectrumTimeSeries")
-        if capacity is None or int(capacity) < 1:
-            raise _lib.SwmhdError("IsotropicSpectrumTimeSeries: capacity (samples) must be given: the spectra stay on the device")
-        self.capacity = int(capacity)
-        self.times, self.iterations = [], []
-        self._spectra = None
+        super().__init__(model, names, schedule, capacity)
 
-    def __len__(self):
-        return len(self.times)
+    def _check_names(self):
+        _check(self.model, self.names, "IsotropicSpectrumTimeSeries")
 
-    @property
-    def spectra(self):
-        """The device tensor of all `capacity` slots; the first len(self) hold samples."""
-        if self._spectra is None:
-            m = self.model
-            dev = m._state[0].device if getattr(m, "members", None) is not None else m._raw_fields[0].data.device
-            self._spectra = torch.empty((self.capacity,) + isotropic_shape(m, self.names), dtype=torch.float64, device=dev)
-        return self._spectra
+    def _sample_shape(self):
+        return isotropic_shape(self.model, self.names)
 
-    def write(self, time=None):
-        """Enqueue the spectra of the model's current state into the next slot."""
-        k = len(self.times)
-        if k >= self.capacity:
-            raise _lib.SwmhdError(f"IsotropicSpectrumTimeSeries: all {self.capacity} slots are written")
-        enqueue_isotropic_spectra(self.model, self.names, out=self.spectra[k])
-        self.times.append(self.model.clock_time if time is None else time)
-        self.iterations.append(self.model.iteration)
-
-    def numpy(self):
-        """The samples written so far as a host array (synchronises)."""
-        return self.spectra[:len(self.times)].cpu().numpy()
+    def _enqueue(self, out):
+        enqueue_isotropic_spectra(self.model, self.names, out=out)
 
     def save(self, path):
         """One .npz: spectra, names, times, iterations, k = s dk of the shells and counts, their mode counts (synchronises)."""
         import numpy as np
         k, counts = isotropic_shells(self.model.grid)
-        np.savez(path, spectra=self.numpy(), names=np.array(self.names), times=np.array(self.times, dtype=np.float64),
-                 iterations=np.array(self.iterations, dtype=np.int64), k=k, counts=counts)
+        self._savez(path, k=k, counts=counts)

@@ -5,8 +5,12 @@
 For every translation unit of the Makefile's OBJS the device side alone is compiled in both directories with the command line `make -n`
 prints for that unit (plus --offload-device-only --no-gpu-bundle-output), then `llvm-objdump -d --no-show-raw-insn` and `llvm-readelf --notes` of the two code
 objects are compared.  Lines that carry the object's path or the __hip_cuid_* symbol (a hash of the path) are left out.  Needs no GPU.
+Per unit also `opcodes_equal`: the sequence of instruction mnemonics, label and symbol lines included, operands ignored (a listing
+that differs only in registers or in the order of a commutative operation's sources has it), and `differing_lines`, the count of
+listing lines that differ.
 Exit status 0: all equal."""
 import concurrent.futures
+import difflib
 import json
 import os
 import re
@@ -40,6 +44,18 @@ def device_listing(csrc, unit, cmd, tmp):
     return text
 
 
+def opcodes(listing):
+    """The first word of every line of a disassembly: the mnemonic of an instruction, the whole of a label or symbol line"""
+    return [l if l.rstrip().endswith(":") else l.split()[0] for l in listing if l.strip()]
+
+
+def differing_lines(a, b):
+    if a == b:
+        return 0
+    ops = difflib.SequenceMatcher(None, a, b, autojunk=False).get_opcodes()
+    return sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != "equal")
+
+
 def main(argv):
     js = None
     if "--json" in argv:
@@ -55,7 +71,8 @@ def main(argv):
         jobs = {(d, u): pool.submit(device_listing, d, u, cmds[d][u], t) for d, t in ((other, ta), (mine, tb)) for u in cmds[d]}
         for u in sorted(cmds[mine]):
             a, b = jobs[(other, u)].result(), jobs[(mine, u)].result()
-            report[u] = {"disassembly_lines": len(b[0]), "notes_lines": len(b[1]), "disassembly_equal": a[0] == b[0], "notes_equal": a[1] == b[1]}
+            report[u] = {"disassembly_lines": len(b[0]), "notes_lines": len(b[1]), "disassembly_equal": a[0] == b[0], "notes_equal": a[1] == b[1],
+                         "opcodes_equal": opcodes(a[0]) == opcodes(b[0]), "differing_lines": differing_lines(a[0], b[0])}
             print(u, report[u], flush=True)
     if js:
         with open(js, "w") as fh:
