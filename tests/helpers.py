@@ -65,6 +65,21 @@ def poison_halo(a, Nx, Ny, Hx, Hy, x=True, y=True):
     return a
 
 
+def same_bits(got, want, what):
+    """The bitwise comparison of the frame tests: `want` rounded to the type of `got`, then NaN in the same places and the same integer
+    bits everywhere else, so -0.0 is not 0.0."""
+    with np.errstate(all="ignore"):
+        want = want.astype(got.dtype)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    gn, wn = np.isnan(got), np.isnan(want)
+    it = np.int64 if got.dtype == np.float64 else np.int32
+    ok = np.array_equal(gn, wn) and np.array_equal(got[~gn].view(it), want[~wn].view(it))
+    if not ok:
+        bad = np.argwhere((gn != wn) | (~gn & ~wn & (np.ascontiguousarray(got).view(it) != np.ascontiguousarray(want).view(it))))
+        print(what, "differs at", bad[:8].tolist(), "of", got.shape, "NaN got/want", int(gn.sum()), int(wn.sum()))
+    assert ok, what
+
+
 G, F = 9.81, 1.0   # gravity and Coriolis parameter of the tendency tests
 
 

@@ -17,6 +17,8 @@ import torch
 
 import derived_cases as DC
 import output_cases as OC
+from helpers import same_bits as _same      # bitwise: NaN in the same places, the same bits everywhere else
+from output_cases import images as _images  # the periodic images the WRAP flags read, also for Nx < Hx
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,20 +28,6 @@ FORMS = {"VectorInvariant": 1, "Conservative": 0}
 SENT = -777.25
 DX, DY, FCOR = 0.1, 0.12, 0.7
 WRAP_X, WRAP_Y = 16, 32
-
-
-def _same(got, want, what):
-    """bitwise: NaN in the same places, the same bits everywhere else (the restatement rounded to the frame's type)"""
-    with np.errstate(all="ignore"):
-        want = want.astype(got.dtype)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    gn, wn = np.isnan(got), np.isnan(want)
-    it = np.int64 if got.dtype == np.float64 else np.int32
-    ok = np.array_equal(gn, wn) and np.array_equal(got[~gn].view(it), want[~wn].view(it))
-    if not ok:
-        bad = np.argwhere((gn != wn) | (~gn & ~wn & (got != want)))
-        print(what, "differs at", bad[:8].tolist(), "of", got.shape, "NaN got/want", int(gn.sum()), int(wn.sum()))
-    assert ok, what
 
 
 def _real(x, sfx):
@@ -60,18 +48,6 @@ def _parents(Nx, Ny, Hx, Hy, sfx, seed, wrap=0):
     if not wrap & (WRAP_X | WRAP_Y):
         keep[Hy - 1, Hx + Nx] = keep[Hy + Ny, Hx - 1] = keep[Hy + Ny, Hx + Nx] = False
     return [np.where(keep, a, np.nan).astype(NP[sfx]) for a in q]
-
-
-def _images(parents, Nx, Ny, Hx, Hy, wrap):
-    """What the WRAP flags make of the parents: the halos of the wrapped directions replaced by the periodic images of the interior
-    (output_cases.wrap_parents, which this equals wherever a period covers the halo; here also for Nx < Hx)."""
-    ix = (np.arange(-Hx, Nx + Hx) % Nx) + Hx if wrap & WRAP_X else np.arange(Nx + 2 * Hx)
-    iy = (np.arange(-Hy, Ny + Hy) % Ny) + Hy if wrap & WRAP_Y else np.arange(Ny + 2 * Hy)
-    out = [np.asarray(a, dtype=np.float64)[np.ix_(iy, ix)] for a in parents]
-    if Nx >= Hx and Ny >= Hy:
-        ref = OC.wrap_parents(parents, Nx, Ny, Hx, Hy, bool(wrap & WRAP_X), bool(wrap & WRAP_Y))
-        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(out, ref))
-    return out
 
 
 class Device:

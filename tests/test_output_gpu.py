@@ -36,6 +36,7 @@ def _same(got, want, what):
     want = want.astype(got.dtype)
     print(what, "max ulp distance", _ulps(got, want))
     assert got.shape == want.shape and np.array_equal(got, want), (what, _ulps(got, want))
+    Hh.same_bits(got, want, what)                          # ... and the sign of every zero
 
 
 def _random_parents(Nx, Ny, dtype, seed):
