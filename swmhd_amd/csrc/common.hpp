@@ -278,43 +278,44 @@ template <typename T> hipError_t launch_tracers_ensemble_strict(const EnsTracerA
 template <typename T> hipError_t launch_tracers_ensemble_params_fast(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s);
 template <typename T> hipError_t launch_tracers_ensemble_params_strict(const EnsParTracerArgs<T> &a, int formulation, hipStream_t s);
 
-// ScalarDiffusivity closure (swmhd_diffusion_rk3_*, diffusion.hip): D_k = coef_k laplace(old_k) of up to 3 + MAX_TRACERS fields in ONE
-// launch, added to what the stage kernels have written: nw[k] += a D_k and, where acc[k] != nullptr, acc[k] += w D_k.  Pointers address
-// interior cell (1,1) like TendArgs; wrap as there.  members > 0: an ensemble -- member m of every parent at ptr + m * stride_m, its
-// coefficients in the DEVICE table coef_tab[m * nfields + k] (coef is not read); with params != nullptr its dt is params[3 m + 2] and
-// the kernel forms a_m = dt a (a: gamma) and, with `anchor`, w_m = dt w (w: the anchor's weight), else w_m = w.
-constexpr int DIFFUSION_MAX_FIELDS = 3 + MAX_TRACERS;   // = SWMHD_DIFFUSION_MAX_FIELDS
+// What the per-stage correction launches (strip_device.inc) share: a term D of the state the stage started from, added to what the stage
+// kernels have written with the weights a (new state) and w (stored tendency or anchor).  Pointers address interior cell (1,1) like
+// TendArgs; wrap as there.  members > 0: an ensemble -- member m of every parent at ptr + m * stride_m; with params != nullptr its dt is
+// params[3 m + 2] and the kernel forms a_m = dt a (a: gamma) and, with `anchor`, w_m = dt w (w: the anchor's weight), else w_m = w.
 template <typename T>
-struct DiffusionArgs {
-    const T *old[DIFFUSION_MAX_FIELDS];
-    T *nw[DIFFUSION_MAX_FIELDS], *acc[DIFFUSION_MAX_FIELDS];
-    T coef[DIFFUSION_MAX_FIELDS];
-    int nfields, Nx, Ny, j0, j1, wrap;
-    long sy;
-    T dx, dy, a, w;
-    int members, anchor;
-    long stride_m;
-    const T *coef_tab, *params;
-};
-template <typename T> hipError_t launch_diffusion_fast(const DiffusionArgs<T> &a, hipStream_t s);
-template <typename T> hipError_t launch_diffusion_strict(const DiffusionArgs<T> &a, hipStream_t s);
-
-// BetaPlane Coriolis (swmhd_coriolis_rk3_*, coriolis.hip): D1 = fc[j] vbar, D2 = -(ff[j] ubar) of the two momentum-like fields q1, q2 in
-// ONE launch, added to what the stage kernels (run with f = 0) have written: n1 += a D1, n2 += a D2 and, where a1 != nullptr (then a2
-// too), a1 += w D1, a2 += w D2.  Pointers address interior cell (1,1) like TendArgs; wrap as there.  frow: the DEVICE table fc[0..Ny)
-// then ff[0..Ny).  members > 0: an ensemble -- member m of every parent at ptr + m * stride_m, its table at frow + m * 2 Ny; params,
-// anchor as in DiffusionArgs.
-template <typename T>
-struct CoriolisArgs {
-    const T *q1, *q2;
-    T *n1, *n2, *a1, *a2;
-    const T *frow;
+struct StripArgs {
     int Nx, Ny, j0, j1, wrap;
     long sy;
     T a, w;
     int members, anchor;
     long stride_m;
     const T *params;
+};
+
+// ScalarDiffusivity closure (swmhd_diffusion_rk3_*, diffusion.hip): D_k = coef_k laplace(old_k) of up to 3 + MAX_TRACERS fields in ONE
+// launch: nw[k] += a D_k and, where acc[k] != nullptr, acc[k] += w D_k.  An ensemble member's coefficients stand in the DEVICE table
+// coef_tab[m * nfields + k] (coef is not read).
+constexpr int DIFFUSION_MAX_FIELDS = 3 + MAX_TRACERS;   // = SWMHD_DIFFUSION_MAX_FIELDS
+template <typename T>
+struct DiffusionArgs : StripArgs<T> {
+    const T *old[DIFFUSION_MAX_FIELDS];
+    T *nw[DIFFUSION_MAX_FIELDS], *acc[DIFFUSION_MAX_FIELDS];
+    T coef[DIFFUSION_MAX_FIELDS];
+    int nfields;
+    T dx, dy;
+    const T *coef_tab;
+};
+template <typename T> hipError_t launch_diffusion_fast(const DiffusionArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_diffusion_strict(const DiffusionArgs<T> &a, hipStream_t s);
+
+// BetaPlane Coriolis (swmhd_coriolis_rk3_*, coriolis.hip): D1 = fc[j] vbar, D2 = -(ff[j] ubar) of the two momentum-like fields q1, q2 in
+// ONE launch, added to what the stage kernels (run with f = 0) have written: n1 += a D1, n2 += a D2 and, where a1 != nullptr (then a2
+// too), a1 += w D1, a2 += w D2.  frow: the DEVICE table fc[0..Ny) then ff[0..Ny); an ensemble member's table at frow + m * 2 Ny.
+template <typename T>
+struct CoriolisArgs : StripArgs<T> {
+    const T *q1, *q2;
+    T *n1, *n2, *a1, *a2;
+    const T *frow;
 };
 template <typename T> hipError_t launch_coriolis_fast(const CoriolisArgs<T> &a, hipStream_t s);
 template <typename T> hipError_t launch_coriolis_strict(const CoriolisArgs<T> &a, hipStream_t s);

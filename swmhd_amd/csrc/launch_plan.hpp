@@ -1,5 +1,5 @@
-// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the Coriolis correction, the zonal-mean
-// kernel, the derived-frame kernel and the zonal-spectrum kernels: what a call will enqueue, decided as data before anything is launched.
+// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the strip-march
+// corrections (Coriolis, diffusion), the zonal-mean kernel, the derived-frame kernel and the zonal-spectrum kernels: what a call will enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
 #pragma once
@@ -432,33 +432,47 @@ inline TracerTiles tracer_tiles(int Nx, int rows, int K, int members) {
     return t;
 }
 
-// ---- the strips of one Coriolis correction (coriolis.hip) ----------------------------------------------------------------------------
-// A wave owns a strip of CORIOLIS_WAVE lanes x vec columns and marches down CORIOLIS_WAVE_ROWS rows of it; the CORIOLIS_WAVES waves of
-// a workgroup are consecutive row segments of one strip.  vec = 16 bytes of elements where `phase` >= 0: the 16-byte phase (in elements)
-// that the interior pointers of all six parents share and the pitches keep -- then the vector groups start `lead` = phase columns left
-// of x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  phase < 0: one element per lane.
-// blockIdx.x = (m nsb + sb) nstrips + strip.
-constexpr int CORIOLIS_WAVE = 64, CORIOLIS_WAVES = 4, CORIOLIS_WAVE_ROWS = 16;   // CORIOLIS_WAVES CORIOLIS_WAVE_ROWS = SWMHD_CORIOLIS_TILE_ROWS
-struct CoriolisPlan {
+// ---- the strips of one per-stage correction launch (strip_device.inc: coriolis.hip, diffusion.hip) -----------------------------------
+// A wave owns a strip of STRIP_WAVE lanes x vec columns and marches down STRIP_WAVE_ROWS rows of it; the STRIP_WAVES waves of a
+// workgroup are consecutive row segments of one strip.  vec = 16 bytes of elements where `phase` >= 0: the 16-byte phase (in elements)
+// that the interior pointers of all parents share and the pitches keep (common_phase) -- then the vector groups start `lead` = phase
+// columns left of x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  phase < 0: one element per lane.
+// blockIdx.x = (l nsb + sb) nstrips + strip, l < launches: the member (Coriolis), member x field (diffusion).
+constexpr int STRIP_WAVE = 64, STRIP_WAVES = 4, STRIP_WAVE_ROWS = 16;   // STRIP_WAVES STRIP_WAVE_ROWS = SWMHD_CORIOLIS_ / SWMHD_DIFFUSION_TILE_ROWS
+struct StripPlan {
     int vec, lead;
-    int nstrips, nsb; // strips of 64 vec columns x blocks of CORIOLIS_WAVES row segments, of one member
-    long blocks;      // nstrips * nsb * members
-    bool none;        // nothing to compute: no rows or no members
+    int nstrips, nsb; // strips of 64 vec columns x blocks of STRIP_WAVES row segments, of one of the launches
+    long blocks;      // nstrips * nsb * launches (0 where too_many)
+    bool none;        // nothing to compute: no columns, no rows or no launches
     bool too_many;    // 2^31 blocks or more: beyond the grid of one launch
 };
-// members: 1 for a single grid
-inline CoriolisPlan coriolis_plan(int Nx, int rows, int elem_size, int phase, int members) {
-    CoriolisPlan p{};
-    p.none = Nx <= 0 || rows <= 0 || members <= 0;
+// launches: 1 for one field of a single grid
+inline StripPlan strip_plan(int Nx, int rows, int elem_size, int phase, int launches) {
+    StripPlan p{};
+    p.none = Nx <= 0 || rows <= 0 || launches <= 0;
     if (p.none) return p;
     p.vec = phase >= 0 ? 16 / elem_size : 1;
     p.lead = phase >= 0 ? phase : 0;
-    const long cols = (long)CORIOLIS_WAVE * p.vec, tile_rows = (long)CORIOLIS_WAVES * CORIOLIS_WAVE_ROWS;
+    const long cols = (long)STRIP_WAVE * p.vec, tile_rows = (long)STRIP_WAVES * STRIP_WAVE_ROWS;
     const long nstrips = ((long)Nx + p.lead + cols - 1) / cols, nsb = ((long)rows + tile_rows - 1) / tile_rows;
     p.nstrips = (int)nstrips; p.nsb = (int)nsb;
-    p.blocks = nstrips * nsb * members;
-    p.too_many = p.blocks >= (1L << 31);
+    p.too_many = nstrips * nsb >= (1L << 31) || nstrips * nsb * launches >= (1L << 31);   // (in this order: the product cannot overflow)
+    if (!p.too_many) p.blocks = nstrips * nsb * launches;
     return p;
+}
+// The 16-byte phase (in elements) that the n pointers of ptrs share (null entries are skipped), or -1: where they differ, or where the
+// row pitch sy or the member pitch stride_m (0: one grid) does not keep it.
+inline int common_phase(int elem_size, long sy, long stride_m, const void *const *ptrs, int n) {
+    const int V = 16 / elem_size;
+    if (sy % V != 0 || stride_m % V != 0) return -1;
+    int ph = -1;
+    for (int k = 0; k < n; ++k) {
+        if (!ptrs[k]) continue;
+        const int q = (int)(((unsigned long)ptrs[k] / (unsigned long)elem_size) % (unsigned long)V);
+        if (ph >= 0 && q != ph) return -1;
+        ph = q;
+    }
+    return ph;
 }
 
 // ---- the rows of one zonal-mean call (zonal.hip) -------------------------------------------------------------------------------------

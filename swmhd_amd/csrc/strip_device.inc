@@ -1,0 +1,147 @@
+// What the per-stage correction launches (diffusion.hip, coriolis.hip) share, stated once; included inside their anonymous namespace,
+// after common.hpp and launch_plan.hpp.  A wave owns a strip of STRIP_WAVE lanes x VEC columns and marches down STRIP_WAVE_ROWS rows of
+// it, VEC = 16 bytes of elements per lane where every pointer of the call has the same 16-byte phase and the pitches keep it (else
+// VEC = 1): launch_plan.hpp strip_plan.  No LDS, no barrier: the STRIP_WAVES waves of a workgroup are consecutive row segments of one
+// strip.  Here: the strict / fast switch and the launcher's name, the vector access, the strip of one lane (Strip), the decoding of
+// blockIdx.x (strip_block), the per-member scalars (strip_scalars), and the host's plan and pick of an instantiation.  The carried
+// rows and the arithmetic are each kernel's own.
+#ifndef SWMHD_STRIP_STRICT
+#error "compile with -DSWMHD_STRIP_STRICT=0 or 1 (Makefile)"
+#endif
+constexpr bool STRICT = (SWMHD_STRIP_STRICT != 0);
+#define LAUNCH_NAME_(base, sfx) base##sfx
+#define LAUNCH_NAME(base, sfx) LAUNCH_NAME_(base, sfx)
+#if SWMHD_STRIP_STRICT
+#define LAUNCH_SFX strict
+#else
+#define LAUNCH_SFX fast
+#endif
+
+template <typename T, int VEC>
+__device__ __forceinline__ void vec_load(const T *p, T (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = p[0];
+    } else {
+        using V = T __attribute__((ext_vector_type(VEC)));
+        const V t = *reinterpret_cast<const V *>(p);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = t[e];
+    }
+}
+template <typename T, int VEC>
+__device__ __forceinline__ void vec_store(T *p, const T (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        p[0] = v[0];
+    } else {
+        using V = T __attribute__((ext_vector_type(VEC)));
+        V t;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) t[e] = v[e];
+        *reinterpret_cast<V *>(p) = t;
+    }
+}
+
+// The VEC columns xv .. xv + VEC - 1 of one lane and their two neighbours.  lead: columns by which the vector groups start left of
+// x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  A column as it is read: -1 and Nx are the halo cells or,
+// wrapped, their periodic images; nothing further out is read.  Lanes outside [0, Nx) load T(0) and store nothing.
+template <typename T, int VEC>
+struct Strip {
+    int Nx, Ny, lane, xv, colw, cole;
+    long sy;
+    bool wrapy, full, okw, oke;
+    int col[VEC];
+    bool ok[VEC], inside[VEC];
+
+    __device__ __forceinline__ Strip(int Nx_, int Ny_, long sy_, int wrap, int strip, int lane_, int lead)
+        : Nx(Nx_), Ny(Ny_), lane(lane_), xv((strip * STRIP_WAVE + lane_) * VEC - lead), sy(sy_), wrapy(wrap & 2) {
+        const bool wrapx = wrap & 1;
+        full = xv >= 0 && xv + VEC <= Nx;
+        auto column = [&](int x, bool &valid) -> int {
+            valid = x >= -1 && x <= Nx;
+            if (wrapx) x = x < 0 ? Nx - 1 : (x >= Nx ? 0 : x);
+            return valid ? x : 0;
+        };
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            col[e] = column(xv + e, ok[e]);
+            inside[e] = xv + e >= 0 && xv + e < Nx;
+        }
+        colw = column(xv - 1, okw);
+        cole = column(xv + VEC, oke);
+    }
+    __device__ __forceinline__ long row_of(int y) const {   // y in [-1, Ny]
+        if (wrapy) y = y < 0 ? Ny - 1 : (y >= Ny ? 0 : y);
+        return (long)y * sy;
+    }
+    __device__ __forceinline__ void load_in(const T *p, T (&v)[VEC]) const {   // p: a row that is read with its halo
+        if (full) {
+            vec_load<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = ok[e] ? p[col[e]] : T(0);
+        }
+    }
+    // the neighbour beyond a lane's group: from the next lane, at the ends of the wave from memory
+    __device__ __forceinline__ T east_of(const T *p, const T (&v)[VEC]) const {
+        T x = __shfl_down(v[0], 1);
+        if (lane == STRIP_WAVE - 1) x = oke ? p[cole] : T(0);
+        return x;
+    }
+    __device__ __forceinline__ T west_of(const T *p, const T (&v)[VEC]) const {
+        T x = __shfl_up(v[VEC - 1], 1);
+        if (lane == 0) x = okw ? p[colw] : T(0);
+        return x;
+    }
+    __device__ __forceinline__ void load_out(const T *p, T (&v)[VEC]) const {   // p: a row that is updated
+        if (full) {
+            vec_load<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
+        }
+    }
+    __device__ __forceinline__ void store_out(T *p, const T (&v)[VEC]) const {
+        if (full) {
+            vec_store<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                if (inside[e]) p[xv + e] = v[e];
+        }
+    }
+};
+
+// blockIdx.x = (outer nsb + sb) nstrips + strip (StripPlan); the wave's rows are [r0, r1), empty (uniformly) past j1
+struct StripBlock {
+    unsigned outer;
+    int strip, r0, r1;
+};
+__device__ __forceinline__ StripBlock strip_block(int nstrips, int nsb, int j0, int j1) {
+    const unsigned ntiles = (unsigned)(nstrips * nsb);
+    const unsigned L = xcd_remap(blockIdx.x, gridDim.x), outer = L / ntiles, tile = L - outer * ntiles;
+    const int strip = (int)(tile % (unsigned)nstrips), sb = (int)(tile / (unsigned)nstrips);
+    const int r0 = j0 + (sb * STRIP_WAVES + (int)threadIdx.y) * STRIP_WAVE_ROWS;
+    return StripBlock{outer, strip, r0, min(r0 + STRIP_WAVE_ROWS, j1)};
+}
+
+// member m of an ensemble with a (g, f, dt) table: the products as the host forms them for one grid
+template <typename T>
+__device__ __forceinline__ void strip_scalars(const StripArgs<T> &a, unsigned m, T &av, T &wv) {
+    if (a.params) {
+        const T dt = a.params[3 * (long)m + 2];
+        av = dt * a.a;
+        if (a.anchor) wv = dt * a.w;
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+// the plan of a call over the n pointers of ptrs (null entries skipped), per_member launches for each member
+template <typename T>
+StripPlan strip_plan_of(const StripArgs<T> &a, const void *const *ptrs, int n, int per_member) {
+    const int phase = common_phase((int)sizeof(T), a.sy, a.members > 0 ? a.stride_m : 0, ptrs, n);
+    return strip_plan(a.Nx, a.j1 - a.j0, (int)sizeof(T), phase, (a.members > 0 ? a.members : 1) * per_member);
+}
+// the instantiation of kernel template k<T, VEC, ENS> that a plan and a call ask for
+#define STRIP_KERNEL(k, T, plan, args)                                                                               \
+    ((args).members > 0 ? ((plan).vec > 1 ? k<T, 16 / (int)sizeof(T), true> : k<T, 1, true>)                         \
+                        : ((plan).vec > 1 ? k<T, 16 / (int)sizeof(T), false> : k<T, 1, false>))

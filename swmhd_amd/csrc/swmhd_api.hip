@@ -224,6 +224,14 @@ int tracers_common(const T *const *q, const T *const *c, T *const *cnew, T *cons
     return hiprc(fl.strict ? launch_tracers_strict<T>(a, form, s) : launch_tracers_fast<T>(a, form, s));
 }
 
+// what the two per-stage correction calls pass on alike (StripArgs, common.hpp)
+template <typename T>
+void set_strip(StripArgs<T> &s, const Grid &g, const Rows &r, const Flags &fl, T a, T w, const Ens *ens) {
+    s.Nx = g.Nx; s.Ny = g.Ny; s.j0 = r.j0; s.j1 = r.j1; s.wrap = fl.wrap; s.sy = (long)g.sy; s.a = a; s.w = w;
+    s.members = ens ? ens->members : 0; s.anchor = fl.anchor; s.stride_m = ens ? (long)ens->stride_m : 0;
+    s.params = ens ? static_cast<const T *>(ens->params) : nullptr;
+}
+
 // swmhd_diffusion_rk3: nw[k] += a coef[k] laplace(old[k]), acc[k] += w coef[k] laplace(old[k]) of up to SWMHD_DIFFUSION_MAX_FIELDS fields in
 // one launch (diffusion.hip).  Every check precedes the first HIP call.  With `ens` (swmhd_ensemble_diffusion_rk3): `coef` is the DEVICE
 // table of members x nfields values and is not looked at; ens->params (optional) brings every member's dt.  The ensemble's own
@@ -268,10 +276,8 @@ int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *
     }
     if (n == 0) return SWMHD_OK;
     for (int k = n; k < DIFFUSION_MAX_FIELDS; ++k) { d.old[k] = nullptr; d.nw[k] = nullptr; d.acc[k] = nullptr; d.coef[k] = T(0); }
-    d.nfields = n; d.Nx = g.Nx; d.Ny = g.Ny; d.j0 = r.j0; d.j1 = r.j1; d.wrap = fl.wrap; d.sy = (long)g.sy;
-    d.dx = T(g.dx); d.dy = T(g.dy); d.a = a; d.w = w;
-    d.members = ens ? ens->members : 0; d.anchor = fl.anchor; d.stride_m = ens ? (long)ens->stride_m : 0;
-    d.coef_tab = ens ? coef : nullptr; d.params = ens ? static_cast<const T *>(ens->params) : nullptr;
+    set_strip(d, g, r, fl, a, w, ens);
+    d.nfields = n; d.dx = T(g.dx); d.dy = T(g.dy); d.coef_tab = ens ? coef : nullptr;
     hipStream_t s = (hipStream_t)stream;
     return hiprc(fl.strict ? launch_diffusion_strict<T>(d, s) : launch_diffusion_fast<T>(d, s));
 }
@@ -307,9 +313,7 @@ int coriolis_common(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const 
     c.q1 = g.interior(q1); c.q2 = g.interior(q2); c.n1 = g.interior(n1); c.n2 = g.interior(n2);
     c.a1 = a1 ? g.interior(a1) : nullptr; c.a2 = a2 ? g.interior(a2) : nullptr;
     c.frow = frow;
-    c.Nx = g.Nx; c.Ny = g.Ny; c.j0 = r.j0; c.j1 = r.j1; c.wrap = fl.wrap; c.sy = (long)g.sy; c.a = a; c.w = w;
-    c.members = ens ? ens->members : 0; c.anchor = fl.anchor; c.stride_m = ens ? (long)ens->stride_m : 0;
-    c.params = ens ? static_cast<const T *>(ens->params) : nullptr;
+    set_strip(c, g, r, fl, a, w, ens);
     hipStream_t s = (hipStream_t)stream;
     return hiprc(fl.strict ? launch_coriolis_strict<T>(c, s) : launch_coriolis_fast<T>(c, s));
 }

@@ -20,9 +20,9 @@ from .closure import check_closure
 from .coriolis import check_coriolis, row_table
 from .fields import _SFX, _stream_ptr
 from .grid import Center, Face
-from .model import RK3_ANCHOR_WEIGHT, ShallowWaterModel, rk3_operands, rk3_stage, tracer_names
-from .shared import (VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups, finish_stage,
-                     formulation_codes, gradient_values)
+from .model import ShallowWaterModel, rk3_operands, rk3_stage, tracer_names
+from .shared import (VectorInvariantFormulation, check_boundary_conditions, correction_operand, diagnostics_dict, fill_groups,
+                     finish_stage, formulation_codes, gradient_values)
 
 LOCS = ((Face, Center), (Center, Face), (Center, Center), (Center, Center))
 
@@ -299,14 +299,11 @@ class ShallowWaterEnsemble:
         """The Coriolis launch of RK3 stage `stage` for every member (swmhd_ensemble_coriolis_rk3_*; with dt None every member's dt comes
         from the table): ShallowWaterModel._coriolis_stage with the rows of member m in block m of the device table."""
         g = self.grid
-        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        gamma = rk3_stage(stage, self._anchor)[0]
         q, new = self._state, self._alt
         par = dt is None
-        acc, w, flag = (None, None), 0.0, 0
-        if anchor and stage == 0:     # with the table the kernel forms dt_m / 4 (SWMHD_RK3_ANCHOR: w is a weight of dt)
-            acc, w, flag = (self.Gn[0].data_ptr(), self.Gn[1].data_ptr()), (RK3_ANCHOR_WEIGHT if par else dt * RK3_ANCHOR_WEIGHT), _lib.RK3_ANCHOR
-        elif not anchor and store:
-            acc, w = (self.Gn[0].data_ptr(), self.Gn[1].data_ptr()), 1.0
+        has, w, flag = correction_operand(stage, self._anchor, dt)
+        acc = (self.Gn[0].data_ptr(), self.Gn[1].data_ptr()) if has else (None, None)
         f = getattr(self._L, f"swmhd_ensemble_coriolis_rk3_{self.sfx}")
         rc = f(q[0].data_ptr(), q[1].data_ptr(), new[0].data_ptr(), new[1].data_ptr(), acc[0], acc[1], self.coriolis_rows.data_ptr(),
                self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride(1), self.parameters.data_ptr() if par else None,
@@ -320,17 +317,14 @@ class ShallowWaterEnsemble:
         """The closure's launch of RK3 stage `stage` for every member (swmhd_ensemble_diffusion_rk3_*; with dt None every member's dt
         comes from the table): ShallowWaterModel._diffusion_stage with the coefficients of member m in row m of the device table."""
         g = self.grid
-        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        gamma = rk3_stage(stage, self._anchor)[0]
         names = self._diffusion_names()
         cur = {**dict(zip(self.names, self._state)), **self._tr}
         new = {**dict(zip(self.names, self._alt)), **self._tr_alt}
         Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
         par = dt is None
-        acc, w, flag = None, 0.0, 0
-        if anchor and stage == 0:     # with the table the kernel forms dt_m / 4 (SWMHD_RK3_ANCHOR: w is a weight of dt)
-            acc, w, flag = self._ptrs([Gn[n] for n in names]), (RK3_ANCHOR_WEIGHT if par else dt * RK3_ANCHOR_WEIGHT), _lib.RK3_ANCHOR
-        elif not anchor and store:
-            acc, w = self._ptrs([Gn[n] for n in names]), 1.0
+        has, w, flag = correction_operand(stage, self._anchor, dt)
+        acc = self._ptrs([Gn[n] for n in names]) if has else None
         f = getattr(self._L, f"swmhd_ensemble_diffusion_rk3_{self.sfx}")
         rc = f(self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc, self.diffusion_coefficients.data_ptr(),
                len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy,

@@ -19,14 +19,9 @@ from .coriolis import check_coriolis, row_table
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
 from .grid import Center, Face
-from .shared import (ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups,
-                     finish_stage, formulation_codes, gradient_values)
+from .shared import (RK3_GAMMA, RK3_ZETA, ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions,
+                     correction_operand, diagnostics_dict, fill_groups, finish_stage, formulation_codes, gradient_values, rk3_stage)
 
-RK3_GAMMA = (8.0 / 15.0, 5.0 / 12.0, 3.0 / 4.0)
-RK3_ZETA = (0.0, -17.0 / 60.0, -5.0 / 12.0)
-
-
-RK3_ANCHOR_WEIGHT = 0.25    # gamma1 + zeta2 = 8/15 - 17/60
 # names a passive tracer may not take: the prognostic fields of either formulation and the derived output fields
 RESERVED_NAMES = ("u", "v", "uh", "vh", "h", "A", "s", "B_x", "B_y")
 
@@ -47,16 +42,6 @@ def tracer_names(tracers):
     if len(names) > _lib.MAX_TRACERS:
         raise _lib.SwmhdError(f"tracers: {len(names)} names, at most {_lib.MAX_TRACERS} (SWMHD_MAX_TRACERS)")
     return names
-
-
-def rk3_stage(stage, anchor):
-    """(gamma, zeta, store_G, anchor) of RK3 stage 0, 1 or 2 -- the schedule of the C step drivers (common.hpp Rk3Buffers).
-    anchor (fast builds, periodic grids): gamma1 + zeta2 = 1/4 and zeta3 = -gamma2 make the step exactly U1 = U0 + dt gamma1 G0,
-    W = U0 + (dt/4) G0, U2 = W + dt gamma2 G1, U3 = W + dt gamma3 G2 -- one stored operand W, 96 B/cell in every stage
-    (swmhd.h SWMHD_RK3_ANCHOR; zeta is the weight of W in the first stage).  Otherwise the classic G- form."""
-    if anchor:
-        return RK3_GAMMA[stage], RK3_ANCHOR_WEIGHT if stage == 0 else 0.0, 0, True
-    return RK3_GAMMA[stage], RK3_ZETA[stage], 1 if stage < 2 else 0, False
 
 
 def rk3_operands(stage, anchor, Gn, Gm):
@@ -413,17 +398,14 @@ class ShallowWaterModel:
         """The Coriolis launch of RK3 stage `stage` under a parameter that varies with y (swmhd_coriolis_rk3_*): D = f(y_j) (vbar, -ubar)
         on the state the stage started from, added with dt gamma to the two new momentum-like fields and, where the stage stores an
         operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
-        the anchor form) -- as _diffusion_stage chooses them.  Order (finish_stage): after _stage_fused and _tracer_stage, BEFORE
+        the anchor form) -- shared.correction_operand.  Order (finish_stage): after _stage_fused and _tracer_stage, BEFORE
         _diffusion_stage and the swaps; with a closure as well the new u is ((stage + a D_coriolis) + a D_closure), and that order
         decides the last bits.  Bounded directions pass no WRAP flag and read the halos the previous fill left current."""
         g = self.grid
-        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        gamma = rk3_stage(stage, self._anchor)[0]
         q, new = self._raw_fields, [self._alt[n] for n in self.names]
-        acc, w = (None, None), 0.0
-        if anchor and stage == 0:
-            acc, w = (self.Gn[0].ptr, self.Gn[1].ptr), dt * RK3_ANCHOR_WEIGHT
-        elif not anchor and store:
-            acc, w = (self.Gn[0].ptr, self.Gn[1].ptr), 1.0
+        has, w, _ = correction_operand(stage, self._anchor, dt)
+        acc = (self.Gn[0].ptr, self.Gn[1].ptr) if has else (None, None)
         f = getattr(self._L, f"swmhd_coriolis_rk3_{self.sfx}")
         rc = f(q[0].ptr, q[1].ptr, new[0].ptr, new[1].ptr, acc[0], acc[1], self.coriolis_rows.data_ptr(), g.Nx, g.Ny, g.Hx, g.Hy,
                q[0].stride_y, dt * gamma, w, 0, g.Ny, (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap, _stream_ptr())
@@ -436,16 +418,13 @@ class ShallowWaterModel:
         the anchor form).  After _stage_fused and _tracer_stage and BEFORE the swaps (finish_stage)."""
         g = self.grid
         P = _lib.ptr_array
-        gamma, _, store, anchor = rk3_stage(stage, self._anchor)
+        gamma = rk3_stage(stage, self._anchor)[0]
         names = [n for n in self.names + self.tracer_names if n in self._diffusion]
         cur = {**self._state, **self._tr}
         new = {**self._alt, **self._tr_alt}
         Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
-        acc, w = None, 0.0
-        if anchor and stage == 0:
-            acc, w = P([Gn[n].ptr for n in names]), dt * RK3_ANCHOR_WEIGHT
-        elif not anchor and store:
-            acc, w = P([Gn[n].ptr for n in names]), 1.0
+        has, w, _ = correction_operand(stage, self._anchor, dt)
+        acc = P([Gn[n].ptr for n in names]) if has else None
         ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
         coef = (ft * len(names))(*[self._diffusion[n] for n in names])
         f = getattr(self._L, f"swmhd_diffusion_rk3_{self.sfx}")

@@ -1,9 +1,23 @@
 """Helpers ShallowWaterModel and the ensembles share on the host: formulation codes, boundary-condition checks, gradient rows, the
-diagnostics dict, and the tail of a fused RK3 stage (tracers and buffer swaps).  Nothing here touches a device itself."""
+diagnostics dict, the RK3 schedule, and the tail of a fused RK3 stage (tracers, corrections and buffer swaps).  Nothing here touches a
+device itself."""
 from . import _lib
 from .grid import FieldBoundaryConditions
 
 VectorInvariantFormulation, ConservativeFormulation = "VectorInvariant", "Conservative"
+RK3_GAMMA = (8.0 / 15.0, 5.0 / 12.0, 3.0 / 4.0)
+RK3_ZETA = (0.0, -17.0 / 60.0, -5.0 / 12.0)
+RK3_ANCHOR_WEIGHT = 0.25    # gamma1 + zeta2 = 8/15 - 17/60
+
+
+def rk3_stage(stage, anchor):
+    """(gamma, zeta, store_G, anchor) of RK3 stage 0, 1 or 2 -- the schedule of the C step drivers (common.hpp Rk3Buffers).
+    anchor (fast builds, periodic grids): gamma1 + zeta2 = 1/4 and zeta3 = -gamma2 make the step exactly U1 = U0 + dt gamma1 G0,
+    W = U0 + (dt/4) G0, U2 = W + dt gamma2 G1, U3 = W + dt gamma3 G2 -- one stored operand W, 96 B/cell in every stage
+    (swmhd.h SWMHD_RK3_ANCHOR; zeta is the weight of W in the first stage).  Otherwise the classic G- form."""
+    if anchor:
+        return RK3_GAMMA[stage], RK3_ANCHOR_WEIGHT if stage == 0 else 0.0, 0, True
+    return RK3_GAMMA[stage], RK3_ZETA[stage], 1 if stage < 2 else 0, False
 
 
 def formulation_codes(formulation, lorentz_forcing):
@@ -37,6 +51,20 @@ def diagnostics_dict(v):
     """The 7 values of swmhd_diagnostics_* (KE, ME, PE, max|u|, max|v|, max|A|, min h) by name, with their total energy."""
     return dict(kinetic_energy=v[0], magnetic_energy=v[1], potential_energy=v[2], total_energy=v[0] + v[1] + v[2],
                 max_abs_u=v[3], max_abs_v=v[4], max_abs_A=v[5], min_h=v[6])
+
+
+def correction_operand(stage, anchor, dt):
+    """(has_operand, w, flag) of a per-stage correction launch (o._coriolis_stage, o._diffusion_stage) of RK3 stage `stage`: whether the
+    stage stores an operand for later stages that the correction must reach too, with which weight, and the flag that says what the
+    weight means.  Classic form: the tendency Gn, weight 1, where the stage stores it.  Anchor form: the anchor W in Gn at stage 0,
+    weight dt / 4 -- with dt None (an ensemble's table) the weight 1/4 of dt, and the kernel forms dt_m / 4 (SWMHD_RK3_ANCHOR, which
+    only the ensemble calls take)."""
+    store = rk3_stage(stage, anchor)[2]
+    if anchor and stage == 0:
+        return True, RK3_ANCHOR_WEIGHT if dt is None else dt * RK3_ANCHOR_WEIGHT, _lib.RK3_ANCHOR
+    if not anchor and store:
+        return True, 1.0, 0
+    return False, 0.0, 0
 
 
 def finish_stage(o, dt, stage, fused=True):

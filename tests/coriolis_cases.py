@@ -23,21 +23,7 @@ SENTINEL = T.SENTINEL
 pad1, correct = DC.pad1, DC.correct
 
 # ---- the stage matrix -----------------------------------------------------------------------------------------------------------------
-TILE_ROWS = 64                      # SWMHD_CORIOLIS_TILE_ROWS: four waves of 16 rows
-
-
-def wave_columns(itemsize, aligned):
-    """Columns of one wave of the kernel: 16 bytes per lane where all parents have the same 16-byte phase and the pitch keeps it."""
-    return 64 * (16 // itemsize) if aligned else 64
-
-
-def stage_shapes(itemsize, aligned):
-    W = wave_columns(itemsize, aligned)
-    return [(1, 1), (2, 3), (3, 3), (7, 9), (65, 17), (129, 9), (W - 1, TILE_ROWS - 1), (W, TILE_ROWS), (W + 1, TILE_ROWS + 1)]
-
-
-def row_ranges(Ny):
-    return [(0, Ny), (1, max(Ny - 1, 1)), (min(2, Ny), min(2, Ny))]      # all rows, the inner rows, an empty range
+from strip_cases import TILE_ROWS, row_ranges, stage_shapes, wave_columns      # noqa: F401  (shared with the other strip-march launch)
 
 
 def row_values(Ny, dtype, seed=0):

@@ -28,7 +28,7 @@ def units(csrc):
     for line in out.splitlines():
         m = re.search(r"-c (\S+)\.hip -o (\S+)\.o$", line)
         if m:
-            cmds[m.group(1)] = line.split()
+            cmds[m.group(2)] = line.split()      # by object: diffusion.hip and coriolis.hip are each built twice
     return cmds
 
 
