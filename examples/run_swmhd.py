@@ -35,6 +35,9 @@ NU on u and v, ETA -- the magnetic diffusivity -- on A and on the dye; one more 
 --formulation jacobian; neither goes with --channel.  In an ensemble run both take comma lists like --coriolis (a sweep of the Reynolds
 or of the magnetic Prandtl number), and a list of several values starts one.  dt is not limited by the closure: the line printed at the
 start gives ScalarDiffusivity.max_stable_dt.
+--hyperviscosity NU4 and --hyperdiffusivity ETA4 add closure = ScalarBiharmonicDiffusivity(nu = NU4, kappa = ETA4) in the same way
+(-NU4 laplace² on u and v, -ETA4 laplace² on A and on the dye; one more launch per RK3 stage), alone or next to --viscosity /
+--diffusivity: the model then takes the tuple of both closures, as Oceananigans does.  The same rules and comma lists apply.
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
@@ -89,6 +92,8 @@ def main():
     ap.add_argument("--dye", action="store_true", help="advect one passive tracer c = tanh(y) with the flow")
     ap.add_argument("--viscosity", default=None, help="nu of ScalarDiffusivity, on u and v (ensemble runs: a comma list, one member per entry)")
     ap.add_argument("--diffusivity", default=None, help="kappa of ScalarDiffusivity, on A and the dye (ensemble runs: a comma list)")
+    ap.add_argument("--hyperviscosity", default=None, help="nu of ScalarBiharmonicDiffusivity, on u and v (ensemble runs: a comma list)")
+    ap.add_argument("--hyperdiffusivity", default=None, help="kappa of ScalarBiharmonicDiffusivity, on A and the dye (ensemble runs: a comma list)")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -104,12 +109,13 @@ def main():
         ap.error("--channel and --gradients go together")
     if a.channel and a.amps:
         ap.error("--channel sweeps --gradients, not --amps")
-    a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts)) or any("," in (x or "") for x in (a.viscosity, a.diffusivity))
+    a.sweep = any(x is not None for x in (a.coriolis, a.gravity, a.dts)) or any("," in (x or "") for x in (a.viscosity, a.diffusivity, a.hyperviscosity, a.hyperdiffusivity))
     a.closure = a.viscosity is not None or a.diffusivity is not None
-    if a.closure and a.channel:
-        ap.error("--viscosity / --diffusivity: not with --channel (the closure runs on periodic grids)")
-    if a.viscosity is not None and a.formulation != "jacobian":
-        ap.error("--viscosity needs --formulation jacobian (the conservative viscous stress is another operator)")
+    a.closure4 = a.hyperviscosity is not None or a.hyperdiffusivity is not None
+    if (a.closure or a.closure4) and a.channel:
+        ap.error("--viscosity / --diffusivity / --hyperviscosity / --hyperdiffusivity: not with --channel (the closures run on periodic grids)")
+    if (a.viscosity is not None or a.hyperviscosity is not None) and a.formulation != "jacobian":
+        ap.error("--viscosity / --hyperviscosity need --formulation jacobian (the conservative viscous stress is another operator)")
     if a.dts and a.frames > 0:
         ap.error("--frames is a schedule in time units: not with a per-member time step (--dts)")
     if a.dts and a.zonal_means > 0:
@@ -136,9 +142,14 @@ def main():
     grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2),
                              topology=("Periodic", "Bounded" if a.channel else "Periodic", "Flat"))
     form = "VectorInvariant" if a.formulation == "jacobian" else "Conservative"
-    closure = S.ScalarDiffusivity(nu=float(a.viscosity or 0.0), kappa=float(a.diffusivity or 0.0)) if a.closure else None
-    if closure is not None:
-        print(f"closure: {closure}, max_stable_dt = {closure.max_stable_dt(grid):.4g} (dt = {a.dt:g})")
+    closures = []
+    if a.closure:
+        closures.append(S.ScalarDiffusivity(nu=float(a.viscosity or 0.0), kappa=float(a.diffusivity or 0.0)))
+    if a.closure4:
+        closures.append(S.ScalarBiharmonicDiffusivity(nu=float(a.hyperviscosity or 0.0), kappa=float(a.hyperdiffusivity or 0.0)))
+    for c in closures:
+        print(f"closure: {c}, max_stable_dt = {c.max_stable_dt(grid):.4g} (dt = {a.dt:g})")
+    closure = None if not closures else (closures[0] if len(closures) == 1 else tuple(closures))
     # --beta B [--coriolis F0]: coriolis = BetaPlane(f0 = F0, beta = B), f = F0 + B y with y = 0 in mid-domain; one more launch per stage
     coriolis = S.BetaPlane(float(a.coriolis) if a.coriolis else configs.F, float(a.beta)) if a.beta is not None else S.FPlane(configs.F)
     if a.beta is not None:
@@ -325,7 +336,8 @@ def run_ensemble(a):
     else:
         amps = [a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)]
     lists = {"--coriolis": floats(a.coriolis or ""), "--gravity": floats(a.gravity or ""), "--dts": floats(a.dts or ""),
-             "--viscosity": floats(a.viscosity or ""), "--diffusivity": floats(a.diffusivity or ""), "--beta": floats(a.beta or "")}
+             "--viscosity": floats(a.viscosity or ""), "--diffusivity": floats(a.diffusivity or ""), "--beta": floats(a.beta or ""),
+             "--hyperviscosity": floats(a.hyperviscosity or ""), "--hyperdiffusivity": floats(a.hyperdiffusivity or "")}
     B = max([len(amps)] + [len(v) for v in lists.values()])
     for name, v in [("--gradients" if a.channel else "--amps", amps)] + [(k, v) for k, v in lists.items() if v]:
         if len(v) not in (1, B):
@@ -342,10 +354,14 @@ def run_ensemble(a):
         A0 = [lambda X, Y, gr=gr: gr * Y for gr in amps]
     else:
         grid = S.RectilinearGrid(size=(N, N), x=(-L / 2, L / 2), y=(-L / 2, L / 2))
-        closure = None
+        closures = []
         if a.closure:
-            closure = S.ScalarDiffusivity(nu=per(lists["--viscosity"], 0.0), kappa=per(lists["--diffusivity"], 0.0))
-            print(f"closure: {closure}, max_stable_dt = {closure.max_stable_dt(grid):.4g}")
+            closures.append(S.ScalarDiffusivity(nu=per(lists["--viscosity"], 0.0), kappa=per(lists["--diffusivity"], 0.0)))
+        if a.closure4:
+            closures.append(S.ScalarBiharmonicDiffusivity(nu=per(lists["--hyperviscosity"], 0.0), kappa=per(lists["--hyperdiffusivity"], 0.0)))
+        for c in closures:
+            print(f"closure: {c}, max_stable_dt = {c.max_stable_dt(grid):.4g}")
+        closure = None if not closures else (closures[0] if len(closures) == 1 else tuple(closures))
         # --beta: coriolis = BetaPlane(f0, beta) with --coriolis as f0, a scalar or one value per member each
         fkw = {"coriolis_f": fs}
         if a.beta is not None:

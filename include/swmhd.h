@@ -775,6 +775,8 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_spectra2d.h"
 /* ScalarDiffusivity closure (swmhd_diffusion_rk3_*, swmhd_ensemble_diffusion_rk3_*): nu laplace(u, v), kappa laplace(A, tracers) per RK3 stage */
 #include "swmhd_diffusion.h"
+/* ScalarBiharmonicDiffusivity closure (swmhd_biharmonic_rk3_*, swmhd_ensemble_biharmonic_rk3_*): -nu4 laplace^2(u, v), -kappa4 laplace^2(A, tracers) */
+#include "swmhd_biharmonic.h"
 /* BetaPlane Coriolis (swmhd_coriolis_rk3_*, swmhd_ensemble_coriolis_rk3_*): f(y) (vbar, -ubar) added to (u, v) or (uh, vh) per RK3 stage */
 #include "swmhd_coriolis.h"
 

@@ -14,11 +14,11 @@ from .output import FieldTimeSeries, TimeInterval, IterationInterval, run
 from .zonal import ZonalMeanTimeSeries
 from .spectra import ZonalSpectrumTimeSeries
 from .spectra2d import IsotropicSpectrumTimeSeries
-from .closure import ScalarDiffusivity
+from .closure import ScalarBiharmonicDiffusivity, ScalarDiffusivity
 from .coriolis import FPlane, BetaPlane, CoriolisProfile
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
            "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble",
-           "BoundedShallowWaterEnsemble", "FieldTimeSeries", "ZonalMeanTimeSeries", "ZonalSpectrumTimeSeries", "IsotropicSpectrumTimeSeries", "ScalarDiffusivity", "FPlane", "BetaPlane",
+           "BoundedShallowWaterEnsemble", "FieldTimeSeries", "ZonalMeanTimeSeries", "ZonalSpectrumTimeSeries", "IsotropicSpectrumTimeSeries", "ScalarDiffusivity", "ScalarBiharmonicDiffusivity", "FPlane", "BetaPlane",
            "CoriolisProfile", "TimeInterval", "IterationInterval", "run", "_lib"]

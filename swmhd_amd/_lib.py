@@ -204,6 +204,13 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_diffusion_rk3_{sfx}")
         f.argtypes = [C.POINTER(p)] * 3 + [p, i, i, i64, i, i, i, i, i64, ft, ft, p, ft, ft, i, i, i, p]
         f.restype = i
+        # ScalarBiharmonicDiffusivity closure: the argument lists of the two diffusion calls
+        f = getattr(lib, f"swmhd_biharmonic_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 3 + [p, i, i, i, i, i, i64, ft, ft, ft, ft, i, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_biharmonic_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 3 + [p, i, i, i64, i, i, i, i, i64, ft, ft, p, ft, ft, i, i, i, p]
+        f.restype = i
         # BetaPlane Coriolis: q1, q2 old, new, acc, frow (device table), ...
         f = getattr(lib, f"swmhd_coriolis_rk3_{sfx}")
         f.argtypes = [p] * 7 + [i, i, i, i, i64, ft, ft, i, i, i, p]
@@ -268,6 +275,8 @@ SPECTRA2D_EXPORTS = ["swmhd_spectra2d_shells", "swmhd_spectra2d_workspace"] + [f
                                                                                for name in ("spectra2d", "ensemble_spectra2d")]
 # the symbols include/swmhd_diffusion.h declares (swmhd.h includes it; tests/test_diffusion_abi.py checks the .so exports each of them)
 DIFFUSION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("diffusion_rk3", "ensemble_diffusion_rk3")]
+# the symbols include/swmhd_biharmonic.h declares (swmhd.h includes it; tests/test_biharmonic_abi.py checks the .so exports each of them)
+BIHARMONIC_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("biharmonic_rk3", "ensemble_biharmonic_rk3")]
 # the symbols include/swmhd_coriolis.h declares (swmhd.h includes it; tests/test_coriolis_abi.py checks the .so exports each of them)
 CORIOLIS_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("coriolis_rk3", "ensemble_coriolis_rk3")]
 RING_ID_BYTES = 128

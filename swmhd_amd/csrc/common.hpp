@@ -307,6 +307,10 @@ struct DiffusionArgs : StripArgs<T> {
 };
 template <typename T> hipError_t launch_diffusion_fast(const DiffusionArgs<T> &a, hipStream_t s);
 template <typename T> hipError_t launch_diffusion_strict(const DiffusionArgs<T> &a, hipStream_t s);
+// ScalarBiharmonicDiffusivity closure (swmhd_biharmonic_rk3_*, biharmonic.hip): the same arguments, D_k = -coef_k laplace(laplace(old_k)),
+// which reads two cells around
+template <typename T> hipError_t launch_biharmonic_fast(const DiffusionArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_biharmonic_strict(const DiffusionArgs<T> &a, hipStream_t s);
 
 // BetaPlane Coriolis (swmhd_coriolis_rk3_*, coriolis.hip): D1 = fc[j] vbar, D2 = -(ff[j] ubar) of the two momentum-like fields q1, q2 in
 // ONE launch, added to what the stage kernels (run with f = 0) have written: n1 += a D1, n2 += a D2 and, where a1 != nullptr (then a2

@@ -1,8 +1,8 @@
-// What the per-stage correction launches (diffusion.hip, coriolis.hip) share, stated once; included inside their anonymous namespace,
+// What the per-stage correction launches (diffusion.hip, coriolis.hip, biharmonic.hip) share, stated once; included inside their anonymous namespace,
 // after common.hpp and launch_plan.hpp.  A wave owns a strip of STRIP_WAVE lanes x VEC columns and marches down STRIP_WAVE_ROWS rows of
 // it, VEC = 16 bytes of elements per lane where every pointer of the call has the same 16-byte phase and the pitches keep it (else
 // VEC = 1): launch_plan.hpp strip_plan.  No LDS, no barrier: the STRIP_WAVES waves of a workgroup are consecutive row segments of one
-// strip.  Here: the strict / fast switch and the launcher's name, the vector access, the strip of one lane (Strip), the decoding of
+// strip.  Here: the strict / fast switch and the launcher's name, the vector access, the strip of one lane (Strip; Strip2 for a stencil of radius 2), the decoding of
 // blockIdx.x (strip_block), the per-member scalars (strip_scalars), and the host's plan and pick of an instantiation.  The carried
 // rows and the arithmetic are each kernel's own.
 #ifndef SWMHD_STRIP_STRICT
@@ -91,6 +91,95 @@ struct Strip {
         T x = __shfl_up(v[VEC - 1], 1);
         if (lane == 0) x = okw ? p[colw] : T(0);
         return x;
+    }
+    __device__ __forceinline__ void load_out(const T *p, T (&v)[VEC]) const {   // p: a row that is updated
+        if (full) {
+            vec_load<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
+        }
+    }
+    __device__ __forceinline__ void store_out(T *p, const T (&v)[VEC]) const {
+        if (full) {
+            vec_store<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                if (inside[e]) p[xv + e] = v[e];
+        }
+    }
+};
+
+// Strip for a stencil of radius 2 (biharmonic.hip): the same lanes, groups and lead, with two columns and two rows around.  A column as
+// it is read: -2 .. Nx + 1 are the halo cells or, wrapped, their periodic images by a TRUE modulus (x mod Nx: a width of 1 or 2 folds
+// more than once); nothing further out is read.  `reach` (0, 1 or 2) of a row: how many columns beyond [0, Nx) the call may read of it --
+// 2 for a row that is computed, 1 and 0 for the first and the second row beyond the computed ones -- so that the reads of a call are the
+// 13-cell diamonds of its cells and no more.  dist: how far a column lies outside [0, Nx) (0: inside).
+template <typename T, int VEC>
+struct Strip2 {
+    int Nx, Ny, lane, xv, colw, cole, colw2, cole2, distw, diste, distw2, diste2;
+    long sy;
+    bool wrapy, full;
+    int col[VEC], dist[VEC];
+    bool inside[VEC];
+
+    __device__ __forceinline__ static int fold(int v, int n) {   // v mod n for v in [-2, n + 1], n >= 1
+        if (v < 0) v += n;
+        if (v < 0) v += n;
+        if (v >= n) v -= n;
+        if (v >= n) v -= n;
+        return v;
+    }
+    __device__ __forceinline__ Strip2(int Nx_, int Ny_, long sy_, int wrap, int strip, int lane_, int lead)
+        : Nx(Nx_), Ny(Ny_), lane(lane_), xv((strip * STRIP_WAVE + lane_) * VEC - lead), sy(sy_), wrapy(wrap & 2) {
+        const bool wrapx = wrap & 1;
+        full = xv >= 0 && xv + VEC <= Nx;
+        auto column = [&](int x, int &d) -> int {
+            d = x < 0 ? -x : (x >= Nx ? x - Nx + 1 : 0);
+            if (d > 2) return 0;   // (never read: reach <= 2)
+            return wrapx ? fold(x, Nx) : x;
+        };
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            col[e] = column(xv + e, dist[e]);
+            inside[e] = dist[e] == 0;
+        }
+        colw = column(xv - 1, distw);
+        cole = column(xv + VEC, diste);
+        colw2 = column(xv - 2, distw2);
+        cole2 = column(xv + VEC + 1, diste2);
+    }
+    __device__ __forceinline__ long row_of(int y) const {   // y in [-2, Ny + 1]
+        if (wrapy) y = fold(y, Ny);
+        return (long)y * sy;
+    }
+    __device__ __forceinline__ void load_in(const T *p, int reach, T (&v)[VEC]) const {   // p: a row that is read with its halo
+        if (full) {
+            vec_load<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = dist[e] <= reach ? p[col[e]] : T(0);
+        }
+    }
+    // the neighbour beyond a lane's group: from the next lane, at the ends of the wave from memory
+    __device__ __forceinline__ T east_of(const T *p, int reach, const T (&v)[VEC]) const {
+        T x = __shfl_down(v[0], 1);
+        if (lane == STRIP_WAVE - 1) x = diste <= reach ? p[cole] : T(0);
+        return x;
+    }
+    __device__ __forceinline__ T west_of(const T *p, int reach, const T (&v)[VEC]) const {
+        T x = __shfl_up(v[VEC - 1], 1);
+        if (lane == 0) x = distw <= reach ? p[colw] : T(0);
+        return x;
+    }
+    // two columns beyond the group, for the two lanes at the ends of the wave, which have no lane to take a derived row value of their
+    // neighbouring column from and form it themselves: from memory; T(0) in every other lane
+    __device__ __forceinline__ T east2_of(const T *p, int reach) const {
+        return (lane == STRIP_WAVE - 1 && diste2 <= reach) ? p[cole2] : T(0);
+    }
+    __device__ __forceinline__ T west2_of(const T *p, int reach) const {
+        return (lane == 0 && distw2 <= reach) ? p[colw2] : T(0);
     }
     __device__ __forceinline__ void load_out(const T *p, T (&v)[VEC]) const {   // p: a row that is updated
         if (full) {

@@ -236,9 +236,11 @@ void set_strip(StripArgs<T> &s, const Grid &g, const Rows &r, const Flags &fl, T
 // one launch (diffusion.hip).  Every check precedes the first HIP call.  With `ens` (swmhd_ensemble_diffusion_rk3): `coef` is the DEVICE
 // table of members x nfields values and is not looked at; ens->params (optional) brings every member's dt.  The ensemble's own
 // argument errors come first.  One grid: the fields with coef == 0 are left out of the launch here.
+// radius: 1 the Laplacian (diffusion_common), 2 the biharmonic operator (biharmonic_common, below): the halo a direction without its
+// WRAP flag needs, and the launcher.  The checks and their order are the same for both.
 template <typename T>
-int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, const Grid &g, T a, T w, const Rows &r,
-                     int flags, void *stream, const Ens *ens = nullptr) {
+int stencil_closure_common(int radius, const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, const Grid &g, T a, T w,
+                           const Rows &r, int flags, void *stream, const Ens *ens) {
     if (ens) {
         if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
         if (g.Ny <= 0 || g.Hy < 0 || g.sy <= 0 || ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
@@ -253,7 +255,7 @@ int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *
         const T *const ak = acc ? acc[k] : nullptr;
         if (ak == nw[k]) return SWMHD_EINVAL;
         for (int m = 0; m < nfields; ++m) {
-            if (nw[k] == old[m] || (ak && ak == old[m])) return SWMHD_EINVAL;   // other workgroups still read old around their rows
+            if (nw[k] == old[m] || (ak && ak == old[m])) return SWMHD_EINVAL;   // other workgroups still read old around their rows (one row around, two for radius 2)
             if (m != k && (nw[k] == nw[m] || (ak && (ak == nw[m] || ak == acc[m])))) return SWMHD_EINVAL;
         }
     }
@@ -263,7 +265,7 @@ int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *
     if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
     if (flags & DIFFUSION_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
-    if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
+    if ((g.Hx < radius && !(fl.wrap & 1)) || (g.Hy < radius && !(fl.wrap & 2))) return SWMHD_EHALO;
     if (r.j0 == r.j1) return SWMHD_OK;
     DiffusionArgs<T> d;
     int n = 0;
@@ -279,7 +281,20 @@ int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *
     set_strip(d, g, r, fl, a, w, ens);
     d.nfields = n; d.dx = T(g.dx); d.dy = T(g.dy); d.coef_tab = ens ? coef : nullptr;
     hipStream_t s = (hipStream_t)stream;
+    if (radius == 2) return hiprc(fl.strict ? launch_biharmonic_strict<T>(d, s) : launch_biharmonic_fast<T>(d, s));
     return hiprc(fl.strict ? launch_diffusion_strict<T>(d, s) : launch_diffusion_fast<T>(d, s));
+}
+template <typename T>
+int diffusion_common(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, const Grid &g, T a, T w, const Rows &r,
+                     int flags, void *stream, const Ens *ens = nullptr) {
+    return stencil_closure_common<T>(1, old, nw, acc, coef, nfields, g, a, w, r, flags, stream, ens);
+}
+// swmhd_biharmonic_rk3: nw[k] -= a coef[k] laplace(laplace(old[k])), acc[k] likewise with w (biharmonic.hip): diffusion_common's arguments,
+// checks and order (include/swmhd_biharmonic.h); SWMHD_EHALO below a halo of 2, and other workgroups read old two rows around theirs.
+template <typename T>
+int biharmonic_common(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, const Grid &g, T a, T w, const Rows &r,
+                      int flags, void *stream, const Ens *ens = nullptr) {
+    return stencil_closure_common<T>(2, old, nw, acc, coef, nfields, g, a, w, r, flags, stream, ens);
 }
 
 // swmhd_coriolis_rk3: n1 += a fc vbar, n2 -= a ff ubar (and a1, a2 with w) in one launch (coriolis.hip).  Every check precedes the first
@@ -650,6 +665,22 @@ SWMHD_DEF_API(f32, float)
 
 SWMHD_DEF_DIFFUSION(f64, double)
 SWMHD_DEF_DIFFUSION(f32, float)
+
+// include/swmhd_biharmonic.h
+#define SWMHD_DEF_BIHARMONIC(sfx, T)                                                                                                                   \
+    int swmhd_biharmonic_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, int Nx, int Ny, int Hx, int Hy,      \
+                                   int64_t sy, T dx, T dy, T a, T w, int j0, int j1, int flags, void *stream) {                                       \
+        return biharmonic_common<T>(old, nw, acc, coef, nfields, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, a, w, Rows{j0, j1}, flags, stream);                \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_biharmonic_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, int members,                \
+                                            int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, T dx, T dy, const T *params, T a, T w,      \
+                                            int j0, int j1, int flags, void *stream) {                                                                \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return biharmonic_common<T>(old, nw, acc, coef, nfields, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, a, w, Rows{j0, j1}, flags, stream, &e);            \
+    }
+
+SWMHD_DEF_BIHARMONIC(f64, double)
+SWMHD_DEF_BIHARMONIC(f32, float)
 
 // include/swmhd_coriolis.h
 #define SWMHD_DEF_CORIOLIS(sfx, T)                                                                                                                     \

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .closure import check_closure
+from .closure import check_closure, closure_for_member
 from .coriolis import check_coriolis, row_table
 from .fields import _SFX, _stream_ptr
 from .grid import Center, Face
@@ -67,7 +67,9 @@ class ShallowWaterEnsemble:
     every coefficient -- a sweep of the Reynolds or the magnetic Prandtl number.  `diffusion_coefficients` is the (members, fields
     with a coefficient) device table; such an ensemble steps stage by stage as one with tracers does, with one more launch per stage
     for all members (swmhd_ensemble_diffusion_rk3_*), under a scalar or a per-member dt.  Without a closure, or with coefficients
-    that are all 0, the ensemble calls exactly what it calls without the argument."""
+    that are all 0, the ensemble calls exactly what it calls without the argument.  `closure=ScalarBiharmonicDiffusivity(...)`, or a
+    tuple with one of each kind, likewise: `biharmonic_coefficients` is its device table, its launch (swmhd_ensemble_biharmonic_rk3_*)
+    follows the Laplacian's."""
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
@@ -78,8 +80,8 @@ class ShallowWaterEnsemble:
         self.coriolis = coriolis
         coriolis_f, self._coriolis = check_coriolis(coriolis, coriolis_f, 1.0)
         self.closure = closure
-        coefs = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
-                              formulation != VectorInvariantFormulation)      # (a Bounded grid: _check_topology, below)
+        coefs, coefs4 = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
+                                      formulation != VectorInvariantFormulation)      # (a Bounded grid: _check_topology, below)
         if decomp is not None or grid.Ny_global != grid.Ny or grid.j_offset != 0:
             raise _lib.SwmhdError("ShallowWaterEnsemble runs on one GPU: no slab decomposition")
         self._check_topology(grid)
@@ -94,6 +96,8 @@ class ShallowWaterEnsemble:
         # the closure's coefficients: a scalar or one value per member each; the fields all of whose values are 0 have no launch
         coefs = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs or {}).items()}
         self._diffusion = {n: c for n, c in coefs.items() if np.any(c != 0.0)} or None
+        coefs4 = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs4 or {}).items()}
+        self._biharmonic = {n: c for n, c in coefs4.items() if np.any(c != 0.0)} or None
         rows = row_table(self._coriolis, grid, self.members) if self._coriolis is not None else None
         self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
         self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
@@ -133,6 +137,11 @@ class ShallowWaterEnsemble:
         if self._diffusion is not None:
             host = np.stack([self._diffusion[n] for n in self._diffusion_names()], axis=1)
             self.diffusion_coefficients = torch.from_numpy(np.ascontiguousarray(host)).to(device=self._state[0].device, dtype=dtype)
+        # the same table of the biharmonic closure (swmhd_ensemble_biharmonic_rk3_*)
+        self.biharmonic_coefficients = None
+        if self._biharmonic is not None:
+            host = np.stack([self._biharmonic[n] for n in self._closure_names(self._biharmonic)], axis=1)
+            self.biharmonic_coefficients = torch.from_numpy(np.ascontiguousarray(host)).to(device=self._state[0].device, dtype=dtype)
         # (members, 2, Ny) on the device, in the ensemble's dtype and rounded to it: fc then ff of every member, the table of
         # swmhd_ensemble_coriolis_rk3_*; built once
         self.coriolis_rows = None
@@ -310,27 +319,37 @@ class ShallowWaterEnsemble:
                gamma if par else dt * gamma, w, 0, g.Ny, self._flags | self._rwrap | flag, _stream_ptr())
         _lib.check(rc, "swmhd_ensemble_coriolis_rk3")
 
+    def _closure_names(self, coefs):
+        return [n for n in self.names + self.tracer_names if n in coefs]
+
     def _diffusion_names(self):
-        return [n for n in self.names + self.tracer_names if n in self._diffusion]
+        return self._closure_names(self._diffusion)
 
     def _diffusion_stage(self, dt, stage):
         """The closure's launch of RK3 stage `stage` for every member (swmhd_ensemble_diffusion_rk3_*; with dt None every member's dt
         comes from the table): ShallowWaterModel._diffusion_stage with the coefficients of member m in row m of the device table."""
+        self._closure_stage(dt, stage, self._diffusion_names(), self.diffusion_coefficients, "swmhd_ensemble_diffusion_rk3")
+
+    def _biharmonic_stage(self, dt, stage):
+        """The biharmonic closure's launch of RK3 stage `stage` for every member (swmhd_ensemble_biharmonic_rk3_*), after
+        _diffusion_stage (finish_stage): ShallowWaterModel._biharmonic_stage with the coefficients of member m in row m of the table."""
+        self._closure_stage(dt, stage, self._closure_names(self._biharmonic), self.biharmonic_coefficients, "swmhd_ensemble_biharmonic_rk3")
+
+    def _closure_stage(self, dt, stage, names, table, call):
         g = self.grid
         gamma = rk3_stage(stage, self._anchor)[0]
-        names = self._diffusion_names()
         cur = {**dict(zip(self.names, self._state)), **self._tr}
         new = {**dict(zip(self.names, self._alt)), **self._tr_alt}
         Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
         par = dt is None
         has, w, flag = correction_operand(stage, self._anchor, dt)
         acc = self._ptrs([Gn[n] for n in names]) if has else None
-        f = getattr(self._L, f"swmhd_ensemble_diffusion_rk3_{self.sfx}")
-        rc = f(self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc, self.diffusion_coefficients.data_ptr(),
+        f = getattr(self._L, f"{call}_{self.sfx}")
+        rc = f(self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc, table.data_ptr(),
                len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy,
                self.parameters.data_ptr() if par else None, gamma if par else dt * gamma, w, 0, g.Ny,
                self._flags | self._rwrap | flag, _stream_ptr())
-        _lib.check(rc, "swmhd_ensemble_diffusion_rk3")
+        _lib.check(rc, call)
 
     def _stage_steps(self, dt, n):
         """n steps stage by stage (dt: the scalar, or None for the table).  Without fused halos every stage ends with the periodic fill
@@ -361,7 +380,7 @@ class ShallowWaterEnsemble:
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        if self._tr or self._diffusion is not None or self._coriolis is not None:        # (the native step driver steps the four fields only, with a scalar f)
+        if self._tr or self._diffusion is not None or self._biharmonic is not None or self._coriolis is not None:        # (the native step driver steps the four fields only, with a scalar f)
             self._stage_steps(dt if dts is None else None, n)
         else:
             self._enqueue_steps(dt if dts is None else None, n, swapped)
@@ -511,7 +530,7 @@ class ShallowWaterEnsemble:
         f = {"coriolis_f": float(self.f_values[m])} if self._coriolis is None else {"coriolis": self._coriolis.for_member(m)}
         return ShallowWaterModel(self.grid, float(self.g_values[m]), formulation=self.formulation,
                                  lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
-                                 tracers=self.tracer_names, closure=self.closure.for_member(m) if self.closure is not None else None, **f)
+                                 tracers=self.tracer_names, closure=closure_for_member(self.closure, m), **f)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""

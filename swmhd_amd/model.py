@@ -88,14 +88,16 @@ class ShallowWaterModel:
                 raise _lib.SwmhdError("tracers with ring= are not supported (SWMHD_ENOTSUP): the slab driver steps the four fields only")
             if not fused:
                 raise _lib.SwmhdError("tracers need the fused stage kernel (SWMHD_ENOTSUP): fused=False has no tracer substep")
-        # closure = ScalarDiffusivity(...): its names and refusals are checked before anything is allocated too.  _diffusion: the
-        # coefficient of every field that has one; None without a closure and with one whose coefficients are all 0, and then the
-        # model makes exactly the calls it makes without the argument
+        # closure = ScalarDiffusivity(...) | ScalarBiharmonicDiffusivity(...) | a tuple with at most one of each: names and refusals are
+        # checked before anything is allocated too.  _diffusion, _biharmonic: the coefficient of every field that has one of that kind;
+        # None without such a closure and with one whose coefficients are all 0, and then the model makes exactly the calls it makes
+        # without it
         self.closure = closure
-        coefs = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
-                              formulation != VectorInvariantFormulation, any(c == _lib.BOUNDED for c in grid.topo_codes()),
-                              decomp is not None and decomp.world_size > 1, ring is not None, fused)
+        coefs, coefs4 = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
+                                      formulation != VectorInvariantFormulation, any(c == _lib.BOUNDED for c in grid.topo_codes()),
+                                      decomp is not None and decomp.world_size > 1, ring is not None, fused)
         self._diffusion = {n: float(c) for n, c in (coefs or {}).items() if float(c) != 0.0} or None
+        self._biharmonic = {n: float(c) for n, c in (coefs4 or {}).items() if float(c) != 0.0} or None
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code, self.lorentz_code, self.names = formulation_codes(formulation, lorentz_forcing)
@@ -416,22 +418,31 @@ class ShallowWaterModel:
         from, for every field with a coefficient, added with dt gamma to the new state (and tracers) and, where the stage stores an
         operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
         the anchor form).  After _stage_fused and _tracer_stage and BEFORE the swaps (finish_stage)."""
+        self._closure_stage(dt, stage, self._diffusion, "swmhd_diffusion_rk3")
+
+    def _biharmonic_stage(self, dt, stage):
+        """The biharmonic closure's launch of RK3 stage `stage` (swmhd_biharmonic_rk3_*): _diffusion_stage with D = -coef
+        laplace(laplace(field)).  After _diffusion_stage and BEFORE the swaps (finish_stage): with both closures the new u is
+        ((stage + a D_laplacian) + a D_biharmonic), and that order decides the last bits."""
+        self._closure_stage(dt, stage, self._biharmonic, "swmhd_biharmonic_rk3")
+
+    def _closure_stage(self, dt, stage, coefs, call):
         g = self.grid
         P = _lib.ptr_array
         gamma = rk3_stage(stage, self._anchor)[0]
-        names = [n for n in self.names + self.tracer_names if n in self._diffusion]
+        names = [n for n in self.names + self.tracer_names if n in coefs]
         cur = {**self._state, **self._tr}
         new = {**self._alt, **self._tr_alt}
         Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
         has, w, _ = correction_operand(stage, self._anchor, dt)
         acc = P([Gn[n].ptr for n in names]) if has else None
         ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
-        coef = (ft * len(names))(*[self._diffusion[n] for n in names])
-        f = getattr(self._L, f"swmhd_diffusion_rk3_{self.sfx}")
+        coef = (ft * len(names))(*[coefs[n] for n in names])
+        f = getattr(self._L, f"{call}_{self.sfx}")
         rc = f(P([cur[n].ptr for n in names]), P([new[n].ptr for n in names]), acc, coef, len(names), g.Nx, g.Ny, g.Hx, g.Hy,
                self._raw_fields[0].stride_y, g.dx, g.dy, dt * gamma, w, 0, g.Ny,
                (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap, _stream_ptr())
-        _lib.check(rc, "swmhd_diffusion_rk3")
+        _lib.check(rc, call)
 
     # --- time_step!(model, dt): RungeKutta3 ------------------------------------------------------------------
     def _native_steps(self, dt, n):
@@ -565,7 +576,7 @@ class ShallowWaterModel:
 
     def _driver_steps(self, dt, n):
         if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)
-                                      and not self._tr and self._diffusion is None
+                                      and not self._tr and self._diffusion is None and self._biharmonic is None
                                       and self._coriolis is None):     # (the native step driver steps the four fields only, with a scalar f)
             return self._native_steps(dt, n)
         for _ in range(n):

@@ -7,7 +7,8 @@ prints for that unit (plus --offload-device-only --no-gpu-bundle-output), then `
 objects are compared.  Lines that carry the object's path or the __hip_cuid_* symbol (a hash of the path) are left out.  Needs no GPU.
 Per unit also `opcodes_equal`: the sequence of instruction mnemonics, label and symbol lines included, operands ignored (a listing
 that differs only in registers or in the order of a commutative operation's sources has it), and `differing_lines`, the count of
-listing lines that differ.
+listing lines that differ.  A unit that only one of the two Makefiles builds is reported as {"only_in": "mine" | "other"} and not
+compared: a change that adds a kernel leaves every older unit to be shown equal.
 Exit status 0: all equal."""
 import concurrent.futures
 import difflib
@@ -65,11 +66,13 @@ def main(argv):
     other = os.path.abspath(argv[0])
     mine = os.path.abspath(argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "swmhd_amd", "csrc"))
     cmds = {d: units(d) for d in (other, mine)}
-    assert sorted(cmds[other]) == sorted(cmds[mine]), "the two Makefiles build different units"
-    report = {}
+    both = sorted(set(cmds[other]) & set(cmds[mine]))
+    report = {u: {"only_in": "mine" if u in cmds[mine] else "other"} for u in sorted(set(cmds[other]) ^ set(cmds[mine]))}
+    for u, r in report.items():
+        print(u, r, flush=True)
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb, concurrent.futures.ThreadPoolExecutor(8) as pool:
-        jobs = {(d, u): pool.submit(device_listing, d, u, cmds[d][u], t) for d, t in ((other, ta), (mine, tb)) for u in cmds[d]}
-        for u in sorted(cmds[mine]):
+        jobs = {(d, u): pool.submit(device_listing, d, u, cmds[d][u], t) for d, t in ((other, ta), (mine, tb)) for u in both}
+        for u in both:
             a, b = jobs[(other, u)].result(), jobs[(mine, u)].result()
             report[u] = {"disassembly_lines": len(b[0]), "notes_lines": len(b[1]), "disassembly_equal": a[0] == b[0], "notes_equal": a[1] == b[1],
                          "opcodes_equal": opcodes(a[0]) == opcodes(b[0]), "differing_lines": differing_lines(a[0], b[0])}
@@ -78,7 +81,7 @@ def main(argv):
         with open(js, "w") as fh:
             json.dump(report, fh, indent=1)
             fh.write("\n")
-    return 0 if all(r["disassembly_equal"] and r["notes_equal"] for r in report.values()) else 1
+    return 0 if all(r["disassembly_equal"] and r["notes_equal"] for r in report.values() if "only_in" not in r) else 1
 
 
 if __name__ == "__main__":
