@@ -38,6 +38,12 @@ start gives ScalarDiffusivity.max_stable_dt.
 --hyperviscosity NU4 and --hyperdiffusivity ETA4 add closure = ScalarBiharmonicDiffusivity(nu = NU4, kappa = ETA4) in the same way
 (-NU4 laplace² on u and v, -ETA4 laplace² on A and on the dye; one more launch per RK3 stage), alone or next to --viscosity /
 --diffusivity: the model then takes the tuple of both closures, as Oceananigans does.  The same rules and comma lists apply.
+--drag R adds Oceananigans' forcing = (u = Relaxation(rate = R), v = Relaxation(rate = R)) (swmhd_amd.Relaxation; uh, vh with
+--formulation divergence): linear drag on the two momentum-like fields, one more launch per RK3 stage.  In an ensemble run a comma list
+gives one member per entry (a sweep of the drag), and a list of several values starts one.  --sponge RATE,WIDTH (with --channel) puts
+Relaxation(rate = RATE, mask = G) on the same two fields, G(y) = exp(-((y - y_south) / WIDTH)²) + exp(-((y - y_north) / WIDTH)²): sponge
+layers that absorb what reaches the walls.  With --drag R as well the two terms are one, Relaxation(rate = 1, mask = R + RATE G).  With --channel either runs ONE Bounded model (one --gradients entry: Bounded ensembles take no forcing).  dt is not
+limited by the forcing: the line printed at the start gives Relaxation.max_stable_dt.
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
@@ -94,6 +100,8 @@ def main():
     ap.add_argument("--diffusivity", default=None, help="kappa of ScalarDiffusivity, on A and the dye (ensemble runs: a comma list)")
     ap.add_argument("--hyperviscosity", default=None, help="nu of ScalarBiharmonicDiffusivity, on u and v (ensemble runs: a comma list)")
     ap.add_argument("--hyperdiffusivity", default=None, help="kappa of ScalarBiharmonicDiffusivity, on A and the dye (ensemble runs: a comma list)")
+    ap.add_argument("--drag", default=None, help="rate of Relaxation on the two momentum-like fields (ensemble runs: a comma list, one member per entry)")
+    ap.add_argument("--sponge", default=None, help="RATE,WIDTH with --channel: Relaxation(rate=RATE, mask=Gaussians of that width at the two walls) on the momentum-like fields")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -126,11 +134,15 @@ def main():
         ap.error("--isotropic-spectra is a schedule in time units: not with a per-member time step (--dts)")
     if a.dye and a.channel:
         ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
-    a.sweep = a.sweep or "," in (a.beta or "")
-    # --channel with --beta: ONE Bounded model (Bounded ensembles take no f(y)), so one gradient, one f0 and one beta
-    one_channel = a.channel and a.beta is not None
-    if one_channel and (a.gravity or a.dts or any("," in (x or "") for x in (a.gradients, a.beta, a.coriolis))):
-        ap.error("--channel with --beta runs one model: one --gradients entry, one --coriolis, one --beta, no --gravity or --dts")
+    a.sweep = a.sweep or "," in (a.beta or "") or "," in (a.drag or "")
+    if a.sponge is not None and (not a.channel or len(a.sponge.split(",")) != 2):
+        ap.error("--sponge RATE,WIDTH needs --channel: the sponge layers stand at the channel's walls")
+    # --channel with --beta, --drag or --sponge: ONE Bounded model (Bounded ensembles take no f(y) and no forcing), so one gradient, one
+    # f0, one beta and one drag
+    one_channel = a.channel and (a.beta is not None or a.drag is not None or a.sponge is not None)
+    if one_channel and (a.gravity or a.dts or any("," in (x or "") for x in (a.gradients, a.beta, a.coriolis, a.drag))):
+        ap.error("--channel with --beta, --drag or --sponge runs one model: one --gradients entry, one --coriolis, one --beta, one --drag, "
+                 "no --gravity or --dts")
     if (a.amps or a.channel or a.sweep) and not one_channel:
         return run_ensemble(a)
     a.sweep = False
@@ -156,8 +168,25 @@ def main():
         print(f"coriolis: {coriolis}")
     gr = float(a.gradients) if a.channel else None
     bcs = {"A": S.FieldBoundaryConditions(north=S.GradientBoundaryCondition(gr), south=S.GradientBoundaryCondition(gr))} if a.channel else None
+    # --drag R: Relaxation(rate = R) on the two momentum-like fields.  --sponge RATE,WIDTH: Relaxation(rate = RATE, mask = G) with G the
+    # two Gaussians at the walls; with both, one Relaxation(rate = 1, mask = R + RATE G): a field has one Relaxation
+    momentum = ("u", "v") if form == "VectorInvariant" else ("uh", "vh")
+    forcing = None
+    if a.sponge is not None:
+        rate, width = (float(x) for x in a.sponge.split(","))
+        south, north = grid.y
+        gaussians = lambda x, y: np.exp(-((y - south) / width) ** 2) + np.exp(-((y - north) / width) ** 2) + 0 * x
+        if a.drag is None:
+            forcing = {n: S.Relaxation(rate, mask=gaussians) for n in momentum}
+        else:
+            drag = float(a.drag)
+            forcing = {n: S.Relaxation(1.0, mask=lambda x, y: drag + rate * gaussians(x, y)) for n in momentum}
+    elif a.drag is not None:
+        forcing = {n: S.Relaxation(float(a.drag)) for n in momentum}
+    for n, r in (forcing or {}).items():
+        print(f"forcing: {n} = {r}, max_stable_dt = {r.max_stable_dt(grid, S.fields.LOCS[n]):.4g} (dt = {a.dt:g})")
     model = S.ShallowWaterModel(grid, configs.G, formulation=form, tracers=("c",) if a.dye else (), closure=closure, coriolis=coriolis,
-                                boundary_conditions=bcs)
+                                boundary_conditions=bcs, forcing=forcing)
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)
     A0 = (lambda X, Y: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp)
     if a.channel:
@@ -337,7 +366,8 @@ def run_ensemble(a):
         amps = [a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)]
     lists = {"--coriolis": floats(a.coriolis or ""), "--gravity": floats(a.gravity or ""), "--dts": floats(a.dts or ""),
              "--viscosity": floats(a.viscosity or ""), "--diffusivity": floats(a.diffusivity or ""), "--beta": floats(a.beta or ""),
-             "--hyperviscosity": floats(a.hyperviscosity or ""), "--hyperdiffusivity": floats(a.hyperdiffusivity or "")}
+             "--hyperviscosity": floats(a.hyperviscosity or ""), "--hyperdiffusivity": floats(a.hyperdiffusivity or ""),
+             "--drag": floats(a.drag or "")}
     B = max([len(amps)] + [len(v) for v in lists.values()])
     for name, v in [("--gradients" if a.channel else "--amps", amps)] + [(k, v) for k, v in lists.items() if v]:
         if len(v) not in (1, B):
@@ -367,7 +397,13 @@ def run_ensemble(a):
         if a.beta is not None:
             fkw = {"coriolis": S.BetaPlane(fs, per(lists["--beta"], 0.0))}
             print(f"coriolis: {fkw['coriolis']}")
-        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, formulation=form, tracers=("c",) if a.dye else (), closure=closure, **fkw)
+        # --drag: Relaxation(rate) on the two momentum-like fields, a scalar or one rate per member
+        forcing = None
+        if a.drag is not None:
+            forcing = {n: S.Relaxation(per(lists["--drag"], 0.0)) for n in (("u", "v") if form == "VectorInvariant" else ("uh", "vh"))}
+            print(f"forcing: {forcing}, max_stable_dt = {min(r.max_stable_dt() for r in forcing.values()):.4g}")
+        ens = S.ShallowWaterEnsemble(grid, len(amps), gs, formulation=form, tracers=("c",) if a.dye else (), closure=closure,
+                                     forcing=forcing, **fkw)
         A0 = [(lambda X, Y, amp=amp: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp) for amp in amps]
     label = "gradient" if a.channel else "amp"
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))

@@ -779,5 +779,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_biharmonic.h"
 /* BetaPlane Coriolis (swmhd_coriolis_rk3_*, swmhd_ensemble_coriolis_rk3_*): f(y) (vbar, -ubar) added to (u, v) or (uh, vh) per RK3 stage */
 #include "swmhd_coriolis.h"
+/* Relaxation forcing (swmhd_relaxation_rk3_*, swmhd_ensemble_relaxation_rk3_*): rate mask (target - phi) added to any prognostic field per RK3 stage */
+#include "swmhd_relaxation.h"
 
 #endif /* SWMHD_H */

@@ -36,6 +36,8 @@ MAX_TRACERS = 8         # SWMHD_MAX_TRACERS: passive tracers per swmhd_tracers_r
 DIFFUSION_MAX_FIELDS = 3 + MAX_TRACERS    # SWMHD_DIFFUSION_MAX_FIELDS: fields per swmhd_diffusion_rk3_* launch
 DIFFUSION_TILE_ROWS = 64                  # SWMHD_DIFFUSION_TILE_ROWS: rows of a workgroup of the diffusion kernel (four waves)
 CORIOLIS_TILE_ROWS = 64                   # SWMHD_CORIOLIS_TILE_ROWS: rows of a workgroup of the Coriolis kernel (four waves)
+RELAXATION_MAX_FIELDS = 4 + MAX_TRACERS   # SWMHD_RELAXATION_MAX_FIELDS: fields per swmhd_relaxation_rk3_* launch
+RELAXATION_TILE_ROWS = 64                 # SWMHD_RELAXATION_TILE_ROWS: rows of a workgroup of the relaxation kernel (four waves)
 
 
 def ensemble_diag_workspace(members, Nx, Ny):
@@ -218,6 +220,13 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_coriolis_rk3_{sfx}")
         f.argtypes = [p] * 7 + [i, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
         f.restype = i
+        # Relaxation forcing: old, new, acc, mask, target (host arrays of device pointers), rate, tval (host arrays | device tables), ...
+        f = getattr(lib, f"swmhd_relaxation_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 5 + [p, p, i, i, i, i, i, i64, ft, ft, i, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_relaxation_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 5 + [p, p, i, i, i64, i64, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
+        f.restype = i
     lib.swmhd_zonal_spectra_workspace.argtypes = [i, i, i, i]
     lib.swmhd_zonal_spectra_workspace.restype = i64
     lib.swmhd_spectra2d_shells.argtypes = [i, i, C.c_double, C.c_double]
@@ -279,6 +288,8 @@ DIFFUSION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in
 BIHARMONIC_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("biharmonic_rk3", "ensemble_biharmonic_rk3")]
 # the symbols include/swmhd_coriolis.h declares (swmhd.h includes it; tests/test_coriolis_abi.py checks the .so exports each of them)
 CORIOLIS_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("coriolis_rk3", "ensemble_coriolis_rk3")]
+# the symbols include/swmhd_relaxation.h declares (swmhd.h includes it; tests/test_relaxation_abi.py checks the .so exports each of them)
+RELAXATION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("relaxation_rk3", "ensemble_relaxation_rk3")]
 RING_ID_BYTES = 128
 
 

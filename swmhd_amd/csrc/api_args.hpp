@@ -108,6 +108,10 @@ constexpr int DIFFUSION_NOTSUP = BOUNDED_FLAGS | KERNEL_FLAGS | SWMHD_GM_IS_PREV
 // wall), so a direction with both its flags is an argument error; SWMHD_RK3_ANCHOR as for the diffusion calls
 constexpr int CORIOLIS_FLAGS = SWMHD_STRICT | WRAP_FLAGS | BOUNDED_FLAGS | SWMHD_RK3_ANCHOR;
 constexpr int CORIOLIS_NOTSUP = KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLAGS | SWMHD_LEAVE_ROOM;
+// swmhd_relaxation_rk3 and its ensemble form: radius 0, so neither the WRAP nor the Bounded flags mean anything to it; both are accepted,
+// a direction with both its flags is an argument error as everywhere; SWMHD_RK3_ANCHOR as for the diffusion calls
+constexpr int RELAXATION_FLAGS = SWMHD_STRICT | WRAP_FLAGS | BOUNDED_FLAGS | SWMHD_RK3_ANCHOR;
+constexpr int RELAXATION_NOTSUP = KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLAGS | SWMHD_LEAVE_ROOM;
 // swmhd_ensemble_*: the periodic family, and the boundary-condition family (swmhd_ensemble_fill_halo, swmhd_ensemble_step_rk3_bc),
 // which accepts Bounded directions and runs the stage in G- form
 constexpr int ENS_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | WRAP_FLAGS | SWMHD_RK3_ANCHOR;

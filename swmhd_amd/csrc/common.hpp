@@ -324,6 +324,23 @@ struct CoriolisArgs : StripArgs<T> {
 template <typename T> hipError_t launch_coriolis_fast(const CoriolisArgs<T> &a, hipStream_t s);
 template <typename T> hipError_t launch_coriolis_strict(const CoriolisArgs<T> &a, hipStream_t s);
 
+// Relaxation forcing (swmhd_relaxation_rk3_*, relaxation.hip): D_k = (rate_k mask_k) (target_k - old_k) of up to 4 + MAX_TRACERS fields in
+// ONE launch: nw[k] += a D_k and, where acc[k] != nullptr, acc[k] += w D_k.  mask[k] == nullptr: no mask; target[k] == nullptr: the scalar
+// tval[k].  An ensemble member's masks and targets stand at ptr + m * mask_stride_m / target_stride_m (0: shared), its rates and scalar
+// targets in the DEVICE tables rate_tab / tval_tab [m * nfields + k] (rate and tval are not read).
+constexpr int RELAXATION_MAX_FIELDS = 4 + MAX_TRACERS;   // = SWMHD_RELAXATION_MAX_FIELDS
+template <typename T>
+struct RelaxationArgs : StripArgs<T> {
+    const T *old[RELAXATION_MAX_FIELDS], *mask[RELAXATION_MAX_FIELDS], *target[RELAXATION_MAX_FIELDS];
+    T *nw[RELAXATION_MAX_FIELDS], *acc[RELAXATION_MAX_FIELDS];
+    T rate[RELAXATION_MAX_FIELDS], tval[RELAXATION_MAX_FIELDS];
+    int nfields;
+    long mask_stride_m, target_stride_m;
+    const T *rate_tab, *tval_tab;
+};
+template <typename T> hipError_t launch_relaxation_fast(const RelaxationArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_relaxation_strict(const RelaxationArgs<T> &a, hipStream_t s);
+
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
 // (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read

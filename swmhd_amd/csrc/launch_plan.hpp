@@ -432,13 +432,13 @@ inline TracerTiles tracer_tiles(int Nx, int rows, int K, int members) {
     return t;
 }
 
-// ---- the strips of one per-stage correction launch (strip_device.inc: coriolis.hip, diffusion.hip) -----------------------------------
+// ---- the strips of one per-stage correction launch (strip_device.inc: coriolis.hip, diffusion.hip, biharmonic.hip, relaxation.hip) -----------------------------------
 // A wave owns a strip of STRIP_WAVE lanes x vec columns and marches down STRIP_WAVE_ROWS rows of it; the STRIP_WAVES waves of a
 // workgroup are consecutive row segments of one strip.  vec = 16 bytes of elements where `phase` >= 0: the 16-byte phase (in elements)
 // that the interior pointers of all parents share and the pitches keep (common_phase) -- then the vector groups start `lead` = phase
 // columns left of x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  phase < 0: one element per lane.
-// blockIdx.x = (l nsb + sb) nstrips + strip, l < launches: the member (Coriolis), member x field (diffusion).
-constexpr int STRIP_WAVE = 64, STRIP_WAVES = 4, STRIP_WAVE_ROWS = 16;   // STRIP_WAVES STRIP_WAVE_ROWS = SWMHD_CORIOLIS_ / SWMHD_DIFFUSION_TILE_ROWS
+// blockIdx.x = (l nsb + sb) nstrips + strip, l < launches: the member (Coriolis), member x field (diffusion, biharmonic, relaxation).
+constexpr int STRIP_WAVE = 64, STRIP_WAVES = 4, STRIP_WAVE_ROWS = 16;   // STRIP_WAVES STRIP_WAVE_ROWS = SWMHD_CORIOLIS_ / SWMHD_DIFFUSION_ / SWMHD_RELAXATION_TILE_ROWS
 struct StripPlan {
     int vec, lead;
     int nstrips, nsb; // strips of 64 vec columns x blocks of STRIP_WAVES row segments, of one of the launches

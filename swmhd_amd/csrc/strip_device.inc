@@ -1,8 +1,8 @@
-// What the per-stage correction launches (diffusion.hip, coriolis.hip, biharmonic.hip) share, stated once; included inside their anonymous namespace,
+// What the per-stage correction launches (diffusion.hip, coriolis.hip, biharmonic.hip, relaxation.hip) share, stated once; included inside their anonymous namespace,
 // after common.hpp and launch_plan.hpp.  A wave owns a strip of STRIP_WAVE lanes x VEC columns and marches down STRIP_WAVE_ROWS rows of
 // it, VEC = 16 bytes of elements per lane where every pointer of the call has the same 16-byte phase and the pitches keep it (else
 // VEC = 1): launch_plan.hpp strip_plan.  No LDS, no barrier: the STRIP_WAVES waves of a workgroup are consecutive row segments of one
-// strip.  Here: the strict / fast switch and the launcher's name, the vector access, the strip of one lane (Strip; Strip2 for a stencil of radius 2), the decoding of
+// strip.  Here: the strict / fast switch and the launcher's name, the vector access, the strip of one lane (Strip; Strip2 for a stencil of radius 2, Strip0 for a term of radius 0), the decoding of
 // blockIdx.x (strip_block), the per-member scalars (strip_scalars), and the host's plan and pick of an instantiation.  The carried
 // rows and the arithmetic are each kernel's own.
 #ifndef SWMHD_STRIP_STRICT
@@ -191,6 +191,45 @@ struct Strip2 {
     }
     __device__ __forceinline__ void store_out(T *p, const T (&v)[VEC]) const {
         if (full) {
+            vec_store<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                if (inside[e]) p[xv + e] = v[e];
+        }
+    }
+};
+
+// Strip for a term of radius 0 (relaxation.hip): the same lanes, groups and lead, no neighbour column and no halo -- every stream of the
+// call is read and written at the lane's own columns inside [0, Nx) and nowhere else.  full: the whole group lies inside (one 16-byte
+// access); any: at least one of its columns does.  The caller decides FULL once per lane, outside its row loop.
+template <typename T, int VEC>
+struct Strip0 {
+    int xv;
+    bool full, any;
+    bool inside[VEC];
+
+    __device__ __forceinline__ Strip0(int Nx, int strip, int lane, int lead) : xv((strip * STRIP_WAVE + lane) * VEC - lead) {
+        full = xv >= 0 && xv + VEC <= Nx;
+        any = false;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            inside[e] = xv + e >= 0 && xv + e < Nx;
+            any = any || inside[e];
+        }
+    }
+    template <bool FULL>
+    __device__ __forceinline__ void load(const T *p, T (&v)[VEC]) const {   // p: a row
+        if constexpr (FULL) {
+            vec_load<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
+        }
+    }
+    template <bool FULL>
+    __device__ __forceinline__ void store(T *p, const T (&v)[VEC]) const {
+        if constexpr (FULL) {
             vec_store<T, VEC>(p + xv, v);
         } else {
 #pragma unroll

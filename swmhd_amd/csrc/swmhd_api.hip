@@ -333,6 +333,67 @@ int coriolis_common(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const 
     return hiprc(fl.strict ? launch_coriolis_strict<T>(c, s) : launch_coriolis_fast<T>(c, s));
 }
 
+// swmhd_relaxation_rk3: nw[k] += a D_k, acc[k] += w D_k with D_k = (rate[k] mask[k]) (target[k] - old[k]) of up to
+// SWMHD_RELAXATION_MAX_FIELDS fields in one launch (relaxation.hip).  Every check precedes the first HIP call, in the order
+// include/swmhd_relaxation.h states.  With `ens` (swmhd_ensemble_relaxation_rk3): `rate` and `tval` are the DEVICE tables of members x
+// nfields values and are not looked at; mask_sm / target_sm pitch the members' masks and targets (0: shared); ens->params (optional)
+// brings every member's dt.  The ensemble's own argument errors come first.  One grid: the fields with rate == 0 are left out of the
+// launch here.
+template <typename T>
+int relaxation_common(const T *const *old, T *const *nw, T *const *acc, const T *const *mask, const T *const *target, const T *rate,
+                      const T *tval, int nfields, const Grid &g, T a, T w, const Rows &r, int flags, void *stream, const Ens *ens = nullptr,
+                      int64_t mask_sm = 0, int64_t target_sm = 0) {
+    if (ens) {
+        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
+        if (g.Ny <= 0 || g.Hy < 0 || g.sy <= 0 || ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
+        if ((mask_sm != 0 && mask_sm < g.min_member_stride()) || (target_sm != 0 && target_sm < g.min_member_stride())) return SWMHD_EINVAL;
+    }
+    if (!old || !nw || !rate || !tval) return SWMHD_EINVAL;
+    if (nfields < 1 || nfields > SWMHD_RELAXATION_MAX_FIELDS) return SWMHD_EINVAL;
+    if (!g.extents_ok() || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
+    if ((flags & ~(RELAXATION_FLAGS | RELAXATION_NOTSUP)) || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
+    for (int k = 0; k < nfields; ++k)
+        if (!old[k] || !nw[k]) return SWMHD_EINVAL;
+    for (int k = 0; k < nfields; ++k) {
+        const T *const ak = acc ? acc[k] : nullptr;
+        if (ak == nw[k]) return SWMHD_EINVAL;
+        for (int m = 0; m < nfields; ++m) {
+            const T *const in[3] = {old[m], mask ? mask[m] : nullptr, target ? target[m] : nullptr};
+            for (const T *p : in)
+                if (p && (nw[k] == p || ak == p)) return SWMHD_EINVAL;   // (radius 0, but a shared mask or target is read by other fields' workgroups)
+            if (m != k && (nw[k] == nw[m] || (ak && (ak == nw[m] || ak == acc[m])))) return SWMHD_EINVAL;
+        }
+    }
+    if (!ens)
+        for (int k = 0; k < nfields; ++k)
+            if (!isfinite((double)rate[k]) || rate[k] < T(0) || !isfinite((double)tval[k])) return SWMHD_EINVAL;
+    if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
+    if (flags & RELAXATION_NOTSUP) return SWMHD_ENOTSUP;
+    const Flags fl = decode_flags(flags);
+    if (r.j0 == r.j1) return SWMHD_OK;
+    RelaxationArgs<T> d;
+    int n = 0;
+    for (int k = 0; k < nfields; ++k) {
+        if (!ens && rate[k] == T(0)) continue;
+        d.old[n] = g.interior(old[k]); d.nw[n] = g.interior(nw[k]);
+        d.acc[n] = (acc && acc[k]) ? g.interior(acc[k]) : nullptr;
+        d.mask[n] = (mask && mask[k]) ? g.interior(mask[k]) : nullptr;
+        d.target[n] = (target && target[k]) ? g.interior(target[k]) : nullptr;
+        d.rate[n] = ens ? T(0) : rate[k]; d.tval[n] = ens ? T(0) : tval[k];
+        ++n;
+    }
+    if (n == 0) return SWMHD_OK;
+    for (int k = n; k < RELAXATION_MAX_FIELDS; ++k) {
+        d.old[k] = nullptr; d.nw[k] = nullptr; d.acc[k] = nullptr; d.mask[k] = nullptr; d.target[k] = nullptr; d.rate[k] = T(0); d.tval[k] = T(0);
+    }
+    set_strip(d, g, r, fl, a, w, ens);
+    d.wrap = 0;   // (nothing around a cell is read)
+    d.nfields = n; d.mask_stride_m = ens ? (long)mask_sm : 0; d.target_stride_m = ens ? (long)target_sm : 0;
+    d.rate_tab = ens ? rate : nullptr; d.tval_tab = ens ? tval : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    return hiprc(fl.strict ? launch_relaxation_strict<T>(d, s) : launch_relaxation_fast<T>(d, s));
+}
+
 // The RK3 step driver.  Periodic: stages in anchor form (fast) and a periodic fill of whatever the kernel does not wrap.  Bounded
 // ensembles (ens->bc, swmhd_ensemble_step_rk3_bc): ShallowWaterModel.time_step's Bounded schedule -- every stage in G- form, then the
 // boundary-condition fill of the four fields, gradient values from the DEVICE table bc_gradient.  ph: the model and dt.
@@ -697,5 +758,24 @@ SWMHD_DEF_BIHARMONIC(f32, float)
 
 SWMHD_DEF_CORIOLIS(f64, double)
 SWMHD_DEF_CORIOLIS(f32, float)
+
+// include/swmhd_relaxation.h
+#define SWMHD_DEF_RELAXATION(sfx, T)                                                                                                                   \
+    int swmhd_relaxation_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *const *mask, const T *const *target, const T *rate,     \
+                                   const T *tval, int nfields, int Nx, int Ny, int Hx, int Hy, int64_t sy, T a, T w, int j0, int j1, int flags,       \
+                                   void *stream) {                                                                                                    \
+        return relaxation_common<T>(old, nw, acc, mask, target, rate, tval, nfields, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags, stream);    \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_relaxation_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *const *mask, const T *const *target,           \
+                                            const T *rate, const T *tval, int nfields, int members, int64_t stride_m, int64_t mask_stride_m,          \
+                                            int64_t target_stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, const T *params, T a, T w, int j0,   \
+                                            int j1, int flags, void *stream) {                                                                        \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return relaxation_common<T>(old, nw, acc, mask, target, rate, tval, nfields, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags, stream,     \
+                                    &e, mask_stride_m, target_stride_m);                                                                              \
+    }
+
+SWMHD_DEF_RELAXATION(f64, double)
+SWMHD_DEF_RELAXATION(f32, float)
 
 }  // extern "C"

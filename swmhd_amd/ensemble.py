@@ -19,6 +19,7 @@ from . import _lib
 from .closure import check_closure, closure_for_member
 from .coriolis import check_coriolis, row_table
 from .fields import _SFX, _stream_ptr
+from .forcing import check_forcing, device_parents, forcing_for_member
 from .grid import Center, Face
 from .model import ShallowWaterModel, rk3_operands, rk3_stage, tracer_names
 from .shared import (VectorInvariantFormulation, check_boundary_conditions, correction_operand, diagnostics_dict, fill_groups,
@@ -69,11 +70,18 @@ class ShallowWaterEnsemble:
     for all members (swmhd_ensemble_diffusion_rk3_*), under a scalar or a per-member dt.  Without a closure, or with coefficients
     that are all 0, the ensemble calls exactly what it calls without the argument.  `closure=ScalarBiharmonicDiffusivity(...)`, or a
     tuple with one of each kind, likewise: `biharmonic_coefficients` is its device table, its launch (swmhd_ensemble_biharmonic_rk3_*)
-    follows the Laplacian's."""
+    follows the Laplacian's.
+
+    Forcing: `forcing={"u": Relaxation(rate, mask, target), ...}` (ShallowWaterModel's argument; swmhd_amd.forcing) with a scalar or one
+    value per member for every rate and scalar target, and masks and target arrays of shape (Ny, Nx) for all members or (members, Ny,
+    Nx) -- a sweep of the drag.  `relaxation_rates` and `relaxation_targets` are the (members, forced fields) device tables; such an
+    ensemble steps stage by stage with one more launch per stage for all members (swmhd_ensemble_relaxation_rk3_*), after the
+    closures' launches, under a scalar or a per-member dt.  Without a forcing, or with rates that are all 0, the ensemble calls exactly
+    what it calls without the argument."""
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, tracers=(), closure=None, coriolis=None):
+                 fuse_halo=True, tracers=(), closure=None, coriolis=None, forcing=None):
         self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
         # coriolis = FPlane | BetaPlane | CoriolisProfile (ShallowWaterModel's argument; values may be per member).  None and FPlane: the
         # f of the stage kernels.  Otherwise they get f = 0 and _coriolis holds the parameter whose rows _coriolis_stage adds
@@ -99,6 +107,9 @@ class ShallowWaterEnsemble:
         coefs4 = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs4 or {}).items()}
         self._biharmonic = {n: c for n, c in coefs4.items() if np.any(c != 0.0)} or None
         rows = row_table(self._coriolis, grid, self.members) if self._coriolis is not None else None
+        # the forcing: names, shapes, values and refusals, the callables evaluated; the fields all of whose rates are 0 have no launch
+        self.forcing = forcing
+        relax = check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, self.members)
         self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
         self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
         self.grid = grid
@@ -147,6 +158,24 @@ class ShallowWaterEnsemble:
         self.coriolis_rows = None
         if rows is not None:
             self.coriolis_rows = torch.from_numpy(rows).to(device=self._state[0].device, dtype=dtype)
+        # the forcing on the device: (members, forced fields) tables of rates and scalar targets, and every mask and target array as
+        # parents of the fields' shape and pitch -- (Py, Px) shared by all members where none of that kind is per member (member stride
+        # 0), else (members, Py, Px) each: the call has one member stride for the masks and one for the targets
+        self._relaxation, self.relaxation_rates, self.relaxation_targets = None, None, None
+        if relax is not None:
+            dev = self._state[0].device
+
+            def parents(arrs):
+                per = any(a is not None and a.ndim == 3 for a in arrs)
+                arrs = [np.broadcast_to(a, (self.members,) + a.shape[-2:]) if (per and a is not None) else a for a in arrs]
+                return [device_parents(grid, a, dtype, dev) for a in arrs], (Py * Px if per else 0)
+            masks, self._mask_stride = parents([m for _, _, m, _ in relax])
+            targets, self._target_stride = parents([t if np.ndim(t) >= 2 else None for _, _, _, t in relax])
+            tvals = [np.zeros(self.members) if np.ndim(t) >= 2 else np.broadcast_to(np.asarray(t, dtype=np.float64), (self.members,))
+                     for _, _, _, t in relax]
+            table = lambda cols: torch.from_numpy(np.ascontiguousarray(np.stack(cols, axis=1))).to(device=dev, dtype=dtype)
+            self.relaxation_rates, self.relaxation_targets = table([r for _, r, _, _ in relax]), table(tvals)
+            self._relaxation = [(n, m, t) for (n, _, _, _), m, t in zip(relax, masks, targets)]
         if g_seq or f_seq:
             self._make_parameters()
 
@@ -335,8 +364,11 @@ class ShallowWaterEnsemble:
         _diffusion_stage (finish_stage): ShallowWaterModel._biharmonic_stage with the coefficients of member m in row m of the table."""
         self._closure_stage(dt, stage, self._closure_names(self._biharmonic), self.biharmonic_coefficients, "swmhd_ensemble_biharmonic_rk3")
 
-    def _closure_stage(self, dt, stage, names, table, call):
-        g = self.grid
+    def _correction_call(self, names, dt, stage):
+        """What the per-stage correction launches over the fields `names` (closures, forcing) pass alike: (old, new, acc) pointer arrays
+        of the state and tracers the stage started from, of what it wrote and -- where the stage stores an operand for later stages,
+        else None -- of that operand; params (the table's pointer with dt None, else None); a (gamma with the table, else dt gamma);
+        w; and the flags (shared.correction_operand)."""
         gamma = rk3_stage(stage, self._anchor)[0]
         cur = {**dict(zip(self.names, self._state)), **self._tr}
         new = {**dict(zip(self.names, self._alt)), **self._tr_alt}
@@ -344,12 +376,31 @@ class ShallowWaterEnsemble:
         par = dt is None
         has, w, flag = correction_operand(stage, self._anchor, dt)
         acc = self._ptrs([Gn[n] for n in names]) if has else None
+        return (self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc,
+                self.parameters.data_ptr() if par else None, gamma if par else dt * gamma, w, self._flags | self._rwrap | flag)
+
+    def _closure_stage(self, dt, stage, names, table, call):
+        g = self.grid
+        old, new, acc, params, a, w, flags = self._correction_call(names, dt, stage)
         f = getattr(self._L, f"{call}_{self.sfx}")
-        rc = f(self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc, table.data_ptr(),
-               len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), g.dx, g.dy,
-               self.parameters.data_ptr() if par else None, gamma if par else dt * gamma, w, 0, g.Ny,
-               self._flags | self._rwrap | flag, _stream_ptr())
+        rc = f(old, new, acc, table.data_ptr(), len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy,
+               self._state[0].stride(1), g.dx, g.dy, params, a, w, 0, g.Ny, flags, _stream_ptr())
         _lib.check(rc, call)
+
+    def _relaxation_stage(self, dt, stage):
+        """The forcing's launch of RK3 stage `stage` for every member (swmhd_ensemble_relaxation_rk3_*; with dt None every member's dt
+        comes from the table): ShallowWaterModel._relaxation_stage with the rate and the scalar target of member m in row m of the
+        device tables, its masks and targets at their member strides (0: shared).  After _biharmonic_stage and BEFORE the swaps
+        (finish_stage): the new field is ((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax)."""
+        g = self.grid
+        rel = self._relaxation
+        old, new, acc, params, a, w, flags = self._correction_call([n for n, _, _ in rel], dt, stage)
+        optional = lambda ts: _lib.ptr_array([t.data_ptr() if t is not None else None for t in ts])
+        f = getattr(self._L, f"swmhd_ensemble_relaxation_rk3_{self.sfx}")
+        rc = f(old, new, acc, optional([m for _, m, _ in rel]), optional([t for _, _, t in rel]), self.relaxation_rates.data_ptr(),
+               self.relaxation_targets.data_ptr(), len(rel), self.members, self.stride_m, self._mask_stride, self._target_stride,
+               g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), params, a, w, 0, g.Ny, flags, _stream_ptr())
+        _lib.check(rc, "swmhd_ensemble_relaxation_rk3")
 
     def _stage_steps(self, dt, n):
         """n steps stage by stage (dt: the scalar, or None for the table).  Without fused halos every stage ends with the periodic fill
@@ -380,7 +431,7 @@ class ShallowWaterEnsemble:
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        if self._tr or self._diffusion is not None or self._biharmonic is not None or self._coriolis is not None:        # (the native step driver steps the four fields only, with a scalar f)
+        if self._tr or self._diffusion is not None or self._biharmonic is not None or self._coriolis is not None or self._relaxation is not None:        # (the native step driver steps the four fields only, with a scalar f)
             self._stage_steps(dt if dts is None else None, n)
         else:
             self._enqueue_steps(dt if dts is None else None, n, swapped)
@@ -530,7 +581,8 @@ class ShallowWaterEnsemble:
         f = {"coriolis_f": float(self.f_values[m])} if self._coriolis is None else {"coriolis": self._coriolis.for_member(m)}
         return ShallowWaterModel(self.grid, float(self.g_values[m]), formulation=self.formulation,
                                  lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
-                                 tracers=self.tracer_names, closure=closure_for_member(self.closure, m), **f)
+                                 tracers=self.tracer_names, closure=closure_for_member(self.closure, m),
+                                 forcing=forcing_for_member(self.forcing, m), **f)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
@@ -549,8 +601,10 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None):
+                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None, forcing=None):
         coriolis_f, varying = check_coriolis(coriolis, coriolis_f, 1.0)       # before anything is allocated
+        check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], tracer_names(tracers), int(members),
+                      bounded_ensemble=True)       # (None and {} pass; anything else is refused before anything is allocated)
         if varying is not None:
             raise _lib.SwmhdError("coriolis = f(y) on a Bounded ensemble is not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is "
                                   "one native call and has no per-stage entry point for the correction launch")

@@ -18,6 +18,7 @@ from .closure import check_closure
 from .coriolis import check_coriolis, row_table
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
+from .forcing import check_forcing, device_parents
 from .grid import Center, Face
 from .shared import (RK3_GAMMA, RK3_ZETA, ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions,
                      correction_operand, diagnostics_dict, fill_groups, finish_stage, formulation_codes, gradient_values, rk3_stage)
@@ -69,7 +70,7 @@ class ShallowWaterModel:
     def __init__(self, grid, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, device="cuda", strict=False, decomp=None, group=None,
                  overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None,
-                 tracers=(), closure=None, coriolis=None):
+                 tracers=(), closure=None, coriolis=None, forcing=None):
         # coriolis = FPlane | BetaPlane | CoriolisProfile (swmhd_amd.coriolis), checked before anything is allocated.  None and FPlane:
         # the scalar f of the stage kernels, exactly the calls made without the argument.  Otherwise the stage kernels get f = 0 and
         # _coriolis holds the parameter whose rows _coriolis_stage adds after every stage
@@ -98,6 +99,12 @@ class ShallowWaterModel:
                                       decomp is not None and decomp.world_size > 1, ring is not None, fused)
         self._diffusion = {n: float(c) for n, c in (coefs or {}).items() if float(c) != 0.0} or None
         self._biharmonic = {n: float(c) for n, c in (coefs4 or {}).items() if float(c) != 0.0} or None
+        # forcing = {"u": Relaxation(...), "h": ..., "c": ...}: names, shapes, values and refusals are checked, and the callables
+        # evaluated, before anything is allocated too.  _relaxation: the forced fields with a rate, in the order of the launch; None
+        # without a forcing and with one whose rates are all 0, and then the model makes exactly the calls it makes without it
+        self.forcing = forcing
+        relax = check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, None,
+                              decomp is not None and decomp.world_size > 1, ring is not None, fused)
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code, self.lorentz_code, self.names = formulation_codes(formulation, lorentz_forcing)
@@ -157,6 +164,13 @@ class ShallowWaterModel:
         self.coriolis_rows = None
         if rows is not None:
             self.coriolis_rows = torch.from_numpy(rows).to(device=self._raw_fields[0].data.device, dtype=dtype)
+        # (name, rate, mask, target) of every forced field: mask and target arrays on the device as parents of the fields' shape and
+        # pitch, in the model's dtype and rounded to it (None: no mask; a float: a scalar target); built once
+        self._relaxation = None
+        if relax is not None:
+            dev = self._raw_fields[0].data.device
+            up = lambda a: device_parents(grid, a, dtype, dev)
+            self._relaxation = [(n, float(r), up(m), up(t) if np.ndim(t) else float(t)) for n, r, m, t in relax]
         # y-slab ring: the native RCCL ring (swmhd_ring_*) when the process group is RCCL; torch.distributed p2p otherwise
         # (gloo rehearsals).  The ring's step driver needs the fused stage kernel and a slab taller than its two strips.
         # `ring`: a swmhd_ring handle created by the caller -- one of swmhd_ring_create_loopback's (loopback_rings below): several
@@ -426,23 +440,51 @@ class ShallowWaterModel:
         ((stage + a D_laplacian) + a D_biharmonic), and that order decides the last bits."""
         self._closure_stage(dt, stage, self._biharmonic, "swmhd_biharmonic_rk3")
 
-    def _closure_stage(self, dt, stage, coefs, call):
-        g = self.grid
+    def _correction_call(self, names, dt, stage):
+        """What the per-stage correction launches over the fields `names` (closures, forcing) pass alike: (old, new, acc) pointer arrays
+        of the state and tracers the stage started from, of what it wrote and -- where the stage stores an operand for later stages,
+        else None -- of that operand; a = dt gamma; w; and the flags (shared.correction_operand)."""
         P = _lib.ptr_array
         gamma = rk3_stage(stage, self._anchor)[0]
-        names = [n for n in self.names + self.tracer_names if n in coefs]
         cur = {**self._state, **self._tr}
         new = {**self._alt, **self._tr_alt}
         Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
         has, w, _ = correction_operand(stage, self._anchor, dt)
         acc = P([Gn[n].ptr for n in names]) if has else None
+        return (P([cur[n].ptr for n in names]), P([new[n].ptr for n in names]), acc, dt * gamma, w,
+                (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap)
+
+    def _closure_stage(self, dt, stage, coefs, call):
+        g = self.grid
+        names = [n for n in self.names + self.tracer_names if n in coefs]
+        old, new, acc, a, w, flags = self._correction_call(names, dt, stage)
         ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
         coef = (ft * len(names))(*[coefs[n] for n in names])
         f = getattr(self._L, f"{call}_{self.sfx}")
-        rc = f(P([cur[n].ptr for n in names]), P([new[n].ptr for n in names]), acc, coef, len(names), g.Nx, g.Ny, g.Hx, g.Hy,
-               self._raw_fields[0].stride_y, g.dx, g.dy, dt * gamma, w, 0, g.Ny,
-               (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap, _stream_ptr())
+        rc = f(old, new, acc, coef, len(names), g.Nx, g.Ny, g.Hx, g.Hy, self._raw_fields[0].stride_y, g.dx, g.dy, a, w, 0, g.Ny,
+               flags, _stream_ptr())
         _lib.check(rc, call)
+
+    def _relaxation_stage(self, dt, stage):
+        """The forcing's launch of RK3 stage `stage` (swmhd_relaxation_rk3_*): D = rate mask (target - field) on the state the stage
+        started from, for every forced field, added with dt gamma to the new state (and tracers) and, where the stage stores an
+        operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
+        the anchor form) -- shared.correction_operand.  Order (finish_stage): after _stage_fused, _tracer_stage, _coriolis_stage,
+        _diffusion_stage and _biharmonic_stage and BEFORE the swaps: the new field is
+        ((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax), and that order decides the last bits.  It reads no halo, so a
+        Bounded grid takes it as a periodic one does; the wall line of the wall-normal velocity is reset by the fill that follows."""
+        g = self.grid
+        P = _lib.ptr_array
+        rel = self._relaxation
+        old, new, acc, a, w, flags = self._correction_call([n for n, _, _, _ in rel], dt, stage)
+        dptr = lambda t: t.data_ptr() if torch.is_tensor(t) else None
+        ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
+        rate = (ft * len(rel))(*[r for _, r, _, _ in rel])
+        tval = (ft * len(rel))(*[0.0 if torch.is_tensor(t) else t for _, _, _, t in rel])
+        f = getattr(self._L, f"swmhd_relaxation_rk3_{self.sfx}")
+        rc = f(old, new, acc, P([dptr(m) for _, _, m, _ in rel]), P([dptr(t) for _, _, _, t in rel]), rate, tval, len(rel),
+               g.Nx, g.Ny, g.Hx, g.Hy, self._raw_fields[0].stride_y, a, w, 0, g.Ny, flags, _stream_ptr())
+        _lib.check(rc, "swmhd_relaxation_rk3")
 
     # --- time_step!(model, dt): RungeKutta3 ------------------------------------------------------------------
     def _native_steps(self, dt, n):
@@ -577,7 +619,7 @@ class ShallowWaterModel:
     def _driver_steps(self, dt, n):
         if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)
                                       and not self._tr and self._diffusion is None and self._biharmonic is None
-                                      and self._coriolis is None):     # (the native step driver steps the four fields only, with a scalar f)
+                                      and self._coriolis is None and self._relaxation is None):     # (the native step driver steps the four fields only, with a scalar f)
             return self._native_steps(dt, n)
         for _ in range(n):
             self.time_step(dt)
