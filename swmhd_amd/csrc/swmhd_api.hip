@@ -3,6 +3,7 @@
 #include "../../include/swmhd.h"
 #include "api_args.hpp"
 #include "common.hpp"
+#include <initializer_list>
 #include <math.h>
 
 using namespace swmhd;
@@ -224,7 +225,60 @@ int tracers_common(const T *const *q, const T *const *c, T *const *cnew, T *cons
     return hiprc(fl.strict ? launch_tracers_strict<T>(a, form, s) : launch_tracers_fast<T>(a, form, s));
 }
 
-// what the two per-stage correction calls pass on alike (StripArgs, common.hpp)
+// ---- what the per-stage correction calls share (swmhd_coriolis_rk3, swmhd_diffusion_rk3, swmhd_biharmonic_rk3, swmhd_relaxation_rk3) ----
+// Every check here answers SWMHD_EINVAL, and every SWMHD_EINVAL check of those calls precedes their other answers (SWMHD_ENOTSUP, then
+// SWMHD_EHALO, then "nothing to do"), so the order among these is not observable (tests/golden/correction_return_codes.json holds the rest).
+// member count and member strides: of the parents, then of a call's per-member masks and targets (0: one for all members); none: a single grid
+bool correction_members_ok(const Ens *ens, const Grid &g, int64_t mask_sm = 0, int64_t target_sm = 0) {
+    if (!ens) return true;
+    const int64_t need = g.min_member_stride();
+    return ens->members >= 1 && ens->members <= SWMHD_ENSEMBLE_MAX_MEMBERS && ens->stride_m >= need && (mask_sm == 0 || mask_sm >= need) &&
+           (target_sm == 0 || target_sm >= need);
+}
+// no output is an input -- other workgroups still read old around their rows, and a mask or target may be shared by several fields -- or
+// another output; a null entry is an absent one
+template <typename T>
+bool outputs_apart(const T *const *out, int nout, const T *const *in, int nin) {
+    for (int k = 0; k < nout; ++k) {
+        if (!out[k]) continue;
+        for (int m = 0; m < nin; ++m)
+            if (out[k] == in[m]) return false;
+        for (int m = 0; m < k; ++m)
+            if (out[k] == out[m]) return false;
+    }
+    return true;
+}
+// a correction over a list of fields: what it reads, what the stage wrote and (optional, as is each of its entries) the stored operand
+template <typename T>
+struct FieldSets {
+    const T *const *old;
+    T *const *nw, *const *acc;
+    int nfields;
+};
+// the checks of such a call, the values of its host tables apart: sets and entries present, 1 .. max_fields fields, members, grid, rows,
+// flags among `known`, a and w finite, outputs apart from old and from the `read_only` lists (at most two; a null list is absent)
+template <typename T>
+bool field_correction_ok(const FieldSets<T> &f, int max_fields, std::initializer_list<const T *const *> read_only, const Grid &g, T a, T w,
+                         const Rows &r, int flags, int known, const Ens *ens, int64_t mask_sm = 0, int64_t target_sm = 0) {
+    constexpr int CAP = SWMHD_RELAXATION_MAX_FIELDS;
+    static_assert(CAP >= SWMHD_DIFFUSION_MAX_FIELDS, "the call with the longest list sizes the arrays below");
+    if (!f.old || !f.nw || f.nfields < 1 || f.nfields > max_fields || max_fields > CAP || read_only.size() > 2) return false;
+    if (!correction_members_ok(ens, g, mask_sm, target_sm)) return false;
+    if (!g.extents_ok() || !g.spacing_ok() || !g.rows_ok(r.j0, r.j1) || (flags & ~known)) return false;
+    if (!isfinite((double)a) || !isfinite((double)w)) return false;
+    const T *out[2 * CAP], *in[3 * CAP];
+    int nin = 0;
+    for (int k = 0; k < f.nfields; ++k) {
+        if (!f.old[k] || !f.nw[k]) return false;
+        out[2 * k] = f.nw[k]; out[2 * k + 1] = f.acc ? f.acc[k] : nullptr;
+        in[nin++] = f.old[k];
+        for (const T *const *list : read_only)
+            if (list) in[nin++] = list[k];
+    }
+    return outputs_apart<T>(out, 2 * f.nfields, in, nin);
+}
+
+// what the per-stage correction calls pass on alike (StripArgs, common.hpp)
 template <typename T>
 void set_strip(StripArgs<T> &s, const Grid &g, const Rows &r, const Flags &fl, T a, T w, const Ens *ens) {
     s.Nx = g.Nx; s.Ny = g.Ny; s.j0 = r.j0; s.j1 = r.j1; s.wrap = fl.wrap; s.sy = (long)g.sy; s.a = a; s.w = w;
@@ -232,52 +286,47 @@ void set_strip(StripArgs<T> &s, const Grid &g, const Rows &r, const Flags &fl, T
     s.params = ens ? static_cast<const T *>(ens->params) : nullptr;
 }
 
+// The fields of `f` that live(k) keeps, packed to the front of d.old, d.nw and d.acc (DiffusionArgs, RelaxationArgs) at interior cell
+// (1,1), the slots behind them nulled.  more(slot, k): what else field k brings into its slot; k < 0: the slot is unused.  Returns the
+// number of fields kept.
+template <typename Args, typename T, typename Live, typename More>
+int pack_fields(Args &d, int slots, const FieldSets<T> &f, const Grid &g, Live live, More more) {
+    int n = 0;
+    for (int k = 0; k < f.nfields; ++k) {
+        if (!live(k)) continue;
+        d.old[n] = g.interior(f.old[k]); d.nw[n] = g.interior(f.nw[k]);
+        d.acc[n] = (f.acc && f.acc[k]) ? g.interior(f.acc[k]) : nullptr;
+        more(n++, k);
+    }
+    for (int k = n; k < slots; ++k) {
+        d.old[k] = nullptr; d.nw[k] = nullptr; d.acc[k] = nullptr;
+        more(k, -1);
+    }
+    return n;
+}
+
 // swmhd_diffusion_rk3: nw[k] += a coef[k] laplace(old[k]), acc[k] += w coef[k] laplace(old[k]) of up to SWMHD_DIFFUSION_MAX_FIELDS fields in
 // one launch (diffusion.hip).  Every check precedes the first HIP call.  With `ens` (swmhd_ensemble_diffusion_rk3): `coef` is the DEVICE
-// table of members x nfields values and is not looked at; ens->params (optional) brings every member's dt.  The ensemble's own
-// argument errors come first.  One grid: the fields with coef == 0 are left out of the launch here.
+// table of members x nfields values and is not looked at; ens->params (optional) brings every member's dt.  One grid: the fields with
+// coef == 0 are left out of the launch here.
 // radius: 1 the Laplacian (diffusion_common), 2 the biharmonic operator (biharmonic_common, below): the halo a direction without its
 // WRAP flag needs, and the launcher.  The checks and their order are the same for both.
 template <typename T>
 int stencil_closure_common(int radius, const T *const *old, T *const *nw, T *const *acc, const T *coef, int nfields, const Grid &g, T a, T w,
                            const Rows &r, int flags, void *stream, const Ens *ens) {
-    if (ens) {
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (g.Ny <= 0 || g.Hy < 0 || g.sy <= 0 || ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
-    }
-    if (!old || !nw || !coef) return SWMHD_EINVAL;
-    if (nfields < 1 || nfields > SWMHD_DIFFUSION_MAX_FIELDS) return SWMHD_EINVAL;
-    if (!g.extents_ok() || !g.spacing_ok() || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
-    if (flags & ~(DIFFUSION_FLAGS | DIFFUSION_NOTSUP)) return SWMHD_EINVAL;
-    for (int k = 0; k < nfields; ++k)
-        if (!old[k] || !nw[k]) return SWMHD_EINVAL;
-    for (int k = 0; k < nfields; ++k) {
-        const T *const ak = acc ? acc[k] : nullptr;
-        if (ak == nw[k]) return SWMHD_EINVAL;
-        for (int m = 0; m < nfields; ++m) {
-            if (nw[k] == old[m] || (ak && ak == old[m])) return SWMHD_EINVAL;   // other workgroups still read old around their rows (one row around, two for radius 2)
-            if (m != k && (nw[k] == nw[m] || (ak && (ak == nw[m] || ak == acc[m])))) return SWMHD_EINVAL;
-        }
-    }
+    const FieldSets<T> f{old, nw, acc, nfields};
+    if (!coef || !field_correction_ok<T>(f, SWMHD_DIFFUSION_MAX_FIELDS, {}, g, a, w, r, flags, DIFFUSION_FLAGS | DIFFUSION_NOTSUP, ens)) return SWMHD_EINVAL;
     if (!ens)
         for (int k = 0; k < nfields; ++k)
             if (!isfinite((double)coef[k]) || coef[k] < T(0)) return SWMHD_EINVAL;
-    if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
     if (flags & DIFFUSION_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
     if ((g.Hx < radius && !(fl.wrap & 1)) || (g.Hy < radius && !(fl.wrap & 2))) return SWMHD_EHALO;
     if (r.j0 == r.j1) return SWMHD_OK;
     DiffusionArgs<T> d;
-    int n = 0;
-    for (int k = 0; k < nfields; ++k) {
-        if (!ens && coef[k] == T(0)) continue;
-        d.old[n] = g.interior(old[k]); d.nw[n] = g.interior(nw[k]);
-        d.acc[n] = (acc && acc[k]) ? g.interior(acc[k]) : nullptr;
-        d.coef[n] = ens ? T(0) : coef[k];
-        ++n;
-    }
+    const int n = pack_fields(d, DIFFUSION_MAX_FIELDS, f, g, [&](int k) { return ens || coef[k] != T(0); },
+                              [&](int slot, int k) { d.coef[slot] = (ens || k < 0) ? T(0) : coef[k]; });
     if (n == 0) return SWMHD_OK;
-    for (int k = n; k < DIFFUSION_MAX_FIELDS; ++k) { d.old[k] = nullptr; d.nw[k] = nullptr; d.acc[k] = nullptr; d.coef[k] = T(0); }
     set_strip(d, g, r, fl, a, w, ens);
     d.nfields = n; d.dx = T(g.dx); d.dy = T(g.dy); d.coef_tab = ens ? coef : nullptr;
     hipStream_t s = (hipStream_t)stream;
@@ -309,17 +358,9 @@ int coriolis_common(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const 
     if ((flags & ~(CORIOLIS_FLAGS | CORIOLIS_NOTSUP)) || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
     const T *const in[2] = {q1, q2};
     const T *const out[4] = {n1, n2, a1, a2};
-    for (int k = 0; k < 4; ++k) {
-        if (!out[k]) continue;
-        if (out[k] == in[0] || out[k] == in[1]) return SWMHD_EINVAL;   // other workgroups still read old around their rows
-        for (int m = 0; m < k; ++m)
-            if (out[k] == out[m]) return SWMHD_EINVAL;
-    }
+    if (!outputs_apart<T>(out, 4, in, 2)) return SWMHD_EINVAL;
     if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
-    if (ens) {
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
-    }
+    if (!correction_members_ok(ens, g)) return SWMHD_EINVAL;
     if (flags & CORIOLIS_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
     if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
@@ -337,55 +378,29 @@ int coriolis_common(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const 
 // SWMHD_RELAXATION_MAX_FIELDS fields in one launch (relaxation.hip).  Every check precedes the first HIP call, in the order
 // include/swmhd_relaxation.h states.  With `ens` (swmhd_ensemble_relaxation_rk3): `rate` and `tval` are the DEVICE tables of members x
 // nfields values and are not looked at; mask_sm / target_sm pitch the members' masks and targets (0: shared); ens->params (optional)
-// brings every member's dt.  The ensemble's own argument errors come first.  One grid: the fields with rate == 0 are left out of the
-// launch here.
+// brings every member's dt.  One grid: the fields with rate == 0 are left out of the launch here.  (Radius 0, but a shared mask or
+// target is read by other fields' workgroups: no output may be one.)
 template <typename T>
 int relaxation_common(const T *const *old, T *const *nw, T *const *acc, const T *const *mask, const T *const *target, const T *rate,
                       const T *tval, int nfields, const Grid &g, T a, T w, const Rows &r, int flags, void *stream, const Ens *ens = nullptr,
                       int64_t mask_sm = 0, int64_t target_sm = 0) {
-    if (ens) {
-        if (ens->members < 1 || ens->members > SWMHD_ENSEMBLE_MAX_MEMBERS) return SWMHD_EINVAL;
-        if (g.Ny <= 0 || g.Hy < 0 || g.sy <= 0 || ens->stride_m < g.min_member_stride()) return SWMHD_EINVAL;
-        if ((mask_sm != 0 && mask_sm < g.min_member_stride()) || (target_sm != 0 && target_sm < g.min_member_stride())) return SWMHD_EINVAL;
-    }
-    if (!old || !nw || !rate || !tval) return SWMHD_EINVAL;
-    if (nfields < 1 || nfields > SWMHD_RELAXATION_MAX_FIELDS) return SWMHD_EINVAL;
-    if (!g.extents_ok() || !g.rows_ok(r.j0, r.j1)) return SWMHD_EINVAL;
-    if ((flags & ~(RELAXATION_FLAGS | RELAXATION_NOTSUP)) || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
-    for (int k = 0; k < nfields; ++k)
-        if (!old[k] || !nw[k]) return SWMHD_EINVAL;
-    for (int k = 0; k < nfields; ++k) {
-        const T *const ak = acc ? acc[k] : nullptr;
-        if (ak == nw[k]) return SWMHD_EINVAL;
-        for (int m = 0; m < nfields; ++m) {
-            const T *const in[3] = {old[m], mask ? mask[m] : nullptr, target ? target[m] : nullptr};
-            for (const T *p : in)
-                if (p && (nw[k] == p || ak == p)) return SWMHD_EINVAL;   // (radius 0, but a shared mask or target is read by other fields' workgroups)
-            if (m != k && (nw[k] == nw[m] || (ak && (ak == nw[m] || ak == acc[m])))) return SWMHD_EINVAL;
-        }
-    }
+    const FieldSets<T> f{old, nw, acc, nfields};
+    if (!rate || !tval || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
+    if (!field_correction_ok<T>(f, SWMHD_RELAXATION_MAX_FIELDS, {mask, target}, g, a, w, r, flags, RELAXATION_FLAGS | RELAXATION_NOTSUP, ens,
+                                mask_sm, target_sm)) return SWMHD_EINVAL;
     if (!ens)
         for (int k = 0; k < nfields; ++k)
             if (!isfinite((double)rate[k]) || rate[k] < T(0) || !isfinite((double)tval[k])) return SWMHD_EINVAL;
-    if (!isfinite((double)a) || !isfinite((double)w)) return SWMHD_EINVAL;
     if (flags & RELAXATION_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
     if (r.j0 == r.j1) return SWMHD_OK;
     RelaxationArgs<T> d;
-    int n = 0;
-    for (int k = 0; k < nfields; ++k) {
-        if (!ens && rate[k] == T(0)) continue;
-        d.old[n] = g.interior(old[k]); d.nw[n] = g.interior(nw[k]);
-        d.acc[n] = (acc && acc[k]) ? g.interior(acc[k]) : nullptr;
-        d.mask[n] = (mask && mask[k]) ? g.interior(mask[k]) : nullptr;
-        d.target[n] = (target && target[k]) ? g.interior(target[k]) : nullptr;
-        d.rate[n] = ens ? T(0) : rate[k]; d.tval[n] = ens ? T(0) : tval[k];
-        ++n;
-    }
+    const int n = pack_fields(d, RELAXATION_MAX_FIELDS, f, g, [&](int k) { return ens || rate[k] != T(0); }, [&](int slot, int k) {
+        d.mask[slot] = (k >= 0 && mask && mask[k]) ? g.interior(mask[k]) : nullptr;
+        d.target[slot] = (k >= 0 && target && target[k]) ? g.interior(target[k]) : nullptr;
+        d.rate[slot] = (ens || k < 0) ? T(0) : rate[k]; d.tval[slot] = (ens || k < 0) ? T(0) : tval[k];
+    });
     if (n == 0) return SWMHD_OK;
-    for (int k = n; k < RELAXATION_MAX_FIELDS; ++k) {
-        d.old[k] = nullptr; d.nw[k] = nullptr; d.acc[k] = nullptr; d.mask[k] = nullptr; d.target[k] = nullptr; d.rate[k] = T(0); d.tval[k] = T(0);
-    }
     set_strip(d, g, r, fl, a, w, ens);
     d.wrap = 0;   // (nothing around a cell is read)
     d.nfields = n; d.mask_stride_m = ens ? (long)mask_sm : 0; d.target_stride_m = ens ? (long)target_sm : 0;

@@ -18,12 +18,13 @@ import torch
 from . import _lib
 from .closure import check_closure, closure_for_member
 from .coriolis import check_coriolis, row_table
+from .corrections import correction_list, live_fields, member_table, needs_stages
 from .fields import _SFX, _stream_ptr
 from .forcing import check_forcing, device_parents, forcing_for_member
 from .grid import Center, Face
-from .model import ShallowWaterModel, rk3_operands, rk3_stage, tracer_names
-from .shared import (VectorInvariantFormulation, check_boundary_conditions, correction_operand, diagnostics_dict, fill_groups,
-                     finish_stage, formulation_codes, gradient_values)
+from .model import ShallowWaterModel, rk3_operands, tracer_names
+from .shared import (VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups, finish_stage,
+                     formulation_codes, gradient_values)
 
 LOCS = ((Face, Center), (Center, Face), (Center, Center), (Center, Center))
 
@@ -84,7 +85,7 @@ class ShallowWaterEnsemble:
                  fuse_halo=True, tracers=(), closure=None, coriolis=None, forcing=None):
         self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
         # coriolis = FPlane | BetaPlane | CoriolisProfile (ShallowWaterModel's argument; values may be per member).  None and FPlane: the
-        # f of the stage kernels.  Otherwise they get f = 0 and _coriolis holds the parameter whose rows _coriolis_stage adds
+        # f of the stage kernels.  Otherwise they get f = 0 and _coriolis holds the parameter whose rows a correction launch adds
         self.coriolis = coriolis
         coriolis_f, self._coriolis = check_coriolis(coriolis, coriolis_f, 1.0)
         self.closure = closure
@@ -102,10 +103,8 @@ class ShallowWaterEnsemble:
             raise _lib.SwmhdError(f"members = {members}: 1 .. {_lib.ENSEMBLE_MAX_MEMBERS}")
         # checked before anything touches a device
         # the closure's coefficients: a scalar or one value per member each; the fields all of whose values are 0 have no launch
-        coefs = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs or {}).items()}
-        self._diffusion = {n: c for n, c in coefs.items() if np.any(c != 0.0)} or None
-        coefs4 = {n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (coefs4 or {}).items()}
-        self._biharmonic = {n: c for n, c in coefs4.items() if np.any(c != 0.0)} or None
+        columns = lambda cs: live_fields({n: per_member_values(c, self.members, f"closure coefficient of {n}")[0] for n, c in (cs or {}).items()})
+        self._diffusion, self._biharmonic = columns(coefs), columns(coefs4)
         rows = row_table(self._coriolis, grid, self.members) if self._coriolis is not None else None
         # the forcing: names, shapes, values and refusals, the callables evaluated; the fields all of whose rates are 0 have no launch
         self.forcing = forcing
@@ -143,28 +142,21 @@ class ShallowWaterEnsemble:
         self.clock_time, self.iteration = 0.0, 0
         self._L = _lib.lib()
         self.parameters, self._table_dt = None, None
-        # (members, fields with a coefficient) on the device, in the ensemble's dtype: the table of swmhd_ensemble_diffusion_rk3_*
-        self.diffusion_coefficients = None
-        if self._diffusion is not None:
-            host = np.stack([self._diffusion[n] for n in self._diffusion_names()], axis=1)
-            self.diffusion_coefficients = torch.from_numpy(np.ascontiguousarray(host)).to(device=self._state[0].device, dtype=dtype)
-        # the same table of the biharmonic closure (swmhd_ensemble_biharmonic_rk3_*)
-        self.biharmonic_coefficients = None
-        if self._biharmonic is not None:
-            host = np.stack([self._biharmonic[n] for n in self._closure_names(self._biharmonic)], axis=1)
-            self.biharmonic_coefficients = torch.from_numpy(np.ascontiguousarray(host)).to(device=self._state[0].device, dtype=dtype)
+        # (members, fields with a coefficient) on the device, in the ensemble's dtype, fields in the order of the launch: the tables of
+        # swmhd_ensemble_diffusion_rk3_* and of swmhd_ensemble_biharmonic_rk3_*
+        dev = self._state[0].device
+        table = lambda cs: member_table([cs[n] for n in self.names + self.tracer_names if n in cs], dtype, dev) if cs is not None else None
+        self.diffusion_coefficients, self.biharmonic_coefficients = table(self._diffusion), table(self._biharmonic)
         # (members, 2, Ny) on the device, in the ensemble's dtype and rounded to it: fc then ff of every member, the table of
         # swmhd_ensemble_coriolis_rk3_*; built once
         self.coriolis_rows = None
         if rows is not None:
-            self.coriolis_rows = torch.from_numpy(rows).to(device=self._state[0].device, dtype=dtype)
+            self.coriolis_rows = torch.from_numpy(rows).to(device=dev, dtype=dtype)
         # the forcing on the device: (members, forced fields) tables of rates and scalar targets, and every mask and target array as
         # parents of the fields' shape and pitch -- (Py, Px) shared by all members where none of that kind is per member (member stride
         # 0), else (members, Py, Px) each: the call has one member stride for the masks and one for the targets
         self._relaxation, self.relaxation_rates, self.relaxation_targets = None, None, None
         if relax is not None:
-            dev = self._state[0].device
-
             def parents(arrs):
                 per = any(a is not None and a.ndim == 3 for a in arrs)
                 arrs = [np.broadcast_to(a, (self.members,) + a.shape[-2:]) if (per and a is not None) else a for a in arrs]
@@ -173,9 +165,11 @@ class ShallowWaterEnsemble:
             targets, self._target_stride = parents([t if np.ndim(t) >= 2 else None for _, _, _, t in relax])
             tvals = [np.zeros(self.members) if np.ndim(t) >= 2 else np.broadcast_to(np.asarray(t, dtype=np.float64), (self.members,))
                      for _, _, _, t in relax]
-            table = lambda cols: torch.from_numpy(np.ascontiguousarray(np.stack(cols, axis=1))).to(device=dev, dtype=dtype)
-            self.relaxation_rates, self.relaxation_targets = table([r for _, r, _, _ in relax]), table(tvals)
+            self.relaxation_rates = member_table([r for _, r, _, _ in relax], dtype, dev)
+            self.relaxation_targets = member_table(tvals, dtype, dev)
             self._relaxation = [(n, m, t) for (n, _, _, _), m, t in zip(relax, masks, targets)]
+        # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
+        self._corrections = correction_list(self, self._state[0].stride(1))
         if g_seq or f_seq:
             self._make_parameters()
 
@@ -333,75 +327,6 @@ class ShallowWaterEnsemble:
         f = getattr(self._L, f"swmhd_ensemble_tracers_rk3_{'params_' if par else ''}{self.sfx}")
         _lib.check(f(*head, self.parameters.data_ptr() if par else dt, *tail), "swmhd_ensemble_tracers_rk3" + ("_params" if par else ""))
 
-    def _coriolis_stage(self, dt, stage):
-        """The Coriolis launch of RK3 stage `stage` for every member (swmhd_ensemble_coriolis_rk3_*; with dt None every member's dt comes
-        from the table): ShallowWaterModel._coriolis_stage with the rows of member m in block m of the device table."""
-        g = self.grid
-        gamma = rk3_stage(stage, self._anchor)[0]
-        q, new = self._state, self._alt
-        par = dt is None
-        has, w, flag = correction_operand(stage, self._anchor, dt)
-        acc = (self.Gn[0].data_ptr(), self.Gn[1].data_ptr()) if has else (None, None)
-        f = getattr(self._L, f"swmhd_ensemble_coriolis_rk3_{self.sfx}")
-        rc = f(q[0].data_ptr(), q[1].data_ptr(), new[0].data_ptr(), new[1].data_ptr(), acc[0], acc[1], self.coriolis_rows.data_ptr(),
-               self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy, q[0].stride(1), self.parameters.data_ptr() if par else None,
-               gamma if par else dt * gamma, w, 0, g.Ny, self._flags | self._rwrap | flag, _stream_ptr())
-        _lib.check(rc, "swmhd_ensemble_coriolis_rk3")
-
-    def _closure_names(self, coefs):
-        return [n for n in self.names + self.tracer_names if n in coefs]
-
-    def _diffusion_names(self):
-        return self._closure_names(self._diffusion)
-
-    def _diffusion_stage(self, dt, stage):
-        """The closure's launch of RK3 stage `stage` for every member (swmhd_ensemble_diffusion_rk3_*; with dt None every member's dt
-        comes from the table): ShallowWaterModel._diffusion_stage with the coefficients of member m in row m of the device table."""
-        self._closure_stage(dt, stage, self._diffusion_names(), self.diffusion_coefficients, "swmhd_ensemble_diffusion_rk3")
-
-    def _biharmonic_stage(self, dt, stage):
-        """The biharmonic closure's launch of RK3 stage `stage` for every member (swmhd_ensemble_biharmonic_rk3_*), after
-        _diffusion_stage (finish_stage): ShallowWaterModel._biharmonic_stage with the coefficients of member m in row m of the table."""
-        self._closure_stage(dt, stage, self._closure_names(self._biharmonic), self.biharmonic_coefficients, "swmhd_ensemble_biharmonic_rk3")
-
-    def _correction_call(self, names, dt, stage):
-        """What the per-stage correction launches over the fields `names` (closures, forcing) pass alike: (old, new, acc) pointer arrays
-        of the state and tracers the stage started from, of what it wrote and -- where the stage stores an operand for later stages,
-        else None -- of that operand; params (the table's pointer with dt None, else None); a (gamma with the table, else dt gamma);
-        w; and the flags (shared.correction_operand)."""
-        gamma = rk3_stage(stage, self._anchor)[0]
-        cur = {**dict(zip(self.names, self._state)), **self._tr}
-        new = {**dict(zip(self.names, self._alt)), **self._tr_alt}
-        Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
-        par = dt is None
-        has, w, flag = correction_operand(stage, self._anchor, dt)
-        acc = self._ptrs([Gn[n] for n in names]) if has else None
-        return (self._ptrs([cur[n] for n in names]), self._ptrs([new[n] for n in names]), acc,
-                self.parameters.data_ptr() if par else None, gamma if par else dt * gamma, w, self._flags | self._rwrap | flag)
-
-    def _closure_stage(self, dt, stage, names, table, call):
-        g = self.grid
-        old, new, acc, params, a, w, flags = self._correction_call(names, dt, stage)
-        f = getattr(self._L, f"{call}_{self.sfx}")
-        rc = f(old, new, acc, table.data_ptr(), len(names), self.members, self.stride_m, g.Nx, g.Ny, g.Hx, g.Hy,
-               self._state[0].stride(1), g.dx, g.dy, params, a, w, 0, g.Ny, flags, _stream_ptr())
-        _lib.check(rc, call)
-
-    def _relaxation_stage(self, dt, stage):
-        """The forcing's launch of RK3 stage `stage` for every member (swmhd_ensemble_relaxation_rk3_*; with dt None every member's dt
-        comes from the table): ShallowWaterModel._relaxation_stage with the rate and the scalar target of member m in row m of the
-        device tables, its masks and targets at their member strides (0: shared).  After _biharmonic_stage and BEFORE the swaps
-        (finish_stage): the new field is ((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax)."""
-        g = self.grid
-        rel = self._relaxation
-        old, new, acc, params, a, w, flags = self._correction_call([n for n, _, _ in rel], dt, stage)
-        optional = lambda ts: _lib.ptr_array([t.data_ptr() if t is not None else None for t in ts])
-        f = getattr(self._L, f"swmhd_ensemble_relaxation_rk3_{self.sfx}")
-        rc = f(old, new, acc, optional([m for _, m, _ in rel]), optional([t for _, _, t in rel]), self.relaxation_rates.data_ptr(),
-               self.relaxation_targets.data_ptr(), len(rel), self.members, self.stride_m, self._mask_stride, self._target_stride,
-               g.Nx, g.Ny, g.Hx, g.Hy, self._state[0].stride(1), params, a, w, 0, g.Ny, flags, _stream_ptr())
-        _lib.check(rc, "swmhd_ensemble_relaxation_rk3")
-
     def _stage_steps(self, dt, n):
         """n steps stage by stage (dt: the scalar, or None for the table).  Without fused halos every stage ends with the periodic fill
         of the state and of the tracers, as the native driver fills the state."""
@@ -431,7 +356,7 @@ class ShallowWaterEnsemble:
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
-        if self._tr or self._diffusion is not None or self._biharmonic is not None or self._coriolis is not None or self._relaxation is not None:        # (the native step driver steps the four fields only, with a scalar f)
+        if needs_stages(self):
             self._stage_steps(dt if dts is None else None, n)
         else:
             self._enqueue_steps(dt if dts is None else None, n, swapped)

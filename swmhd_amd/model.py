@@ -8,20 +8,19 @@ Reference call sites being mirrored:
 One `time_step(dt)` == Oceananigans' RK3 `time_step!`: 3 x {calculate_tendencies!, rk3_substep!, store_tendencies!
 (pointer swap), update_state! (halo fill)}.  All arithmetic happens in libswmhd.so; there is no CPU path.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
 from .closure import check_closure
 from .coriolis import check_coriolis, row_table
+from .corrections import correction_list, live_fields, needs_stages
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
 from .forcing import check_forcing, device_parents
 from .grid import Center, Face
 from .shared import (RK3_GAMMA, RK3_ZETA, ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions,
-                     correction_operand, diagnostics_dict, fill_groups, finish_stage, formulation_codes, gradient_values, rk3_stage)
+                     diagnostics_dict, fill_groups, finish_stage, formulation_codes, gradient_values, rk3_stage)
 
 # names a passive tracer may not take: the prognostic fields of either formulation and the derived output fields
 RESERVED_NAMES = ("u", "v", "uh", "vh", "h", "A", "s", "B_x", "B_y")
@@ -73,7 +72,7 @@ class ShallowWaterModel:
                  tracers=(), closure=None, coriolis=None, forcing=None):
         # coriolis = FPlane | BetaPlane | CoriolisProfile (swmhd_amd.coriolis), checked before anything is allocated.  None and FPlane:
         # the scalar f of the stage kernels, exactly the calls made without the argument.  Otherwise the stage kernels get f = 0 and
-        # _coriolis holds the parameter whose rows _coriolis_stage adds after every stage
+        # _coriolis holds the parameter whose rows a correction launch adds after every stage (corrections.correction_list)
         self.coriolis = coriolis
         coriolis_f, self._coriolis = check_coriolis(coriolis, coriolis_f, 1.0, decomp is not None and decomp.world_size > 1,
                                                     ring is not None, fused)
@@ -97,8 +96,8 @@ class ShallowWaterModel:
         coefs, coefs4 = check_closure(closure, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names,
                                       formulation != VectorInvariantFormulation, any(c == _lib.BOUNDED for c in grid.topo_codes()),
                                       decomp is not None and decomp.world_size > 1, ring is not None, fused)
-        self._diffusion = {n: float(c) for n, c in (coefs or {}).items() if float(c) != 0.0} or None
-        self._biharmonic = {n: float(c) for n, c in (coefs4 or {}).items() if float(c) != 0.0} or None
+        self._diffusion = live_fields({n: float(c) for n, c in (coefs or {}).items()})
+        self._biharmonic = live_fields({n: float(c) for n, c in (coefs4 or {}).items()})
         # forcing = {"u": Relaxation(...), "h": ..., "c": ...}: names, shapes, values and refusals are checked, and the callables
         # evaluated, before anything is allocated too.  _relaxation: the forced fields with a rate, in the order of the launch; None
         # without a forcing and with one whose rates are all 0, and then the model makes exactly the calls it makes without it
@@ -171,6 +170,8 @@ class ShallowWaterModel:
             dev = self._raw_fields[0].data.device
             up = lambda a: device_parents(grid, a, dtype, dev)
             self._relaxation = [(n, float(r), up(m), up(t) if np.ndim(t) else float(t)) for n, r, m, t in relax]
+        # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
+        self._corrections = correction_list(self, self._raw_fields[0].stride_y)
         # y-slab ring: the native RCCL ring (swmhd_ring_*) when the process group is RCCL; torch.distributed p2p otherwise
         # (gloo rehearsals).  The ring's step driver needs the fused stage kernel and a slab taller than its two strips.
         # `ring`: a swmhd_ring handle created by the caller -- one of swmhd_ring_create_loopback's (loopback_rings below): several
@@ -410,82 +411,6 @@ class ShallowWaterModel:
                dt, gamma, zeta, store, 0, g.Ny, flags, _stream_ptr())
         _lib.check(rc, "swmhd_tracers_rk3")
 
-    def _coriolis_stage(self, dt, stage):
-        """The Coriolis launch of RK3 stage `stage` under a parameter that varies with y (swmhd_coriolis_rk3_*): D = f(y_j) (vbar, -ubar)
-        on the state the stage started from, added with dt gamma to the two new momentum-like fields and, where the stage stores an
-        operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
-        the anchor form) -- shared.correction_operand.  Order (finish_stage): after _stage_fused and _tracer_stage, BEFORE
-        _diffusion_stage and the swaps; with a closure as well the new u is ((stage + a D_coriolis) + a D_closure), and that order
-        decides the last bits.  Bounded directions pass no WRAP flag and read the halos the previous fill left current."""
-        g = self.grid
-        gamma = rk3_stage(stage, self._anchor)[0]
-        q, new = self._raw_fields, [self._alt[n] for n in self.names]
-        has, w, _ = correction_operand(stage, self._anchor, dt)
-        acc = (self.Gn[0].ptr, self.Gn[1].ptr) if has else (None, None)
-        f = getattr(self._L, f"swmhd_coriolis_rk3_{self.sfx}")
-        rc = f(q[0].ptr, q[1].ptr, new[0].ptr, new[1].ptr, acc[0], acc[1], self.coriolis_rows.data_ptr(), g.Nx, g.Ny, g.Hx, g.Hy,
-               q[0].stride_y, dt * gamma, w, 0, g.Ny, (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap, _stream_ptr())
-        _lib.check(rc, "swmhd_coriolis_rk3")
-
-    def _diffusion_stage(self, dt, stage):
-        """The closure's launch of RK3 stage `stage` (swmhd_diffusion_rk3_*): D = coef laplace(field) on the state the stage started
-        from, for every field with a coefficient, added with dt gamma to the new state (and tracers) and, where the stage stores an
-        operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
-        the anchor form).  After _stage_fused and _tracer_stage and BEFORE the swaps (finish_stage)."""
-        self._closure_stage(dt, stage, self._diffusion, "swmhd_diffusion_rk3")
-
-    def _biharmonic_stage(self, dt, stage):
-        """The biharmonic closure's launch of RK3 stage `stage` (swmhd_biharmonic_rk3_*): _diffusion_stage with D = -coef
-        laplace(laplace(field)).  After _diffusion_stage and BEFORE the swaps (finish_stage): with both closures the new u is
-        ((stage + a D_laplacian) + a D_biharmonic), and that order decides the last bits."""
-        self._closure_stage(dt, stage, self._biharmonic, "swmhd_biharmonic_rk3")
-
-    def _correction_call(self, names, dt, stage):
-        """What the per-stage correction launches over the fields `names` (closures, forcing) pass alike: (old, new, acc) pointer arrays
-        of the state and tracers the stage started from, of what it wrote and -- where the stage stores an operand for later stages,
-        else None -- of that operand; a = dt gamma; w; and the flags (shared.correction_operand)."""
-        P = _lib.ptr_array
-        gamma = rk3_stage(stage, self._anchor)[0]
-        cur = {**self._state, **self._tr}
-        new = {**self._alt, **self._tr_alt}
-        Gn = {**dict(zip(self.names, self.Gn)), **dict(zip(self.tracer_names, self._tGn))}
-        has, w, _ = correction_operand(stage, self._anchor, dt)
-        acc = P([Gn[n].ptr for n in names]) if has else None
-        return (P([cur[n].ptr for n in names]), P([new[n].ptr for n in names]), acc, dt * gamma, w,
-                (_lib.STRICT if self.strict else _lib.FAST) | self._rwrap)
-
-    def _closure_stage(self, dt, stage, coefs, call):
-        g = self.grid
-        names = [n for n in self.names + self.tracer_names if n in coefs]
-        old, new, acc, a, w, flags = self._correction_call(names, dt, stage)
-        ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
-        coef = (ft * len(names))(*[coefs[n] for n in names])
-        f = getattr(self._L, f"{call}_{self.sfx}")
-        rc = f(old, new, acc, coef, len(names), g.Nx, g.Ny, g.Hx, g.Hy, self._raw_fields[0].stride_y, g.dx, g.dy, a, w, 0, g.Ny,
-               flags, _stream_ptr())
-        _lib.check(rc, call)
-
-    def _relaxation_stage(self, dt, stage):
-        """The forcing's launch of RK3 stage `stage` (swmhd_relaxation_rk3_*): D = rate mask (target - field) on the state the stage
-        started from, for every forced field, added with dt gamma to the new state (and tracers) and, where the stage stores an
-        operand for later stages, to it: the tendency Gn with weight 1 (classic form), or the anchor W in Gn with dt / 4 (stage 0 of
-        the anchor form) -- shared.correction_operand.  Order (finish_stage): after _stage_fused, _tracer_stage, _coriolis_stage,
-        _diffusion_stage and _biharmonic_stage and BEFORE the swaps: the new field is
-        ((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax), and that order decides the last bits.  It reads no halo, so a
-        Bounded grid takes it as a periodic one does; the wall line of the wall-normal velocity is reset by the fill that follows."""
-        g = self.grid
-        P = _lib.ptr_array
-        rel = self._relaxation
-        old, new, acc, a, w, flags = self._correction_call([n for n, _, _, _ in rel], dt, stage)
-        dptr = lambda t: t.data_ptr() if torch.is_tensor(t) else None
-        ft = ctypes.c_double if self.sfx == "f64" else ctypes.c_float
-        rate = (ft * len(rel))(*[r for _, r, _, _ in rel])
-        tval = (ft * len(rel))(*[0.0 if torch.is_tensor(t) else t for _, _, _, t in rel])
-        f = getattr(self._L, f"swmhd_relaxation_rk3_{self.sfx}")
-        rc = f(old, new, acc, P([dptr(m) for _, _, m, _ in rel]), P([dptr(t) for _, _, _, t in rel]), rate, tval, len(rel),
-               g.Nx, g.Ny, g.Hx, g.Hy, self._raw_fields[0].stride_y, a, w, 0, g.Ny, flags, _stream_ptr())
-        _lib.check(rc, "swmhd_relaxation_rk3")
-
     # --- time_step!(model, dt): RungeKutta3 ------------------------------------------------------------------
     def _native_steps(self, dt, n):
         """n RK3 steps in ONE C call that enqueues every launch: the native ring driver (swmhd_ring_step_rk3_*) on a slab, the step
@@ -618,8 +543,7 @@ class ShallowWaterModel:
 
     def _driver_steps(self, dt, n):
         if self._ring is not None or (not self.decomp.ring and self.fused and self.tendency_events is None and not any(self._bounded)
-                                      and not self._tr and self._diffusion is None and self._biharmonic is None
-                                      and self._coriolis is None and self._relaxation is None):     # (the native step driver steps the four fields only, with a scalar f)
+                                      and not needs_stages(self)):
             return self._native_steps(dt, n)
         for _ in range(n):
             self.time_step(dt)

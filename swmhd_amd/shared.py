@@ -54,7 +54,7 @@ def diagnostics_dict(v):
 
 
 def correction_operand(stage, anchor, dt):
-    """(has_operand, w, flag) of a per-stage correction launch (o._coriolis_stage, o._diffusion_stage, o._biharmonic_stage, o._relaxation_stage) of RK3 stage `stage`: whether the
+    """(has_operand, w, flag) of a per-stage correction launch (corrections.Correction.launch) of RK3 stage `stage`: whether the
     stage stores an operand for later stages that the correction must reach too, with which weight, and the flag that says what the
     weight means.  Classic form: the tendency Gn, weight 1, where the stage stores it.  Anchor form: the anchor W in Gn at stage 0,
     weight dt / 4 -- with dt None (an ensemble's table) the weight 1/4 of dt, and the kernel forms dt_m / 4 (SWMHD_RK3_ANCHOR, which
@@ -70,23 +70,14 @@ def correction_operand(stage, anchor, dt):
 def finish_stage(o, dt, stage, fused=True):
     """What follows the state's launch of RK3 stage `stage` of `o` (a ShallowWaterModel or a ShallowWaterEnsemble), before its halo
     fill: the tracers through the same stage in one launch (o._tracer_stage), advected by the state the stage STARTED from -- still
-    o._state here -- then, under a Coriolis parameter that varies with y, its one launch on that same state, correcting the two
-    momentum-like fields the stage kernel wrote with f = 0 (o._coriolis_stage) -- then, with a closure, its one diffusion launch on that
-    same state, correcting what the launches before it have written (o._diffusion_stage) -- then, with a biharmonic closure, its one
-    launch on that same state likewise (o._biharmonic_stage) -- then, with a forcing, its one relaxation launch on that same state likewise
-    (o._relaxation_stage): the new field is ((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax); in this order, which decides the
-    last bits where several are present -- then the pointer swaps: the new tracers and the new state become current, and G- <- Gn for both
-    (store_tendencies!, 0 bytes).  fused=False: the state was advanced in place by a substep, only its G sets swap."""
+    o._state here -- then the correction launches of o._corrections on that same state, each correcting what the launches before it
+    have written, in the order of the list (corrections.correction_list states it: it decides the last bits) -- then the pointer
+    swaps: the new tracers and the new state become current, and G- <- Gn for both (store_tendencies!, 0 bytes).  fused=False: the
+    state was advanced in place by a substep, only its G sets swap."""
     if o._tr:
         o._tracer_stage(dt, stage)
-    if getattr(o, "_coriolis", None) is not None:
-        o._coriolis_stage(dt, stage)
-    if getattr(o, "_diffusion", None) is not None:
-        o._diffusion_stage(dt, stage)
-    if getattr(o, "_biharmonic", None) is not None:
-        o._biharmonic_stage(dt, stage)
-    if getattr(o, "_relaxation", None) is not None:
-        o._relaxation_stage(dt, stage)
+    for c in o._corrections:
+        c.launch(o, dt, stage)
     if o._tr:
         o._tr, o._tr_alt = o._tr_alt, o._tr
         o._tGn, o._tGm = o._tGm, o._tGn

@@ -12,6 +12,9 @@ schedule, one halo fill, shared set-up helpers).  To record it again, check that
 run, on a machine with the GPU and the built library,
     python tests/host_call_cases.py [path of the .json, default tests/golden/host_calls.json]
 Re-record it only together with a deliberate change of the C calls; a refactor of the host layer must reproduce it unchanged.
+The H_ scenarios -- the four per-stage correction launches (Coriolis, the two closures, the forcing), alone, together, on a channel, in
+ensembles, and given arguments that leave none -- were recorded the same way from the commit before those launches were folded into
+one ordered list (swmhd_amd/corrections.py); the sixteen older scenarios decoded to the same transcripts before and after.
 
 Shapes: 20 x 12 is narrower than one 64-column tile and no multiple of the 16-row tile, and at Ny = 12 >= Hy every wrap and fill branch
 is live; 16 x 12 with three members gives the ensemble's fold mapping more than one tile per member in y only.  Larger shapes add no
@@ -205,6 +208,94 @@ def ensemble(S, t, per_member, bounded_y):
     e.synchronize()
 
 
+# --- the per-stage correction launches: BetaPlane Coriolis, the two closures, the Relaxation forcing ------------------------------
+def _mask(X, Y):
+    return 0.5 + 0.5 * np.cos(np.pi * X) + 0.0 * Y
+
+
+def _target(X, Y):
+    return 0.1 * np.sin(np.pi * Y / 1.2) + 0.0 * X
+
+
+def _correction(S, kind):
+    """The keyword arguments of a model with the one correction `kind`."""
+    if kind == "coriolis":
+        return dict(coriolis=S.BetaPlane(f0=1.0, beta=0.5))
+    if kind == "diffusion":         # h has no coefficient and A's is 0: the field filter drops two of the four
+        return dict(closure=S.ScalarDiffusivity(nu=1e-3, kappa={"A": 0.0, "c": 2e-3}), tracers=("c",))
+    if kind == "biharmonic":
+        return dict(closure=S.ScalarBiharmonicDiffusivity(nu=1e-6, kappa={"A": 2e-6}))
+    # a mask and a target array, a scalar target, and a rate of 0 (that field has no part in the launch)
+    return dict(forcing={"u": S.Relaxation(0.5, mask=_mask, target=_target), "h": S.Relaxation(0.2, target=1.0), "A": S.Relaxation(0.0)})
+
+
+def _all_corrections(S):
+    return dict(coriolis=S.BetaPlane(f0=1.0, beta=0.5),
+                closure=(S.ScalarDiffusivity(nu=1e-3, kappa={"A": 2e-3, "d": 1e-3}), S.ScalarBiharmonicDiffusivity(nu=1e-6, kappa={"c": 3e-6})),
+                forcing={"v": S.Relaxation(0.5, mask=_mask), "h": S.Relaxation(0.2, target=_target), "c": S.Relaxation(0.1, target=0.3)})
+
+
+def one_correction(S, t, kind, strict):
+    m = _model(S, t, strict=strict, **_correction(S, kind))
+    t.do("time_step", m.time_step, DT)
+    t.do("time_steps(3)", m.time_steps, 3, DT)
+    m.synchronize()
+
+
+def all_corrections(S, t, strict):
+    m = _model(S, t, strict=strict, tracers=("c", "d"), **_all_corrections(S))
+    t.do("time_step", m.time_step, DT)
+    t.do("time_steps(3)", m.time_steps, 3, DT)
+    t.do("capture_graph", m.capture_graph, DT)
+    t.do("time_steps(5)", m.time_steps, 5, DT)
+    m.synchronize()
+
+
+def channel_corrections(S, t, strict):
+    """(Periodic, Bounded): the two corrections a Bounded grid takes."""
+    kw = dict(_correction(S, "coriolis"), **_correction(S, "relaxation"))
+    m = _model(S, t, (P, B), strict=strict, boundary_conditions={"A": _a_gradient(S)}, **kw)
+    t.do("time_step", m.time_step, DT)
+    t.do("time_steps(3)", m.time_steps, 3, DT)
+    m.synchronize()
+
+
+def absent_corrections(S, t, given):
+    """Arguments that leave no correction: the transcript with them is the transcript without them (test_host_calls_gpu asserts it)."""
+    kw = dict(coriolis_f=0.7)
+    if given:
+        kw = dict(coriolis=S.FPlane(0.7), forcing={},
+                  closure=(S.ScalarDiffusivity(nu=0.0, kappa={"A": 0.0}), S.ScalarBiharmonicDiffusivity(nu=0.0, kappa=0.0)))
+    m = _model(S, t, **kw)
+    t.do("time_step", m.time_step, DT)
+    t.do("time_steps(3)", m.time_steps, 3, DT)
+    m.synchronize()
+
+
+def ensemble_corrections(S, t, table, per_member_dt, member_targets, tracers=()):
+    """A periodic ensemble with all four corrections.  table: per-member g, so that the ensemble has its parameter table and every
+    correction call takes dt from it; without it (scalar g, scalar dt) the calls take a = dt gamma and no table."""
+    members = 3
+    grid = _grid(S, 16, 12, (P, P))
+    dt = [DT, 0.5 * DT, 0.75 * DT] if per_member_dt else DT
+    X = np.linspace(0.0, 1.0, grid.Nx)[None, :] + np.zeros((grid.Ny, 1))
+    target = np.stack([0.1 * (k + 1) * np.sin(np.pi * X) for k in range(members)]) if member_targets else 0.05
+    e = S.ShallowWaterEnsemble(
+        grid, members, gravitational_acceleration=[9.81, 9.0, 10.5] if table else 9.81, tracers=tracers,
+        coriolis=S.BetaPlane(f0=1.0, beta=[0.5, 0.0, -0.3]),
+        closure=(S.ScalarDiffusivity(nu=[1e-3, 2e-3, 0.0], kappa={"A": 1e-3}), S.ScalarBiharmonicDiffusivity(nu=1e-6)),
+        forcing={"u": S.Relaxation([0.5, 0.2, 0.1], mask=np.cos(np.pi * X) ** 2, target=target),
+                 "h": S.Relaxation([0.2, 0.0, 0.3], target=[1.0, 1.1, 0.9]), "A": S.Relaxation(0.0)})
+    t.watch(e)
+    t.do("set", lambda: e.set(**_initial(e.names, e.tracer_names)))
+    t.do("time_step", e.time_step, dt)
+    t.do("time_steps(3)", e.time_steps, 3, dt)
+    if not per_member_dt:
+        t.do("capture_graph", e.capture_graph, dt)
+        t.do("time_steps(4)", e.time_steps, 4, dt)
+    e.synchronize()
+
+
 VI, CONS = "VectorInvariant", "Conservative"
 SCENARIOS = {
     "A_periodic_fast": (periodic_fast, {}),
@@ -223,6 +314,17 @@ SCENARIOS = {
     "G_ensemble_per_member": (ensemble, dict(per_member=True, bounded_y=False)),
     "G_bounded_ensemble_scalar": (ensemble, dict(per_member=False, bounded_y=True)),
     "G_bounded_ensemble_per_member": (ensemble, dict(per_member=True, bounded_y=True)),
+    **{f"H_{kind}_{'strict' if strict else 'fast'}": (one_correction, dict(kind=kind, strict=strict))
+       for kind in ("coriolis", "diffusion", "biharmonic", "relaxation") for strict in (False, True)},
+    "H_all_fast": (all_corrections, dict(strict=False)),
+    "H_all_strict": (all_corrections, dict(strict=True)),
+    "H_channel_fast": (channel_corrections, dict(strict=False)),
+    "H_channel_strict": (channel_corrections, dict(strict=True)),
+    "H_absent_given": (absent_corrections, dict(given=True)),
+    "H_absent_plain": (absent_corrections, dict(given=False)),
+    "H_ensemble_scalar_dt": (ensemble_corrections, dict(table=True, per_member_dt=False, member_targets=False)),
+    "H_ensemble_per_member_dt": (ensemble_corrections, dict(table=True, per_member_dt=True, member_targets=True)),
+    "H_ensemble_no_table_tracers": (ensemble_corrections, dict(table=False, per_member_dt=False, member_targets=True, tracers=("c",))),
 }
 
 

@@ -199,30 +199,39 @@ def test_constructor_refusals_before_any_device(swmhd, monkeypatch):
         S.ShallowWaterModel(g, coriolis=S.CoriolisProfile(lambda y: np.full_like(y, np.nan)))
 
 
+class _Entry:
+    """A recording entry of a model's _corrections."""
+
+    def __init__(self, name):
+        self.name = name
+
+    def launch(self, o, dt, stage):
+        assert o._state == "state"          # before the swaps
+        o.log.append(self.name)
+
+
 class _Stub:
-    """What finish_stage touches of a model, with the stage methods recording their calls."""
+    """What finish_stage touches of a model, with the tracer stage and the entries of _corrections recording their calls."""
 
     def __init__(self, coriolis, diffusion, tracers):
         self.log = []
         self._coriolis, self._diffusion = coriolis, diffusion
+        self._corrections = ([_Entry("coriolis")] if coriolis is not None else []) + ([_Entry("diffusion")] if diffusion is not None else [])
         self._tr, self._tr_alt, self._tGn, self._tGm = ({"c": 1} if tracers else {}), {}, [], []
         self._state, self._alt, self.Gn, self.Gm = "state", "alt", "Gn", "Gm"
 
     def _tracer_stage(self, dt, stage):
         self.log.append("tracers")
 
-    def _coriolis_stage(self, dt, stage):
-        assert self._state == "state"          # before the swaps
-        self.log.append("coriolis")
-
-    def _diffusion_stage(self, dt, stage):
-        assert self._state == "state"
-        self.log.append("diffusion")
-
 
 def test_none_and_fplane_leave_the_stage_as_it_was(swmhd):
-    """finish_stage calls _coriolis_stage only where the constructor kept a parameter that varies with y -- after the tracers, before
-    the closure, before the swaps -- and the constructors keep none for None and FPlane (check_coriolis, above)."""
+    """finish_stage launches the Coriolis correction only where the constructor kept a parameter that varies with y -- after the
+    tracers, before the closure, before the swaps -- and the constructors keep none for None and FPlane (check_coriolis, above).  The
+    list the constructors build has its four kinds in the order of the launches."""
+    import types
+
+    import torch
+    from swmhd_amd.corrections import correction_list
     from swmhd_amd.shared import finish_stage
     for tracers in (False, True):
         for diffusion in (None, {"A": 1e-3}):
@@ -234,6 +243,16 @@ def test_none_and_fplane_leave_the_stage_as_it_was(swmhd):
             assert beta.log == (["tracers"] if tracers else []) + ["coriolis"] + (["diffusion"] if diffusion else [])
             assert [x for x in beta.log if x != "coriolis"] == plain.log
             assert (beta._state, beta._alt, beta.Gn, beta.Gm) == ("alt", "state", "Gm", "Gn")
+    # what correction_list reads of a model with all four kinds (host tensors stand in for the device tables: nothing is launched)
+    g = swmhd.RectilinearGrid(size=(8, 8), x=(0, 1), y=(0, 1))
+    o = types.SimpleNamespace(grid=g, names=("u", "v", "h", "A"), tracer_names=("c",), sfx="f64", _coriolis=object(),
+                              coriolis_rows=torch.zeros(2, 8, dtype=torch.float64), _diffusion={"u": 1e-3, "A": 2e-3},
+                              _biharmonic={"c": 1e-6}, _relaxation=[("h", 0.5, None, 1.0), ("c", 0.1, torch.zeros(14, 14, dtype=torch.float64), 0.0)])
+    built = correction_list(o, 14)
+    assert [c.stem for c in built] == ["coriolis", "diffusion", "biharmonic", "relaxation"]
+    assert [c.names for c in built] == [("u", "v"), ("u", "A"), ("c",), ("h", "c")]
+    o._coriolis = o._diffusion = o._biharmonic = o._relaxation = None
+    assert correction_list(o, 14) == []
 
 
 def test_potential_vorticity_is_refused_under_f_of_y(swmhd):

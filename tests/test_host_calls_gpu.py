@@ -19,6 +19,14 @@ def test_golden_covers_the_scenarios(golden):
     assert sorted(golden) == sorted(HC.SCENARIOS)
 
 
+def test_arguments_that_leave_no_correction_change_no_call(swmhd, golden):
+    """closure= with all coefficients 0, forcing={} and coriolis=FPlane(f): argument by argument the calls of the model built without
+    them, now and in the recording."""
+    given, plain = (json.loads(json.dumps(HC.run(swmhd, name))) for name in ("H_absent_given", "H_absent_plain"))
+    assert given == plain
+    assert golden["H_absent_given"] == golden["H_absent_plain"]
+
+
 @pytest.mark.parametrize("name", sorted(HC.SCENARIOS))
 def test_host_calls_are_the_recorded_ones(swmhd, golden, name):
     got = json.loads(json.dumps(HC.run(swmhd, name)))
