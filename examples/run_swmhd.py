@@ -44,6 +44,10 @@ gives one member per entry (a sweep of the drag), and a list of several values s
 Relaxation(rate = RATE, mask = G) on the same two fields, G(y) = exp(-((y - y_south) / WIDTH)²) + exp(-((y - y_north) / WIDTH)²): sponge
 layers that absorb what reaches the walls.  With --drag R as well the two terms are one, Relaxation(rate = 1, mask = R + RATE G).  With --channel either runs ONE Bounded model (one --gradients entry: Bounded ensembles take no forcing).  dt is not
 limited by the forcing: the line printed at the start gives Relaxation.max_stable_dt.
+--stir RATE,KF[,DK] [--seed N] stirs u and v with swmhd_amd.StochasticForcing(rate = RATE, k_f = KF, dk = DK): a random stream function
+in the ring of wavenumbers KF - DK/2 <= |k| < KF + DK/2 (DK: the grid's lowest wavenumber unless given), white in time, exactly
+non-divergent, renewed on the device every step and reproducible from the seed; RATE is the mean kinetic-energy injection per unit
+mass and time.  With --drag the two fields carry both terms: the forced-dissipative run.  One periodic model, --formulation jacobian.
 
     python examples/run_swmhd.py --amps 0.1,0.5,1.0 [other options as above]
 runs one member per A amplitude as ONE ensemble (swmhd_amd.ShallowWaterEnsemble: every member stepped by the same three launches per RK3
@@ -102,6 +106,8 @@ def main():
     ap.add_argument("--hyperdiffusivity", default=None, help="kappa of ScalarBiharmonicDiffusivity, on A and the dye (ensemble runs: a comma list)")
     ap.add_argument("--drag", default=None, help="rate of Relaxation on the two momentum-like fields (ensemble runs: a comma list, one member per entry)")
     ap.add_argument("--sponge", default=None, help="RATE,WIDTH with --channel: Relaxation(rate=RATE, mask=Gaussians of that width at the two walls) on the momentum-like fields")
+    ap.add_argument("--stir", default=None, help="RATE,KF[,DK]: StochasticForcing(rate=RATE, k_f=KF, dk=DK or the grid's lowest wavenumber) on u and v (one periodic model, --formulation jacobian)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --stir")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -135,6 +141,10 @@ def main():
     if a.dye and a.channel:
         ap.error("--dye: not with --channel (Bounded ensembles carry no tracers)")
     a.sweep = a.sweep or "," in (a.beta or "") or "," in (a.drag or "")
+    if a.stir is not None and (a.channel or a.formulation != "jacobian" or len(a.stir.split(",")) not in (2, 3)):
+        ap.error("--stir RATE,KF[,DK]: a periodic grid and --formulation jacobian (the stirring is a stream function's, for u and v)")
+    if a.stir is not None and (a.amps or a.sweep):
+        ap.error("--stir runs one model: not with an ensemble run")
     if a.sponge is not None and (not a.channel or len(a.sponge.split(",")) != 2):
         ap.error("--sponge RATE,WIDTH needs --channel: the sponge layers stand at the channel's walls")
     # --channel with --beta, --drag or --sponge: ONE Bounded model (Bounded ensembles take no f(y) and no forcing), so one gradient, one
@@ -185,6 +195,13 @@ def main():
         forcing = {n: S.Relaxation(float(a.drag)) for n in momentum}
     for n, r in (forcing or {}).items():
         print(f"forcing: {n} = {r}, max_stable_dt = {r.max_stable_dt(grid, S.fields.LOCS[n]):.4g} (dt = {a.dt:g})")
+    # --stir RATE,KF[,DK]: ONE StochasticForcing under both momentum names (a random stream function in the ring |k| = KF +- DK/2, white
+    # in time, renewed every step on the device), beside the drag where there is one: a field carries (Relaxation, StochasticForcing)
+    if a.stir is not None:
+        vals = [float(x) for x in a.stir.split(",")]
+        stir = S.StochasticForcing(vals[0], vals[1], vals[2] if len(vals) > 2 else 2 * np.pi / L, seed=a.seed)
+        print(f"forcing: {stir} on u, v: {len(S.forcing_modes(grid, stir.k_f, stir.dk))} modes")
+        forcing = {n: ((forcing[n], stir) if forcing and n in forcing else stir) for n in momentum}
     model = S.ShallowWaterModel(grid, configs.G, formulation=form, tracers=("c",) if a.dye else (), closure=closure, coriolis=coriolis,
                                 boundary_conditions=bcs, forcing=forcing)
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)

@@ -781,5 +781,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_coriolis.h"
 /* Relaxation forcing (swmhd_relaxation_rk3_*, swmhd_ensemble_relaxation_rk3_*): rate mask (target - phi) added to any prognostic field per RK3 stage */
 #include "swmhd_relaxation.h"
+/* Stochastic forcing (swmhd_stochastic_coefficients_*, swmhd_stochastic_rk3_* and their ensemble forms): band-limited white-noise stirring per RK3 step */
+#include "swmhd_stochastic.h"
 
 #endif /* SWMHD_H */

@@ -38,6 +38,10 @@ DIFFUSION_TILE_ROWS = 64                  # SWMHD_DIFFUSION_TILE_ROWS: rows of a
 CORIOLIS_TILE_ROWS = 64                   # SWMHD_CORIOLIS_TILE_ROWS: rows of a workgroup of the Coriolis kernel (four waves)
 RELAXATION_MAX_FIELDS = 4 + MAX_TRACERS   # SWMHD_RELAXATION_MAX_FIELDS: fields per swmhd_relaxation_rk3_* launch
 RELAXATION_TILE_ROWS = 64                 # SWMHD_RELAXATION_TILE_ROWS: rows of a workgroup of the relaxation kernel (four waves)
+STOCHASTIC_MAX_FIELDS = 4 + MAX_TRACERS   # SWMHD_STOCHASTIC_MAX_FIELDS: fields per swmhd_stochastic_rk3_* launch, groups per draw
+STOCHASTIC_MAX_MODES = 256                # SWMHD_STOCHASTIC_MAX_MODES: Fourier modes of one field
+STOCHASTIC_TILE_ROWS = 64                 # SWMHD_STOCHASTIC_TILE_ROWS: rows of a workgroup of the stochastic kernel (four waves)
+STOCHASTIC_MODE_CHUNK = 4                 # SWMHD_STOCHASTIC_MODE_CHUNK: modes whose x tables a lane holds in registers at a time
 
 
 def ensemble_diag_workspace(members, Nx, Ny):
@@ -227,6 +231,20 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_relaxation_rk3_{sfx}")
         f.argtypes = [C.POINTER(p)] * 5 + [p, p, i, i, i64, i64, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
         f.restype = i
+        # Stochastic forcing, the draw: counter (device), coef, amp0, ktx, kty (host arrays of device pointers), nmodes, kind (host), ...
+        f = getattr(lib, f"swmhd_stochastic_coefficients_{sfx}")
+        f.argtypes = [p] + [C.POINTER(p)] * 4 + [C.POINTER(i), C.POINTER(i), i, C.c_uint64, C.c_uint32, C.c_double, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_stochastic_coefficients_{sfx}")
+        f.argtypes = [p] + [C.POINTER(p)] * 4 + [C.POINTER(i), C.POINTER(i), i, i, i64, i64, C.c_uint64, p, C.c_double, p]
+        f.restype = i
+        # the correction: old, new, acc, coef, xtab, ytab (host arrays of device pointers), nmodes (host), nfields, x_pitch, y_pitch, ...
+        f = getattr(lib, f"swmhd_stochastic_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 6 + [C.POINTER(i), i, i64, i64, i, i, i, i, i64, ft, ft, i, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_stochastic_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 6 + [C.POINTER(i), i, i64, i64, i, i64, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
+        f.restype = i
     lib.swmhd_zonal_spectra_workspace.argtypes = [i, i, i, i]
     lib.swmhd_zonal_spectra_workspace.restype = i64
     lib.swmhd_spectra2d_shells.argtypes = [i, i, C.c_double, C.c_double]
@@ -290,6 +308,9 @@ BIHARMONIC_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name i
 CORIOLIS_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("coriolis_rk3", "ensemble_coriolis_rk3")]
 # the symbols include/swmhd_relaxation.h declares (swmhd.h includes it; tests/test_relaxation_abi.py checks the .so exports each of them)
 RELAXATION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("relaxation_rk3", "ensemble_relaxation_rk3")]
+# the symbols include/swmhd_stochastic.h declares (swmhd.h includes it; tests/test_stochastic_abi.py checks the .so exports each of them)
+STOCHASTIC_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
+                      for name in ("stochastic_coefficients", "ensemble_stochastic_coefficients", "stochastic_rk3", "ensemble_stochastic_rk3")]
 RING_ID_BYTES = 128
 
 

@@ -71,11 +71,31 @@ class Correction:
         _lib.check(rc, self.symbol)
 
 
+class StochasticCorrection(Correction):
+    """The stochastic forcing's launch (swmhd_[ensemble_]stochastic_rk3_*): Correction's call with the coefficient draw of the step
+    (swmhd_[ensemble_]stochastic_coefficients_*, which advances the device counter) enqueued in front of the stage-0 launch, so that
+    the coefficients are renewed once per step and held over its three stages.  The amplitude carries 1/sqrt(dt), which the draw is
+    given as one number: an ensemble whose corrections are handed dt None (a parameter table) hands over step_dt, the one dt its
+    members share, and the call goes without the table."""
+
+    needs_step_dt = True      # (shared.finish_stage hands over the one dt the members share beside dt)
+
+    def launch(self, o, dt, stage, step_dt=None):
+        st = o._stochastic
+        if dt is None:
+            dt = step_dt
+        if dt is None:
+            raise _lib.SwmhdError("StochasticForcing with a per-member dt is not supported (SWMHD_ENOTSUP): its amplitude carries 1/sqrt(dt)")
+        if stage == 0:
+            st.draw(o, dt)
+        super().launch(o, dt, stage)
+
+
 def correction_list(o, stride_y):
-    """The active corrections of `o` (its data attributes _coriolis, _diffusion, _biharmonic and _relaxation: None where inactive) in
-    the order of their launches: Coriolis, Laplacian, biharmonic, relaxation.  Each corrects what the launches before it have
-    written, so the new field is ((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax), and this order decides the last bits where
-    several are present.  Empty without any: then the object may step through its native driver (needs_stages).  stride_y: the
+    """The active corrections of `o` (its data attributes _coriolis, _diffusion, _biharmonic, _relaxation and _stochastic: None where
+    inactive) in the order of their launches: Coriolis, Laplacian, biharmonic, relaxation, stochastic.  Each corrects what the launches
+    before it have written, so the new field is (((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax) + a F_stoch), and this order
+    decides the last bits where several are present.  Empty without any: then the object may step through its native driver (needs_stages).  stride_y: the
     pitch of the object's fields.  A further term is one more entry here, after the ones whose result it is to correct: its stem,
     its fields and its `middle`; the C entry points take the argument layout Correction states."""
     ens = hasattr(o, "members")
@@ -102,6 +122,14 @@ def correction_list(o, stride_y):
             strides = ()
         out.append(Correction(o, stride_y, "relaxation", [r[0] for r in rel], (parents(-2), parents(-1), *tables, len(rel)),
                               member_strides=strides))
+    if getattr(o, "_stochastic", None) is not None:
+        # F = the sum of the step's random Fourier modes; _stochastic.fields: (name, mode count, coefficients, x table, y table) of
+        # every stirred field.  It reads no state: `old` goes along for the common layout only
+        st = o._stochastic
+        col = lambda k: [f[k] for f in st.fields]
+        middle = (_lib.ptr_array(col(2)), _lib.ptr_array(col(3)), _lib.ptr_array(col(4)), (ctypes.c_int * len(st.fields))(*col(1)),
+                  len(st.fields), st.x_pitch, st.y_pitch)
+        out.append(StochasticCorrection(o, stride_y, "stochastic", col(0), middle, member_strides=(st.coef_stride,) if ens else ()))
     return out
 
 

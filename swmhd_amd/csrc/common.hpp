@@ -341,6 +341,40 @@ struct RelaxationArgs : StripArgs<T> {
 template <typename T> hipError_t launch_relaxation_fast(const RelaxationArgs<T> &a, hipStream_t s);
 template <typename T> hipError_t launch_relaxation_strict(const RelaxationArgs<T> &a, hipStream_t s);
 
+// Stochastic forcing (swmhd_stochastic_rk3_*, stochastic.hip): F_k = sum over M[k] modes of cx (P cy + Q sy) + sx (Q cy - P sy) of up to
+// 4 + MAX_TRACERS fields in ONE launch: nw[k] += a F_k and, where acc[k] != nullptr, acc[k] += w F_k.  coef[k]: P[0 .. M) then Q[0 .. M);
+// xtab[k] / ytab[k]: rows 2 m (cos) and 2 m + 1 (sin) of xp / yp elements, at column / row 0 of the interior.  An ensemble member's
+// coefficients stand at coef[k] + m * coef_stride_m; the tables are shared.  old is carried for pack_fields and never read.
+constexpr int STOCHASTIC_MAX_FIELDS = 4 + MAX_TRACERS;   // = SWMHD_STOCHASTIC_MAX_FIELDS
+constexpr int STOCHASTIC_MAX_MODES = 256;                // = SWMHD_STOCHASTIC_MAX_MODES
+constexpr int STOCHASTIC_MODE_CHUNK = 4;                 // = SWMHD_STOCHASTIC_MODE_CHUNK
+template <typename T>
+struct StochasticArgs : StripArgs<T> {
+    const T *old[STOCHASTIC_MAX_FIELDS], *coef[STOCHASTIC_MAX_FIELDS], *xtab[STOCHASTIC_MAX_FIELDS], *ytab[STOCHASTIC_MAX_FIELDS];
+    T *nw[STOCHASTIC_MAX_FIELDS], *acc[STOCHASTIC_MAX_FIELDS];
+    int M[STOCHASTIC_MAX_FIELDS];
+    int nfields;
+    long xp, yp, coef_stride_m;
+};
+template <typename T> hipError_t launch_stochastic_fast(const StochasticArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_stochastic_strict(const StochasticArgs<T> &a, hipStream_t s);
+// The coefficient draw of one time step (swmhd_stochastic_coefficients_*, stochastic_coefficients.hip): one workgroup per member.
+// kind 0: coef = P, Q of M each; kind 1: Pu, Qu, Pv, Qv of M each.  amp0, ktx, kty: DEVICE doubles; member m reads amp0 + m * amp_stride_m
+// and writes coef + m * coef_stride_m, with substreams[m] (nullptr: `substream` for the one member).
+template <typename T>
+struct StochasticCoefArgs {
+    unsigned long long *counter;
+    T *coef[STOCHASTIC_MAX_FIELDS];
+    const double *amp0[STOCHASTIC_MAX_FIELDS], *ktx[STOCHASTIC_MAX_FIELDS], *kty[STOCHASTIC_MAX_FIELDS];
+    int M[STOCHASTIC_MAX_FIELDS], kind[STOCHASTIC_MAX_FIELDS];
+    int ngroups, members;
+    long coef_stride_m, amp_stride_m;
+    unsigned seed_lo, seed_hi, substream;
+    const unsigned *substreams;
+    double sdt;
+};
+template <typename T> hipError_t launch_stochastic_coefficients(const StochasticCoefArgs<T> &a, hipStream_t s);
+
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
 // (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read

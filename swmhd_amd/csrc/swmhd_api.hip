@@ -409,6 +409,78 @@ int relaxation_common(const T *const *old, T *const *nw, T *const *acc, const T 
     return hiprc(fl.strict ? launch_relaxation_strict<T>(d, s) : launch_relaxation_fast<T>(d, s));
 }
 
+// swmhd_stochastic_rk3: nw[k] += a F_k, acc[k] += w F_k with F_k the sum of nmodes[k] Fourier modes from the tables and the step's
+// coefficient pairs, of up to SWMHD_STOCHASTIC_MAX_FIELDS fields in one launch (stochastic.hip).  Every check precedes the first HIP
+// call, in the order include/swmhd_stochastic.h states: relaxation_common's, then the tables.  With `ens`
+// (swmhd_ensemble_stochastic_rk3): coef_sm pitches the members' coefficients; a parameter table (a per-member dt) is refused.  The
+// fields without modes are left out of the launch here.
+template <typename T>
+bool table_ok(const T *p) { return p && (uintptr_t)p % sizeof(T) == 0; }
+template <typename T>
+int stochastic_common(const T *const *old, T *const *nw, T *const *acc, const T *const *coef, const T *const *xtab, const T *const *ytab,
+                      const int *nmodes, int nfields, int64_t xp, int64_t yp, const Grid &g, T a, T w, const Rows &r, int flags, void *stream,
+                      const Ens *ens = nullptr, int64_t coef_sm = 0) {
+    const FieldSets<T> f{old, nw, acc, nfields};
+    if (bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
+    if (!field_correction_ok<T>(f, SWMHD_STOCHASTIC_MAX_FIELDS, {}, g, a, w, r, flags, RELAXATION_FLAGS | RELAXATION_NOTSUP, ens)) return SWMHD_EINVAL;
+    if (!coef || !xtab || !ytab || !nmodes || xp < g.Nx || yp < g.Ny) return SWMHD_EINVAL;
+    for (int k = 0; k < nfields; ++k) {
+        if (nmodes[k] < 0 || nmodes[k] > SWMHD_STOCHASTIC_MAX_MODES) return SWMHD_EINVAL;
+        if (nmodes[k] == 0) continue;
+        if (!table_ok(coef[k]) || !table_ok(xtab[k]) || !table_ok(ytab[k])) return SWMHD_EINVAL;
+        if (ens && coef_sm < 2 * (int64_t)nmodes[k]) return SWMHD_EINVAL;
+    }
+    if (ens && ens->params) return SWMHD_ENOTSUP;
+    if (flags & RELAXATION_NOTSUP) return SWMHD_ENOTSUP;
+    const Flags fl = decode_flags(flags);
+    if (r.j0 == r.j1) return SWMHD_OK;
+    StochasticArgs<T> d;
+    const int n = pack_fields(d, STOCHASTIC_MAX_FIELDS, f, g, [&](int k) { return nmodes[k] != 0; }, [&](int slot, int k) {
+        d.coef[slot] = k >= 0 ? coef[k] : nullptr; d.xtab[slot] = k >= 0 ? xtab[k] : nullptr; d.ytab[slot] = k >= 0 ? ytab[k] : nullptr;
+        d.M[slot] = k >= 0 ? nmodes[k] : 0;
+    });
+    if (n == 0) return SWMHD_OK;
+    set_strip(d, g, r, fl, a, w, ens);
+    d.wrap = 0;   // (nothing around a cell is read)
+    d.params = nullptr;
+    d.nfields = n; d.xp = (long)xp; d.yp = (long)yp; d.coef_stride_m = ens ? (long)coef_sm : 0;
+    hipStream_t s = (hipStream_t)stream;
+    return hiprc(fl.strict ? launch_stochastic_strict<T>(d, s) : launch_stochastic_fast<T>(d, s));
+}
+
+// swmhd_stochastic_coefficients: the draw of one time step (stochastic_coefficients.hip).  Without `ens`: one grid, with `substream`.
+template <typename T>
+int stochastic_coefficients_common(uint64_t *counter, T *const *coef, const double *const *amp0, const double *const *ktx,
+                                   const double *const *kty, const int *nmodes, const int *kind, int ngroups, bool ens, int members,
+                                   int64_t coef_sm, int64_t amp_sm, uint64_t seed, uint32_t substream, const uint32_t *substreams, double sdt,
+                                   void *stream) {
+    if (!counter || (uintptr_t)counter % 8 != 0 || !coef || !amp0 || !nmodes || !kind) return SWMHD_EINVAL;
+    if (ngroups < 1 || ngroups > SWMHD_STOCHASTIC_MAX_FIELDS) return SWMHD_EINVAL;
+    if (!isfinite(sdt) || !(sdt > 0.0)) return SWMHD_EINVAL;
+    if (ens && (members < 1 || members > SWMHD_ENSEMBLE_MAX_MEMBERS || !substreams)) return SWMHD_EINVAL;
+    StochasticCoefArgs<T> d;
+    for (int g = 0; g < STOCHASTIC_MAX_FIELDS; ++g) {
+        d.coef[g] = nullptr; d.amp0[g] = d.ktx[g] = d.kty[g] = nullptr; d.M[g] = 0; d.kind[g] = 0;
+    }
+    for (int g = 0; g < ngroups; ++g) {
+        const int M = nmodes[g];
+        if (M < 1 || M > SWMHD_STOCHASTIC_MAX_MODES) return SWMHD_EINVAL;
+        if (kind[g] != SWMHD_STOCHASTIC_SCALAR && kind[g] != SWMHD_STOCHASTIC_PAIR) return SWMHD_EINVAL;
+        const bool pair = kind[g] == SWMHD_STOCHASTIC_PAIR;
+        if (!table_ok(coef[g]) || !table_ok(amp0[g])) return SWMHD_EINVAL;
+        if (pair && (!ktx || !kty || !table_ok(ktx[g]) || !table_ok(kty[g]))) return SWMHD_EINVAL;
+        if (ens && (coef_sm < (pair ? 4 : 2) * (int64_t)M || (amp_sm != 0 && amp_sm < M))) return SWMHD_EINVAL;
+        d.coef[g] = coef[g]; d.amp0[g] = amp0[g]; d.ktx[g] = pair ? ktx[g] : nullptr; d.kty[g] = pair ? kty[g] : nullptr;
+        d.M[g] = M; d.kind[g] = kind[g];
+    }
+    d.counter = reinterpret_cast<unsigned long long *>(counter);
+    d.ngroups = ngroups; d.members = ens ? members : 1;
+    d.coef_stride_m = ens ? (long)coef_sm : 0; d.amp_stride_m = ens ? (long)amp_sm : 0;
+    d.seed_lo = (unsigned)(seed & 0xffffffffull); d.seed_hi = (unsigned)(seed >> 32);
+    d.substream = substream; d.substreams = ens ? substreams : nullptr; d.sdt = sdt;
+    return hiprc(launch_stochastic_coefficients<T>(d, (hipStream_t)stream));
+}
+
 // The RK3 step driver.  Periodic: stages in anchor form (fast) and a periodic fill of whatever the kernel does not wrap.  Bounded
 // ensembles (ens->bc, swmhd_ensemble_step_rk3_bc): ShallowWaterModel.time_step's Bounded schedule -- every stage in G- form, then the
 // boundary-condition fill of the four fields, gradient values from the DEVICE table bc_gradient.  ph: the model and dt.
@@ -792,5 +864,38 @@ SWMHD_DEF_CORIOLIS(f32, float)
 
 SWMHD_DEF_RELAXATION(f64, double)
 SWMHD_DEF_RELAXATION(f32, float)
+
+// include/swmhd_stochastic.h
+#define SWMHD_DEF_STOCHASTIC(sfx, T)                                                                                                                   \
+    int swmhd_stochastic_coefficients_##sfx(uint64_t *counter, T *const *coef, const double *const *amp0, const double *const *ktx,                   \
+                                            const double *const *kty, const int *nmodes, const int *kind, int ngroups, uint64_t seed,                 \
+                                            uint32_t substream, double sdt, void *stream) {                                                           \
+        return stochastic_coefficients_common<T>(counter, coef, amp0, ktx, kty, nmodes, kind, ngroups, false, 0, 0, 0, seed, substream, nullptr,      \
+                                                 sdt, stream);                                                                                        \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_stochastic_coefficients_##sfx(uint64_t *counter, T *const *coef, const double *const *amp0, const double *const *ktx,          \
+                                                     const double *const *kty, const int *nmodes, const int *kind, int ngroups, int members,          \
+                                                     int64_t coef_stride_m, int64_t amp_stride_m, uint64_t seed, const uint32_t *substream,           \
+                                                     double sdt, void *stream) {                                                                      \
+        return stochastic_coefficients_common<T>(counter, coef, amp0, ktx, kty, nmodes, kind, ngroups, true, members, coef_stride_m, amp_stride_m,    \
+                                                 seed, 0, substream, sdt, stream);                                                                    \
+    }                                                                                                                                                 \
+    int swmhd_stochastic_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *const *coef, const T *const *xtab,                      \
+                                   const T *const *ytab, const int *nmodes, int nfields, int64_t xp, int64_t yp, int Nx, int Ny, int Hx, int Hy,      \
+                                   int64_t sy, T a, T w, int j0, int j1, int flags, void *stream) {                                                   \
+        return stochastic_common<T>(old, nw, acc, coef, xtab, ytab, nmodes, nfields, xp, yp, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags,     \
+                                    stream);                                                                                                          \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_stochastic_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *const *coef, const T *const *xtab,             \
+                                            const T *const *ytab, const int *nmodes, int nfields, int64_t xp, int64_t yp, int members,                \
+                                            int64_t stride_m, int64_t coef_stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, const T *params,     \
+                                            T a, T w, int j0, int j1, int flags, void *stream) {                                                      \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return stochastic_common<T>(old, nw, acc, coef, xtab, ytab, nmodes, nfields, xp, yp, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags,     \
+                                    stream, &e, coef_stride_m);                                                                                       \
+    }
+
+SWMHD_DEF_STOCHASTIC(f64, double)
+SWMHD_DEF_STOCHASTIC(f32, float)
 
 }  // extern "C"

@@ -20,9 +20,10 @@ from .closure import check_closure, closure_for_member
 from .coriolis import check_coriolis, row_table
 from .corrections import correction_list, live_fields, member_table, needs_stages
 from .fields import _SFX, _stream_ptr
-from .forcing import check_forcing, device_parents, forcing_for_member
+from .forcing import check_forcing, check_stochastic, device_parents, forcing_for_member
 from .grid import Center, Face
 from .model import ShallowWaterModel, rk3_operands, tracer_names
+from .stochastic import StochasticState
 from .shared import (VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups, finish_stage,
                      formulation_codes, gradient_values)
 
@@ -109,6 +110,9 @@ class ShallowWaterEnsemble:
         # the forcing: names, shapes, values and refusals, the callables evaluated; the fields all of whose rates are 0 have no launch
         self.forcing = forcing
         relax = check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, self.members)
+        # its StochasticForcing entries (swmhd_amd.stochastic): a scalar or per-member rate, member m draws with stream + m
+        stir = check_stochastic(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, self.members,
+                                formulation != VectorInvariantFormulation)
         self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
         self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
         self.grid = grid
@@ -168,6 +172,8 @@ class ShallowWaterEnsemble:
             self.relaxation_rates = member_table([r for _, r, _, _ in relax], dtype, dev)
             self.relaxation_targets = member_table(tvals, dtype, dev)
             self._relaxation = [(n, m, t) for (n, _, _, _), m, t in zip(relax, masks, targets)]
+        # the stochastic forcing on the device: one step counter and one set of coefficient pairs per member; None where inactive
+        self._stochastic = StochasticState(stir, grid, dtype, dev, self.members) if stir is not None else None
         # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
         self._corrections = correction_list(self, self._state[0].stride(1))
         if g_seq or f_seq:
@@ -327,13 +333,14 @@ class ShallowWaterEnsemble:
         f = getattr(self._L, f"swmhd_ensemble_tracers_rk3_{'params_' if par else ''}{self.sfx}")
         _lib.check(f(*head, self.parameters.data_ptr() if par else dt, *tail), "swmhd_ensemble_tracers_rk3" + ("_params" if par else ""))
 
-    def _stage_steps(self, dt, n):
-        """n steps stage by stage (dt: the scalar, or None for the table).  Without fused halos every stage ends with the periodic fill
+    def _stage_steps(self, dt, n, step_dt=None):
+        """n steps stage by stage (dt: the scalar, or None for the table; step_dt: the one dt all members share, or None where they
+        differ -- what a correction whose call takes no table is given).  Without fused halos every stage ends with the periodic fill
         of the state and of the tracers, as the native driver fills the state."""
         for _ in range(n):
             for stage in range(3):
                 self._stage_fused(dt, stage)
-                finish_stage(self, dt, stage)
+                finish_stage(self, dt, stage, step_dt=step_dt)
                 if not self._rwrap:
                     self.update_state()
 
@@ -352,12 +359,15 @@ class ShallowWaterEnsemble:
             _lib.check(f(*head, self.parameters.data_ptr(), self.form_code, self.lorentz_code, *tail), "swmhd_ensemble_step_rk3_params")
 
     def _native_steps(self, dt, n):
+        if self._stochastic is not None and is_per_member(dt):
+            raise _lib.SwmhdError("StochasticForcing with a per-member dt is not supported (SWMHD_ENOTSUP): its amplitude carries "
+                                  "1/sqrt(dt), which the coefficient draw takes as one number")
         dts = self._dt_values(dt)
         if dts is not None:
             self._set_table_dt(dts)
         swapped = ctypes.c_int(0)
         if needs_stages(self):
-            self._stage_steps(dt if dts is None else None, n)
+            self._stage_steps(dt if dts is None else None, n, None if is_per_member(dt) else float(dt))
         else:
             self._enqueue_steps(dt if dts is None else None, n, swapped)
         if swapped.value:
@@ -377,6 +387,8 @@ class ShallowWaterEnsemble:
         at the captured values."""
         self._ensure_halos()
         saved = self._state + self.Gm + [self._tr[n] for n in self.tracer_names] + self._tGm
+        if self._stochastic is not None:      # the warm-up steps advance the step counters: a replayed run draws what an eager run draws
+            saved = saved + [self._stochastic.counter]
         keep = [t.clone() for t in saved]
         t0, i0 = self._clock_state(), self.iteration
         side = torch.cuda.Stream()
@@ -499,6 +511,8 @@ class ShallowWaterEnsemble:
         for k, n in enumerate(self.tracer_names):
             model._tr[n].data.copy_(self._tr[n][m])
             model._tGm[k].data.copy_(self._tGm[k][m])
+        if self._stochastic is not None and model._stochastic is not None:
+            model._stochastic.counter.copy_(self._stochastic.counter[m:m + 1])
         model.clock_time, model.iteration = float(self.clock_times[m]), self.iteration
         return model
 

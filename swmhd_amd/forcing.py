@@ -11,6 +11,7 @@ from . import _lib
 from .closure import RK3_REAL_AXIS_BOUND
 from .fields import LOCS
 from .grid import Center
+from .stochastic import MAX_MODES, PAIR, SCALAR, StochasticForcing, forcing_modes
 
 
 def _nodes(grid, loc):
@@ -125,13 +126,75 @@ class Relaxation:
         return math.inf if rmax == 0.0 else RK3_REAL_AXIS_BOUND / rmax
 
 
+def split_entry(name, value):
+    """(Relaxation or None, StochasticForcing or None) of one value of the `forcing=` dict: either class, or a tuple with at most one
+    of each."""
+    items = value if isinstance(value, tuple) else (value,)
+    relax = [v for v in items if isinstance(v, Relaxation)]
+    stir = [v for v in items if isinstance(v, StochasticForcing)]
+    if not items or len(relax) + len(stir) != len(items) or len(relax) > 1 or len(stir) > 1:
+        bad = next((v for v in items if not isinstance(v, (Relaxation, StochasticForcing))), value)
+        raise _lib.SwmhdError(f"forcing of {name!r}: a Relaxation, a StochasticForcing or a tuple with at most one of each, not "
+                              f"{type(bad).__name__}")
+    return (relax[0] if relax else None), (stir[0] if stir else None)
+
+
+def check_stochastic(forcing, grid, names, tracer_names, members=None, conservative=False):
+    """The refusals of the StochasticForcing entries of `forcing` (which has passed check_forcing), before anything is
+    allocated, and the draw groups of the model: a list of dicts (kind, names, forcing, modes, rate) in the order of the fields, rate a
+    float or an array (members,) -- or None without the class or with rates that are all 0, and then the model makes exactly the calls
+    it makes without it."""
+    if not forcing:
+        return None
+    fields = tuple(names) + tuple(tracer_names)
+    stir = {n: s for n, s in ((n, split_entry(n, v)[1]) for n, v in forcing.items()) if s is not None}
+    if not stir:
+        return None
+    if grid.topo_codes() != (_lib.PERIODIC, _lib.PERIODIC):
+        raise _lib.SwmhdError("StochasticForcing needs a (Periodic, Periodic) grid (SWMHD_ENOTSUP): its modes are periodic")
+    mom = fields[:2]
+    if any(n in stir for n in mom):
+        if conservative:
+            raise _lib.SwmhdError(f"StochasticForcing on {mom[0]!r}, {mom[1]!r} is not supported (SWMHD_ENOTSUP): the conservative "
+                                  "formulation would need h F; stir the vector-invariant model")
+        if not all(n in stir for n in mom) or stir[mom[0]] is not stir[mom[1]]:
+            raise _lib.SwmhdError(f"StochasticForcing on the momentum: the SAME object under {mom[0]!r} and {mom[1]!r} (one stream "
+                                  "function stirs both); one name without the other is refused")
+    first = next(iter(stir.values()))
+    if any((s.seed, s.stream) != (first.seed, first.stream) for s in stir.values()):
+        raise _lib.SwmhdError("StochasticForcing: the entries of one model share one seed and one stream (their draws differ by group)")
+    groups = []
+    for n in fields:
+        s = stir.get(n)
+        if s is None or n == mom[1]:
+            continue
+        pair = n == mom[0]
+        if np.ndim(s.rate) == 1 and (members is None or s.rate.shape[0] != members):
+            raise _lib.SwmhdError(f"forcing of {n}: {s.rate.shape[0]} rates" + (" belong to an ensemble" if members is None else
+                                                                                   f" for {members} members (a scalar or one per member)"))
+        modes = forcing_modes(grid, s.k_f, s.dk)
+        if len(modes) == 0 or len(modes) > MAX_MODES:
+            raise _lib.SwmhdError(f"forcing of {n}: {len(modes)} modes in the ring k_f = {s.k_f}, dk = {s.dk} (1 .. {MAX_MODES}: "
+                                  "SWMHD_STOCHASTIC_MAX_MODES)")
+        groups.append(dict(kind=PAIR if pair else SCALAR, names=mom if pair else (n,), forcing=s, modes=modes, rate=s.rate))
+    if not any(np.any(np.asarray(g["rate"]) != 0.0) for g in groups):
+        return None
+    return groups
+
+
 def forcing_for_member(forcing, m):
-    """The `forcing=` argument of member m of an ensemble: every Relaxation in it by its for_member."""
-    return None if forcing is None else {n: r.for_member(m) for n, r in forcing.items()}
+    """The `forcing=` argument of member m of an ensemble: every Relaxation and StochasticForcing in it by its for_member; one
+    StochasticForcing under two names stays one object."""
+    if forcing is None:
+        return None
+    made = {}
+    one = lambda v: made.setdefault(id(v), v.for_member(m))
+    return {n: tuple(one(v) for v in r) if isinstance(r, tuple) else one(r) for n, r in forcing.items()}
 
 
 def check_forcing(forcing, grid, names, tracer_names, members=None, slabs=False, ring=False, fused=True, bounded_ensemble=False):
-    """The refusals of a model or ensemble with `forcing`, before anything is allocated.  Returns the forced fields in the order of
+    """The refusals of a model or ensemble with `forcing`, before anything is allocated; a value is a Relaxation, a StochasticForcing
+    (swmhd_amd.stochastic, whose own refusals check_stochastic makes) or a tuple with at most one of each.  Returns the forced fields in the order of
     `names` then `tracer_names`, as a list of (name, rate, mask, target) of host values (Relaxation.evaluate; rate a float or an array
     (members,)), the fields whose rates are all 0 left out -- or None where nothing is left, and then the model makes exactly the calls
     it makes without the argument."""
@@ -149,8 +212,7 @@ def check_forcing(forcing, grid, names, tracer_names, members=None, slabs=False,
                 raise _lib.SwmhdError(f"forcing of {n!r}: this formulation's prognostic field is {other[n]!r}, and the term acts on the "
                                       "prognostic field of its name")
             raise _lib.SwmhdError(f"forcing of {n!r}: the prognostic fields are {fields!r}")
-        if not isinstance(r, Relaxation):
-            raise _lib.SwmhdError(f"forcing of {n!r}: a Relaxation, not {type(r).__name__}")
+        split_entry(n, r)      # a Relaxation, a StochasticForcing or a tuple with at most one of each
     if bounded_ensemble:
         raise _lib.SwmhdError("forcing on a Bounded ensemble is not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is one native "
                               "call and has no per-stage entry point for the correction launch")
@@ -163,7 +225,7 @@ def check_forcing(forcing, grid, names, tracer_names, members=None, slabs=False,
                               "started from")
     out = []
     for n in fields:
-        r = forcing.get(n)
+        r = split_entry(n, forcing[n])[0] if n in forcing else None
         if r is None:
             continue
         mask, target = r.evaluate(grid, LOCS.get(n, (Center, Center)), n, members)

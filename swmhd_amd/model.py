@@ -17,7 +17,8 @@ from .coriolis import check_coriolis, row_table
 from .corrections import correction_list, live_fields, needs_stages
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
-from .forcing import check_forcing, device_parents
+from .forcing import check_forcing, check_stochastic, device_parents
+from .stochastic import StochasticState
 from .grid import Center, Face
 from .shared import (RK3_GAMMA, RK3_ZETA, ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions,
                      diagnostics_dict, fill_groups, finish_stage, formulation_codes, gradient_values, rk3_stage)
@@ -104,6 +105,10 @@ class ShallowWaterModel:
         self.forcing = forcing
         relax = check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, None,
                               decomp is not None and decomp.world_size > 1, ring is not None, fused)
+        # the StochasticForcing entries of `forcing` (swmhd_amd.stochastic): their draw groups; None without the class and with rates
+        # that are all 0, and then nothing is allocated or enqueued for it
+        stir = check_stochastic(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, None,
+                                formulation != VectorInvariantFormulation)
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code, self.lorentz_code, self.names = formulation_codes(formulation, lorentz_forcing)
@@ -170,6 +175,8 @@ class ShallowWaterModel:
             dev = self._raw_fields[0].data.device
             up = lambda a: device_parents(grid, a, dtype, dev)
             self._relaxation = [(n, float(r), up(m), up(t) if np.ndim(t) else float(t)) for n, r, m, t in relax]
+        # the stochastic forcing on the device: step counter, coefficient pairs, tables (StochasticState); None where inactive
+        self._stochastic = StochasticState(stir, grid, dtype, self._raw_fields[0].data.device) if stir is not None else None
         # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
         self._corrections = correction_list(self, self._raw_fields[0].stride_y)
         # y-slab ring: the native RCCL ring (swmhd_ring_*) when the process group is RCCL; torch.distributed p2p otherwise
@@ -499,6 +506,8 @@ class ShallowWaterModel:
         self._ensure_halos()
         saved = self._raw_fields + self.Gm + [self._tr[n] for n in self.tracer_names] + self._tGm
         keep = [f.data.clone() for f in saved]
+        # the step counter of a stochastic forcing: the warm-up steps draw and advance it, a replayed run must draw what an eager run draws
+        counter = self._stochastic.counter.clone() if self._stochastic is not None else None
         t0, i0 = self.clock_time, self.iteration
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -514,6 +523,8 @@ class ShallowWaterModel:
         self._graph_roles = self._roles()
         for f, k in zip(saved, keep):   # capture does not execute; undo the two warm-up steps (which left every role where it was)
             f.data.copy_(k)
+        if counter is not None:
+            self._stochastic.counter.copy_(counter)
         self._halo_stale = False
         self.clock_time, self.iteration = t0, i0
         return self
@@ -643,7 +654,8 @@ class ShallowWaterModel:
                  **{n: f.numpy() for n, f in zip(self.names, self.fields)},
                  **{"Gm_" + n: f.numpy() for n, f in zip(self.names, self.Gm)},
                  **{"tracer_" + n: self._tr[n].numpy() for n in self.tracer_names},
-                 **{"tracer_Gm_" + n: f.numpy() for n, f in zip(self.tracer_names, self._tGm)})
+                 **{"tracer_Gm_" + n: f.numpy() for n, f in zip(self.tracer_names, self._tGm)},
+                 **({"stochastic_counter": self._stochastic.counter_values()} if self._stochastic is not None else {}))
 
     def load_checkpoint(self, path):
         import numpy as np
@@ -657,6 +669,8 @@ class ShallowWaterModel:
         for n, f in zip(self.tracer_names, self._tGm):
             self._tr[n].data.copy_(torch.from_numpy(z["tracer_" + n]).to(f.data.dtype))
             f.data.copy_(torch.from_numpy(z["tracer_Gm_" + n]).to(f.data.dtype))
+        if self._stochastic is not None and "stochastic_counter" in z.files:      # (older checkpoints have none: the counter stays)
+            self._stochastic.set_counter(z["stochastic_counter"])
         self.clock_time, self.iteration = float(z["time"]), int(z["iteration"])
         return self
 
