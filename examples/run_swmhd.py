@@ -44,6 +44,11 @@ gives one member per entry (a sweep of the drag), and a list of several values s
 Relaxation(rate = RATE, mask = G) on the same two fields, G(y) = exp(-((y - y_south) / WIDTH)²) + exp(-((y - y_north) / WIDTH)²): sponge
 layers that absorb what reaches the walls.  With --drag R as well the two terms are one, Relaxation(rate = 1, mask = R + RATE G).  With --channel either runs ONE Bounded model (one --gradients entry: Bounded ensembles take no forcing).  dt is not
 limited by the forcing: the line printed at the start gives Relaxation.max_stable_dt.
+--bump HEIGHT,WIDTH runs over bathymetry = HEIGHT exp(-(x² + y²) / WIDTH²) (ShallowWaterModel(bathymetry=...)): a Gaussian hill at the
+domain centre, subtracted from the initial h so that the surface h + b starts flat.  --body-force F0,K adds swmhd_amd.Source(F0 sin(K y))
+to the first momentum-like field: the steady force of a Kolmogorov flow; it combines with --drag, --beta and --stir.  Either runs one
+model, with one more launch per RK3 stage for both together.
+
 --stir RATE,KF[,DK] [--seed N] stirs u and v with swmhd_amd.StochasticForcing(rate = RATE, k_f = KF, dk = DK): a random stream function
 in the ring of wavenumbers KF - DK/2 <= |k| < KF + DK/2 (DK: the grid's lowest wavenumber unless given), white in time, exactly
 non-divergent, renewed on the device every step and reproducible from the seed; RATE is the mean kinetic-energy injection per unit
@@ -108,6 +113,8 @@ def main():
     ap.add_argument("--sponge", default=None, help="RATE,WIDTH with --channel: Relaxation(rate=RATE, mask=Gaussians of that width at the two walls) on the momentum-like fields")
     ap.add_argument("--stir", default=None, help="RATE,KF[,DK]: StochasticForcing(rate=RATE, k_f=KF, dk=DK or the grid's lowest wavenumber) on u and v (one periodic model, --formulation jacobian)")
     ap.add_argument("--seed", type=int, default=0, help="seed of --stir")
+    ap.add_argument("--bump", default=None, help="HEIGHT,WIDTH: bathymetry = a Gaussian hill of that height and width at the domain centre, subtracted from the initial h (one model)")
+    ap.add_argument("--body-force", default=None, help="F0,K: Source(F0 sin(K y)) on the first momentum-like field, a Kolmogorov force (one model)")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -145,11 +152,16 @@ def main():
         ap.error("--stir RATE,KF[,DK]: a periodic grid and --formulation jacobian (the stirring is a stream function's, for u and v)")
     if a.stir is not None and (a.amps or a.sweep):
         ap.error("--stir runs one model: not with an ensemble run")
+    for opt, val in (("--bump HEIGHT,WIDTH", a.bump), ("--body-force F0,K", a.body_force)):
+        if val is not None and len(val.split(",")) != 2:
+            ap.error(f"{opt}: two numbers")
+        if val is not None and (a.amps or a.sweep):
+            ap.error(f"{opt} runs one model: not with an ensemble run")
     if a.sponge is not None and (not a.channel or len(a.sponge.split(",")) != 2):
         ap.error("--sponge RATE,WIDTH needs --channel: the sponge layers stand at the channel's walls")
     # --channel with --beta, --drag or --sponge: ONE Bounded model (Bounded ensembles take no f(y) and no forcing), so one gradient, one
     # f0, one beta and one drag
-    one_channel = a.channel and (a.beta is not None or a.drag is not None or a.sponge is not None)
+    one_channel = a.channel and (a.beta is not None or a.drag is not None or a.sponge is not None or a.bump is not None or a.body_force is not None)
     if one_channel and (a.gravity or a.dts or any("," in (x or "") for x in (a.gradients, a.beta, a.coriolis, a.drag))):
         ap.error("--channel with --beta, --drag or --sponge runs one model: one --gradients entry, one --coriolis, one --beta, one --drag, "
                  "no --gravity or --dts")
@@ -202,8 +214,24 @@ def main():
         stir = S.StochasticForcing(vals[0], vals[1], vals[2] if len(vals) > 2 else 2 * np.pi / L, seed=a.seed)
         print(f"forcing: {stir} on u, v: {len(S.forcing_modes(grid, stir.k_f, stir.dk))} modes")
         forcing = {n: ((forcing[n], stir) if forcing and n in forcing else stir) for n in momentum}
+    # --body-force F0,K: Source(F0 sin(K y)) under the first momentum-like field (an acceleration in both formulations), beside whatever
+    # that field carries already: the steady force of a Kolmogorov flow.  One more launch per RK3 stage for it and --bump together
+    if a.body_force is not None:
+        f0, kk = (float(x) for x in a.body_force.split(","))
+        push = S.Source(lambda x, y: f0 * np.sin(kk * y) + 0 * x)
+        print(f"forcing: {momentum[0]} = Source({f0:g} sin({kk:g} y))")
+        forcing = dict(forcing or {})
+        held = forcing.get(momentum[0], ())
+        forcing[momentum[0]] = (held if isinstance(held, tuple) else (held,)) + (push,)
+    # --bump HEIGHT,WIDTH: bathymetry = a Gaussian hill at the domain centre; h stays the fluid thickness, so the initial h is 1 - b
+    # and the surface h + b starts flat
+    bump = None
+    if a.bump is not None:
+        height, width = (float(x) for x in a.bump.split(","))
+        bump = lambda x, y: height * np.exp(-(x ** 2 + y ** 2) / width ** 2)
+        print(f"bathymetry: a Gaussian hill, height {height:g}, width {width:g}")
     model = S.ShallowWaterModel(grid, configs.G, formulation=form, tracers=("c",) if a.dye else (), closure=closure, coriolis=coriolis,
-                                boundary_conditions=bcs, forcing=forcing)
+                                boundary_conditions=bcs, forcing=forcing, bathymetry=bump)
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)
     A0 = (lambda X, Y: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp)
     if a.channel:
@@ -211,7 +239,8 @@ def main():
     u0 = lambda X, Y: 5 * Y * np.exp(-(X ** 2 + Y ** 2))
     v0 = lambda X, Y: -5 * X * np.exp(-(X ** 2 + Y ** 2))
     n1, n2 = model.names[:2]
-    model.set(**{n1: u0, n2: v0, "h": lambda X, Y: np.ones_like(X), "A": A0})      # h = 1: (uh, vh) = (u, v)
+    h0 = (lambda X, Y: np.ones_like(X)) if bump is None else (lambda X, Y: 1.0 - bump(X, Y))
+    model.set(**{n1: u0, n2: v0, "h": h0, "A": A0})      # h = 1: (uh, vh) = (u, v); over a hill (uh, vh) start as (u, v) all the same
     if a.dye:
         model.set(c=lambda X, Y: np.tanh(Y))
     nsteps = int(round(a.stop_time / a.dt))

@@ -783,5 +783,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_relaxation.h"
 /* Stochastic forcing (swmhd_stochastic_coefficients_*, swmhd_stochastic_rk3_* and their ensemble forms): band-limited white-noise stirring per RK3 step */
 #include "swmhd_stochastic.h"
+/* Static sources (swmhd_source_rk3_*, swmhd_ensemble_source_rk3_*): bathymetry and steady body forces, a fixed field (times the face thickness) added per RK3 stage */
+#include "swmhd_source.h"
 
 #endif /* SWMHD_H */

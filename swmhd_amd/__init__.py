@@ -16,11 +16,11 @@ from .spectra import ZonalSpectrumTimeSeries
 from .spectra2d import IsotropicSpectrumTimeSeries
 from .closure import ScalarBiharmonicDiffusivity, ScalarDiffusivity
 from .coriolis import FPlane, BetaPlane, CoriolisProfile
-from .forcing import Relaxation
+from .forcing import Relaxation, Source
 from .stochastic import StochasticForcing, forcing_modes
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
            "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble",
            "BoundedShallowWaterEnsemble", "FieldTimeSeries", "ZonalMeanTimeSeries", "ZonalSpectrumTimeSeries", "IsotropicSpectrumTimeSeries", "ScalarDiffusivity", "ScalarBiharmonicDiffusivity", "FPlane", "BetaPlane",
-           "CoriolisProfile", "Relaxation", "StochasticForcing", "forcing_modes", "TimeInterval", "IterationInterval", "run", "_lib"]
+           "CoriolisProfile", "Relaxation", "Source", "StochasticForcing", "forcing_modes", "TimeInterval", "IterationInterval", "run", "_lib"]

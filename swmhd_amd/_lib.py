@@ -38,6 +38,9 @@ DIFFUSION_TILE_ROWS = 64                  # SWMHD_DIFFUSION_TILE_ROWS: rows of a
 CORIOLIS_TILE_ROWS = 64                   # SWMHD_CORIOLIS_TILE_ROWS: rows of a workgroup of the Coriolis kernel (four waves)
 RELAXATION_MAX_FIELDS = 4 + MAX_TRACERS   # SWMHD_RELAXATION_MAX_FIELDS: fields per swmhd_relaxation_rk3_* launch
 RELAXATION_TILE_ROWS = 64                 # SWMHD_RELAXATION_TILE_ROWS: rows of a workgroup of the relaxation kernel (four waves)
+SOURCE_MAX_FIELDS = 4 + MAX_TRACERS       # SWMHD_SOURCE_MAX_FIELDS: fields per swmhd_source_rk3_* launch
+SOURCE_TILE_ROWS = 64                     # SWMHD_SOURCE_TILE_ROWS: rows of a workgroup of the source kernel (four waves)
+SOURCE_PLAIN, SOURCE_X_FACE, SOURCE_Y_FACE = 0, 1, 2    # SWMHD_SOURCE_*: the source as it is, times the thickness at the x / y face
 STOCHASTIC_MAX_FIELDS = 4 + MAX_TRACERS   # SWMHD_STOCHASTIC_MAX_FIELDS: fields per swmhd_stochastic_rk3_* launch, groups per draw
 STOCHASTIC_MAX_MODES = 256                # SWMHD_STOCHASTIC_MAX_MODES: Fourier modes of one field
 STOCHASTIC_TILE_ROWS = 64                 # SWMHD_STOCHASTIC_TILE_ROWS: rows of a workgroup of the stochastic kernel (four waves)
@@ -231,6 +234,13 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_relaxation_rk3_{sfx}")
         f.argtypes = [C.POINTER(p)] * 5 + [p, p, i, i, i64, i64, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
         f.restype = i
+        # Static sources: old, new, acc, source (host arrays of device pointers), kind (host array), nfields, thickness, ...
+        f = getattr(lib, f"swmhd_source_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [C.POINTER(i), i, i, i, i, i, i, i64, ft, ft, i, i, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_source_rk3_{sfx}")
+        f.argtypes = [C.POINTER(p)] * 4 + [C.POINTER(i), i, i, i, i64, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
+        f.restype = i
         # Stochastic forcing, the draw: counter (device), coef, amp0, ktx, kty (host arrays of device pointers), nmodes, kind (host), ...
         f = getattr(lib, f"swmhd_stochastic_coefficients_{sfx}")
         f.argtypes = [p] + [C.POINTER(p)] * 4 + [C.POINTER(i), C.POINTER(i), i, C.c_uint64, C.c_uint32, C.c_double, p]
@@ -311,6 +321,8 @@ RELAXATION_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name i
 # the symbols include/swmhd_stochastic.h declares (swmhd.h includes it; tests/test_stochastic_abi.py checks the .so exports each of them)
 STOCHASTIC_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
                       for name in ("stochastic_coefficients", "ensemble_stochastic_coefficients", "stochastic_rk3", "ensemble_stochastic_rk3")]
+# the symbols include/swmhd_source.h declares (swmhd.h includes it; tests/test_source_abi.py checks the .so exports each of them)
+SOURCE_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("source_rk3", "ensemble_source_rk3")]
 RING_ID_BYTES = 128
 
 

@@ -92,9 +92,10 @@ class StochasticCorrection(Correction):
 
 
 def correction_list(o, stride_y):
-    """The active corrections of `o` (its data attributes _coriolis, _diffusion, _biharmonic, _relaxation and _stochastic: None where
-    inactive) in the order of their launches: Coriolis, Laplacian, biharmonic, relaxation, stochastic.  Each corrects what the launches
-    before it have written, so the new field is (((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax) + a F_stoch), and this order
+    """The active corrections of `o` (its data attributes _coriolis, _diffusion, _biharmonic, _relaxation, _source and _stochastic: None
+    where inactive) in the order of their launches: Coriolis, Laplacian, biharmonic, relaxation, source, stochastic.  Each corrects what
+    the launches before it have written, so the new field is ((((((stage + a D_cor) + a D_lap) + a D_bih) + a D_relax) + a D_src) +
+    a F_stoch), and this order
     decides the last bits where several are present.  Empty without any: then the object may step through its native driver (needs_stages).  stride_y: the
     pitch of the object's fields.  A further term is one more entry here, after the ones whose result it is to correct: its stem,
     its fields and its `middle`; the C entry points take the argument layout Correction states."""
@@ -122,6 +123,17 @@ def correction_list(o, stride_y):
             strides = ()
         out.append(Correction(o, stride_y, "relaxation", [r[0] for r in rel], (parents(-2), parents(-1), *tables, len(rel)),
                               member_strides=strides))
+    if getattr(o, "_source", None) is not None:
+        # D = S, or S times the thickness of the state the stage started from at the field's face (the conservative uh, vh); _source:
+        # (name, kind, S) of every field with a static source -- bathymetry and Source entries --, S a device parent.  Where a kind needs
+        # the thickness, h goes along in the call's field list without a source of its own
+        src = o._source
+        names = [n for n in order if n in [s[0] for s in src] or n == o._source_thickness]
+        by = {s[0]: s for s in src}
+        middle = (_lib.ptr_array([by[n][2].data_ptr() if n in by else None for n in names]),
+                  (ctypes.c_int * len(names))(*[by[n][1] if n in by else _lib.SOURCE_PLAIN for n in names]), len(names),
+                  names.index(o._source_thickness) if o._source_thickness is not None else -1)
+        out.append(Correction(o, stride_y, "source", names, middle, member_strides=(o._source_stride,) if ens else ()))
     if getattr(o, "_stochastic", None) is not None:
         # F = the sum of the step's random Fourier modes; _stochastic.fields: (name, mode count, coefficients, x table, y table) of
         # every stirred field.  It reads no state: `old` goes along for the common layout only

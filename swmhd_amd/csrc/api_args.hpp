@@ -112,6 +112,10 @@ constexpr int CORIOLIS_NOTSUP = KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLA
 // a direction with both its flags is an argument error as everywhere; SWMHD_RK3_ANCHOR as for the diffusion calls
 constexpr int RELAXATION_FLAGS = SWMHD_STRICT | WRAP_FLAGS | BOUNDED_FLAGS | SWMHD_RK3_ANCHOR;
 constexpr int RELAXATION_NOTSUP = KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLAGS | SWMHD_LEAVE_ROOM;
+// swmhd_source_rk3 and its ensemble form take relaxation's flags: the WRAP flags say where the thickness one cell west or south of a
+// row's cells is read (the periodic image, else the filled halo), the Bounded flags only that the direction is not wrapped
+constexpr int SOURCE_FLAGS = RELAXATION_FLAGS;
+constexpr int SOURCE_NOTSUP = RELAXATION_NOTSUP;
 // swmhd_ensemble_*: the periodic family, and the boundary-condition family (swmhd_ensemble_fill_halo, swmhd_ensemble_step_rk3_bc),
 // which accepts Bounded directions and runs the stage in G- form
 constexpr int ENS_FLAGS = SWMHD_STRICT | SWMHD_TILE_KERNEL | WRAP_FLAGS | SWMHD_RK3_ANCHOR;

@@ -341,6 +341,23 @@ struct RelaxationArgs : StripArgs<T> {
 template <typename T> hipError_t launch_relaxation_fast(const RelaxationArgs<T> &a, hipStream_t s);
 template <typename T> hipError_t launch_relaxation_strict(const RelaxationArgs<T> &a, hipStream_t s);
 
+// Static sources (swmhd_source_rk3_*, source.hip): D_k = src_k (kind 0) or the thickness `hold` of the state the stage started from,
+// interpolated to the x face (kind 1) or the y face (kind 2), times src_k, of up to 4 + MAX_TRACERS fields in ONE launch: nw[k] += a D_k
+// and, where acc[k] != nullptr, acc[k] += w D_k.  An ensemble member's sources stand at ptr + m * source_stride_m (0: shared), its
+// thickness at hold + m * stride_m.  old is carried for pack_fields and never read.
+constexpr int SOURCE_MAX_FIELDS = 4 + MAX_TRACERS;   // = SWMHD_SOURCE_MAX_FIELDS
+template <typename T>
+struct SourceArgs : StripArgs<T> {
+    const T *old[SOURCE_MAX_FIELDS], *src[SOURCE_MAX_FIELDS];
+    T *nw[SOURCE_MAX_FIELDS], *acc[SOURCE_MAX_FIELDS];
+    int kind[SOURCE_MAX_FIELDS];
+    const T *hold;
+    int nfields;
+    long source_stride_m;
+};
+template <typename T> hipError_t launch_source_fast(const SourceArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_source_strict(const SourceArgs<T> &a, hipStream_t s);
+
 // Stochastic forcing (swmhd_stochastic_rk3_*, stochastic.hip): F_k = sum over M[k] modes of cx (P cy + Q sy) + sx (Q cy - P sy) of up to
 // 4 + MAX_TRACERS fields in ONE launch: nw[k] += a F_k and, where acc[k] != nullptr, acc[k] += w F_k.  coef[k]: P[0 .. M) then Q[0 .. M);
 // xtab[k] / ytab[k]: rows 2 m (cos) and 2 m + 1 (sin) of xp / yp elements, at column / row 0 of the interior.  An ensemble member's

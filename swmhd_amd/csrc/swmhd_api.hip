@@ -448,6 +448,41 @@ int stochastic_common(const T *const *old, T *const *nw, T *const *acc, const T 
     return hiprc(fl.strict ? launch_stochastic_strict<T>(d, s) : launch_stochastic_fast<T>(d, s));
 }
 
+// swmhd_source_rk3: nw[k] += a D_k, acc[k] += w D_k with D_k = source[k], or source[k] times old[thickness] interpolated to the x face
+// (kind 1) or the y face (kind 2), of up to SWMHD_SOURCE_MAX_FIELDS fields in one launch (source.hip).  Every check precedes the first
+// HIP call, in the order include/swmhd_source.h states.  With `ens` (swmhd_ensemble_source_rk3): source_sm pitches the members' sources
+// (0: shared); ens->params (optional) brings every member's dt.  The fields without a source are left out of the launch here.
+template <typename T>
+int source_common(const T *const *old, T *const *nw, T *const *acc, const T *const *source, const int *kind, int nfields, int thickness,
+                  const Grid &g, T a, T w, const Rows &r, int flags, void *stream, const Ens *ens = nullptr, int64_t source_sm = 0) {
+    const FieldSets<T> f{old, nw, acc, nfields};
+    if (!source || !kind || bounded_wrap_conflict(flags)) return SWMHD_EINVAL;
+    if (!field_correction_ok<T>(f, SWMHD_SOURCE_MAX_FIELDS, {source}, g, a, w, r, flags, SOURCE_FLAGS | SOURCE_NOTSUP, ens, source_sm)) return SWMHD_EINVAL;
+    if (thickness < -1 || thickness >= nfields) return SWMHD_EINVAL;
+    bool weighted = false;
+    for (int k = 0; k < nfields; ++k) {
+        if (kind[k] < SWMHD_SOURCE_PLAIN || kind[k] > SWMHD_SOURCE_Y_FACE) return SWMHD_EINVAL;
+        weighted = weighted || (source[k] && kind[k] != SWMHD_SOURCE_PLAIN);
+    }
+    if (weighted && thickness < 0) return SWMHD_EINVAL;
+    if (flags & SOURCE_NOTSUP) return SWMHD_ENOTSUP;
+    const Flags fl = decode_flags(flags);
+    if (weighted && ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2)))) return SWMHD_EHALO;
+    if (r.j0 == r.j1) return SWMHD_OK;
+    SourceArgs<T> d;
+    const int n = pack_fields(d, SOURCE_MAX_FIELDS, f, g, [&](int k) { return source[k] != nullptr; }, [&](int slot, int k) {
+        d.src[slot] = k >= 0 ? g.interior(source[k]) : nullptr;
+        d.kind[slot] = k >= 0 ? kind[k] : 0;
+    });
+    if (n == 0) return SWMHD_OK;
+    set_strip(d, g, r, fl, a, w, ens);
+    d.hold = weighted ? g.interior(old[thickness]) : nullptr;
+    d.nfields = n; d.source_stride_m = ens ? (long)source_sm : 0;
+    hipStream_t s = (hipStream_t)stream;
+    return hiprc(fl.strict ? launch_source_strict<T>(d, s) : launch_source_fast<T>(d, s));
+}
+static_assert(SOURCE_MAX_FIELDS == SWMHD_SOURCE_MAX_FIELDS && SWMHD_SOURCE_MAX_FIELDS <= SWMHD_RELAXATION_MAX_FIELDS, "common.hpp mirrors swmhd_source.h; field_correction_ok sizes its arrays by the relaxation call");
+
 // swmhd_stochastic_coefficients: the draw of one time step (stochastic_coefficients.hip).  Without `ens`: one grid, with `substream`.
 template <typename T>
 int stochastic_coefficients_common(uint64_t *counter, T *const *coef, const double *const *amp0, const double *const *ktx,
@@ -897,5 +932,22 @@ SWMHD_DEF_RELAXATION(f32, float)
 
 SWMHD_DEF_STOCHASTIC(f64, double)
 SWMHD_DEF_STOCHASTIC(f32, float)
+
+// include/swmhd_source.h
+#define SWMHD_DEF_SOURCE(sfx, T)                                                                                                                       \
+    int swmhd_source_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *const *source, const int *kind, int nfields,                \
+                               int thickness, int Nx, int Ny, int Hx, int Hy, int64_t sy, T a, T w, int j0, int j1, int flags, void *stream) {        \
+        return source_common<T>(old, nw, acc, source, kind, nfields, thickness, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags, stream);         \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_source_rk3_##sfx(const T *const *old, T *const *nw, T *const *acc, const T *const *source, const int *kind, int nfields,       \
+                                        int thickness, int members, int64_t stride_m, int64_t source_stride_m, int Nx, int Ny, int Hx, int Hy,        \
+                                        int64_t sy, const T *params, T a, T w, int j0, int j1, int flags, void *stream) {                             \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return source_common<T>(old, nw, acc, source, kind, nfields, thickness, Grid{Nx, Ny, Hx, Hy, sy}, a, w, Rows{j0, j1}, flags, stream, &e,      \
+                                source_stride_m);                                                                                                     \
+    }
+
+SWMHD_DEF_SOURCE(f64, double)
+SWMHD_DEF_SOURCE(f32, float)
 
 }  // extern "C"

@@ -20,7 +20,7 @@ from .closure import check_closure, closure_for_member
 from .coriolis import check_coriolis, row_table
 from .corrections import correction_list, live_fields, member_table, needs_stages
 from .fields import _SFX, _stream_ptr
-from .forcing import check_forcing, check_stochastic, device_parents, forcing_for_member
+from .forcing import check_bathymetry, check_forcing, check_source, check_stochastic, device_parents, forcing_for_member
 from .grid import Center, Face
 from .model import ShallowWaterModel, rk3_operands, tracer_names
 from .stochastic import StochasticState
@@ -76,14 +76,15 @@ class ShallowWaterEnsemble:
 
     Forcing: `forcing={"u": Relaxation(rate, mask, target), ...}` (ShallowWaterModel's argument; swmhd_amd.forcing) with a scalar or one
     value per member for every rate and scalar target, and masks and target arrays of shape (Ny, Nx) for all members or (members, Ny,
-    Nx) -- a sweep of the drag.  `relaxation_rates` and `relaxation_targets` are the (members, forced fields) device tables; such an
+    Nx) -- a sweep of the drag; a `Source(value)` takes a scalar per member or an array (members, Ny, Nx), and `bathymetry=` an array
+    (Ny, Nx) for all members or (members, Ny, Nx) (one more launch per stage, swmhd_ensemble_source_rk3_*, after the relaxation's).  `relaxation_rates` and `relaxation_targets` are the (members, forced fields) device tables; such an
     ensemble steps stage by stage with one more launch per stage for all members (swmhd_ensemble_relaxation_rk3_*), after the
     closures' launches, under a scalar or a per-member dt.  Without a forcing, or with rates that are all 0, the ensemble calls exactly
     what it calls without the argument."""
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, tracers=(), closure=None, coriolis=None, forcing=None):
+                 fuse_halo=True, tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None):
         self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
         # coriolis = FPlane | BetaPlane | CoriolisProfile (ShallowWaterModel's argument; values may be per member).  None and FPlane: the
         # f of the stage kernels.  Otherwise they get f = 0 and _coriolis holds the parameter whose rows a correction launch adds
@@ -115,6 +116,12 @@ class ShallowWaterEnsemble:
                                 formulation != VectorInvariantFormulation)
         self.g_values, g_seq = per_member_values(gravitational_acceleration, self.members, "gravitational_acceleration")
         self.f_values, f_seq = per_member_values(coriolis_f, self.members, "coriolis_f")
+        # bathymetry (ShallowWaterModel's argument; also (members, Ny, Nx)) and the Source entries of `forcing`: one static field per
+        # forced field, per member where b, g or a Source is, else one array for all members
+        self.bathymetry = check_bathymetry(bathymetry, grid, self.members)
+        sources, self._source_thickness = check_source(forcing, self.bathymetry, grid, formulation_codes(formulation, lorentz_forcing)[2],
+                                                       self.tracer_names, self.g_values if g_seq else float(gravitational_acceleration),
+                                                       self.members, formulation != VectorInvariantFormulation)
         self.grid = grid
         self.g = self.g_values if g_seq else float(gravitational_acceleration)
         self.f = self.f_values if f_seq else float(coriolis_f)
@@ -172,6 +179,14 @@ class ShallowWaterEnsemble:
             self.relaxation_rates = member_table([r for _, r, _, _ in relax], dtype, dev)
             self.relaxation_targets = member_table(tvals, dtype, dev)
             self._relaxation = [(n, m, t) for (n, _, _, _), m, t in zip(relax, masks, targets)]
+        # the static sources on the device: parents of the fields' shape and pitch -- (Py, Px) shared by all members where no field is per
+        # member (member stride 0), else (members, Py, Px) each: the call has one member stride for the sources
+        self._source, self._source_stride = None, 0
+        if sources is not None:
+            per = any(S.ndim == 3 for _, _, S in sources)
+            self._source_stride = Py * Px if per else 0
+            self._source = [(n, k, device_parents(grid, np.broadcast_to(S, (self.members,) + S.shape[-2:]) if per else S, dtype, dev))
+                            for n, k, S in sources]
         # the stochastic forcing on the device: one step counter and one set of coefficient pairs per member; None where inactive
         self._stochastic = StochasticState(stir, grid, dtype, dev, self.members) if stir is not None else None
         # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
@@ -521,7 +536,8 @@ class ShallowWaterEnsemble:
         return ShallowWaterModel(self.grid, float(self.g_values[m]), formulation=self.formulation,
                                  lorentz_forcing=self.lorentz_forcing, dtype=self.dtype, device=self._state[0].device, strict=self.strict,
                                  tracers=self.tracer_names, closure=closure_for_member(self.closure, m),
-                                 forcing=forcing_for_member(self.forcing, m), **f)
+                                 forcing=forcing_for_member(self.forcing, m),
+                                 bathymetry=self.bathymetry[m] if np.ndim(self.bathymetry) == 3 else self.bathymetry, **f)
 
     def synchronize(self):
         """Wait for everything enqueued; afterwards the halos of every member are current."""
@@ -540,8 +556,9 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None, forcing=None):
+                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None):
         coriolis_f, varying = check_coriolis(coriolis, coriolis_f, 1.0)       # before anything is allocated
+        check_bathymetry(bathymetry, grid, int(members), bounded_ensemble=True)      # (None passes; anything else is refused)
         check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], tracer_names(tracers), int(members),
                       bounded_ensemble=True)       # (None and {} pass; anything else is refused before anything is allocated)
         if varying is not None:

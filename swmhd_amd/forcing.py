@@ -1,8 +1,13 @@
 """Relaxation: Oceananigans' `forcing = (u = Relaxation(rate, mask, target), h = ...)` for the shallow-water MHD engine -- the term
 rate * mask(x, y) * (target(x, y) - φ) added to the tendency of the prognostic field φ of that name, one extra launch per RK3 stage for
 all forced fields (swmhd_relaxation_rk3_* in include/swmhd_relaxation.h).  Large-scale drag is Relaxation(rate) on the two momentum-like
-fields, a sponge layer a Relaxation with a mask, Newtonian relaxation of h one with a target array.  Only device_parents touches a
-device, and only when a model that has passed its checks asks for it."""
+fields, a sponge layer a Relaxation with a mask, Newtonian relaxation of h one with a target array.
+
+Source and `bathymetry=`: a field that does not change in time added to the tendency, under "uh" / "vh" times the thickness at the
+face -- a steady body force and the slope of the bottom, which the host folds into one static field per forced field (check_source),
+one extra launch per RK3 stage (swmhd_source_rk3_* in include/swmhd_source.h).
+
+Only device_parents touches a device, and only when a model that has passed its checks asks for it."""
 import math
 
 import numpy as np
@@ -126,17 +131,162 @@ class Relaxation:
         return math.inf if rmax == 0.0 else RK3_REAL_AXIS_BOUND / rmax
 
 
+class Source:
+    """A steady source: `value` added to the tendency of the prognostic field it is given for, every RK3 stage (swmhd_source_rk3_* in
+    include/swmhd_source.h) -- a Kolmogorov body force, a tracer source.  value: a callable (x, y) evaluated once, when the model is
+    built, on the grid's own nodes at the location of the field (x of shape (1, Nx), y of shape (Ny, 1)); an array (Ny, Nx); or a
+    scalar.  For a ShallowWaterEnsemble also an array (members, Ny, Nx) or one scalar per member.  Under "uh" / "vh" it is an
+    acceleration as under "u" / "v": the device multiplies it by the thickness at the face.  It does not depend on time or on the
+    state, and it does not limit the time step."""
+
+    def __init__(self, value):
+        if callable(value):
+            self.value = value
+            return
+        try:
+            arr = np.array(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            arr = None
+        if arr is None or arr.ndim > 3:
+            raise _lib.SwmhdError(f"Source: value = {type(value).__name__}: a callable (x, y), an array (Ny, Nx) or a scalar")
+        if not np.all(np.isfinite(arr)):
+            raise _lib.SwmhdError("Source: value has values that are not finite")
+        self.value = float(arr) if arr.ndim == 0 else arr
+
+    def __repr__(self):
+        v = self.value
+        return f"Source({v.__name__ if callable(v) else (f'array{v.shape}' if np.ndim(v) else repr(v))})"
+
+    @property
+    def per_member(self):
+        """True where the value holds one scalar or one array per member of an ensemble."""
+        return not callable(self.value) and np.ndim(self.value) in (1, 3)
+
+    def for_member(self, m):
+        """The Source of member m of an ensemble."""
+        return Source(self.value[m]) if self.per_member else self
+
+    def evaluate(self, grid, loc, name="", members=None):
+        """The value on `grid` at `loc` as float64 host values: an array (Ny, Nx), or (members, Ny, Nx) where it is per member.
+        members None: a single model, which takes nothing per member.  SwmhdError for a wrong shape or a value that is not finite."""
+        shape = (grid.Ny, grid.Nx)
+        v = self.value
+        if callable(v):
+            arr = np.asarray(v(*_nodes(grid, loc)), dtype=np.float64)
+            try:
+                arr = np.broadcast_to(arr, shape).copy()
+            except ValueError:
+                raise _lib.SwmhdError(f"forcing of {name}: Source(x, y) has shape {arr.shape}, not {shape}") from None
+            if not np.all(np.isfinite(arr)):
+                raise _lib.SwmhdError(f"forcing of {name}: Source(x, y) has values that are not finite")
+            return arr
+        if members is None and self.per_member:
+            raise _lib.SwmhdError(f"forcing of {name}: per-member values belong to an ensemble")
+        if np.ndim(v) == 0:
+            return np.full(shape, float(v))
+        if np.ndim(v) == 1:
+            if v.shape[0] != members:
+                raise _lib.SwmhdError(f"forcing of {name}: {v.shape[0]} sources for {members} members (a scalar or one per member)")
+            return np.broadcast_to(v[:, None, None], (members,) + shape).copy()
+        ok = (shape,) if members is None else (shape, (members,) + shape)
+        if v.shape not in ok:
+            raise _lib.SwmhdError(f"forcing of {name}: Source of shape {v.shape}, expected {' or '.join(map(str, ok))}")
+        return v.copy()
+
+
+def check_bathymetry(bathymetry, grid, members=None, slabs=False, ring=False, fused=True, bounded_ensemble=False):
+    """`bathymetry=` of a model or an ensemble as float64 host values at the cell centres: None, an array (Ny, Nx) or, for an ensemble,
+    (members, Ny, Nx); a callable (x, y) is evaluated once on the centres.  The refusals are made here, before anything is allocated."""
+    if bathymetry is None:
+        return None
+    if bounded_ensemble:
+        raise _lib.SwmhdError("bathymetry on a Bounded ensemble is not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is one native "
+                              "call and has no per-stage entry point for the correction launch")
+    if slabs:
+        raise _lib.SwmhdError("bathymetry on a y-slab decomposition is not supported (SWMHD_ENOTSUP): one rank only")
+    if ring:
+        raise _lib.SwmhdError("bathymetry with ring= is not supported (SWMHD_ENOTSUP): the slab driver steps the four fields only")
+    if not fused:
+        raise _lib.SwmhdError("bathymetry needs the fused stage kernel (SWMHD_ENOTSUP): fused=False leaves no copy of the state a stage "
+                              "started from")
+    shape = (grid.Ny, grid.Nx)
+    if callable(bathymetry):
+        b = np.asarray(bathymetry(*_nodes(grid, (Center, Center))), dtype=np.float64)
+        try:
+            b = np.broadcast_to(b, shape).copy()
+        except ValueError:
+            raise _lib.SwmhdError(f"bathymetry(x, y) has shape {b.shape}, not {shape}") from None
+    else:
+        try:
+            b = np.array(bathymetry, dtype=np.float64)
+        except (TypeError, ValueError):
+            b = None
+        ok = (shape,) if members is None else (shape, (members,) + shape)
+        if b is None or b.shape not in ok:
+            raise _lib.SwmhdError(f"bathymetry = {type(bathymetry).__name__}" + (f" of shape {b.shape}" if b is not None else "") +
+                                  f": a callable (x, y), an array {' or '.join(map(str, ok))}, or None")
+    if not np.all(np.isfinite(b)):
+        raise _lib.SwmhdError("bathymetry has values that are not finite")
+    return b
+
+
+def bathymetry_slope(b, g, spacing, axis, periodic):
+    """-g ((b[i] - b[i-1]) / spacing) along `axis` (-1: x, -2: y) in float64, the operations in this order: the acceleration of the
+    bottom's slope at the faces of that direction.  b is wrapped in a Periodic direction; on the wall line of a Bounded one (face 0) the
+    value is 0 -- the boundary fill resets that line anyway.  g: a float, or an array (members, 1, 1)."""
+    d = (b - np.roll(b, 1, axis=axis)) / spacing
+    if not periodic:
+        d[(Ellipsis, 0) if axis == -1 else (Ellipsis, 0, slice(None))] = 0.0
+    return -(g * d)
+
+
+def check_source(forcing, bathymetry, grid, names, tracer_names, g, members=None, conservative=False):
+    """The static sources of a model or an ensemble whose `forcing` has passed check_forcing and whose `bathymetry` check_bathymetry:
+    per field the final S in float64, built once --
+        S_u = F_u - g ((b[i,j] - b[i-1,j]) / dx),  S_v = F_v - g ((b[i,j] - b[i,j-1]) / dy),  S = F for h, A and the tracers,
+    F the field's Source or 0 (bathymetry_slope has the wrap and the walls).  Returns (sources, thickness): sources a list of (name,
+    kind, S) in the order of `names` then `tracer_names`, S of shape (Ny, Nx) or, where anything is per member, (members, Ny, Nx), kind
+    SWMHD_SOURCE_PLAIN or, for uh / vh of the conservative formulation, _X_FACE / _Y_FACE (the expression is the same: the device
+    multiplies by the thickness at the face); the fields whose S is identically 0 left out.  thickness: "h" where a kind needs it, else
+    None.  (None, None) where nothing is left, and then the model makes exactly the calls it makes without the arguments.
+    g: a float, or an array (members,)."""
+    fields = tuple(names) + tuple(tracer_names)
+    F = {}
+    for n in fields:
+        s = split_entry(n, forcing[n])[2] if (forcing and n in forcing) else None
+        if s is not None:
+            F[n] = s.evaluate(grid, LOCS.get(n, (Center, Center)), n, members)
+    if bathymetry is not None:
+        tx, ty = grid.topo_codes()
+        gv = np.asarray(g, dtype=np.float64)
+        gv = float(gv) if gv.ndim == 0 else gv[:, None, None]
+        for n, spacing, axis, topo in ((names[0], grid.dx, -1, tx), (names[1], grid.dy, -2, ty)):
+            slope = bathymetry_slope(bathymetry, gv, spacing, axis, topo == _lib.PERIODIC)
+            F[n] = F[n] + slope if n in F else slope
+    out = []
+    for n in fields:
+        if n in F and np.any(F[n] != 0.0):
+            kind = _lib.SOURCE_PLAIN
+            if conservative and n in names[:2]:
+                kind = _lib.SOURCE_X_FACE if n == names[0] else _lib.SOURCE_Y_FACE
+            out.append((n, kind, F[n]))
+    if not out:
+        return None, None
+    return out, ("h" if any(k != _lib.SOURCE_PLAIN for _, k, _ in out) else None)
+
+
 def split_entry(name, value):
-    """(Relaxation or None, StochasticForcing or None) of one value of the `forcing=` dict: either class, or a tuple with at most one
-    of each."""
+    """(Relaxation or None, StochasticForcing or None, Source or None) of one value of the `forcing=` dict: one of the classes, or a
+    tuple with at most one of each."""
     items = value if isinstance(value, tuple) else (value,)
     relax = [v for v in items if isinstance(v, Relaxation)]
     stir = [v for v in items if isinstance(v, StochasticForcing)]
-    if not items or len(relax) + len(stir) != len(items) or len(relax) > 1 or len(stir) > 1:
-        bad = next((v for v in items if not isinstance(v, (Relaxation, StochasticForcing))), value)
-        raise _lib.SwmhdError(f"forcing of {name!r}: a Relaxation, a StochasticForcing or a tuple with at most one of each, not "
+    source = [v for v in items if isinstance(v, Source)]
+    if not items or len(relax) + len(stir) + len(source) != len(items) or len(relax) > 1 or len(stir) > 1 or len(source) > 1:
+        bad = next((v for v in items if not isinstance(v, (Relaxation, StochasticForcing, Source))), value)
+        raise _lib.SwmhdError(f"forcing of {name!r}: a Relaxation, a StochasticForcing, a Source or a tuple with at most one of each, not "
                               f"{type(bad).__name__}")
-    return (relax[0] if relax else None), (stir[0] if stir else None)
+    return (relax[0] if relax else None), (stir[0] if stir else None), (source[0] if source else None)
 
 
 def check_stochastic(forcing, grid, names, tracer_names, members=None, conservative=False):
@@ -183,7 +333,7 @@ def check_stochastic(forcing, grid, names, tracer_names, members=None, conservat
 
 
 def forcing_for_member(forcing, m):
-    """The `forcing=` argument of member m of an ensemble: every Relaxation and StochasticForcing in it by its for_member; one
+    """The `forcing=` argument of member m of an ensemble: every Relaxation, Source and StochasticForcing in it by its for_member; one
     StochasticForcing under two names stays one object."""
     if forcing is None:
         return None
@@ -194,14 +344,15 @@ def forcing_for_member(forcing, m):
 
 def check_forcing(forcing, grid, names, tracer_names, members=None, slabs=False, ring=False, fused=True, bounded_ensemble=False):
     """The refusals of a model or ensemble with `forcing`, before anything is allocated; a value is a Relaxation, a StochasticForcing
-    (swmhd_amd.stochastic, whose own refusals check_stochastic makes) or a tuple with at most one of each.  Returns the forced fields in the order of
+    (swmhd_amd.stochastic, whose own refusals check_stochastic makes), a Source (check_source builds its field) or a tuple with at most
+    one of each.  Returns the forced fields in the order of
     `names` then `tracer_names`, as a list of (name, rate, mask, target) of host values (Relaxation.evaluate; rate a float or an array
     (members,)), the fields whose rates are all 0 left out -- or None where nothing is left, and then the model makes exactly the calls
     it makes without the argument."""
     if forcing is None:
         return None
     if not isinstance(forcing, dict):
-        raise _lib.SwmhdError(f"forcing: a dict {{field name: Relaxation}} or None, not {type(forcing).__name__}")
+        raise _lib.SwmhdError(f"forcing: a dict {{field name: Relaxation | StochasticForcing | Source}} or None, not {type(forcing).__name__}")
     if not forcing:
         return None
     fields = tuple(names) + tuple(tracer_names)
@@ -212,7 +363,7 @@ def check_forcing(forcing, grid, names, tracer_names, members=None, slabs=False,
                 raise _lib.SwmhdError(f"forcing of {n!r}: this formulation's prognostic field is {other[n]!r}, and the term acts on the "
                                       "prognostic field of its name")
             raise _lib.SwmhdError(f"forcing of {n!r}: the prognostic fields are {fields!r}")
-        split_entry(n, r)      # a Relaxation, a StochasticForcing or a tuple with at most one of each
+        split_entry(n, r)      # a Relaxation, a StochasticForcing, a Source or a tuple with at most one of each
     if bounded_ensemble:
         raise _lib.SwmhdError("forcing on a Bounded ensemble is not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is one native "
                               "call and has no per-stage entry point for the correction launch")

@@ -17,7 +17,7 @@ from .coriolis import check_coriolis, row_table
 from .corrections import correction_list, live_fields, needs_stages
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
-from .forcing import check_forcing, check_stochastic, device_parents
+from .forcing import check_bathymetry, check_forcing, check_source, check_stochastic, device_parents
 from .stochastic import StochasticState
 from .grid import Center, Face
 from .shared import (RK3_GAMMA, RK3_ZETA, ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions,
@@ -70,7 +70,7 @@ class ShallowWaterModel:
     def __init__(self, grid, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, device="cuda", strict=False, decomp=None, group=None,
                  overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None,
-                 tracers=(), closure=None, coriolis=None, forcing=None):
+                 tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None):
         # coriolis = FPlane | BetaPlane | CoriolisProfile (swmhd_amd.coriolis), checked before anything is allocated.  None and FPlane:
         # the scalar f of the stage kernels, exactly the calls made without the argument.  Otherwise the stage kernels get f = 0 and
         # _coriolis holds the parameter whose rows a correction launch adds after every stage (corrections.correction_list)
@@ -109,6 +109,14 @@ class ShallowWaterModel:
         # that are all 0, and then nothing is allocated or enqueued for it
         stir = check_stochastic(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, None,
                                 formulation != VectorInvariantFormulation)
+        # bathymetry = b(x, y) at the cell centres (a callable, an array (Ny, Nx) or None): h stays the fluid thickness, the surface is
+        # h + b.  Its slope and the Source entries of `forcing` are one static field per forced field, built here in float64, before
+        # anything is allocated: _source is the list of (name, kind, S) of a correction launch (corrections.correction_list); None
+        # without either and with fields that are all 0 (a constant b), and then the model makes exactly the calls it makes without them
+        self.bathymetry = check_bathymetry(bathymetry, grid, None, decomp is not None and decomp.world_size > 1, ring is not None, fused)
+        sources, self._source_thickness = check_source(forcing, self.bathymetry, grid, formulation_codes(formulation, lorentz_forcing)[2],
+                                                       self.tracer_names, float(gravitational_acceleration), None,
+                                                       formulation != VectorInvariantFormulation)
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code, self.lorentz_code, self.names = formulation_codes(formulation, lorentz_forcing)
@@ -175,6 +183,11 @@ class ShallowWaterModel:
             dev = self._raw_fields[0].data.device
             up = lambda a: device_parents(grid, a, dtype, dev)
             self._relaxation = [(n, float(r), up(m), up(t) if np.ndim(t) else float(t)) for n, r, m, t in relax]
+        # (name, kind, S) of every field with a static source: S on the device as a parent of the fields' shape and pitch, rounded once to
+        # the model's dtype; built once
+        self._source = None
+        if sources is not None:
+            self._source = [(n, k, device_parents(grid, S, dtype, self._raw_fields[0].data.device)) for n, k, S in sources]
         # the stochastic forcing on the device: step counter, coefficient pairs, tables (StochasticState); None where inactive
         self._stochastic = StochasticState(stir, grid, dtype, self._raw_fields[0].data.device) if stir is not None else None
         # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
