@@ -48,6 +48,12 @@ limited by the forcing: the line printed at the start gives Relaxation.max_stabl
 domain centre, subtracted from the initial h so that the surface h + b starts flat.  --body-force F0,K adds swmhd_amd.Source(F0 sin(K y))
 to the first momentum-like field: the steady force of a Kolmogorov flow; it combines with --drag, --beta and --stir.  Either runs one
 model, with one more launch per RK3 stage for both together.
+--particles N [--track A,h] carries Lagrangian particles with the flow (ShallowWaterModel(particles=swmhd_amd.LagrangianParticles(...)):
+Oceananigans' LagrangianParticles with tracked_fields): a lattice of ceil(sqrt(N))^2 particles seeded at cell-centred points in row-major
+order, advanced on the device in one more launch per RK3 stage.  swmhd_amd.ParticleTimeSeries collects x, y and the --track fields (the
+model's prognostic names and the dye) along the trajectories on the schedule of --frames (without --frames: the first and the last
+state) and writes <out>/particles.npz at the end.  With A among them the run prints the drift of A along the trajectories beside A's own
+range: in the ideal model A is frozen into the flow, so the drift measures the scheme's numerical resistivity.  One model.
 
 --stir RATE,KF[,DK] [--seed N] stirs u and v with swmhd_amd.StochasticForcing(rate = RATE, k_f = KF, dk = DK): a random stream function
 in the ring of wavenumbers KF - DK/2 <= |k| < KF + DK/2 (DK: the grid's lowest wavenumber unless given), white in time, exactly
@@ -115,6 +121,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="seed of --stir")
     ap.add_argument("--bump", default=None, help="HEIGHT,WIDTH: bathymetry = a Gaussian hill of that height and width at the domain centre, subtracted from the initial h (one model)")
     ap.add_argument("--body-force", default=None, help="F0,K: Source(F0 sin(K y)) on the first momentum-like field, a Kolmogorov force (one model)")
+    ap.add_argument("--particles", type=int, default=0, help="N: carry a lattice of ceil(sqrt(N))^2 Lagrangian particles; written to <out>/particles.npz (one model)")
+    ap.add_argument("--track", default="A", help="with --particles: comma-separated fields sampled along the trajectories (prognostic names, c with --dye)")
     ap.add_argument("--out", default="swmhd_out")
     ap.add_argument("--plot-case", default=None, help="one of the reference's plotted runs, e.g. jacobian_formulation/64x64_low_B_low_U")
     argv = sys.argv[1:]
@@ -165,6 +173,8 @@ def main():
     if one_channel and (a.gravity or a.dts or any("," in (x or "") for x in (a.gradients, a.beta, a.coriolis, a.drag))):
         ap.error("--channel with --beta, --drag or --sponge runs one model: one --gradients entry, one --coriolis, one --beta, one --drag, "
                  "no --gravity or --dts")
+    if a.particles < 0 or (a.particles and (a.amps or a.sweep or (a.channel and not one_channel))):
+        ap.error("--particles N runs one model: not with an ensemble run (with --channel: beside --beta, --drag, --sponge, --bump or --body-force)")
     if (a.amps or a.channel or a.sweep) and not one_channel:
         return run_ensemble(a)
     a.sweep = False
@@ -230,8 +240,17 @@ def main():
         height, width = (float(x) for x in a.bump.split(","))
         bump = lambda x, y: height * np.exp(-(x ** 2 + y ** 2) / width ** 2)
         print(f"bathymetry: a Gaussian hill, height {height:g}, width {width:g}")
+    # --particles N: a lattice of ceil(sqrt(N))^2 particles at cell-centred points of the domain, row-major (neighbours in memory are
+    # neighbours in space: their gathers share cache lines until the flow scrambles them)
+    particles = None
+    if a.particles:
+        n = int(np.ceil(np.sqrt(a.particles)))
+        pts = -L / 2 + (np.arange(n) + 0.5) * (L / n)
+        PX, PY = np.meshgrid(pts, pts)
+        particles = S.LagrangianParticles(PX.ravel(), PY.ravel(), tracked_fields=tuple(t.strip() for t in a.track.split(",") if t.strip()))
+        print(f"particles: a {n} x {n} lattice, tracked fields ({', '.join(particles.tracked_fields)})")
     model = S.ShallowWaterModel(grid, configs.G, formulation=form, tracers=("c",) if a.dye else (), closure=closure, coriolis=coriolis,
-                                boundary_conditions=bcs, forcing=forcing, bathymetry=bump)
+                                boundary_conditions=bcs, forcing=forcing, bathymetry=bump, particles=particles)
     amp = a.amp if a.amp is not None else (0.5 if a.ic == "uniform" or form == "Conservative" else 0.1)
     A0 = (lambda X, Y: amp * np.abs(Y)) if a.ic == "uniform" else configs.two_gaussians(amp)
     if a.channel:
@@ -263,7 +282,10 @@ def main():
     zonal, zevery = zonal_writer(a, model, nsteps)
     spectra, severy = spectra_writer(a, model, nsteps)
     iso, ievery = isotropic_writer(a, model, nsteps)
+    parts, pevery = particle_writer(a, model, nsteps)
     model.time_step(a.dt)
+    if pevery == 1:
+        parts.write()
     if fevery == 1:
         series.write()
     if zevery == 1:
@@ -287,7 +309,11 @@ def main():
             n = min(n, severy - model.iteration % severy)
         if ievery:
             n = min(n, ievery - model.iteration % ievery)
+        if pevery:
+            n = min(n, pevery - model.iteration % pevery)
         model.time_steps(n, a.dt)
+        if pevery and model.iteration % pevery == 0:
+            parts.write(time=model.iteration * a.dt)          # one sampler launch and row copies, no synchronisation
         if fevery and model.iteration % fevery == 0:
             series.write(time=model.iteration * a.dt)         # one launch, no synchronisation
         if zevery and model.iteration % zevery == 0:
@@ -312,6 +338,7 @@ def main():
     save_zonal(a, zonal)
     save_spectra(a, spectra)
     save_isotropic(a, iso)
+    save_particles(a, parts)
     if a.energies:
         with open(a.energies, "w", newline="") as f:
             w = csv.writer(f); w.writerow(["time", "kinetic", "magnetic", "potential", "total"]); w.writerows(rows)
@@ -396,6 +423,32 @@ def save_isotropic(a, iso):
         os.makedirs(a.out, exist_ok=True)
         iso.save(os.path.join(a.out, "isotropic_spectra.npz"))
         print(f"{len(iso)} samples of the isotropic spectra ({', '.join(iso.names)}) -> {os.path.join(a.out, 'isotropic_spectra.npz')}")
+
+
+def particle_writer(a, model, nsteps):
+    """--particles: (ParticleTimeSeries, steps between samples), or (None, 0).  The schedule of --frames; without it the first and the
+    last state."""
+    if not a.particles:
+        return None, 0
+    import swmhd_amd as S
+    sched = S.TimeInterval(a.frames) if a.frames > 0 else S.IterationInterval(max(nsteps, 1))
+    every = sched.steps(a.dt)
+    parts = S.ParticleTimeSeries(model, names=("x", "y") + model.particles.tracked_fields, schedule=sched, capacity=nsteps // every + 1)
+    parts.write()           # the initial state, as the frames
+    return parts, every
+
+
+def save_particles(a, parts):
+    if parts is None:
+        return
+    os.makedirs(a.out, exist_ok=True)
+    parts.save(os.path.join(a.out, "particles.npz"))
+    print(f"{len(parts)} samples of {parts.model.particles.P} particles ({', '.join(parts.names)}) -> {os.path.join(a.out, 'particles.npz')}")
+    if "A" in parts.names and len(parts) > 1:
+        A = parts.numpy()[:, parts.names.index("A")]
+        drift = np.abs(A[-1] - A[0])
+        print(f"A along the trajectories: drift max {drift.max():.3e}, rms {np.sqrt(np.mean(drift ** 2)):.3e}; "
+              f"range of A over the particles {A[0].max() - A[0].min():.3e}")
 
 
 def run_ensemble(a):

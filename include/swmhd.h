@@ -785,5 +785,7 @@ int swmhd_ensemble_output_fields_f32(const float *q1, const float *q2, const flo
 #include "swmhd_stochastic.h"
 /* Static sources (swmhd_source_rk3_*, swmhd_ensemble_source_rk3_*): bathymetry and steady body forces, a fixed field (times the face thickness) added per RK3 stage */
 #include "swmhd_source.h"
+/* Lagrangian particles (swmhd_particles_rk3_*, swmhd_particles_sample_* and their ensemble forms): positions advected through each RK3 stage, fields sampled at them */
+#include "swmhd_particles.h"
 
 #endif /* SWMHD_H */

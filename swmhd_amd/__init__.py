@@ -18,9 +18,10 @@ from .closure import ScalarBiharmonicDiffusivity, ScalarDiffusivity
 from .coriolis import FPlane, BetaPlane, CoriolisProfile
 from .forcing import Relaxation, Source
 from .stochastic import StochasticForcing, forcing_modes
+from .particles import LagrangianParticles, ParticleTimeSeries
 
 __all__ = ["RectilinearGrid", "Periodic", "Bounded", "Flat", "Center", "Face", "Field", "GradientBoundaryCondition", "FieldBoundaryConditions",
            "lorentz_force_func", "div_lorentz", "ShallowWaterModel", "VectorInvariantFormulation",
            "ConservativeFormulation", "SlabDecomposition", "exchange_y_halos", "ShallowWaterEnsemble",
            "BoundedShallowWaterEnsemble", "FieldTimeSeries", "ZonalMeanTimeSeries", "ZonalSpectrumTimeSeries", "IsotropicSpectrumTimeSeries", "ScalarDiffusivity", "ScalarBiharmonicDiffusivity", "FPlane", "BetaPlane",
-           "CoriolisProfile", "Relaxation", "Source", "StochasticForcing", "forcing_modes", "TimeInterval", "IterationInterval", "run", "_lib"]
+           "CoriolisProfile", "Relaxation", "Source", "StochasticForcing", "forcing_modes", "LagrangianParticles", "ParticleTimeSeries", "TimeInterval", "IterationInterval", "run", "_lib"]

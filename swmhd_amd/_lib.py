@@ -45,6 +45,9 @@ STOCHASTIC_MAX_FIELDS = 4 + MAX_TRACERS   # SWMHD_STOCHASTIC_MAX_FIELDS: fields 
 STOCHASTIC_MAX_MODES = 256                # SWMHD_STOCHASTIC_MAX_MODES: Fourier modes of one field
 STOCHASTIC_TILE_ROWS = 64                 # SWMHD_STOCHASTIC_TILE_ROWS: rows of a workgroup of the stochastic kernel (four waves)
 STOCHASTIC_MODE_CHUNK = 4                 # SWMHD_STOCHASTIC_MODE_CHUNK: modes whose x tables a lane holds in registers at a time
+PARTICLES_BLOCK = 256                     # SWMHD_PARTICLES_BLOCK: particles of a workgroup of the particle kernels (one lane each)
+PARTICLES_MAX_FIELDS = 4 + MAX_TRACERS    # SWMHD_PARTICLES_MAX_FIELDS: fields per swmhd_particles_sample_* launch
+PARTICLES_CENTER_X, PARTICLES_CENTER_Y = 1, 2    # SWMHD_PARTICLES_CENTER_*: a sampled field's nodes are cell centres in that direction
 
 
 def ensemble_diag_workspace(members, Nx, Ny):
@@ -255,6 +258,21 @@ def _declare(lib):
         f = getattr(lib, f"swmhd_ensemble_stochastic_rk3_{sfx}")
         f.argtypes = [C.POINTER(p)] * 6 + [C.POINTER(i), i, i64, i64, i, i64, i64, i, i, i, i, i64, p, ft, ft, i, i, i, p]
         f.restype = i
+        # Lagrangian particles: q1, q2, h, x, y, gx, gy, P, [members, stride_m,] grid, x0, y0, dx, dy (doubles), form, [params,] dt, gamma, zeta
+        d = C.c_double
+        f = getattr(lib, f"swmhd_particles_rk3_{sfx}")
+        f.argtypes = [p] * 7 + [i64, i, i, i, i, i64, d, d, d, d, i, d, d, d, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_particles_rk3_{sfx}")
+        f.argtypes = [p] * 7 + [i64, i, i64, i, i, i, i, i64, d, d, d, d, i, p, d, d, d, i, p]
+        f.restype = i
+        # the sampler: fields (host array of device pointers), loc (host array), nfields, x, y, out, P, [members, stride_m,] grid, ...
+        f = getattr(lib, f"swmhd_particles_sample_{sfx}")
+        f.argtypes = [C.POINTER(p), C.POINTER(i), i, p, p, p, i64, i, i, i, i, i64, d, d, d, d, i, p]
+        f.restype = i
+        f = getattr(lib, f"swmhd_ensemble_particles_sample_{sfx}")
+        f.argtypes = [C.POINTER(p), C.POINTER(i), i, p, p, p, i64, i, i64, i, i, i, i, i64, d, d, d, d, i, p]
+        f.restype = i
     lib.swmhd_zonal_spectra_workspace.argtypes = [i, i, i, i]
     lib.swmhd_zonal_spectra_workspace.restype = i64
     lib.swmhd_spectra2d_shells.argtypes = [i, i, C.c_double, C.c_double]
@@ -323,6 +341,9 @@ STOCHASTIC_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
                       for name in ("stochastic_coefficients", "ensemble_stochastic_coefficients", "stochastic_rk3", "ensemble_stochastic_rk3")]
 # the symbols include/swmhd_source.h declares (swmhd.h includes it; tests/test_source_abi.py checks the .so exports each of them)
 SOURCE_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32") for name in ("source_rk3", "ensemble_source_rk3")]
+# the symbols include/swmhd_particles.h declares (swmhd.h includes it; tests/test_particles_abi.py checks the .so exports each of them)
+PARTICLES_EXPORTS = [f"swmhd_{name}_{sfx}" for sfx in ("f64", "f32")
+                     for name in ("particles_rk3", "ensemble_particles_rk3", "particles_sample", "ensemble_particles_sample")]
 RING_ID_BYTES = 128
 
 

@@ -146,5 +146,5 @@ def correction_list(o, stride_y):
 
 
 def needs_stages(o):
-    """Whether `o` must step stage by stage: its native step driver steps the four fields only, with a scalar f."""
-    return bool(o._tr or o._corrections)
+    """Whether `o` must step stage by stage: its native step driver steps the four fields only, with a scalar f, and no particles."""
+    return bool(o._tr or o._corrections or getattr(o, "particles", None) is not None)

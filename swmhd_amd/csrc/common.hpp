@@ -392,6 +392,43 @@ struct StochasticCoefArgs {
 };
 template <typename T> hipError_t launch_stochastic_coefficients(const StochasticCoefArgs<T> &a, hipStream_t s);
 
+// Lagrangian particles (swmhd_particles_rk3_*, swmhd_particles_sample_*, particles.hip; include/swmhd_particles.h states the scheme).
+// Field pointers address interior cell (1,1) like TendArgs; x, y, gx, gy (and out) are dense per member.  mode_x, mode_y: how a
+// direction is indexed and folded -- PARTICLE_WRAP: the true modulus, interior cells only; PARTICLE_PERIODIC: the parent as it is
+// (clamped), folded periodically; PARTICLE_BOUNDED: the parent as it is, reflected.  members > 0: an ensemble, member = blockIdx.x / nblk;
+// with params != nullptr its dt is params[3 m + 2], widened.
+constexpr int PARTICLES_BLOCK = 256;        // = SWMHD_PARTICLES_BLOCK
+constexpr int PARTICLES_MAX_FIELDS = 12;    // = SWMHD_PARTICLES_MAX_FIELDS
+constexpr int PARTICLE_WRAP = 0, PARTICLE_PERIODIC = 1, PARTICLE_BOUNDED = 2;
+struct ParticleGrid {
+    long P;
+    int Nx, Ny, Hx, Hy;
+    long sy;
+    double x0, y0, dx, dy;
+    int mode_x, mode_y;
+    int members;
+    long stride_m;
+    unsigned nblk;      // workgroups of one member: ceil(P / PARTICLES_BLOCK)
+};
+template <typename T>
+struct ParticleArgs : ParticleGrid {
+    const T *q1, *q2, *h;
+    double *x, *y, *gx, *gy;
+    int cons;
+    double dt, gamma, zeta;
+    const T *params;
+};
+template <typename T>
+struct ParticleSampleArgs : ParticleGrid {
+    const T *f[PARTICLES_MAX_FIELDS];
+    int loc[PARTICLES_MAX_FIELDS];
+    int nfields;
+    const double *x, *y;
+    double *out;
+};
+template <typename T> hipError_t launch_particles(const ParticleArgs<T> &a, hipStream_t s);
+template <typename T> hipError_t launch_particles_sample(const ParticleSampleArgs<T> &a, hipStream_t s);
+
 // energies + extrema; workspace >= SWMHD_DIAG_WORKSPACE doubles, out = 7 doubles (both device memory).  members > 0: an ensemble,
 // rows [j0, j1) of each member at ptr + m * stride_m, out = members x 7, workspace >= SWMHD_ENSEMBLE_DIAG_WORKSPACE.  params != nullptr
 // (ensembles only): member m's g is params[3 m] (DEVICE table), grav is not read

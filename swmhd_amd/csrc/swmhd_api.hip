@@ -409,6 +409,70 @@ int relaxation_common(const T *const *old, T *const *nw, T *const *acc, const T 
     return hiprc(fl.strict ? launch_relaxation_strict<T>(d, s) : launch_relaxation_fast<T>(d, s));
 }
 
+// swmhd_particles_rk3, swmhd_particles_sample (particles.hip): the flags both take, what the grid of a call must be, and how a
+// direction is indexed and folded.  Every check precedes the first HIP call, in the order include/swmhd_particles.h states.
+constexpr int PARTICLES_FLAGS = SWMHD_STRICT | WRAP_FLAGS | BOUNDED_FLAGS;
+constexpr int PARTICLES_NOTSUP = KERNEL_FLAGS | SWMHD_GM_IS_PREV_STATE | OPEN_FLAGS | SWMHD_LEAVE_ROOM | SWMHD_RK3_ANCHOR;
+static_assert(PARTICLES_BLOCK == SWMHD_PARTICLES_BLOCK && PARTICLES_MAX_FIELDS == SWMHD_PARTICLES_MAX_FIELDS, "common.hpp mirrors swmhd_particles.h");
+inline bool particles_grid_ok(const Grid &g, double x0, double y0, int64_t P, int flags) {
+    if (!g.extents_ok() || !g.spacing_ok() || !isfinite(g.dx) || !isfinite(g.dy) || !isfinite(x0) || !isfinite(y0)) return false;
+    if ((flags & ~(PARTICLES_FLAGS | PARTICLES_NOTSUP)) || bounded_wrap_conflict(flags) || P < 0) return false;
+    return true;
+}
+inline int particles_after_einval(const Grid &g, int flags) {
+    if (flags & PARTICLES_NOTSUP) return SWMHD_ENOTSUP;
+    const Flags fl = decode_flags(flags);
+    if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
+    return SWMHD_OK;
+}
+inline void set_particle_grid(ParticleGrid &a, const Grid &g, double x0, double y0, int64_t P, int flags, const Ens *ens) {
+    a.P = (long)P; a.Nx = g.Nx; a.Ny = g.Ny; a.Hx = g.Hx; a.Hy = g.Hy; a.sy = (long)g.sy;
+    a.x0 = x0; a.y0 = y0; a.dx = g.dx; a.dy = g.dy;
+    a.mode_x = (flags & SWMHD_WRAP_X) ? PARTICLE_WRAP : ((flags & SWMHD_BOUNDED_X) ? PARTICLE_BOUNDED : PARTICLE_PERIODIC);
+    a.mode_y = (flags & SWMHD_WRAP_Y) ? PARTICLE_WRAP : ((flags & SWMHD_BOUNDED_Y) ? PARTICLE_BOUNDED : PARTICLE_PERIODIC);
+    a.members = ens ? ens->members : 0; a.stride_m = ens ? (long)ens->stride_m : 0; a.nblk = 0;
+}
+template <typename T>
+int particles_common(const T *q1, const T *q2, const T *h, double *x, double *y, double *gx, double *gy, int64_t P, const Grid &g, double x0,
+                     double y0, int form, double dt, double gamma, double zeta, int flags, void *stream, const Ens *ens = nullptr) {
+    if (!q1 || !q2 || !x || !y || !gx || !gy) return SWMHD_EINVAL;
+    if (x == y || x == gx || x == gy || y == gx || y == gy || gx == gy) return SWMHD_EINVAL;
+    if (!particles_grid_ok(g, x0, y0, P, flags)) return SWMHD_EINVAL;
+    if (!isfinite(dt) || !isfinite(gamma) || !isfinite(zeta)) return SWMHD_EINVAL;
+    if (!formulation_ok(form) || (form == SWMHD_CONSERVATIVE && !h)) return SWMHD_EINVAL;
+    if (!correction_members_ok(ens, g)) return SWMHD_EINVAL;
+    if (const int rc = particles_after_einval(g, flags)) return rc;
+    if (P == 0) return SWMHD_OK;
+    ParticleArgs<T> a;
+    set_particle_grid(a, g, x0, y0, P, flags, ens);
+    a.q1 = g.interior(q1); a.q2 = g.interior(q2); a.h = h ? g.interior(h) : nullptr;
+    a.x = x; a.y = y; a.gx = gx; a.gy = gy;
+    a.cons = form == SWMHD_CONSERVATIVE;
+    a.params = ens ? (const T *)ens->params : nullptr;
+    a.dt = a.params ? 1.0 : dt; a.gamma = gamma; a.zeta = zeta;
+    return hiprc(launch_particles<T>(a, (hipStream_t)stream));
+}
+template <typename T>
+int particles_sample_common(const T *const *fields, const int *loc, int nfields, const double *x, const double *y, double *out, int64_t P,
+                            const Grid &g, double x0, double y0, int flags, void *stream, const Ens *ens = nullptr) {
+    if (!fields || !loc || !x || !y || !out || nfields < 1 || nfields > SWMHD_PARTICLES_MAX_FIELDS) return SWMHD_EINVAL;
+    for (int k = 0; k < nfields; ++k)
+        if (!fields[k] || loc[k] < 0 || loc[k] > (SWMHD_PARTICLES_CENTER_X | SWMHD_PARTICLES_CENTER_Y)) return SWMHD_EINVAL;
+    if (out == x || out == y) return SWMHD_EINVAL;
+    if (!particles_grid_ok(g, x0, y0, P, flags)) return SWMHD_EINVAL;
+    if (!correction_members_ok(ens, g)) return SWMHD_EINVAL;
+    if (const int rc = particles_after_einval(g, flags)) return rc;
+    if (P == 0) return SWMHD_OK;
+    ParticleSampleArgs<T> a;
+    set_particle_grid(a, g, x0, y0, P, flags, ens);
+    for (int k = 0; k < PARTICLES_MAX_FIELDS; ++k) {
+        a.f[k] = k < nfields ? g.interior(fields[k]) : nullptr;
+        a.loc[k] = k < nfields ? loc[k] : 0;
+    }
+    a.nfields = nfields; a.x = x; a.y = y; a.out = out;
+    return hiprc(launch_particles_sample<T>(a, (hipStream_t)stream));
+}
+
 // swmhd_stochastic_rk3: nw[k] += a F_k, acc[k] += w F_k with F_k the sum of nmodes[k] Fourier modes from the tables and the step's
 // coefficient pairs, of up to SWMHD_STOCHASTIC_MAX_FIELDS fields in one launch (stochastic.hip).  Every check precedes the first HIP
 // call, in the order include/swmhd_stochastic.h states: relaxation_common's, then the tables.  With `ens`
@@ -949,5 +1013,34 @@ SWMHD_DEF_STOCHASTIC(f32, float)
 
 SWMHD_DEF_SOURCE(f64, double)
 SWMHD_DEF_SOURCE(f32, float)
+
+// include/swmhd_particles.h
+#define SWMHD_DEF_PARTICLES(sfx, T)                                                                                                                    \
+    int swmhd_particles_rk3_##sfx(const T *q1, const T *q2, const T *h, double *x, double *y, double *gx, double *gy, int64_t P, int Nx, int Ny,      \
+                                  int Hx, int Hy, int64_t sy, double x0, double y0, double dx, double dy, int form, double dt, double gamma,          \
+                                  double zeta, int flags, void *stream) {                                                                             \
+        return particles_common<T>(q1, q2, h, x, y, gx, gy, P, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, x0, y0, form, dt, gamma, zeta, flags, stream);       \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_particles_rk3_##sfx(const T *q1, const T *q2, const T *h, double *x, double *y, double *gx, double *gy, int64_t P,             \
+                                           int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, double x0, double y0,           \
+                                           double dx, double dy, int form, const T *params, double dt, double gamma, double zeta, int flags,          \
+                                           void *stream) {                                                                                            \
+        const Ens e{members, stride_m, false, params != nullptr, params};                                                                             \
+        return particles_common<T>(q1, q2, h, x, y, gx, gy, P, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, x0, y0, form, dt, gamma, zeta, flags, stream, &e);   \
+    }                                                                                                                                                 \
+    int swmhd_particles_sample_##sfx(const T *const *fields, const int *loc, int nfields, const double *x, const double *y, double *out, int64_t P,   \
+                                     int Nx, int Ny, int Hx, int Hy, int64_t sy, double x0, double y0, double dx, double dy, int flags,               \
+                                     void *stream) {                                                                                                  \
+        return particles_sample_common<T>(fields, loc, nfields, x, y, out, P, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, x0, y0, flags, stream);               \
+    }                                                                                                                                                 \
+    int swmhd_ensemble_particles_sample_##sfx(const T *const *fields, const int *loc, int nfields, const double *x, const double *y, double *out,     \
+                                              int64_t P, int members, int64_t stride_m, int Nx, int Ny, int Hx, int Hy, int64_t sy, double x0,        \
+                                              double y0, double dx, double dy, int flags, void *stream) {                                             \
+        const Ens e{members, stride_m, false, false, nullptr};                                                                                        \
+        return particles_sample_common<T>(fields, loc, nfields, x, y, out, P, Grid{Nx, Ny, Hx, Hy, sy, dx, dy}, x0, y0, flags, stream, &e);           \
+    }
+
+SWMHD_DEF_PARTICLES(f64, double)
+SWMHD_DEF_PARTICLES(f32, float)
 
 }  // extern "C"

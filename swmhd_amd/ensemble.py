@@ -23,6 +23,7 @@ from .fields import _SFX, _stream_ptr
 from .forcing import check_bathymetry, check_forcing, check_source, check_stochastic, device_parents, forcing_for_member
 from .grid import Center, Face
 from .model import ShallowWaterModel, rk3_operands, tracer_names
+from .particles import check_particles
 from .stochastic import StochasticState
 from .shared import (VectorInvariantFormulation, check_boundary_conditions, diagnostics_dict, fill_groups, finish_stage,
                      formulation_codes, gradient_values)
@@ -84,7 +85,7 @@ class ShallowWaterEnsemble:
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None):
+                 fuse_halo=True, tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None, particles=None):
         self.tracer_names = tracer_names(tracers)      # checked before anything touches a device
         # coriolis = FPlane | BetaPlane | CoriolisProfile (ShallowWaterModel's argument; values may be per member).  None and FPlane: the
         # f of the stage kernels.  Otherwise they get f = 0 and _coriolis holds the parameter whose rows a correction launch adds
@@ -122,6 +123,9 @@ class ShallowWaterEnsemble:
         sources, self._source_thickness = check_source(forcing, self.bathymetry, grid, formulation_codes(formulation, lorentz_forcing)[2],
                                                        self.tracer_names, self.g_values if g_seq else float(gravitational_acceleration),
                                                        self.members, formulation != VectorInvariantFormulation)
+        # particles = LagrangianParticles(x, y, tracked_fields), x and y of shape (P,) or (members, P): refusals and the positions brought
+        # into the domain, before anything is allocated
+        seeds = check_particles(particles, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, self.members)
         self.grid = grid
         self.g = self.g_values if g_seq else float(gravitational_acceleration)
         self.f = self.f_values if f_seq else float(coriolis_f)
@@ -191,6 +195,10 @@ class ShallowWaterEnsemble:
         self._stochastic = StochasticState(stir, grid, dtype, dev, self.members) if stir is not None else None
         # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
         self._corrections = correction_list(self, self._state[0].stride(1))
+        # the particles of every member on the device: x, y and the stored velocity G-, (members, P) float64 (finish_stage runs their launch)
+        self.particles = particles
+        if particles is not None:
+            particles.bind(self, seeds, dev)
         if g_seq or f_seq:
             self._make_parameters()
 
@@ -404,6 +412,8 @@ class ShallowWaterEnsemble:
         saved = self._state + self.Gm + [self._tr[n] for n in self.tracer_names] + self._tGm
         if self._stochastic is not None:      # the warm-up steps advance the step counters: a replayed run draws what an eager run draws
             saved = saved + [self._stochastic.counter]
+        if self.particles is not None:        # the warm-up steps move the particles
+            saved = saved + self.particles.state_tensors()
         keep = [t.clone() for t in saved]
         t0, i0 = self._clock_state(), self.iteration
         side = torch.cuda.Stream()
@@ -556,11 +566,15 @@ class BoundedShallowWaterEnsemble(ShallowWaterEnsemble):
 
     def __init__(self, grid, members, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, strict=False, device="cuda", member_stride=None, decomp=None,
-                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None):
+                 fuse_halo=True, boundary_conditions=None, tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None,
+                 particles=None):
         coriolis_f, varying = check_coriolis(coriolis, coriolis_f, 1.0)       # before anything is allocated
         check_bathymetry(bathymetry, grid, int(members), bounded_ensemble=True)      # (None passes; anything else is refused)
         check_forcing(forcing, grid, formulation_codes(formulation, lorentz_forcing)[2], tracer_names(tracers), int(members),
                       bounded_ensemble=True)       # (None and {} pass; anything else is refused before anything is allocated)
+        if particles is not None:     # before anything is allocated
+            raise _lib.SwmhdError("particles on a Bounded ensemble are not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is one "
+                                  "native call and has no per-stage entry point for the particles' launch")
         if varying is not None:
             raise _lib.SwmhdError("coriolis = f(y) on a Bounded ensemble is not supported (SWMHD_ENOTSUP): swmhd_ensemble_step_rk3_bc is "
                                   "one native call and has no per-stage entry point for the correction launch")

@@ -18,6 +18,7 @@ from .corrections import correction_list, live_fields, needs_stages
 from .distributed import SlabDecomposition, agree_rc, exchange_y_halos
 from .fields import Field, _SFX, _stream_ptr
 from .forcing import check_bathymetry, check_forcing, check_source, check_stochastic, device_parents
+from .particles import check_particles
 from .stochastic import StochasticState
 from .grid import Center, Face
 from .shared import (RK3_GAMMA, RK3_ZETA, ConservativeFormulation, VectorInvariantFormulation, check_boundary_conditions,
@@ -70,7 +71,7 @@ class ShallowWaterModel:
     def __init__(self, grid, gravitational_acceleration=9.81, coriolis_f=1.0, formulation=VectorInvariantFormulation,
                  lorentz_forcing=True, dtype=torch.float64, device="cuda", strict=False, decomp=None, group=None,
                  overlap=True, fused=True, kernel="auto", fuse_halo=True, native_ring=True, boundary_conditions=None, ring=None,
-                 tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None):
+                 tracers=(), closure=None, coriolis=None, forcing=None, bathymetry=None, particles=None):
         # coriolis = FPlane | BetaPlane | CoriolisProfile (swmhd_amd.coriolis), checked before anything is allocated.  None and FPlane:
         # the scalar f of the stage kernels, exactly the calls made without the argument.  Otherwise the stage kernels get f = 0 and
         # _coriolis holds the parameter whose rows a correction launch adds after every stage (corrections.correction_list)
@@ -117,6 +118,10 @@ class ShallowWaterModel:
         sources, self._source_thickness = check_source(forcing, self.bathymetry, grid, formulation_codes(formulation, lorentz_forcing)[2],
                                                        self.tracer_names, float(gravitational_acceleration), None,
                                                        formulation != VectorInvariantFormulation)
+        # particles = LagrangianParticles(x, y, tracked_fields) (swmhd_amd.particles): refusals and the positions brought into the domain,
+        # before anything is allocated.  None: the model makes exactly the calls it makes without the argument
+        seeds = check_particles(particles, grid, formulation_codes(formulation, lorentz_forcing)[2], self.tracer_names, None,
+                                decomp is not None and decomp.world_size > 1, ring is not None, fused)
         self.grid, self.g, self.f = grid, float(gravitational_acceleration), float(coriolis_f)
         self.formulation = formulation
         self.form_code, self.lorentz_code, self.names = formulation_codes(formulation, lorentz_forcing)
@@ -192,6 +197,10 @@ class ShallowWaterModel:
         self._stochastic = StochasticState(stir, grid, dtype, self._raw_fields[0].data.device) if stir is not None else None
         # the correction launches that follow every stage, in their order (finish_stage runs them); empty without any
         self._corrections = correction_list(self, self._raw_fields[0].stride_y)
+        # the particles on the device: x, y and the stored velocity G-, float64 whatever the dtype; finish_stage runs their launch
+        self.particles = particles
+        if particles is not None:
+            particles.bind(self, seeds, self._raw_fields[0].data.device)
         # y-slab ring: the native RCCL ring (swmhd_ring_*) when the process group is RCCL; torch.distributed p2p otherwise
         # (gloo rehearsals).  The ring's step driver needs the fused stage kernel and a slab taller than its two strips.
         # `ring`: a swmhd_ring handle created by the caller -- one of swmhd_ring_create_loopback's (loopback_rings below): several
@@ -521,6 +530,9 @@ class ShallowWaterModel:
         keep = [f.data.clone() for f in saved]
         # the step counter of a stochastic forcing: the warm-up steps draw and advance it, a replayed run must draw what an eager run draws
         counter = self._stochastic.counter.clone() if self._stochastic is not None else None
+        # the particles' positions and stored velocity: the warm-up steps move them
+        parts = self.particles.state_tensors() if self.particles is not None else []
+        keep_parts = [t.clone() for t in parts]
         t0, i0 = self.clock_time, self.iteration
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -538,6 +550,8 @@ class ShallowWaterModel:
             f.data.copy_(k)
         if counter is not None:
             self._stochastic.counter.copy_(counter)
+        for t, k in zip(parts, keep_parts):
+            t.copy_(k)
         self._halo_stale = False
         self.clock_time, self.iteration = t0, i0
         return self
@@ -668,7 +682,9 @@ class ShallowWaterModel:
                  **{"Gm_" + n: f.numpy() for n, f in zip(self.names, self.Gm)},
                  **{"tracer_" + n: self._tr[n].numpy() for n in self.tracer_names},
                  **{"tracer_Gm_" + n: f.numpy() for n, f in zip(self.tracer_names, self._tGm)},
-                 **({"stochastic_counter": self._stochastic.counter_values()} if self._stochastic is not None else {}))
+                 **({"stochastic_counter": self._stochastic.counter_values()} if self._stochastic is not None else {}),
+                 **({"particles_x": self.particles.x.cpu().numpy(), "particles_y": self.particles.y.cpu().numpy()}
+                    if self.particles is not None else {}))      # (G- is dead at step boundaries: zeta_1 = 0)
 
     def load_checkpoint(self, path):
         import numpy as np
@@ -684,6 +700,9 @@ class ShallowWaterModel:
             f.data.copy_(torch.from_numpy(z["tracer_Gm_" + n]).to(f.data.dtype))
         if self._stochastic is not None and "stochastic_counter" in z.files:      # (older checkpoints have none: the counter stays)
             self._stochastic.set_counter(z["stochastic_counter"])
+        if self.particles is not None and "particles_x" in z.files:      # (a checkpoint without particles: the positions stay)
+            self.particles.x.copy_(torch.from_numpy(z["particles_x"]))
+            self.particles.y.copy_(torch.from_numpy(z["particles_y"]))
         self.clock_time, self.iteration = float(z["time"]), int(z["iteration"])
         return self
 

@@ -71,8 +71,8 @@ def finish_stage(o, dt, stage, fused=True, step_dt=None):
     """What follows the state's launch of RK3 stage `stage` of `o` (a ShallowWaterModel or a ShallowWaterEnsemble), before its halo
     fill: the tracers through the same stage in one launch (o._tracer_stage), advected by the state the stage STARTED from -- still
     o._state here -- then the correction launches of o._corrections on that same state, each correcting what the launches before it
-    have written, in the order of the list (corrections.correction_list states it: it decides the last bits) -- then the pointer
-    swaps: the new tracers and the new state become current, and G- <- Gn for both (store_tendencies!, 0 bytes).  fused=False: the
+    have written, in the order of the list (corrections.correction_list states it: it decides the last bits) -- then the particles'
+    launch on that state (o.particles, where the object has them) -- then the pointer swaps: the new tracers and the new state become current, and G- <- Gn for both (store_tendencies!, 0 bytes).  fused=False: the
     state was advanced in place by a substep, only its G sets swap.  step_dt: with dt None (an ensemble's table), the one dt all members
     share, or None where they differ; handed to the corrections that ask for it (needs_step_dt), every other entry is called as launch(o, dt, stage)."""
     if o._tr:
@@ -82,6 +82,9 @@ def finish_stage(o, dt, stage, fused=True, step_dt=None):
             c.launch(o, dt, stage, step_dt)
         else:
             c.launch(o, dt, stage)
+    # Lagrangian particles (swmhd_amd.particles): one launch, advected by the state the stage STARTED from -- still o._state here
+    if getattr(o, "particles", None) is not None:
+        o.particles.launch(o, dt, stage)
     if o._tr:
         o._tr, o._tr_alt = o._tr_alt, o._tr
         o._tGn, o._tGm = o._tGm, o._tGn
