@@ -24,6 +24,8 @@ struct Grid {
     bool extents_ok() const { return Nx > 0 && Ny > 0 && Hx >= 0 && Hy >= 0 && stride_ok(); }
     bool spacing_ok() const { return dx > 0.0 && dy > 0.0; }   // (NaN fails)
     bool halo_at_least(int n) const { return Hx >= n && Hy >= n; }
+    // a stencil of this radius finds its cells in every direction: in the halo, or, in the directions of `wrap`, in the periodic image
+    bool halo_or_wrap(int radius, int wrap) const { return (Hx >= radius || (wrap & 1)) && (Hy >= radius || (wrap & 2)); }
     // one period covers the halo in the directions of `wrap` (bit 0 x, bit 1 y)
     bool period_covers_halo(int wrap) const { return !((wrap & 1) && Hx > Nx) && !((wrap & 2) && Hy > Ny); }
     bool rows_ok(int j0, int j1, int ext = 0) const { return j0 >= -ext && j1 <= Ny + ext && j0 <= j1; }

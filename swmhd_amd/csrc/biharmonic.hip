@@ -26,7 +26,7 @@
 namespace swmhd {
 namespace {
 
-#include "strip_device.inc"   // STRICT, vec_load / vec_store, Strip2, strip_block, strip_scalars, strip_plan_of, STRIP_KERNEL
+#include "strip_device.inc"   // STRICT, Strip2, strip_block, strip_scalars, strip_plan_of, STRIP_KERNEL, strip_launch
 
 template <typename T, int VEC, bool ENS>
 __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_biharmonic(DiffusionArgs<T> a, T rdx2, T rdy2, int lead, int nstrips, int nsb) {
@@ -94,8 +94,8 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_biharmonic(Diffusio
         if (st.lane == 0) Lw = lap(w0, w2, v0[0], wm, wp);
         if (st.lane == STRIP_WAVE - 1) Le = lap(e0, v0[VEC - 1], e2, em, ep);
         T un[VEC], ua[VEC];
-        st.load_out(nw + ro, un);
-        if (acc) st.load_out(acc + ro, ua);
+        st.cols.load(nw + ro, un);
+        if (acc) st.cols.load(acc + ro, ua);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const T l = L0[e], lw = e == 0 ? Lw : L0[e > 0 ? e - 1 : 0], le = e == VEC - 1 ? Le : L0[e < VEC - 1 ? e + 1 : e];
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_biharmonic(Diffusio
             un[e] = un[e] + av * D;
             ua[e] = acc ? ua[e] + wv * D : T(0);
         }
-        st.store_out(nw + ro, un);
-        if (acc) st.store_out(acc + ro, ua);
+        st.cols.store(nw + ro, un);
+        if (acc) st.cols.store(acc + ro, ua);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             Lm[e] = L0[e];
@@ -132,11 +132,8 @@ hipError_t LAUNCH_NAME(launch_biharmonic_, LAUNCH_SFX)(const DiffusionArgs<T> &a
     const void *ptrs[3 * DIFFUSION_MAX_FIELDS];
     for (int k = 0; k < a.nfields; ++k) { ptrs[3 * k] = a.old[k]; ptrs[3 * k + 1] = a.nw[k]; ptrs[3 * k + 2] = a.acc[k]; }
     const StripPlan p = strip_plan_of<T>(a, ptrs, 3 * a.nfields, a.nfields);
-    if (p.none) return hipSuccess;
-    if (p.too_many) return hipErrorInvalidConfiguration;
     const T rdx2 = T(1) / (a.dx * a.dx), rdy2 = T(1) / (a.dy * a.dy);
-    hipLaunchKernelGGL(STRIP_KERNEL(k_biharmonic, T, p, a), dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, a, rdx2, rdy2, p.lead, p.nstrips, p.nsb);
-    return hipGetLastError();
+    return strip_launch(STRIP_KERNEL(k_biharmonic, T, p, a), p, s, a, rdx2, rdy2);
 }
 template hipError_t LAUNCH_NAME(launch_biharmonic_, LAUNCH_SFX)<double>(const DiffusionArgs<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_biharmonic_, LAUNCH_SFX)<float>(const DiffusionArgs<float> &, hipStream_t);

@@ -23,7 +23,7 @@
 namespace swmhd {
 namespace {
 
-#include "strip_device.inc"   // STRICT, vec_load / vec_store, Strip, strip_block, strip_scalars, strip_plan_of, STRIP_KERNEL: shared with diffusion.hip
+#include "strip_device.inc"   // STRICT, Strip, strip_block, strip_scalars, strip_plan_of, STRIP_KERNEL, strip_launch
 
 // the mean of four values at a cell corner: s = the pair of row j' (west + east of it), n = the pair of the row above
 template <typename T>
@@ -69,11 +69,11 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_coriolis(CoriolisAr
         const T vp_w = st.west_of(p, vp);
         const T fc = frow[j], ff = frow[Ny + j];
         T w1[VEC], w2[VEC], c1[VEC], c2[VEC];
-        st.load_out(n1 + ro, w1);
-        st.load_out(n2 + ro, w2);
+        st.cols.load(n1 + ro, w1);
+        st.cols.load(n2 + ro, w2);
         if (a1) {
-            st.load_out(a1 + ro, c1);
-            st.load_out(a2 + ro, c2);
+            st.cols.load(a1 + ro, c1);
+            st.cols.load(a2 + ro, c2);
         }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
@@ -85,11 +85,11 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_coriolis(CoriolisAr
             c1[e] = a1 ? c1[e] + wv * D1 : T(0);
             c2[e] = a1 ? c2[e] + wv * D2 : T(0);
         }
-        st.store_out(n1 + ro, w1);
-        st.store_out(n2 + ro, w2);
+        st.cols.store(n1 + ro, w1);
+        st.cols.store(n2 + ro, w2);
         if (a1) {
-            st.store_out(a1 + ro, c1);
-            st.store_out(a2 + ro, c2);
+            st.cols.store(a1 + ro, c1);
+            st.cols.store(a2 + ro, c2);
         }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
@@ -107,10 +107,7 @@ template <typename T>
 hipError_t LAUNCH_NAME(launch_coriolis_, LAUNCH_SFX)(const CoriolisArgs<T> &a, hipStream_t s) {
     const void *const ptrs[6] = {a.q1, a.q2, a.n1, a.n2, a.a1, a.a2};
     const StripPlan p = strip_plan_of<T>(a, ptrs, 6, 1);
-    if (p.none) return hipSuccess;
-    if (p.too_many) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(STRIP_KERNEL(k_coriolis, T, p, a), dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, a, p.lead, p.nstrips, p.nsb);
-    return hipGetLastError();
+    return strip_launch(STRIP_KERNEL(k_coriolis, T, p, a), p, s, a);
 }
 template hipError_t LAUNCH_NAME(launch_coriolis_, LAUNCH_SFX)<double>(const CoriolisArgs<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_coriolis_, LAUNCH_SFX)<float>(const CoriolisArgs<float> &, hipStream_t);

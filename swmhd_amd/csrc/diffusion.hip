@@ -22,7 +22,7 @@
 namespace swmhd {
 namespace {
 
-#include "strip_device.inc"   // STRICT, vec_load / vec_store, Strip, strip_block, strip_scalars, strip_plan_of, STRIP_KERNEL: shared with coriolis.hip
+#include "strip_device.inc"   // STRICT, Strip, strip_block, strip_scalars, strip_plan_of, STRIP_KERNEL, strip_launch
 
 template <typename T, int VEC, bool ENS>
 __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_diffusion(DiffusionArgs<T> a, T rdx2, T rdy2, int lead, int nstrips, int nsb) {
@@ -56,8 +56,8 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_diffusion(Diffusion
         const long ro = (long)j * sy;
         const T west = st.west_of(old + ro, v0), east = st.east_of(old + ro, v0);
         T un[VEC], ua[VEC];
-        st.load_out(nw + ro, un);
-        if (acc) st.load_out(acc + ro, ua);
+        st.cols.load(nw + ro, un);
+        if (acc) st.cols.load(acc + ro, ua);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const T p = v0[e], pw = e == 0 ? west : v0[e > 0 ? e - 1 : 0], pe = e == VEC - 1 ? east : v0[e < VEC - 1 ? e + 1 : e];
@@ -73,8 +73,8 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES) void k_diffusion(Diffusion
             un[e] = un[e] + av * D;
             ua[e] = acc ? ua[e] + wv * D : T(0);
         }
-        st.store_out(nw + ro, un);
-        if (acc) st.store_out(acc + ro, ua);
+        st.cols.store(nw + ro, un);
+        if (acc) st.cols.store(acc + ro, ua);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             vm[e] = v0[e];
@@ -90,11 +90,8 @@ hipError_t LAUNCH_NAME(launch_diffusion_, LAUNCH_SFX)(const DiffusionArgs<T> &a,
     const void *ptrs[3 * DIFFUSION_MAX_FIELDS];
     for (int k = 0; k < a.nfields; ++k) { ptrs[3 * k] = a.old[k]; ptrs[3 * k + 1] = a.nw[k]; ptrs[3 * k + 2] = a.acc[k]; }
     const StripPlan p = strip_plan_of<T>(a, ptrs, 3 * a.nfields, a.nfields);
-    if (p.none) return hipSuccess;
-    if (p.too_many) return hipErrorInvalidConfiguration;
     const T rdx2 = T(1) / (a.dx * a.dx), rdy2 = T(1) / (a.dy * a.dy);
-    hipLaunchKernelGGL(STRIP_KERNEL(k_diffusion, T, p, a), dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, a, rdx2, rdy2, p.lead, p.nstrips, p.nsb);
-    return hipGetLastError();
+    return strip_launch(STRIP_KERNEL(k_diffusion, T, p, a), p, s, a, rdx2, rdy2);
 }
 template hipError_t LAUNCH_NAME(launch_diffusion_, LAUNCH_SFX)<double>(const DiffusionArgs<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_diffusion_, LAUNCH_SFX)<float>(const DiffusionArgs<float> &, hipStream_t);

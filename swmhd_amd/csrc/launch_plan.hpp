@@ -1,9 +1,10 @@
-// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the strip-march
-// corrections (Coriolis, diffusion), the zonal-mean kernel, the derived-frame kernel and the zonal-spectrum kernels: what a call will enqueue, decided as data before anything is launched.
+// Host-only launch planning of the fused tendency kernels, the Lorentz operator kernels, the tracer stage kernel, the six strip-march
+// corrections (Coriolis, diffusion, biharmonic, relaxation, source, stochastic), the zonal-mean kernel, the derived-frame kernel and the zonal-spectrum kernels: what a call will enqueue, decided as data before anything is launched.
 // No kernel, no launch call, no device memory: the only HIP call is the compute-unit query of device_cu_count(), so this header also
 // compiles into a plain host program (tests/launch_plan_check.cpp).  Internal, like common.hpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <initializer_list>
 #include <stdlib.h>
 
 namespace swmhd {
@@ -432,12 +433,13 @@ inline TracerTiles tracer_tiles(int Nx, int rows, int K, int members) {
     return t;
 }
 
-// ---- the strips of one per-stage correction launch (strip_device.inc: coriolis.hip, diffusion.hip, biharmonic.hip, relaxation.hip) -----------------------------------
+// ---- the strips of one per-stage correction launch (strip_device.inc: coriolis.hip, diffusion.hip, biharmonic.hip, relaxation.hip,
+// source.hip, stochastic.hip) ---------------------------------------------------------------------------------------------------------
 // A wave owns a strip of STRIP_WAVE lanes x vec columns and marches down STRIP_WAVE_ROWS rows of it; the STRIP_WAVES waves of a
 // workgroup are consecutive row segments of one strip.  vec = 16 bytes of elements where `phase` >= 0: the 16-byte phase (in elements)
 // that the interior pointers of all parents share and the pitches keep (common_phase) -- then the vector groups start `lead` = phase
 // columns left of x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  phase < 0: one element per lane.
-// blockIdx.x = (l nsb + sb) nstrips + strip, l < launches: the member (Coriolis), member x field (diffusion, biharmonic, relaxation).
+// blockIdx.x = (l nsb + sb) nstrips + strip, l < launches: the member (Coriolis), member x field (the five others).
 constexpr int STRIP_WAVE = 64, STRIP_WAVES = 4, STRIP_WAVE_ROWS = 16;   // STRIP_WAVES STRIP_WAVE_ROWS = SWMHD_CORIOLIS_ / SWMHD_DIFFUSION_ / SWMHD_RELAXATION_TILE_ROWS
 struct StripPlan {
     int vec, lead;
@@ -473,6 +475,17 @@ inline int common_phase(int elem_size, long sy, long stride_m, const void *const
         ph = q;
     }
     return ph;
+}
+// The plan of one correction call: rows rows of Nx columns of every parent in ptrs (n entries, null ones skipped), per_member launches
+// for each member (members <= 0: one grid, whose stride_m is not looked at).  The phase is common_phase's, kept by `further` too: the
+// pitches of a kind beyond sy and stride_m (a mask's or a source's member pitch, the pitch of a table) -- 0: shared or not applicable,
+// which keeps every phase.
+inline StripPlan strip_call_plan(int Nx, int rows, int elem_size, const void *const *ptrs, int n, long sy, int members, long stride_m,
+                                 int per_member, std::initializer_list<long> further = {}) {
+    int phase = common_phase(elem_size, sy, members > 0 ? stride_m : 0, ptrs, n);
+    for (const long pitch : further)
+        if (pitch % (16 / elem_size) != 0) phase = -1;
+    return strip_plan(Nx, rows, elem_size, phase, (members > 0 ? members : 1) * per_member);
 }
 
 // ---- the rows of one zonal-mean call (zonal.hip) -------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@
 namespace swmhd {
 namespace {
 
-#include "strip_device.inc"   // STRICT, vec_load / vec_store, Strip0, strip_block, strip_scalars, STRIP_KERNEL
+#include "strip_device.inc"   // STRICT, Strip0, strip_block, strip_scalars, strip_pipeline, strip_plan_of, STRIP_KERNEL, strip_launch
 
 template <typename T>
 struct RelaxPtrs {
@@ -65,25 +65,7 @@ __device__ __forceinline__ void relax_march(const Strip0<T, VEC> &st, const Rela
         st.template store<FULL>(q.nw + ro, un);
         if constexpr (ACC) st.template store<FULL>(q.acc + ro, ua);
     };
-    // The steady loop has no branch inside: B's loads are issued before A's row is finished and A's next loads before B's row is, so
-    // every wait is for one row's loads while the other row's are in flight.  The last one or two rows follow it.
-    Row A, B;
-    int j = r0;
-    load_row(j, A);
-    while (j + 2 < r1) {
-        load_row(j + 1, B);
-        finish_row(j, A);
-        load_row(j + 2, A);
-        finish_row(j + 1, B);
-        j += 2;
-    }
-    if (j + 1 < r1) {
-        load_row(j + 1, B);
-        finish_row(j, A);
-        finish_row(j + 1, B);
-    } else {
-        finish_row(j, A);
-    }
+    strip_pipeline<Row>(r0, r1, load_row, finish_row);
 }
 
 template <typename T, int VEC, bool MASK, bool TARGET, bool ACC>
@@ -141,15 +123,10 @@ hipError_t LAUNCH_NAME(launch_relaxation_, LAUNCH_SFX)(const RelaxationArgs<T> &
     for (int k = 0; k < a.nfields; ++k) {
         ptrs[5 * k] = a.old[k]; ptrs[5 * k + 1] = a.nw[k]; ptrs[5 * k + 2] = a.acc[k]; ptrs[5 * k + 3] = a.mask[k]; ptrs[5 * k + 4] = a.target[k];
     }
-    // the phase every pointer of the call shares, which the masks' and the targets' member pitches must keep as well
-    int phase = common_phase((int)sizeof(T), a.sy, a.members > 0 ? a.stride_m : 0, ptrs, 5 * a.nfields);
-    const long V = 16 / (long)sizeof(T);
-    if (a.members > 0 && (a.mask_stride_m % V != 0 || a.target_stride_m % V != 0)) phase = -1;
-    const StripPlan p = strip_plan(a.Nx, a.j1 - a.j0, (int)sizeof(T), phase, (a.members > 0 ? a.members : 1) * a.nfields);
-    if (p.none) return hipSuccess;
-    if (p.too_many) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(STRIP_KERNEL(k_relaxation, T, p, a), dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, a, p.lead, p.nstrips, p.nsb);
-    return hipGetLastError();
+    // (the masks' and the targets' member pitches are read for an ensemble only)
+    const bool ens = a.members > 0;
+    const StripPlan p = strip_plan_of<T>(a, ptrs, 5 * a.nfields, a.nfields, {ens ? a.mask_stride_m : 0, ens ? a.target_stride_m : 0});
+    return strip_launch(STRIP_KERNEL(k_relaxation, T, p, a), p, s, a);
 }
 template hipError_t LAUNCH_NAME(launch_relaxation_, LAUNCH_SFX)<double>(const RelaxationArgs<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_relaxation_, LAUNCH_SFX)<float>(const RelaxationArgs<float> &, hipStream_t);

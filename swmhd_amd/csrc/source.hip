@@ -12,7 +12,7 @@
 //
 // Work: the strip march of strip_device.inc (launch_plan.hpp strip_plan, unchanged; one launch per member and field).  The kind of a
 // field and whether it has an acc are decided ONCE per workgroup (uniform).
-//   kind 0 (source_plain): Strip0 and relaxation.hip's software pipeline -- two row buffers A and B in turn, the loads of every stream of
+//   kind 0 (source_plain): Strip0 and the software pipeline of strip_pipeline -- two row buffers A and B in turn, the loads of every stream of
 //     a row (S, nw, acc) issued together and one row ahead, whether a lane's group lies wholly inside the row decided once per lane.
 //     Nothing of `old` is read.
 //   kind 1, 2 (source_weighted): Strip (radius 1: the wrap of row_of and of the columns), the same two buffers.  The west h of a lane's
@@ -27,7 +27,7 @@
 namespace swmhd {
 namespace {
 
-#include "strip_device.inc"   // STRICT, vec_load / vec_store, Strip, Strip0, strip_block, strip_scalars, STRIP_KERNEL
+#include "strip_device.inc"   // STRICT, vec_load, Strip, Strip0, strip_block, strip_scalars, strip_pipeline, strip_plan_of, STRIP_KERNEL, strip_launch
 
 template <typename T>
 struct SourcePtrs {
@@ -65,24 +65,7 @@ __device__ __forceinline__ void source_plain_march(const Strip0<T, VEC> &st, con
         st.template store<FULL>(q.nw + ro, un);
         if constexpr (ACC) st.template store<FULL>(q.acc + ro, ua);
     };
-    // relaxation.hip's steady loop: B's loads before A's row is finished, A's next loads before B's row is; no branch inside
-    Row A, B;
-    int j = r0;
-    load_row(j, A);
-    while (j + 2 < r1) {
-        load_row(j + 1, B);
-        finish_row(j, A);
-        load_row(j + 2, A);
-        finish_row(j + 1, B);
-        j += 2;
-    }
-    if (j + 1 < r1) {
-        load_row(j + 1, B);
-        finish_row(j, A);
-        finish_row(j + 1, B);
-    } else {
-        finish_row(j, A);
-    }
+    strip_pipeline<Row>(r0, r1, load_row, finish_row);
 }
 
 template <typename T, int VEC, bool ACC>
@@ -99,15 +82,15 @@ __device__ __forceinline__ void source_weighted(const SourceArgs<T> &a, const St
     // the columns of h a lane reads: its own inside [0, Nx) and, for the x face, column -1 (the halo cell or its periodic image)
     bool okh[VEC];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) okh[e] = KIND == 1 ? (st.ok[e] && st.xv + e < st.Nx) : st.inside[e];
+    for (int e = 0; e < VEC; ++e) okh[e] = KIND == 1 ? (st.ok[e] && st.cols.xv + e < st.Nx) : st.cols.inside[e];
     // lane 0 of a wave has no lane to its west: where its first column is a cell, it reads the column before from memory
-    const bool west_mem = KIND == 1 && st.lane == 0 && st.xv >= 0 && st.xv < st.Nx;
+    const bool west_mem = KIND == 1 && st.lane == 0 && st.cols.xv >= 0 && st.cols.xv < st.Nx;
     struct Row {
         T h[VEC], s[VEC], un[VEC], ua[VEC], hw;
     };
     auto load_h = [&](const T *p, T (&v)[VEC]) {
-        if (st.full) {
-            vec_load<T, VEC>(p + st.xv, v);
+        if (st.cols.full) {
+            vec_load<T, VEC>(p + st.cols.xv, v);
         } else {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) v[e] = okh[e] ? p[st.col[e]] : T(0);
@@ -117,9 +100,9 @@ __device__ __forceinline__ void source_weighted(const SourceArgs<T> &a, const St
         const long ro = (long)j * q.sy;
         load_h(q.h + ro, w.h);
         if constexpr (KIND == 1) w.hw = west_mem ? q.h[ro + st.colw] : T(0);
-        st.load_out(q.src + ro, w.s);
-        st.load_out(q.nw + ro, w.un);
-        if constexpr (ACC) st.load_out(q.acc + ro, w.ua);
+        st.cols.load(q.src + ro, w.s);
+        st.cols.load(q.nw + ro, w.un);
+        if constexpr (ACC) st.cols.load(q.acc + ro, w.ua);
     };
     auto finish_row = [&](int j, const Row &w, const T (&south)[VEC]) {
         const long ro = (long)j * q.sy;
@@ -135,8 +118,8 @@ __device__ __forceinline__ void source_weighted(const SourceArgs<T> &a, const St
             D[e] = ((other + w.h[e]) / T(2)) * w.s[e];
         }
         source_update<T, VEC, ACC>(D, w.un, w.ua, q.av, q.wv, un, ua);
-        st.store_out(q.nw + ro, un);
-        if constexpr (ACC) st.store_out(q.acc + ro, ua);
+        st.cols.store(q.nw + ro, un);
+        if constexpr (ACC) st.cols.store(q.acc + ro, ua);
     };
     auto carry = [&](T (&c)[VEC], const Row &w) {
         if constexpr (KIND == 2) {
@@ -149,6 +132,8 @@ __device__ __forceinline__ void source_weighted(const SourceArgs<T> &a, const St
 #pragma unroll
     for (int e = 0; e < VEC; ++e) c[e] = T(0);
     if constexpr (KIND == 2) load_h(q.h + st.row_of(r0 - 1), c);
+    // strip_pipeline's march with the carry behind each finished row, written out: handed to strip_pipeline (a carry hook and closures
+    // that hold c) the one-element kernels come out with other instructions (profiles/strip_scaffold/README.md)
     Row A, B;
     int j = r0;
     load_row(j, A);
@@ -211,15 +196,9 @@ hipError_t LAUNCH_NAME(launch_source_, LAUNCH_SFX)(const SourceArgs<T> &a, hipSt
         ptrs[3 * k] = a.nw[k]; ptrs[3 * k + 1] = a.acc[k]; ptrs[3 * k + 2] = a.src[k];
     }
     ptrs[3 * a.nfields] = a.hold;
-    // the phase every pointer of the call shares, which the sources' member pitch must keep as well
-    int phase = common_phase((int)sizeof(T), a.sy, a.members > 0 ? a.stride_m : 0, ptrs, 3 * a.nfields + 1);
-    const long V = 16 / (long)sizeof(T);
-    if (a.members > 0 && a.source_stride_m % V != 0) phase = -1;
-    const StripPlan p = strip_plan(a.Nx, a.j1 - a.j0, (int)sizeof(T), phase, (a.members > 0 ? a.members : 1) * a.nfields);
-    if (p.none) return hipSuccess;
-    if (p.too_many) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(STRIP_KERNEL(k_source, T, p, a), dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, a, p.lead, p.nstrips, p.nsb);
-    return hipGetLastError();
+    // (the sources' member pitch is read for an ensemble only)
+    const StripPlan p = strip_plan_of<T>(a, ptrs, 3 * a.nfields + 1, a.nfields, {a.members > 0 ? a.source_stride_m : 0});
+    return strip_launch(STRIP_KERNEL(k_source, T, p, a), p, s, a);
 }
 template hipError_t LAUNCH_NAME(launch_source_, LAUNCH_SFX)<double>(const SourceArgs<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_source_, LAUNCH_SFX)<float>(const SourceArgs<float> &, hipStream_t);

@@ -11,7 +11,7 @@
 // two FMA per mode and cell.  Roundings and the fast bound: include/swmhd_stochastic.h.
 //
 // Work: the strip geometry of strip_device.inc (Strip0; launch_plan.hpp strip_plan, unchanged; one launch per member and field), but
-// unlike the four memory-bound terms this one is compute-bound (2 M FMA per cell against 16 or 32 bytes), so the march is turned inside
+// unlike the five memory-bound terms this one is compute-bound (2 M FMA per cell against 16 or 32 bytes), so the march is turned inside
 // out: a lane keeps its columns AND one accumulator for each of its wave's STRIP_WAVE_ROWS rows, and the modes go by in chunks of
 // STOCHASTIC_MODE_CHUNK.  Per chunk the workgroup (four waves, 64 rows of one strip) forms R, T of the chunk's modes and its rows once,
 // into LDS (2 x 4 x 64 values: 4 KiB in fp64) -- 4 flops per mode and ROW instead of per mode and cell -- and a lane loads the chunk's cx,
@@ -27,7 +27,7 @@
 namespace swmhd {
 namespace {
 
-#include "strip_device.inc"   // STRICT, vec_load / vec_store, Strip0, strip_block, STRIP_KERNEL
+#include "strip_device.inc"   // STRICT, Strip0, strip_block, strip_plan_of, STRIP_KERNEL, strip_launch
 
 constexpr int MC = STOCHASTIC_MODE_CHUNK;
 constexpr int TILE_ROWS = STRIP_WAVES * STRIP_WAVE_ROWS;
@@ -38,12 +38,6 @@ template <typename T>
 struct alignas(2 * sizeof(T)) RowFactor {
     T R, Tm;
 };
-
-template <typename T, int VEC>
-__device__ __forceinline__ void table_row(const Strip0<T, VEC> &st, const T *p, T (&v)[VEC]) {
-    if (st.full) st.template load<true>(p, v);
-    else st.template load<false>(p, v);
-}
 
 // F[rr][e] of the rows [0, nrows) of this wave gains the modes [0, mc) of the chunk in LDS.  WHOLE: mc == MC and nrows == STRIP_WAVE_ROWS
 template <typename T, int VEC, bool WHOLE>
@@ -121,8 +115,8 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES, 2) void k_stochastic(Stoch
 #pragma unroll
             for (int c = 0; c < MC; ++c) {
                 if (c < mc) {
-                    table_row<T, VEC>(st, xt + (long)(2 * (m0 + c)) * xp, cx[c]);
-                    table_row<T, VEC>(st, xt + (long)(2 * (m0 + c) + 1) * xp, sx[c]);
+                    st.load(xt + (long)(2 * (m0 + c)) * xp, cx[c]);
+                    st.load(xt + (long)(2 * (m0 + c) + 1) * xp, sx[c]);
                 } else {
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) cx[c][e] = sx[c][e] = T(0);   // (never used)
@@ -140,6 +134,8 @@ __global__ __launch_bounds__(STRIP_WAVE *STRIP_WAVES, 2) void k_stochastic(Stoch
         if (rr < nrows) {
             const long ro = (long)(r0 + rr) * a.sy;
             T un[VEC], ua[VEC];
+            // (st.load / st.store would form nw + ro and acc + ro once, ahead of the branch on st.full, not once in each of its arms:
+            //  another instruction mix in all eight kernels, so the four dispatches of the updated rows stay written out)
             if (st.full) st.template load<true>(nw + ro, un);
             else st.template load<false>(nw + ro, un);
             if (acc) {
@@ -169,14 +165,9 @@ hipError_t LAUNCH_NAME(launch_stochastic_, LAUNCH_SFX)(const StochasticArgs<T> &
     for (int k = 0; k < a.nfields; ++k) {
         ptrs[3 * k] = a.nw[k]; ptrs[3 * k + 1] = a.acc[k]; ptrs[3 * k + 2] = a.xtab[k];
     }
-    // the phase the parents and the x tables share, which the pitch of the x tables must keep as well
-    int phase = common_phase((int)sizeof(T), a.sy, a.members > 0 ? a.stride_m : 0, ptrs, 3 * a.nfields);
-    if (a.xp % (16 / (long)sizeof(T)) != 0) phase = -1;
-    const StripPlan p = strip_plan(a.Nx, a.j1 - a.j0, (int)sizeof(T), phase, (a.members > 0 ? a.members : 1) * a.nfields);
-    if (p.none) return hipSuccess;
-    if (p.too_many) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(STRIP_KERNEL(k_stochastic, T, p, a), dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, a, p.lead, p.nstrips, p.nsb);
-    return hipGetLastError();
+    // (the x tables are shared by the members: their pitch counts for one grid too)
+    const StripPlan p = strip_plan_of<T>(a, ptrs, 3 * a.nfields, a.nfields, {a.xp});
+    return strip_launch(STRIP_KERNEL(k_stochastic, T, p, a), p, s, a);
 }
 template hipError_t LAUNCH_NAME(launch_stochastic_, LAUNCH_SFX)<double>(const StochasticArgs<double> &, hipStream_t);
 template hipError_t LAUNCH_NAME(launch_stochastic_, LAUNCH_SFX)<float>(const StochasticArgs<float> &, hipStream_t);

@@ -1,10 +1,12 @@
-// What the per-stage correction launches (diffusion.hip, coriolis.hip, biharmonic.hip, relaxation.hip) share, stated once; included inside their anonymous namespace,
-// after common.hpp and launch_plan.hpp.  A wave owns a strip of STRIP_WAVE lanes x VEC columns and marches down STRIP_WAVE_ROWS rows of
-// it, VEC = 16 bytes of elements per lane where every pointer of the call has the same 16-byte phase and the pitches keep it (else
-// VEC = 1): launch_plan.hpp strip_plan.  No LDS, no barrier: the STRIP_WAVES waves of a workgroup are consecutive row segments of one
-// strip.  Here: the strict / fast switch and the launcher's name, the vector access, the strip of one lane (Strip; Strip2 for a stencil of radius 2, Strip0 for a term of radius 0), the decoding of
-// blockIdx.x (strip_block), the per-member scalars (strip_scalars), and the host's plan and pick of an instantiation.  The carried
-// rows and the arithmetic are each kernel's own.
+// What the six per-stage correction launches (coriolis.hip, diffusion.hip, biharmonic.hip, relaxation.hip, source.hip, stochastic.hip)
+// share, stated once; included inside their anonymous namespace, after common.hpp and launch_plan.hpp.  A wave owns a strip of STRIP_WAVE
+// lanes x VEC columns and marches down STRIP_WAVE_ROWS rows of it, VEC = 16 bytes of elements per lane where every pointer of the call has
+// the same 16-byte phase and the pitches keep it (else VEC = 1): launch_plan.hpp strip_call_plan.  The STRIP_WAVES waves of a workgroup
+// are consecutive row segments of one strip.  Here: the strict / fast switch and the launcher's name, the vector access, the columns of
+// one lane (StripCols) and the strips built on them (Strip0 for a term of radius 0, Strip for a stencil of radius 1, Strip2 for radius 2),
+// the decoding of blockIdx.x (strip_block), the per-member scalars (strip_scalars), the two-buffer
+// row pipeline of the terms that carry nothing from row to row (strip_pipeline), and the host's plan, pick of an instantiation and
+// launch (strip_plan_of, STRIP_KERNEL, strip_launch).  The carried rows and the arithmetic are each kernel's own.
 #ifndef SWMHD_STRIP_STRICT
 #error "compile with -DSWMHD_STRIP_STRICT=0 or 1 (Makefile)"
 #endif
@@ -41,21 +43,83 @@ __device__ __forceinline__ void vec_store(T *p, const T (&v)[VEC]) {
     }
 }
 
-// The VEC columns xv .. xv + VEC - 1 of one lane and their two neighbours.  lead: columns by which the vector groups start left of
-// x = 0, so that a group inside [0, Nx) is 16-byte aligned in every parent.  A column as it is read: -1 and Nx are the halo cells or,
-// wrapped, their periodic images; nothing further out is read.  Lanes outside [0, Nx) load T(0) and store nothing.
+// The VEC columns xv .. xv + VEC - 1 of one lane, and the access to a row that is updated: read and written at the lane's own columns
+// inside [0, Nx) and nowhere else.  lead: columns by which the vector groups start left of x = 0, so that a group inside [0, Nx) is
+// 16-byte aligned in every parent.  full: the whole group lies inside (one 16-byte access).  Columns outside [0, Nx) load T(0) and store
+// nothing.  load / store<FULL>: for a caller that decides FULL once per lane, outside its row loop; load / store: decided at the access.
+// inside[] is filled by the strip built on this, in the one loop over the columns in which it fills what else it keeps per column (two
+// loops give the same values and another instruction order in half of the kernels: profiles/strip_scaffold/README.md).
+template <typename T, int VEC>
+struct StripCols {
+    int xv;
+    bool full;
+    bool inside[VEC];
+
+    __device__ __forceinline__ StripCols(int Nx, int strip, int lane, int lead) : xv((strip * STRIP_WAVE + lane) * VEC - lead) {
+        full = xv >= 0 && xv + VEC <= Nx;
+    }
+    __device__ __forceinline__ bool is_inside(int e, int Nx) const { return xv + e >= 0 && xv + e < Nx; }
+    template <bool FULL>
+    __device__ __forceinline__ void load(const T *p, T (&v)[VEC]) const {   // p: a row
+        if constexpr (FULL) {
+            vec_load<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
+        }
+    }
+    template <bool FULL>
+    __device__ __forceinline__ void store(T *p, const T (&v)[VEC]) const {
+        if constexpr (FULL) {
+            vec_store<T, VEC>(p + xv, v);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                if (inside[e]) p[xv + e] = v[e];
+        }
+    }
+    __device__ __forceinline__ void load(const T *p, T (&v)[VEC]) const {
+        if (full) load<true>(p, v);
+        else load<false>(p, v);
+    }
+    __device__ __forceinline__ void store(T *p, const T (&v)[VEC]) const {
+        if (full) store<true>(p, v);
+        else store<false>(p, v);
+    }
+};
+
+// Strip for a term of radius 0 (relaxation.hip, stochastic.hip, the plain fields of source.hip): no neighbour column and no halo.
+// any: at least one of the lane's columns lies inside [0, Nx).
+template <typename T, int VEC>
+struct Strip0 : StripCols<T, VEC> {
+    bool any;
+
+    __device__ __forceinline__ Strip0(int Nx, int strip, int lane, int lead) : StripCols<T, VEC>(Nx, strip, lane, lead) {
+        any = false;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            this->inside[e] = this->is_inside(e, Nx);
+            any = any || this->inside[e];
+        }
+    }
+};
+
+// Strip for a stencil of radius 1 (coriolis.hip, diffusion.hip, the weighted fields of source.hip): the lane's columns and their two
+// neighbours.  A column as it is read: -1 and Nx are the halo cells or, wrapped, their periodic images; nothing further out is read.
+// Lanes outside [0, Nx) load T(0).
 template <typename T, int VEC>
 struct Strip {
-    int Nx, Ny, lane, xv, colw, cole;
+    int Nx, Ny, lane, colw, cole;
     long sy;
-    bool wrapy, full, okw, oke;
+    bool wrapy, okw, oke;
     int col[VEC];
-    bool ok[VEC], inside[VEC];
+    bool ok[VEC];
+    StripCols<T, VEC> cols;   // (a member, and the last: as a base class, laid out first, it gives source.hip's one-element kernels other instructions)
 
     __device__ __forceinline__ Strip(int Nx_, int Ny_, long sy_, int wrap, int strip, int lane_, int lead)
-        : Nx(Nx_), Ny(Ny_), lane(lane_), xv((strip * STRIP_WAVE + lane_) * VEC - lead), sy(sy_), wrapy(wrap & 2) {
+        : Nx(Nx_), Ny(Ny_), lane(lane_), sy(sy_), wrapy(wrap & 2), cols(Nx_, strip, lane_, lead) {
         const bool wrapx = wrap & 1;
-        full = xv >= 0 && xv + VEC <= Nx;
+        const int xv = cols.xv;
         auto column = [&](int x, bool &valid) -> int {
             valid = x >= -1 && x <= Nx;
             if (wrapx) x = x < 0 ? Nx - 1 : (x >= Nx ? 0 : x);
@@ -64,7 +128,7 @@ struct Strip {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             col[e] = column(xv + e, ok[e]);
-            inside[e] = xv + e >= 0 && xv + e < Nx;
+            cols.inside[e] = cols.is_inside(e, Nx);
         }
         colw = column(xv - 1, okw);
         cole = column(xv + VEC, oke);
@@ -74,8 +138,8 @@ struct Strip {
         return (long)y * sy;
     }
     __device__ __forceinline__ void load_in(const T *p, T (&v)[VEC]) const {   // p: a row that is read with its halo
-        if (full) {
-            vec_load<T, VEC>(p + xv, v);
+        if (cols.full) {
+            vec_load<T, VEC>(p + cols.xv, v);
         } else {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) v[e] = ok[e] ? p[col[e]] : T(0);
@@ -92,23 +156,6 @@ struct Strip {
         if (lane == 0) x = okw ? p[colw] : T(0);
         return x;
     }
-    __device__ __forceinline__ void load_out(const T *p, T (&v)[VEC]) const {   // p: a row that is updated
-        if (full) {
-            vec_load<T, VEC>(p + xv, v);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
-        }
-    }
-    __device__ __forceinline__ void store_out(T *p, const T (&v)[VEC]) const {
-        if (full) {
-            vec_store<T, VEC>(p + xv, v);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e)
-                if (inside[e]) p[xv + e] = v[e];
-        }
-    }
 };
 
 // Strip for a stencil of radius 2 (biharmonic.hip): the same lanes, groups and lead, with two columns and two rows around.  A column as
@@ -118,11 +165,11 @@ struct Strip {
 // 13-cell diamonds of its cells and no more.  dist: how far a column lies outside [0, Nx) (0: inside).
 template <typename T, int VEC>
 struct Strip2 {
-    int Nx, Ny, lane, xv, colw, cole, colw2, cole2, distw, diste, distw2, diste2;
+    int Nx, Ny, lane, colw, cole, colw2, cole2, distw, diste, distw2, diste2;
     long sy;
-    bool wrapy, full;
+    bool wrapy;
     int col[VEC], dist[VEC];
-    bool inside[VEC];
+    StripCols<T, VEC> cols;
 
     __device__ __forceinline__ static int fold(int v, int n) {   // v mod n for v in [-2, n + 1], n >= 1
         if (v < 0) v += n;
@@ -132,9 +179,9 @@ struct Strip2 {
         return v;
     }
     __device__ __forceinline__ Strip2(int Nx_, int Ny_, long sy_, int wrap, int strip, int lane_, int lead)
-        : Nx(Nx_), Ny(Ny_), lane(lane_), xv((strip * STRIP_WAVE + lane_) * VEC - lead), sy(sy_), wrapy(wrap & 2) {
+        : Nx(Nx_), Ny(Ny_), lane(lane_), sy(sy_), wrapy(wrap & 2), cols(Nx_, strip, lane_, lead) {
         const bool wrapx = wrap & 1;
-        full = xv >= 0 && xv + VEC <= Nx;
+        const int xv = cols.xv;
         auto column = [&](int x, int &d) -> int {
             d = x < 0 ? -x : (x >= Nx ? x - Nx + 1 : 0);
             if (d > 2) return 0;   // (never read: reach <= 2)
@@ -143,7 +190,7 @@ struct Strip2 {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             col[e] = column(xv + e, dist[e]);
-            inside[e] = dist[e] == 0;
+            cols.inside[e] = dist[e] == 0;
         }
         colw = column(xv - 1, distw);
         cole = column(xv + VEC, diste);
@@ -155,8 +202,8 @@ struct Strip2 {
         return (long)y * sy;
     }
     __device__ __forceinline__ void load_in(const T *p, int reach, T (&v)[VEC]) const {   // p: a row that is read with its halo
-        if (full) {
-            vec_load<T, VEC>(p + xv, v);
+        if (cols.full) {
+            vec_load<T, VEC>(p + cols.xv, v);
         } else {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) v[e] = dist[e] <= reach ? p[col[e]] : T(0);
@@ -180,62 +227,6 @@ struct Strip2 {
     }
     __device__ __forceinline__ T west2_of(const T *p, int reach) const {
         return (lane == 0 && distw2 <= reach) ? p[colw2] : T(0);
-    }
-    __device__ __forceinline__ void load_out(const T *p, T (&v)[VEC]) const {   // p: a row that is updated
-        if (full) {
-            vec_load<T, VEC>(p + xv, v);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
-        }
-    }
-    __device__ __forceinline__ void store_out(T *p, const T (&v)[VEC]) const {
-        if (full) {
-            vec_store<T, VEC>(p + xv, v);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e)
-                if (inside[e]) p[xv + e] = v[e];
-        }
-    }
-};
-
-// Strip for a term of radius 0 (relaxation.hip): the same lanes, groups and lead, no neighbour column and no halo -- every stream of the
-// call is read and written at the lane's own columns inside [0, Nx) and nowhere else.  full: the whole group lies inside (one 16-byte
-// access); any: at least one of its columns does.  The caller decides FULL once per lane, outside its row loop.
-template <typename T, int VEC>
-struct Strip0 {
-    int xv;
-    bool full, any;
-    bool inside[VEC];
-
-    __device__ __forceinline__ Strip0(int Nx, int strip, int lane, int lead) : xv((strip * STRIP_WAVE + lane) * VEC - lead) {
-        full = xv >= 0 && xv + VEC <= Nx;
-        any = false;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            inside[e] = xv + e >= 0 && xv + e < Nx;
-            any = any || inside[e];
-        }
-    }
-    template <bool FULL>
-    __device__ __forceinline__ void load(const T *p, T (&v)[VEC]) const {   // p: a row
-        if constexpr (FULL) {
-            vec_load<T, VEC>(p + xv, v);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = inside[e] ? p[xv + e] : T(0);
-        }
-    }
-    template <bool FULL>
-    __device__ __forceinline__ void store(T *p, const T (&v)[VEC]) const {
-        if constexpr (FULL) {
-            vec_store<T, VEC>(p + xv, v);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e)
-                if (inside[e]) p[xv + e] = v[e];
-        }
     }
 };
 
@@ -262,14 +253,57 @@ __device__ __forceinline__ void strip_scalars(const StripArgs<T> &a, unsigned m,
     }
 }
 
+// The march of a term that carries nothing from row to row, as a software pipeline: two row buffers A and B in turn, the loads of every
+// stream of a row issued together (load_row) and one row ahead of its arithmetic and stores (finish_row), with no copy between the
+// buffers.  The steady loop has no branch inside: B's loads are issued before A's row is finished and A's next loads before B's row is,
+// so every wait is for one row's loads while the other row's are in flight.  The last one or two rows follow it.  carry(row): what a
+// finished row leaves for the next one's finish_row; the default leaves nothing.  (The weighted fields of source.hip, which carry one
+// row of h, keep this march written out -- and the default goes through the hook, not around it: either change gives the kernels
+// other instructions, profiles/strip_scaffold/README.md.)
+template <typename Row, typename Load, typename Finish, typename Carry>
+__device__ __forceinline__ void strip_pipeline(int r0, int r1, Load load_row, Finish finish_row, Carry carry) {
+    Row A, B;
+    int j = r0;
+    load_row(j, A);
+    while (j + 2 < r1) {
+        load_row(j + 1, B);
+        finish_row(j, A);
+        carry(A);
+        load_row(j + 2, A);
+        finish_row(j + 1, B);
+        carry(B);
+        j += 2;
+    }
+    if (j + 1 < r1) {
+        load_row(j + 1, B);
+        finish_row(j, A);
+        carry(A);
+        finish_row(j + 1, B);
+    } else {
+        finish_row(j, A);
+    }
+}
+template <typename Row, typename Load, typename Finish>
+__device__ __forceinline__ void strip_pipeline(int r0, int r1, Load load_row, Finish finish_row) {
+    strip_pipeline<Row>(r0, r1, load_row, finish_row, [](const Row &) {});
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-// the plan of a call over the n pointers of ptrs (null entries skipped), per_member launches for each member
+// the plan of a call (launch_plan.hpp strip_call_plan) over the n pointers of ptrs, per_member launches for each member; further: the
+// pitches of the kind that must keep the phase besides sy and stride_m
 template <typename T>
-StripPlan strip_plan_of(const StripArgs<T> &a, const void *const *ptrs, int n, int per_member) {
-    const int phase = common_phase((int)sizeof(T), a.sy, a.members > 0 ? a.stride_m : 0, ptrs, n);
-    return strip_plan(a.Nx, a.j1 - a.j0, (int)sizeof(T), phase, (a.members > 0 ? a.members : 1) * per_member);
+StripPlan strip_plan_of(const StripArgs<T> &a, const void *const *ptrs, int n, int per_member, std::initializer_list<long> further = {}) {
+    return strip_call_plan(a.Nx, a.j1 - a.j0, (int)sizeof(T), ptrs, n, a.sy, a.members, a.stride_m, per_member, further);
 }
 // the instantiation of kernel template k<T, VEC, ENS> that a plan and a call ask for
 #define STRIP_KERNEL(k, T, plan, args)                                                                               \
     ((args).members > 0 ? ((plan).vec > 1 ? k<T, 16 / (int)sizeof(T), true> : k<T, 1, true>)                         \
                         : ((plan).vec > 1 ? k<T, 16 / (int)sizeof(T), false> : k<T, 1, false>))
+// the launch of a picked kernel(args..., lead, nstrips, nsb) over the plan's workgroups; nothing to compute is no error
+template <typename K, typename... Args>
+hipError_t strip_launch(K kernel, const StripPlan &p, hipStream_t s, const Args &...args) {
+    if (p.none) return hipSuccess;
+    if (p.too_many) return hipErrorInvalidConfiguration;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.blocks), dim3(STRIP_WAVE, STRIP_WAVES), 0, s, args..., p.lead, p.nstrips, p.nsb);
+    return hipGetLastError();
+}

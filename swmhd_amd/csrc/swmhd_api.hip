@@ -321,7 +321,7 @@ int stencil_closure_common(int radius, const T *const *old, T *const *nw, T *con
             if (!isfinite((double)coef[k]) || coef[k] < T(0)) return SWMHD_EINVAL;
     if (flags & DIFFUSION_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
-    if ((g.Hx < radius && !(fl.wrap & 1)) || (g.Hy < radius && !(fl.wrap & 2))) return SWMHD_EHALO;
+    if (!g.halo_or_wrap(radius, fl.wrap)) return SWMHD_EHALO;
     if (r.j0 == r.j1) return SWMHD_OK;
     DiffusionArgs<T> d;
     const int n = pack_fields(d, DIFFUSION_MAX_FIELDS, f, g, [&](int k) { return ens || coef[k] != T(0); },
@@ -363,7 +363,7 @@ int coriolis_common(const T *q1, const T *q2, T *n1, T *n2, T *a1, T *a2, const 
     if (!correction_members_ok(ens, g)) return SWMHD_EINVAL;
     if (flags & CORIOLIS_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
-    if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
+    if (!g.halo_or_wrap(1, fl.wrap)) return SWMHD_EHALO;
     if (r.j0 == r.j1) return SWMHD_OK;
     CoriolisArgs<T> c;
     c.q1 = g.interior(q1); c.q2 = g.interior(q2); c.n1 = g.interior(n1); c.n2 = g.interior(n2);
@@ -422,7 +422,7 @@ inline bool particles_grid_ok(const Grid &g, double x0, double y0, int64_t P, in
 inline int particles_after_einval(const Grid &g, int flags) {
     if (flags & PARTICLES_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
-    if ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2))) return SWMHD_EHALO;
+    if (!g.halo_or_wrap(1, fl.wrap)) return SWMHD_EHALO;
     return SWMHD_OK;
 }
 inline void set_particle_grid(ParticleGrid &a, const Grid &g, double x0, double y0, int64_t P, int flags, const Ens *ens) {
@@ -531,7 +531,7 @@ int source_common(const T *const *old, T *const *nw, T *const *acc, const T *con
     if (weighted && thickness < 0) return SWMHD_EINVAL;
     if (flags & SOURCE_NOTSUP) return SWMHD_ENOTSUP;
     const Flags fl = decode_flags(flags);
-    if (weighted && ((g.Hx < 1 && !(fl.wrap & 1)) || (g.Hy < 1 && !(fl.wrap & 2)))) return SWMHD_EHALO;
+    if (weighted && !g.halo_or_wrap(1, fl.wrap)) return SWMHD_EHALO;
     if (r.j0 == r.j1) return SWMHD_OK;
     SourceArgs<T> d;
     const int n = pack_fields(d, SOURCE_MAX_FIELDS, f, g, [&](int k) { return source[k] != nullptr; }, [&](int slot, int k) {

@@ -24,7 +24,17 @@ SENTINEL = T.SENTINEL
 MAX_FIELDS = 12                     # SWMHD_RELAXATION_MAX_FIELDS
 
 # ---- the stage matrix: the geometry of the strip-march launches, read from strip_cases -------------------------------------------------
-from strip_cases import TILE_ROWS, row_ranges, stage_shapes, wave_columns      # noqa: F401,E402
+from strip_cases import TILE_ROWS, row_ranges, wave_columns      # noqa: F401,E402
+from strip_cases import stage_shapes as strip_stage_shapes      # noqa: E402
+
+# wave segments of exactly 2 and 4 rows: the two-buffer march (csrc/strip_device.inc strip_pipeline) ends in its even tail without a
+# steady trip, and after exactly one
+SHORT_SHAPES = [(3, 2), (3, 4)]
+
+
+def stage_shapes(itemsize, aligned):
+    return strip_stage_shapes(itemsize, aligned) + SHORT_SHAPES
+
 
 # the six kinds of a field: (has a mask array, target "zero" (the default 0) | "scalar" | "array")
 FIELD_KINDS = [(m, t) for m in (False, True) for t in ("zero", "scalar", "array")]

@@ -1,7 +1,7 @@
-"""The geometry of the stage matrices of the two strip-march correction launches (csrc/strip_device.inc: the BetaPlane Coriolis launch
-and the ScalarDiffusivity closure), which coriolis_cases.py and diffusion_cases.py share, and which tests/strip_plan_check.cpp plans.
+"""The geometry of the stage matrices of the six strip-march correction launches (csrc/strip_device.inc: Coriolis, diffusion, biharmonic,
+relaxation, source, stochastic), which their *_cases.py share, and which tests/strip_plan_check.cpp plans.
 No numpy, no device."""
-TILE_ROWS = 64                      # SWMHD_CORIOLIS_TILE_ROWS = SWMHD_DIFFUSION_TILE_ROWS: four waves of 16 rows
+TILE_ROWS = 64                      # SWMHD_CORIOLIS_TILE_ROWS = SWMHD_DIFFUSION_TILE_ROWS = ...: four waves of 16 rows
 
 
 def wave_columns(itemsize, aligned):

@@ -218,13 +218,31 @@ def test_ensemble_members_are_single_grid_calls(swmhd, sfx, members):
             _ensemble_abi_case(L, sfx, t, members, name, geo, strict)
 
 
+# the targets' member pitch ALONE breaks the phase: stride_y and stride_m multiples of four elements, an odd target_stride_m -- one element
+# per lane, two strips of 64 columns, one row block
+TARGET_PITCH_GEOMETRY = dict(Nx={"f64": 65, "f32": 65}, Ny=17, sy={"f64": 72, "f32": 72}, gap=8, target_gap=9, vec=False)
+
+
+@pytest.mark.parametrize("sfx", ["f64", "f32"])
+def test_ensemble_target_pitch_alone_takes_the_element_path(swmhd, sfx):
+    """Two members of 65 x 17 whose parents would take the 16-byte path and whose target arrays lie an odd number of elements apart:
+    the assertions of test_ensemble_members_are_single_grid_calls -- bitwise the per-member single-grid calls in strict, the sentinels
+    in the gaps untouched."""
+    geo = TARGET_PITCH_GEOMETRY
+    size = (geo["Ny"] + 2 * H) * geo["sy"][sfx]
+    assert geo["sy"][sfx] % 4 == 0 and (size + geo["gap"]) % 4 == 0 and (size + geo["target_gap"]) % 2 == 1
+    for strict in (True, False):
+        _ensemble_abi_case(swmhd._lib, sfx, NPDT[sfx], 2, "target-elem", geo, strict)
+
+
 def _ensemble_abi_case(L, sfx, t, members, name, geo, strict):
     Nx, Ny, n = geo["Nx"][sfx], geo["Ny"], 3
     sy = geo["sy"][sfx]
     size = (Ny + 2 * H) * sy
     stride_m = size + geo["gap"]
+    target_stride_m = size + geo.get("target_gap", geo["gap"])
     V = 16 // np.dtype(t).itemsize
-    assert (sy % V == 0 and stride_m % V == 0) == geo["vec"]
+    assert (sy % V == 0 and stride_m % V == 0 and target_stride_m % V == 0) == geo["vec"]
     ft = ctypes.c_double if sfx == "f64" else ctypes.c_float
     cases = [Case(Nx, Ny, sy, t, 20 + m) for m in range(members)]
     kinds = [(False, "scalar"), (True, "array"), (True, "zero")]
@@ -245,20 +263,20 @@ def _ensemble_abi_case(L, sfx, t, members, name, geo, strict):
     u = np.uint64 if sfx == "f64" else np.uint32
     V_ = ctypes.c_void_p
 
-    def pack(arrs, fill):        # (n, members * stride_m): field k of member m at [k, m * stride_m:]
-        out = np.full((n, members * stride_m), fill, dtype=t)
+    def pack(arrs, fill, pitch=stride_m):        # (n, members * pitch): field k of member m at [k, m * pitch:]
+        out = np.full((n, members * pitch), fill, dtype=t)
         for m, a in enumerate(arrs):
-            out[:, m * stride_m:m * stride_m + size] = a[:n].reshape(n, size)
+            out[:, m * pitch:m * pitch + size] = a[:n].reshape(n, size)
         return torch.from_numpy(out).cuda()
 
     def run_ensemble(par, w, anchor, rows):
         ins = [c.inputs(rows, [k for k in range(n) if rates[m, k] == 0]) for m, c in enumerate(cases)]
-        old_d, target_d = pack([i[0] for i in ins], np.nan), pack([i[2] for i in ins], np.nan)
+        old_d, target_d = pack([i[0] for i in ins], np.nan), pack([i[2] for i in ins], np.nan, target_stride_m)
         mask_d = torch.from_numpy(ins[0][1][:n]).cuda()      # one mask set for all members
         new_d, acc_d = pack([c.new for c in cases], RC.SENTINEL), pack([c.acc for c in cases], RC.SENTINEL)
         rate_d, tval_d, par_d = torch.from_numpy(rates).cuda(), torch.from_numpy(tvals).cuda(), torch.from_numpy(params).cuda()
         rc = ens(ptrs(old_d, n), ptrs(new_d, n), ptrs(acc_d, n), ptrs(mask_d, n, has_mask), ptrs(target_d, n, has_target), rate_d.data_ptr(),
-                 tval_d.data_ptr(), n, members, stride_m, 0, stride_m, Nx, Ny, H, H, sy, par_d.data_ptr() if par else None,
+                 tval_d.data_ptr(), n, members, stride_m, 0, target_stride_m, Nx, Ny, H, H, sy, par_d.data_ptr() if par else None,
                  float(gamma) if par else float(dts[0] * gamma), w, rows[0], rows[1], flags | (L.RK3_ANCHOR if anchor else 0), None)
         L.check(rc, "swmhd_ensemble_relaxation_rk3")
         torch.cuda.synchronize()

@@ -236,13 +236,31 @@ def test_ensemble_members_are_single_grid_calls(swmhd, sfx, members):
             _ensemble_abi_case(L, sfx, t, members, name, geo, strict)
 
 
+# the sources' member pitch ALONE breaks the phase: stride_y and stride_m multiples of four elements, an odd source_stride_m -- one element
+# per lane, two strips of 64 columns, one row block
+SOURCE_PITCH_GEOMETRY = dict(Nx={"f64": 65, "f32": 65}, Ny=17, sy={"f64": 72, "f32": 72}, gap=8, source_gap=9, vec=False)
+
+
+@pytest.mark.parametrize("sfx", ["f64", "f32"])
+def test_ensemble_source_pitch_alone_takes_the_element_path(swmhd, sfx):
+    """Two members of 65 x 17 whose parents would take the 16-byte path and whose per-member sources lie an odd number of elements
+    apart: the assertions of test_ensemble_members_are_single_grid_calls -- bitwise the per-member single-grid calls in strict, the
+    sentinels in the gaps untouched."""
+    geo = SOURCE_PITCH_GEOMETRY
+    size = (geo["Ny"] + 2 * H) * geo["sy"][sfx]
+    assert geo["sy"][sfx] % 4 == 0 and (size + geo["gap"]) % 4 == 0 and (size + geo["source_gap"]) % 2 == 1
+    for strict in (True, False):
+        _ensemble_abi_case(swmhd._lib, sfx, NPDT[sfx], 2, "source-elem", geo, strict)
+
+
 def _ensemble_abi_case(L, sfx, t, members, name, geo, strict):
     Nx, Ny, n = geo["Nx"][sfx], geo["Ny"], 4
     sy = geo["sy"][sfx]
     size = (Ny + 2 * H) * sy
     stride_m = size + geo["gap"]
+    source_stride_m = size + geo.get("source_gap", geo["gap"])      # of the sources given per member
     V = 16 // np.dtype(t).itemsize
-    assert (sy % V == 0 and stride_m % V == 0) == geo["vec"]
+    assert (sy % V == 0 and stride_m % V == 0 and source_stride_m % V == 0) == geo["vec"]
     es = np.dtype(t).itemsize
     thick, dead = layout(n)
     live = [k for k in range(n) if k not in dead]
@@ -258,10 +276,10 @@ def _ensemble_abi_case(L, sfx, t, members, name, geo, strict):
     has_src = [k not in dead for k in range(n)]
     u = np.uint64 if sfx == "f64" else np.uint32
 
-    def pack(arrs, fill):        # (n, members * stride_m): field k of member m at [k, m * stride_m:]
-        out = np.full((n, members * stride_m), fill, dtype=t)
+    def pack(arrs, fill, pitch=stride_m):        # (n, members * pitch): field k of member m at [k, m * pitch:]
+        out = np.full((n, members * pitch), fill, dtype=t)
         for m, a in enumerate(arrs):
-            out[:, m * stride_m:m * stride_m + size] = a[:n].reshape(n, size)
+            out[:, m * pitch:m * pitch + size] = a[:n].reshape(n, size)
         return torch.from_numpy(out).cuda()
 
     def run_ensemble(mode, par, w, anchor, rows):
@@ -270,7 +288,7 @@ def _ensemble_abi_case(L, sfx, t, members, name, geo, strict):
         old_d = pack([i[0] for i in ins], np.nan)
         new_d, acc_d = pack([c.new for c in cases], SC.SENTINEL), pack([c.acc for c in cases], SC.SENTINEL)
         if mode == "member":
-            src_d, src_sm = pack([i[1] for i in ins], np.nan), stride_m
+            src_d, src_sm = pack([i[1] for i in ins], np.nan, source_stride_m), source_stride_m
             src_p = ptrs(src_d, n, has_src)
         else:
             shift = 1 if mode == "shifted" else 0

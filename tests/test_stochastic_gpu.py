@@ -225,10 +225,26 @@ def test_stage_matrix(swmhd, sfx, strict, pitch):
 def test_ensemble_members_are_single_grid_calls(swmhd, sfx, strict):
     """Three members with their own coefficients (the tables are the ensemble's), a padded member stride: member m of new and acc is
     bitwise the single-grid call with that member's coefficients.  NaN in every halo cell, in old and between the members."""
+    Nx = 66
+    _ensemble_abi_case(swmhd, sfx, strict, 3, (Nx, 17), _pitch(Nx, True))
+
+
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
+@pytest.mark.parametrize("sfx", ["f64", "f32"])
+def test_ensemble_table_pitch_alone_takes_the_element_path(swmhd, sfx, strict):
+    """Two members of 65 x 17 whose parents would take the 16-byte path (stride_y and stride_m multiples of four elements) and whose x
+    tables have an odd pitch: the assertions of test_ensemble_members_are_single_grid_calls."""
+    Nx = 65
+    xp = _pitch(Nx, False)
+    assert _pitch(Nx, True) % 4 == 0 and xp % 2 == 1
+    _ensemble_abi_case(swmhd, sfx, strict, 2, (Nx, 17), xp)
+
+
+def _ensemble_abi_case(swmhd, sfx, strict, members, shape, xp):
     B = swmhd._lib
     L = B.lib()
     t, ft = NPDT[sfx], FLOAT[sfx]
-    members, (Nx, Ny) = 3, (66, 17)
+    Nx, Ny = shape
     sy = _pitch(Nx, True)
     c = Case(Nx, Ny, sy, t, 9)
     ks = [0, 3, 4]
@@ -240,9 +256,10 @@ def test_ensemble_members_are_single_grid_calls(swmhd, sfx, strict):
     for i, cf in enumerate(coefs):
         table[i, :, :cf.shape[1]] = cf
     d_table = _dev(table)
-    keep, _, xtab, ytab = c.device_tables(sy)
+    keep, _, xtab, ytab = c.device_tables(xp)
     es = np.dtype(t).itemsize
     stride_m = (Ny + 2 * H) * sy + 4
+    assert stride_m % 4 == 0
     flags = B.STRICT if strict else B.FAST
 
     def parents(src):
@@ -255,7 +272,7 @@ def test_ensemble_members_are_single_grid_calls(swmhd, sfx, strict):
     pick = lambda lst: (V * len(ks))(*[lst[k] for k in ks])
     cptr = (V * len(ks))(*[d_table.data_ptr() + i * members * cstride * es for i in range(len(ks))])
     rc = getattr(L, f"swmhd_ensemble_stochastic_rk3_{sfx}")(ptrs(d_old, ks), ptrs(d_new, ks), ptrs(d_acc, ks), cptr, pick(xtab), pick(ytab),
-                                                           _ints(Ms), len(ks), sy, Ny, members, stride_m, cstride, Nx, Ny, H, H, sy, None,
+                                                           _ints(Ms), len(ks), xp, Ny, members, stride_m, cstride, Nx, Ny, H, H, sy, None,
                                                            ft(A_STAGE), ft(W_STAGE), 0, Ny, flags, None)
     assert rc == 0
     torch.cuda.synchronize()
@@ -266,7 +283,7 @@ def test_ensemble_members_are_single_grid_calls(swmhd, sfx, strict):
         s_old = _dev(np.full((NF, (Ny + 2 * H) * sy), np.nan, dtype=t))
         one = (V * len(ks))(*[d_table.data_ptr() + (i * members + m) * cstride * es for i in range(len(ks))])
         rc = getattr(L, f"swmhd_stochastic_rk3_{sfx}")(ptrs(s_old, ks), ptrs(s_new, ks), ptrs(s_acc, ks), one, pick(xtab), pick(ytab), _ints(Ms),
-                                                      len(ks), sy, Ny, Nx, Ny, H, H, sy, ft(A_STAGE), ft(W_STAGE), 0, Ny, flags, None)
+                                                      len(ks), xp, Ny, Nx, Ny, H, H, sy, ft(A_STAGE), ft(W_STAGE), 0, Ny, flags, None)
         assert rc == 0
         torch.cuda.synchronize()
         u = np.uint64 if t == np.float64 else np.uint32

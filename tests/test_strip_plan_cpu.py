@@ -1,8 +1,11 @@
-"""CPU test of the launch plan of the two strip-march correction launches (strip_plan and common_phase in swmhd_amd/csrc/launch_plan.hpp:
-the Coriolis and the diffusion kernels): a host program prints the plan (tests/strip_plan_check.cpp: its own main, launch_plan.hpp only)
+"""CPU test of the launch plan of the six strip-march correction launches (strip_plan, common_phase and strip_call_plan in
+swmhd_amd/csrc/launch_plan.hpp: Coriolis, diffusion, biharmonic, relaxation, source, stochastic): a host program prints the plan (tests/strip_plan_check.cpp: its own main, launch_plan.hpp only)
 and the lines are compared with what the kernels' shape implies -- a wave of 64 lanes x vec columns marching 16 rows, four waves to a
 workgroup, the workgroups of launch l (a member, or a member's field) after those of launch l - 1 -- for every shape of the stage
-matrices (tests/strip_cases.py) in both precisions at every phase, "nothing to do", and the refusal from 2^31 workgroups on."""
+matrices (tests/strip_cases.py) in both precisions at every phase, "nothing to do", and the refusal from 2^31 workgroups on; and the
+plan of a whole call, whose phase the further pitches of its kind (a mask's, a target's or a source's member pitch, the pitch of the
+stochastic x tables) must keep as well -- 0 standing for "shared or not applicable"."""
+import itertools
 import os
 import subprocess
 
@@ -108,3 +111,45 @@ def test_common_phase(exe):
                 assert _run(exe, "phase", itemsize, 2 * V, 0, *same[:k], other, *same[k:]) == [["phase", "-1"]]
             assert _run(exe, "phase", itemsize, 2 * V + 1, 0, *same) == [["phase", "-1"]]           # the row pitch does not keep the phase
             assert _run(exe, "phase", itemsize, 2 * V, 5 * V + 1, *same) == [["phase", "-1"]]       # nor does the member pitch
+
+
+def test_call_plan_further_pitches(exe):
+    """strip_call_plan: common_phase's phase, kept or lost by the further pitches, then strip_plan's plan of it."""
+    Nx, rows, members, per = 65, 17, 2, 3
+
+    def call(itemsize, sy, members, stride_m, further, addrs):
+        out = _run(exe, "call", Nx, rows, itemsize, sy, members, stride_m, per, len(further), *further, *addrs)
+        assert len(out) == 1 and out[0][0] == "call"
+        return [int(v) for v in out[0][1:]]
+
+    def plan(itemsize, phase, launches):
+        return [int(v) for v in _run(exe, "plan", Nx, rows, itemsize, phase, launches)[0][6:]]
+
+    for itemsize in (8, 4):
+        V = 16 // itemsize
+        for ph in range(V):
+            base = 4096 + ph * itemsize
+            addrs = [base, base + 16 * 7, 0, base + 16 * 1000]
+            sy, stride_m = 20 * V, 600 * V
+            kept, lost = plan(itemsize, ph, members * per), plan(itemsize, -1, members * per)
+            assert kept[:2] == [V, ph] and lost[:2] == [1, 0]
+            # no further pitches: common_phase's answer, on the cases test_common_phase has
+            assert _run(exe, "phase", itemsize, sy, stride_m, *addrs) == [["phase", str(ph)]]
+            assert call(itemsize, sy, members, stride_m, [], addrs) == kept
+            assert call(itemsize, sy + 1, members, stride_m, [], addrs) == lost
+            assert call(itemsize, sy, members, stride_m + 1, [], addrs) == lost
+            assert call(itemsize, sy, members, stride_m, [], addrs[:1] + [base + itemsize] + addrs[1:]) == lost
+            # one grid: stride_m is not looked at, and there is one launch per field
+            assert call(itemsize, sy, 0, stride_m + 1, [], addrs) == plan(itemsize, ph, per)
+            # 0 and multiples of 16 / itemsize keep the phase, anything else loses it, in any order
+            good, bad = [0, V, 7 * V, 1000 * V], [1, V + 1, 1000 * V - 1] + ([2, 3, 5 * V + 2] if V == 4 else [])
+            for f in good:
+                assert call(itemsize, sy, members, stride_m, [f], addrs) == kept, (itemsize, ph, f)
+            for f in bad:
+                assert call(itemsize, sy, members, stride_m, [f], addrs) == lost, (itemsize, ph, f)
+            for fs in ([0, V], [7 * V, 0, 1000 * V]):
+                assert all(call(itemsize, sy, members, stride_m, list(p), addrs) == kept for p in itertools.permutations(fs))
+            for fs in ([0, 1], [V, V + 1, 0], [1, 3, 2 * V]):
+                assert all(call(itemsize, sy, members, stride_m, list(p), addrs) == lost for p in itertools.permutations(fs))
+            # a phase lost already stays lost
+            assert call(itemsize, sy + 1, members, stride_m, [0, V], addrs) == lost

@@ -7,7 +7,7 @@ prints for that unit (plus --offload-device-only --no-gpu-bundle-output), then `
 objects are compared.  Lines that carry the object's path or the __hip_cuid_* symbol (a hash of the path) are left out.  Needs no GPU.
 Per unit also `opcodes_equal`: the sequence of instruction mnemonics, label and symbol lines included, operands ignored (a listing
 that differs only in registers or in the order of a commutative operation's sources has it), and `differing_lines`, the count of
-listing lines that differ.  A unit that only one of the two Makefiles builds is reported as {"only_in": "mine" | "other"} and not
+listing lines that differ, and `mix_equal`: symbol by symbol the same count of every mnemonic (instructions moved, none added).  A unit that only one of the two Makefiles builds is reported as {"only_in": "mine" | "other"} and not
 compared: a change that adds a kernel leaves every older unit to be shown equal.
 Exit status 0: all equal."""
 import concurrent.futures
@@ -50,6 +50,18 @@ def opcodes(listing):
     return [l if l.rstrip().endswith(":") else l.split()[0] for l in listing if l.strip()]
 
 
+def mix(listing):
+    """Per symbol of a disassembly, how often each instruction mnemonic occurs in it: what a reordering of instructions leaves alone"""
+    out, sym = {}, None
+    for l in listing:
+        m = re.match(r"[0-9a-f]+ <(\S+)>:$", l.strip())
+        if m:
+            sym = out.setdefault(m.group(1), {})
+        elif l.strip() and not l.rstrip().endswith(":") and sym is not None:
+            sym[l.split()[0]] = sym.get(l.split()[0], 0) + 1
+    return out
+
+
 def differing_lines(a, b):
     if a == b:
         return 0
@@ -75,7 +87,7 @@ def main(argv):
         for u in both:
             a, b = jobs[(other, u)].result(), jobs[(mine, u)].result()
             report[u] = {"disassembly_lines": len(b[0]), "notes_lines": len(b[1]), "disassembly_equal": a[0] == b[0], "notes_equal": a[1] == b[1],
-                         "opcodes_equal": opcodes(a[0]) == opcodes(b[0]), "differing_lines": differing_lines(a[0], b[0])}
+                         "opcodes_equal": opcodes(a[0]) == opcodes(b[0]), "mix_equal": mix(a[0]) == mix(b[0]), "differing_lines": differing_lines(a[0], b[0])}
             print(u, report[u], flush=True)
     if js:
         with open(js, "w") as fh:
